@@ -5,7 +5,8 @@ A "step" is one pass of the hot path (k_short + k_cov; k_reads + k_long for long
 synthetic 150 bp paired-end reads (config 2 of BASELINE.json: 10 M reads over 4 x 25 Mb contigs).
 Each rank owns its own batch (records shard by read batch: weak scaling, no data-path collective);
 at the end of the job the flat uint64 state vectors are summed onto rank 0 with one RCCL reduce.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0 (`ms_per_step`: wall milliseconds of one timed step).  `--dump-outputs DIR` also writes the counts the
+timed steps left as .npy files, so that two builds can be compared on the same seeded inputs.
 """
 import argparse
 import json
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--no-large", action="store_true", help="skip e2e_large (100 M reads over 24 GRCh38-length contigs as a 10 GB file) and e2e_shard_proxy (one worker's eighth of config 3)")
     ap.add_argument("--large-reads", type=int, default=100_000_000)
     ap.add_argument("--only-large", action="store_true", help="(development) only e2e_large and e2e_shard_proxy, printed as one JSON object")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the counts they left (what Aggregator.finalize returns to a caller of the timed path) "
+                         "as DIR/lane<i>.<name>.npy in float64; the inputs are seeded, so two builds can be compared array for array")
     args = ap.parse_args()
     if args.workload == "config3":
         return config3_line(args)
@@ -133,6 +137,7 @@ def main():
             dist.reduce(vec, dst=0, op=dist.ReduceOp.SUM)
     barrier()
     elapsed = time.perf_counter() - t0
+    total = None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_gpu_rehearsal else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -141,6 +146,8 @@ def main():
             agg.state_import_device(vec.data_ptr())
             total = agg.finalize()
             assert int(total[0]["scalars"][4]) == (args.reads * args.steps * world - int(total[0]["scalars"][0]) - int(total[0]["scalars"][3])) % 2 ** 32
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, total if total is not None else agg.finalize())
 
     e2e_sharded = None
     if world > 1 and not args.no_e2e and not long_reads:
@@ -233,6 +240,29 @@ def main():
         agg.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, counts):
+    """--dump-outputs: every array of the finalized counts (one dict per read group, _abi.counts_to_dict) as path/lane<i>.<name>.npy in float64;
+    integer fields become one-element arrays, the sketch rows an (n, 6) array of (q, k, sumCount, F0, f1, F2).  An array with no elements
+    (the sketch of a run without --sketch) is not written.  All of it is well under 64 MB."""
+    arrays = {}
+    for li, lane in enumerate(counts):
+        for k, v in lane.items():
+            a = np.array(v, dtype=np.uint64)
+            if k == "sketch":
+                a = a.reshape(-1, 6)
+            if a.size:
+                arrays["lane%d.%s" % (li, k)] = np.atleast_1d(a)
+    big = [k for k, a in arrays.items() if int(a.max()) >= 2 ** 53]
+    if big:
+        raise SystemExit("bench.py --dump-outputs: counts of %s do not fit float64 exactly" % ", ".join(big))
+    nbytes = sum(a.size * 8 for a in arrays.values())
+    if nbytes > 64 << 20:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than 64 MB" % nbytes)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a.astype(np.float64))
 
 
 def launch_ranks(args):
@@ -405,7 +435,7 @@ def program_runs(exe, cli, reads, n_runs, tmp, tag):
         m = re.search(r"record loop ([0-9.]+) s", r.stderr)
         ls = re.search(r"record loop starts: ([0-9.]+) s after launch", r.stderr)
         runs.append({"wall_s": dt, "reads_per_s": reads / dt, "record_loop_s": float(m.group(1)) if m else None, "loop_start_s": float(ls.group(1)) if ls else None,
-                     "reader": "gpu" if "records decoded on the GPU" in r.stderr else "host", "timing": [ln for ln in r.stderr.splitlines() if ln.startswith(("[timing]", "[gpu reader] open"))]})
+                     "reader": "gpu" if "records decoded on the GPU" in r.stderr else "host"})
     assert all(filecmp.cmp(os.path.join(tmp, tag + "0.bamqc"), os.path.join(tmp, "%s%d.bamqc" % (tag, k)), shallow=False) for k in range(1, n_runs))
     return sorted(runs, key=lambda x: x["wall_s"])[n_runs // 2], runs
 
@@ -527,8 +557,7 @@ def e2e_leg(args, refs, cpu_kernel_value):
             assert r.returncode == 0, r.stderr[-2000:]
             m = re.search(r"record loop ([0-9.]+) s", r.stderr)
             runs.append({"args": extra, "wall_s": dt, "reads_per_s": args.reads / dt, "record_loop_s": float(m.group(1)) if m else None,
-                         "reader": "gpu (inflate, CRC, record walk and column decode on the card)" if "records decoded on the GPU" in r.stderr else "host",
-                         "timing": [ln for ln in r.stderr.splitlines() if ln.startswith("[timing]")]})
+                         "reader": "gpu (inflate, CRC, record walk and column decode on the card)" if "records decoded on the GPU" in r.stderr else "host"})
         assert all(filecmp.cmp(os.path.join(tmp, "o0.bamqc"), os.path.join(tmp, "o%d.bamqc" % k), shallow=False) for k in (1, 2))
         lanes = bamqc_text.parse(os.path.join(tmp, "o1.bamqc"))
         bamqc_text.check_invariants(lanes["L1"], n_records=args.reads, read_len=args.read_len)
