@@ -23,6 +23,7 @@
 extern "C" {
 void bqc_launch_cov_final(const StateLayout&, uint64_t*, const uint32_t* carry, const uint32_t* parity, const uint8_t* started, const uint8_t* sel, uint32_t count_start, hipStream_t);
 void bqc_launch_ref_nibbles(const uint8_t* dna5, uint64_t len, uint32_t* out, uint64_t n_dwords, hipStream_t);
+uint32_t bqc_long_slots_cap(uint32_t max_read_len, uint32_t n_cu);
 hipError_t bqc_long_init();
 hipError_t bqc_short_init();
 }
@@ -131,12 +132,14 @@ extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
         CCHK(hipMemcpy(c->d_fasta_index, c->fasta_index.data(), 4 * c->fasta_index.size(), hipMemcpyHostToDevice));
     }
     cstamp(7);
-    c->t8_slots_cap = std::max(1024u, 4u * c->n_cu);
+    // k_long's scratch: a slot per workgroup it can launch — n_cu, or one per KL_ROW cycles of the longest read accepted
+    c->kl_slots_cap = bqc_long_slots_cap(opt->max_read_len, c->n_cu);
+    c->t8_slots_cap = std::max(std::max(1024u, 4u * c->n_cu), c->kl_slots_cap);
     CCHK(hipMalloc(&c->d_t8rows, (size_t)c->t8_slots_cap * BQC_T8_SPW * 65536));
     CCHK(hipMalloc(&c->d_t8used, (size_t)c->t8_slots_cap * BQC_T8_USED * 4));
     cstamp(8);
-    CCHK(hipMalloc(&c->d_kl_cyc, (size_t)c->n_cu * 2 * 6 * 1024 * 4));
-    CCHK(hipMalloc(&c->d_kl_cyc_used, (size_t)c->n_cu * 4));
+    CCHK(hipMalloc(&c->d_kl_cyc, (size_t)c->kl_slots_cap * 2 * 6 * 1024 * 4));
+    CCHK(hipMalloc(&c->d_kl_cyc_used, (size_t)c->kl_slots_cap * 4));
     CCHK(hipMalloc(&c->d_carry, (size_t)opt->n_lanes * 2 * 2000 * 4));
     CCHK(hipMalloc(&c->d_parity, ((size_t)opt->n_lanes + 1) * 4));
     CCHK(hipMalloc(&c->d_started, opt->n_lanes));

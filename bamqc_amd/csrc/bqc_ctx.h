@@ -154,6 +154,7 @@ struct bqc_ctx {
     // per-cycle counter tiles of k_long's workgroups (48 KiB each; d_kl_cyc_used[wg] = written), summed by k_long_cyc_fold in the same launch
     uint32_t* d_kl_cyc = nullptr;
     uint32_t* d_kl_cyc_used = nullptr;
+    uint32_t kl_slots_cap = 0;  // workgroups d_kl_cyc / d_kl_cyc_used have room for (bqc_long_slots_cap)
     uint32_t t8_slots_used = 0, t8_slots_cap = 0;
     uint64_t t8_lanes[4] = {0, 0, 0, 0}; // read groups (bit per lane) of the batches whose rows are in the table
     std::vector<std::pair<void*, size_t>> pool; // device buffers of freed batches, reused by bqc_upload (hipMalloc / hipFree cost milliseconds)

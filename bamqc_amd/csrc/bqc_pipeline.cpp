@@ -21,8 +21,8 @@
 extern "C" {
 void bqc_launch_reads_chunks(const DevBatch&, const StateLayout&, uint64_t*, const DevRefs&, uint32_t*, uint32_t grid, uint32_t fast_table, hipStream_t);
 void bqc_launch_nm_extra(const DevBatch&, const StateLayout&, uint64_t*, const DevRefs&, uint32_t*, hipStream_t);
-void bqc_launch_long(const DevBatch&, const StateLayout&, uint64_t*, const DevRefs&, uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t* t8rows, uint32_t* t8_used, uint32_t t8_lane, uint32_t* cyc_tiles, uint32_t* cyc_used, hipStream_t);
-uint32_t bqc_long_slots(uint32_t max_len_ub, uint32_t n_chunks_ub, uint32_t n_cu);
+void bqc_launch_long(const DevBatch&, const StateLayout&, uint64_t*, const DevRefs&, uint32_t*, uint32_t*, uint32_t max_len_ub, uint32_t max_read_len, uint32_t, uint32_t, uint32_t* t8rows, uint32_t* t8_used, uint32_t t8_lane, uint32_t* cyc_tiles, uint32_t* cyc_used, uint32_t slot_cap, hipStream_t);
+uint32_t bqc_long_slots(uint32_t max_len_ub, uint32_t max_read_len, uint32_t n_chunks_ub, uint32_t n_cu);
 void bqc_launch_cov(const DevBatch&, const StateLayout&, uint64_t*, uint32_t* carry, uint32_t* parity, const uint8_t* lane_mask, uint8_t* started,
                     const uint8_t* started_after, uint32_t n_lanes, hipStream_t);
 void bqc_launch_add_words(uint64_t* state, const uint64_t* idx, const uint64_t* val, uint32_t n, hipStream_t);
@@ -531,12 +531,15 @@ static int enqueue_kernels(bqc_ctx* c, BatchMem& m)
         bqc_launch_reads_chunks(d, c->sl, c->d_state, refs, err, std::min(m.n_chunks_slow_ub, c->n_cu * 8), 0, c->stream);
         tick(c, "k_reads(generic)");
         HIPCHK(c, hipMemsetAsync(m.d_rsum, 0, 12ull * d.n_reads, c->stream));
-        const uint32_t slots = bqc_long_slots(m.max_len_slow, m.n_chunks_slow_ub, c->n_cu); // a slot of 8-mer scratch rows per workgroup, as for k_short
+        // a slot of 8-mer scratch rows and a per-cycle tile per workgroup (the grid stops at max_read_len: longer reads are refused)
+        const uint32_t slots = bqc_long_slots(m.max_len_slow, c->opt.max_read_len, m.n_chunks_slow_ub, c->n_cu);
+        if (slots > c->kl_slots_cap || slots > c->t8_slots_cap)
+            return bqc_fail(c, BQC_ERR_DEVICE, "internal error: k_long needs %u scratch slots, the context has %u / %u", slots, c->kl_slots_cap, c->t8_slots_cap);
         if (c->t8_slots_used + slots > c->t8_slots_cap) bqc_state_ready(c);
         for (int k = 0; k < 4; ++k) c->t8_lanes[k] |= m.lane_bits[k];
-        bqc_launch_long(d, c->sl, c->d_state, refs, err, m.d_rsum, m.max_len_slow, m.n_chunks_slow_ub, c->n_cu,
+        bqc_launch_long(d, c->sl, c->d_state, refs, err, m.d_rsum, m.max_len_slow, c->opt.max_read_len, m.n_chunks_slow_ub, c->n_cu,
                         c->d_t8rows + (size_t)c->t8_slots_used * BQC_T8_SPW * 16384u, c->d_t8used + (size_t)c->t8_slots_used * BQC_T8_USED, m.t8_lane, c->d_kl_cyc,
-                        c->d_kl_cyc_used, c->stream);
+                        c->d_kl_cyc_used, std::min(c->kl_slots_cap, c->t8_slots_cap - c->t8_slots_used), c->stream);
         c->t8_slots_used += slots;
         tick(c, "k_long");
     }

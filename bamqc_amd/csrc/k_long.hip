@@ -137,10 +137,14 @@ __device__ __forceinline__ void kl_lut_byte(uint32_t (&d)[4], const uint32_t* e)
 __global__ __launch_bounds__(KL_WAVES * 64) void k_long(DevBatch b, StateLayout sl, uint64_t* __restrict__ state, DevRefs refs,
                                                             uint32_t* __restrict__ err, uint32_t* __restrict__ rsum /* [n_reads][3] */,
                                                             uint4* __restrict__ t8rows, uint32_t* __restrict__ t8_used, uint32_t t8_lane,
-                                                            uint4* __restrict__ cyc_tiles, uint32_t* __restrict__ cyc_used)
+                                                            uint4* __restrict__ cyc_tiles, uint32_t* __restrict__ cyc_used, uint32_t slot_cap)
 {
     extern __shared__ uint32_t lds[];
     const uint32_t wg = blockIdx.y * gridDim.x + blockIdx.x; // this workgroup's slot of the scratch rows
+    if (wg >= slot_cap) { // the host sized the scratch for fewer workgroups than were launched: touch none of it
+        if (threadIdx.x == 0) atomicOr(err, BQC_DEVERR_INTERNAL);
+        return;
+    }
     if ((uint32_t)(uintptr_t)(lds_u32*)lds != 0u) { // the 8-mer atomics address LDS directly (KL_T8 at LDS address 0)
         if (threadIdx.x == 0) { atomicOr(err, BQC_DEVERR_INTERNAL); t8_used[wg * BQC_T8_USED] = 0; cyc_used[wg] = 0; }
         return;
@@ -598,13 +602,13 @@ __global__ __launch_bounds__(KL_WAVES * 64) void k_long(DevBatch b, StateLayout 
 
 // the per-cycle tiles of the workgroups of one row (blockIdx.y), summed and added to the read group's counters: thread per tile word
 __global__ __launch_bounds__(256) void k_long_cyc_fold(const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ used, uint32_t gx, StateLayout sl,
-                                                          uint64_t* __restrict__ state, uint32_t lane)
+                                                          uint64_t* __restrict__ state, uint32_t lane, uint32_t slot_cap)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y; // i < 2 * 6 * 1024
     uint64_t v = 0;
     for (uint32_t x = 0; x < gx; ++x) {
         const uint32_t wg = y * gx + x;
-        if (used[wg]) v += tiles[(size_t)wg * (2 * 6 * 1024) + i];
+        if (wg < slot_cap && used[wg]) v += tiles[(size_t)wg * (2 * 6 * 1024) + i];
     }
     if (!v) return;
     const uint32_t m = i / (6 * 1024), c = (i / 1024) % 6, jj = i % 1024, w = jj % 64, t = jj / 64;
@@ -643,35 +647,48 @@ extern "C" hipError_t bqc_long_init()
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_long), hipFuncAttributeMaxDynamicSharedMemorySize, KL_WORDS * 4);
 }
 
-static void kl_grid(uint32_t max_len_ub, uint32_t n_chunks_ub, uint32_t n_cu, uint32_t& gx, uint32_t& rows)
+// The grid: rows = ceil(longest read / KL_ROW) (at most max_read_len: a longer read is refused — k_prep flags it — and the rows
+// beyond the limit are not launched), gx = n_cu / rows workgroups per row, at least one.  A launch has gx * rows <=
+// max(n_cu, rows) workgroups; bqc_long_slots_cap is that bound for the longest read the context accepts.
+static void kl_grid(uint32_t max_len_ub, uint32_t max_read_len, uint32_t n_chunks_ub, uint32_t n_cu, uint32_t& gx, uint32_t& rows)
 {
-    rows = max_len_ub ? (max_len_ub + KL_ROW - 1) / KL_ROW : 1u;
+    const uint32_t len = max_len_ub < max_read_len ? max_len_ub : max_read_len;
+    rows = len ? (uint32_t)(((uint64_t)len + KL_ROW - 1) / KL_ROW) : 1u;
     gx = n_cu / rows ? n_cu / rows : 1u; // one workgroup per CU (119 KB of LDS each): gx * rows <= n_cu where possible
     if (gx > n_chunks_ub) gx = n_chunks_ub;
 }
 
-// workgroups (= slots of the 8-mer scratch rows) a launch with these bounds has
-extern "C" uint32_t bqc_long_slots(uint32_t max_len_ub, uint32_t n_chunks_ub, uint32_t n_cu)
+// workgroups (= slots of the 8-mer scratch rows, per-cycle tiles) a launch with these bounds has
+extern "C" uint32_t bqc_long_slots(uint32_t max_len_ub, uint32_t max_read_len, uint32_t n_chunks_ub, uint32_t n_cu)
 {
     if (n_chunks_ub == 0) return 0;
     uint32_t gx, rows;
-    kl_grid(max_len_ub, n_chunks_ub, n_cu, gx, rows);
+    kl_grid(max_len_ub, max_read_len, n_chunks_ub, n_cu, gx, rows);
     return gx * rows;
 }
 
+// the scratch slots a context with this read-length limit allocates for k_long: enough for any launch (bqc_long_slots)
+extern "C" uint32_t bqc_long_slots_cap(uint32_t max_read_len, uint32_t n_cu)
+{
+    const uint32_t rows = max_read_len ? (uint32_t)(((uint64_t)max_read_len + KL_ROW - 1) / KL_ROW) : 1u;
+    return rows > n_cu ? rows : n_cu;
+}
+
 // n_chunks_ub / max_len_ub: host-side upper bounds (the exact values are in the batch descriptor on the device); t8rows / t8_used:
-// bqc_long_slots() slots of the scratch table
+// bqc_long_slots() slots of the scratch table; slot_cap: slots of t8rows / t8_used / cyc_tiles / cyc_used that exist (a workgroup
+// beyond them reports BQC_DEVERR_INTERNAL instead of writing)
 extern "C" void bqc_launch_long(const DevBatch& b, const StateLayout& sl, uint64_t* state, const DevRefs& refs, uint32_t* err,
-                                uint32_t* rsum, uint32_t max_len_ub, uint32_t n_chunks_ub, uint32_t n_cu, uint32_t* t8rows, uint32_t* t8_used,
-                                uint32_t t8_lane, uint32_t* cyc_tiles /* [slots][2 * 6 * 1024] */, uint32_t* cyc_used, hipStream_t s)
+                                uint32_t* rsum, uint32_t max_len_ub, uint32_t max_read_len, uint32_t n_chunks_ub, uint32_t n_cu, uint32_t* t8rows,
+                                uint32_t* t8_used, uint32_t t8_lane, uint32_t* cyc_tiles /* [slots][2 * 6 * 1024] */, uint32_t* cyc_used,
+                                uint32_t slot_cap, hipStream_t s)
 {
     if (n_chunks_ub == 0) return;
     static const hipError_t attr_once = bqc_long_init(); // (at the first launch: see bqc_launch_short)
     (void)attr_once;
     uint32_t gx, rows;
-    kl_grid(max_len_ub, n_chunks_ub, n_cu, gx, rows);
-    hipLaunchKernelGGL(k_long, dim3(gx, rows), dim3(KL_WAVES * 64), KL_WORDS * 4, s, b, sl, state, refs, err, rsum, (uint4*)t8rows, t8_used, t8_lane, (uint4*)cyc_tiles, cyc_used);
-    hipLaunchKernelGGL(k_long_cyc_fold, dim3(2 * 6 * 1024 / 256, rows), dim3(256), 0, s, cyc_tiles, cyc_used, gx, sl, state, t8_lane);
+    kl_grid(max_len_ub, max_read_len, n_chunks_ub, n_cu, gx, rows);
+    hipLaunchKernelGGL(k_long, dim3(gx, rows), dim3(KL_WAVES * 64), KL_WORDS * 4, s, b, sl, state, refs, err, rsum, (uint4*)t8rows, t8_used, t8_lane, (uint4*)cyc_tiles, cyc_used, slot_cap);
+    hipLaunchKernelGGL(k_long_cyc_fold, dim3(2 * 6 * 1024 / 256, rows), dim3(256), 0, s, cyc_tiles, cyc_used, gx, sl, state, t8_lane, slot_cap);
     const uint32_t g2 = n_chunks_ub < n_cu * 8 ? n_chunks_ub : n_cu * 8;
     hipLaunchKernelGGL(k_long_finish, dim3(g2), dim3(256), 0, s, b, sl, state, rsum);
 }
