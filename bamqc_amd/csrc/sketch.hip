@@ -6,14 +6,17 @@
 // char), keeps the 128-bit cyclic-polynomial state of both strands in registers and emits
 // hash = h.lo ^ ht.lo for every window of k consecutive valid bases.  StreamCounter state is a
 // commutative monoid (StreamCounter::join :95-112), so per hash we do: sumCount (ballot), F2 table
-// (exact counts, privatised in LDS as u32, 32768 bins), and the level-w 4-bit saturating counter as
-// a u32 global counter that is only incremented while its value is < 15 (value = min(15, raw)).
-// Levels whose 524288 counters are all saturated are skipped entirely (the reference's M[w] early-out,
-// StreamCounter.hpp:81-83), which removes almost all global traffic on large inputs.
+// (exact counts, privatised in LDS as u32 while it has at most 32768 bins, else global u64 atomics),
+// and the level-w 4-bit saturating counter as a u32 global counter that is only incremented while its
+// value is < 15 (value = min(15, raw)).  Both tables are sized from the error rate e as the reference's
+// (F2size = 32768 and 524288 counters per level at the default e = 0.01).  Levels whose counters are all
+// saturated are skipped entirely (the reference's M[w] early-out, StreamCounter.hpp:81-83), which removes
+// almost all global traffic on large inputs.
 // Estimators F0 / f1 / F2 (doubles, log/pow) run on the host exactly as the reference's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 #include "kernels_common.h"
@@ -124,24 +127,29 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x3 __attribute__((aligned(1))) u32x3_u;
 typedef u32x4 __attribute__((aligned(1))) u32x4_u;
 
-#define SK_F2 32768
+#define SK_F2 32768                                 // largest F2 table kept in LDS (e >= ~0.0079); larger ones live in global memory only
 #define SK_PT (SK_F2 + 256 + 64 + 16)                 // pair tables behind the small tables (16-byte aligned)
 #define SK_PAIRS (2 * 17 * 16)                     // [2 strands][16 leaving nibbles + none][16 entering nibbles]
 #define SK_WORDS (SK_PT + 2 * SK_PAIRS * 4)          // two tables of 16-byte entries
 #define SK_THREADS 1024
+#define SK_MEM_MARGIN (1ull << 30)                 // device memory sketch_create leaves free beside the sketch tables
 
+// GF2 (global F2): the F2 table is larger than the LDS copy (F2size > SK_F2, e < ~0.0079): every F2 increment goes to the
+// global table, as those of a foreign lane's reads always do.  Chosen per launch, so the LDS form's hash loop is unchanged.
+template <bool GF2>
 __global__ __launch_bounds__(SK_THREADS) void k_sketch(DevBatch b, const DevSketch* __restrict__ dsk, const PairParams* __restrict__ pps,
                                                           const uint64_t* __restrict__ hv_all, const uint8_t* __restrict__ idx_tab,
                                                           uint32_t n_pairs, uint32_t per_block)
 {
     extern __shared__ uint32_t lds[];
-    uint32_t* f2 = lds;                                   // [SK_F2]
+    uint32_t* f2 = lds;                                   // [F2size] (of SK_F2 words; unused with GF2)
     uint64_t* hv = (uint64_t*)(lds + SK_F2);              // [2][32][2]: table, table rotated by k
     uint32_t* lm = lds + SK_F2 + 256;                     // [32] successful increments per level, [32] = sumCount
     uint8_t* ix = (uint8_t*)(lds + SK_F2 + 256 + 64);     // [2][16] nibble -> idx, [32] twin
     const uint32_t pair = blockIdx.y;
     const PairParams P = pps[pair];
-    for (uint32_t i = threadIdx.x; i < SK_F2; i += blockDim.x) f2[i] = 0;
+    const uint32_t f2n = GF2 ? 0u : P.f2_mask + 1u;       // words of the LDS copy
+    for (uint32_t i = threadIdx.x; i < f2n; i += blockDim.x) f2[i] = 0;
     for (uint32_t i = threadIdx.x; i < 128; i += blockDim.x) hv[i] = hv_all[pair * 128 + i];
     for (uint32_t i = threadIdx.x; i < 64; i += blockDim.x) lm[i] = 0;
     for (uint32_t i = threadIdx.x; i < 64; i += blockDim.x) ix[i] = idx_tab[i];
@@ -184,7 +192,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch(DevBatch b, const DevSket
         if (fl != blane) { // block-uniform: flush the privatised F2 / M counters of the previous lane
             if (blane != 0xFFFFFFFFu) {
                 const DevSketch D = dsk[blane * n_pairs + pair];
-                for (uint32_t i = threadIdx.x; i < SK_F2; i += blockDim.x) { const uint32_t v = f2[i]; if (v) { gadd(D.f2 + i, v); f2[i] = 0; } }
+                for (uint32_t i = threadIdx.x; i < f2n; i += blockDim.x) { const uint32_t v = f2[i]; if (v) { gadd(D.f2 + i, v); f2[i] = 0; } }
                 if (threadIdx.x < 33) { const uint32_t v = lm[threadIdx.x]; if (v) { gadd(D.misc + (threadIdx.x == 32 ? 0 : 1 + threadIdx.x), v); lm[threadIdx.x] = 0; } }
             }
             blane = fl;
@@ -329,7 +337,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch(DevBatch b, const DevSket
                         if ((Emit >> jj) & 1u) {
                             // ---- StreamCounter::operator()(hash), StreamCounter.hpp:68-93
                             const uint64_t hash = hl ^ tl;
-                            if (mine) atomicAdd(&f2[(uint32_t)hash & P.f2_mask], 1u);
+                            if (!GF2 && mine) atomicAdd(&f2[(uint32_t)hash & P.f2_mask], 1u);
                             else gadd(D.f2 + ((uint32_t)hash & P.f2_mask), 1);
                             // bitScanForward (lsb.cpp:26-29), clamped to the last of the 32 levels: the lowest set bit of the hash's low word,
                             // 31 when that word is zero (__ffs(0) - 1 wraps to 0xFFFFFFFF)
@@ -338,7 +346,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch(DevBatch b, const DevSket
                                 const uint32_t index = (uint32_t)(hash >> (w + 1u)) & P.ctr_mask;
                                 // fire and forget: the counter's value is min(15, raw); k_sketch_levels clamps the raw counts after every
                                 // batch and finds the levels in which every counter has reached 15
-                                gadd32(D.counters + ((w << P.ctr_shift) + index), 1u); // (32 levels x ctr_per_level counters: far below 2^32)
+                                gadd32(D.counters + ((w << P.ctr_shift) + index), 1u); // (32 x ctr_per_level <= 2^32: sketch_create)
                             }
                         }
                     }
@@ -351,7 +359,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch(DevBatch b, const DevSket
     if (blane != 0xFFFFFFFFu) {
         const DevSketch D = dsk[blane * n_pairs + pair];
         block_sync();
-        for (uint32_t i = threadIdx.x; i < SK_F2; i += blockDim.x) { const uint32_t v = f2[i]; if (v) gadd(D.f2 + i, v); }
+        for (uint32_t i = threadIdx.x; i < f2n; i += blockDim.x) { const uint32_t v = f2[i]; if (v) gadd(D.f2 + i, v); }
         if (threadIdx.x < 33) { const uint32_t v = lm[threadIdx.x]; if (v) gadd(D.misc + (threadIdx.x == 32 ? 0 : 1 + threadIdx.x), v); }
     }
 }
@@ -428,13 +436,20 @@ SketchDevice* sketch_create(const bqc_sketch_options& so, uint32_t n_lanes, hipS
     for (int k : sk->ks) if (k < 1 || k > 63) { err = "k must be in 1..63"; delete sk; return nullptr; }
     sk->n_lanes = n_lanes;
     sk->n_pairs = so.n_q * so.n_k;
-    // StreamCounter ctor, StreamCounter.hpp:25-46
-    size_t numcounts = (size_t)(48.0 / (so.e * so.e) + 1);
-    sk->f2size = round_up_pow2((size_t)(2.0 / (so.e * so.e) + 1));
+    // StreamCounter ctor, StreamCounter.hpp:25-46; at most 2^27 counters per level: k_sketch's counter index (w << ctr_shift) + index
+    // is 32-bit (checked on the double first: a tiny e would overflow the conversion)
+    const double n_counts = 48.0 / (so.e * so.e) + 1;
+    size_t numcounts = n_counts < 1e15 ? (size_t)n_counts : ~(size_t)0 >> 1;
     if (numcounts < 8192) numcounts = 8192;
+    if ((numcounts + 15) / 16 > ((size_t)1 << 23)) {
+        char m[256];
+        snprintf(m, sizeof m, "error rate %g is below the smallest supported (about 0.0006): the sketch would need more than 2^27 counters per level",
+                 so.e);
+        err = m; delete sk; return nullptr;
+    }
+    sk->f2size = round_up_pow2((size_t)(2.0 / (so.e * so.e) + 1));
     size_t size = round_up_pow2((numcounts + 15) / 16);
     sk->ctr_per_level = size * 16;
-    if (sk->f2size != SK_F2) { err = "only error rates with a 32768-entry F2 table (e.g. the default 0.01) are supported on the GPU"; delete sk; return nullptr; }
     // character tables
     std::vector<uint64_t> hv((size_t)sk->n_pairs * 128);
     // seed 0: RepHash::seed(0) takes (int)time(NULL) (RepHash.cpp:5-7; ReadQualityHasher.hpp:16-18 leaves the default-constructed,
@@ -470,6 +485,17 @@ SketchDevice* sketch_create(const bqc_sketch_options& so, uint32_t n_lanes, hipS
     const size_t per = sk->ctr_per_level * 32 * 4 + sk->f2size * 8 + 64 * 8;
     const size_t n = (size_t)n_lanes * sk->n_pairs;
     sk->arena_bytes = per * n + hv.size() * 8 + 64 + sizeof(DevSketch) * n + sizeof(PairParams) * sk->n_pairs + 4096;
+    { // refuse what does not fit, before allocating, with SK_MEM_MARGIN left for the rest of the context (batches, reader)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { err = "hipMemGetInfo failed"; delete sk; return nullptr; }
+        if (sk->arena_bytes + SK_MEM_MARGIN > free_b) {
+            char m[384];
+            snprintf(m, sizeof m, "error rate %g needs %zu bytes of sketch tables (%u read groups x %u (k, q) pairs x %zu bytes), "
+                     "the device has %zu bytes free (%zu kept for the rest of the context)", so.e, sk->arena_bytes, n_lanes, sk->n_pairs, per,
+                     free_b, (size_t)SK_MEM_MARGIN);
+            err = m; delete sk; return nullptr;
+        }
+    }
     if (hipMalloc(&sk->arena, sk->arena_bytes) != hipSuccess) { err = "hipMalloc failed for the sketch tables"; delete sk; return nullptr; }
     char* p = (char*)sk->arena;
     (void)hipMemsetAsync(sk->arena, 0, sk->arena_bytes, s);
@@ -491,8 +517,8 @@ SketchDevice* sketch_create(const bqc_sketch_options& so, uint32_t n_lanes, hipS
     ok = ok && hipMemcpy(sk->d_idx, idx, 64, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(sk->d_ds, sk->ds.data(), sizeof(DevSketch) * n, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(sk->d_pp, sk->pp.data(), sizeof(PairParams) * sk->n_pairs, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sketch), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   SK_WORDS * 4) == hipSuccess;
+    ok = ok && hipFuncSetAttribute(sk->f2size > SK_F2 ? reinterpret_cast<const void*>(&k_sketch<true>) : reinterpret_cast<const void*>(&k_sketch<false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, SK_WORDS * 4) == hipSuccess;
     if (!ok) { err = "sketch table upload failed"; sketch_destroy(sk); return nullptr; }
     return sk;
 }
@@ -517,8 +543,12 @@ void sketch_process(SketchDevice* sk, const DevBatch& b, hipStream_t s)
     uint32_t per = (b.n_reads + grid - 1) / grid;
     per = ((per + SK_THREADS - 1) / SK_THREADS) * SK_THREADS;
     grid = (b.n_reads + per - 1) / per;
-    hipLaunchKernelGGL(k_sketch, dim3(grid, sk->n_pairs), dim3(SK_THREADS), SK_WORDS * 4, s, b, sk->d_ds, sk->d_pp,
-                       (const uint64_t*)sk->d_hv, sk->d_idx, sk->n_pairs, per);
+    if (sk->f2size > SK_F2)
+        hipLaunchKernelGGL(k_sketch<true>, dim3(grid, sk->n_pairs), dim3(SK_THREADS), SK_WORDS * 4, s, b, sk->d_ds, sk->d_pp,
+                           (const uint64_t*)sk->d_hv, sk->d_idx, sk->n_pairs, per);
+    else
+        hipLaunchKernelGGL(k_sketch<false>, dim3(grid, sk->n_pairs), dim3(SK_THREADS), SK_WORDS * 4, s, b, sk->d_ds, sk->d_pp,
+                           (const uint64_t*)sk->d_hv, sk->d_idx, sk->n_pairs, per);
     const uint32_t n = sk->n_lanes * sk->n_pairs;
     hipLaunchKernelGGL(k_sketch_levels, dim3(n, 32, (uint32_t)((sk->ctr_per_level + SK_SLICE - 1) / SK_SLICE)), dim3(256), 0, s, sk->d_ds, sk->d_pp, sk->n_pairs);
     hipLaunchKernelGGL(k_sketch_levels_commit, dim3((n + 63) / 64), dim3(64), 0, s, sk->d_ds, sk->d_pp, sk->n_pairs, n);
