@@ -118,6 +118,7 @@ struct bqc_anchored {
     const CovEntry* d_cov = nullptr;  // the caller's device buffer with the anchors of the batch's reads
     uint32_t n = 0;
     bool completed = false;
+    bool released = false;            // on the engine's free list
     static const uint32_t kInline = 1u << 17;
 };
 struct AnchorEngine {
@@ -127,8 +128,10 @@ struct AnchorEngine {
     uint32_t* d_bound = nullptr;
     void* d_scratch = nullptr;
     size_t cap_n = 0;                 // reads the scratch buffers are sized for
-    std::mutex m;                     // the free list (handles come back from the submitting thread)
+    std::mutex m;                     // the free list and `outstanding` (handles come back from the submitting thread)
     std::vector<bqc_anchored*> free_list, all;
+    bqc_anchored* outstanding = nullptr; // enqueued, not yet completed or discarded: its summary and window table are in the scratch
+                                         // buffers, which are single: bqc_anchor_enqueue refuses another batch until then
     std::string err;
 };
 

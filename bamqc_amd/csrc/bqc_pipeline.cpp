@@ -802,6 +802,15 @@ extern "C" int bqc_submit_async(bqc_ctx* c, const bqc_batch* b, uint64_t* ticket
 // anchors made on the card (include/bamqc.h: bqc_anchor_*; anchor.h, k_anchor.hip)
 // ---------------------------------------------------------------------------------------------------
 static int anchor_fail(bqc_ctx* c, const char* what) { c->anchor.err = what; return -BQC_ERR_DEVICE; }
+// a handle back on the free list (E.m held)
+static void anchor_release_locked(AnchorEngine& E, bqc_anchored* a)
+{
+    if (E.outstanding == a) E.outstanding = nullptr;
+    if (a->released) return;
+    a->released = true;
+    E.free_list.push_back(a);
+}
+static void anchor_release(AnchorEngine& E, bqc_anchored* a) { std::lock_guard<std::mutex> lk(E.m); anchor_release_locked(E, a); }
 extern "C" const char* bqc_anchor_error(const bqc_ctx* c) { return c ? c->anchor.err.c_str() : ""; }
 
 extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, void* stream, bqc_anchored** out)
@@ -812,6 +821,10 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     // one read group, and the whole stream from its first batch on (a shard that starts inside the stream sets its first reads aside on
     // the card as the host's pass would: AnchorState::pending)
     if (c->opt.n_lanes != 1 || (c->shard.tail && c->shard.resolved) || E.mode.load() == 2) return 1;
+    {   // (one batch at a time: the scratch buffers hold the summary and window table of the one enqueued before until it is completed)
+        std::lock_guard<std::mutex> lk(E.m);
+        if (E.outstanding) { E.err = "bqc_anchor_enqueue: the batch enqueued before has not been completed or discarded"; return -BQC_ERR_STATE; }
+    }
     if (hipSetDevice(c->device) != hipSuccess) return anchor_fail(c, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = b->n_reads;
@@ -834,7 +847,7 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     bqc_anchored* a = nullptr;
     {
         std::lock_guard<std::mutex> lk(E.m);
-        if (!E.free_list.empty()) { a = E.free_list.back(); E.free_list.pop_back(); }
+        if (!E.free_list.empty()) { a = E.free_list.back(); E.free_list.pop_back(); a->released = false; }
     }
     if (!a) {
         a = new bqc_anchored();
@@ -864,13 +877,16 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     A.parts = (AnchorPart*)q;
     E.d_bound = A.first_of;
     const size_t n_first = std::min<size_t>(2 * n + 16, A.first_cap); // (windows a batch of n reads can reach)
-    if (hipMemsetAsync(A.first_of, 0xFF, 4 * n_first, st) != hipSuccess) { std::lock_guard<std::mutex> lk(E.m); E.free_list.push_back(a); return anchor_fail(c, "memset failed"); }
+    if (hipMemsetAsync(A.first_of, 0xFF, 4 * n_first, st) != hipSuccess) { anchor_release(E, a); return anchor_fail(c, "memset failed"); }
     bqc_launch_anchor(A, st);
     if (hipMemcpyAsync(a->h_sum, E.d_sum, sizeof(AnchorSummary), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(a->h_bound, A.first_of, sizeof(uint32_t) * std::min<size_t>(bqc_anchored::kInline, n_first), hipMemcpyDeviceToHost, st) != hipSuccess) {
-        std::lock_guard<std::mutex> lk(E.m);
-        E.free_list.push_back(a);
+        anchor_release(E, a);
         return anchor_fail(c, "copy failed");
+    }
+    {
+        std::lock_guard<std::mutex> lk(E.m);
+        E.outstanding = a;
     }
     E.mode = 1;
     *out = a;
@@ -881,13 +897,16 @@ extern "C" int bqc_anchor_complete(bqc_ctx* c, bqc_anchored* a, bqc_anchor_info*
 {
     if (!c || !a) return -BQC_ERR_ARG;
     AnchorEngine& E = c->anchor;
+    {   // (whatever the outcome, the scratch buffers are free for the next batch once this returns)
+        std::lock_guard<std::mutex> lk(E.m);
+        if (E.outstanding == a) E.outstanding = nullptr;
+    }
     const AnchorSummary& S = *a->h_sum;
     if (info) { info->n_noqual = S.n_noqual; info->rid_min = S.rid_min; info->rid_max = S.rid_max; }
     if (S.flags & AN_FLAG_BOUND_OVERFLOW) return anchor_fail(c, "internal error: boundary list overflow");
     if (S.flags & AN_FLAG_TOO_MANY_BREAKS) { // the card has left its state alone: this batch and what follows are the host's
         E.mode = 2;
-        std::lock_guard<std::mutex> lk(E.m);
-        E.free_list.push_back(a);
+        anchor_release(E, a);
         return 1;
     }
     if (S.n_cand > S.n_pending && (size_t)S.last_rel + 1 > bqc_anchored::kInline) { // (sparse data: the rest of the table, before the next batch's kernels reuse the buffer)
@@ -905,11 +924,13 @@ extern "C" int bqc_anchor_complete(bqc_ctx* c, bqc_anchored* a, bqc_anchor_info*
     return 0;
 }
 
+// a handle bqc_submit_anchored has not consumed: the card's window state has moved past its batch, which now goes through
+// bqc_submit* with host anchors, so the host keeps the state from here on
 extern "C" void bqc_anchor_discard(bqc_ctx* c, bqc_anchored* a)
 {
     if (!c || !a) return;
-    std::lock_guard<std::mutex> lk(c->anchor.m);
-    c->anchor.free_list.push_back(a);
+    c->anchor.mode = 2;
+    anchor_release(c->anchor, a);
 }
 
 extern "C" int bqc_submit_anchored(bqc_ctx* c, const bqc_batch* b, bqc_anchored* a, uint64_t* ticket)
@@ -917,7 +938,7 @@ extern "C" int bqc_submit_anchored(bqc_ctx* c, const bqc_batch* b, bqc_anchored*
     if (!c || !b || !a || !a->completed || a->n != b->n_reads) return bqc_fail(c, BQC_ERR_ARG, "bqc_submit_anchored: bad argument");
     if (b->n_nm_extra) return bqc_fail(c, BQC_ERR_ARG, "bqc_submit_anchored: further NM values belong to batches decoded on the host");
     const int rc = submit_impl(c, b, true, ticket, a);
-    bqc_anchor_discard(c, a);
+    anchor_release(c->anchor, a);
     return rc;
 }
 
@@ -925,7 +946,7 @@ void bqc_anchor_destroy(bqc_ctx* c)
 {
     AnchorEngine& E = c->anchor;
     for (bqc_anchored* a : E.all) { if (a->h_sum) (void)hipHostFree(a->h_sum); if (a->h_bound) (void)hipHostFree(a->h_bound); delete a; }
-    E.all.clear(); E.free_list.clear();
+    E.all.clear(); E.free_list.clear(); E.outstanding = nullptr;
     if (E.d_state) (void)hipFree(E.d_state);
     if (E.d_sum) (void)hipFree(E.d_sum);
     if (E.d_scratch) (void)hipFree(E.d_scratch);

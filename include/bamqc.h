@@ -238,8 +238,15 @@ int bqc_submit_async(bqc_ctx* ctx, const bqc_batch* batch, uint64_t* ticket);
  *                        untouched until bqc_batch_uploaded(ticket) says 1, which for such a batch means "its kernels are through";
  *                        at least 512 bytes of the same allocation must lie in front of and behind each of seq, qual and cigar (the
  *                        kernels' vector loads run over the ends).
+ *   bqc_anchor_discard   returns a handle that bqc_submit_anchored will not consume (the caller's decode of the batch failed, or
+ *                        bqc_anchor_complete said < 0).  The card's window state has already moved past that batch, so anchoring
+ *                        ends with it: the next bqc_anchor_enqueue returns 1, and this batch and every later one go through
+ *                        bqc_submit* with host columns.  After bqc_anchor_complete said 1 the handle is released already.
  * Batches must be anchored in stream order and submitted in the same order; the anchor calls may be made by another thread than the
- * submit calls (the program's decode thread and its submitting thread). */
+ * submit calls (the program's decode thread and its submitting thread).  One handle at a time: while a handle is enqueued and
+ * neither completed nor discarded, bqc_anchor_enqueue refuses the next batch with -BQC_ERR_STATE and leaves the card's state as it
+ * is (the anchor kernels' scratch and summary buffers are single; completing k before enqueueing k+1 is what keeps k's window table).
+ * Completed handles waiting for bqc_submit_anchored do not count: any number of those may be held. */
 typedef struct bqc_anchored bqc_anchored;
 typedef struct bqc_anchor_info {
     uint32_t n_noqual;        /* primary first / last records without qualities (check_read_len's message, QualityCheck.hpp:70-79) */
