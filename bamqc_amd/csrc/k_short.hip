@@ -71,6 +71,15 @@ __device__ __forceinline__ bool t8_flush(uint32_t* lds, uint64_t* __restrict__ e
     return false;
 }
 
+// LDS layout of the triplet bins.  The bank of a dword is its index mod 32, and KS_TRIP and the 256-word group tables are
+// multiples of 32, so the bank of bin c(j-1) r(j) c(j) r(j+1) would be its low 5 bits: r(j) bit 0, c(j), r(j+1).  A counted
+// position nearly always has r(j) = c(j), and its 64 likely bins would fall on 16 banks.  Stored instead at index
+// ix ^ ((ix >> 2) & 0x11): r(j) bit 0 ^= c(j-1) bit 0 and r(j+1) bit 0 ^= c(j) bit 0, which puts those 64 bins on all 32 banks,
+// two per bank.  The map is its own inverse; k_short applies it to the whole [r c] stream at once (ks_trip_stream).
+__device__ __forceinline__ uint32_t ks_trip_bin(uint32_t ix) { return ix ^ ((ix >> 2) & 0x11u); }
+// The same on a funnel-shifted stream whose bins start at bit offsets 4k: every bit 4k takes the XOR of bit 4k + 2.
+__device__ __forceinline__ uint32_t ks_trip_stream(uint32_t s) { return s ^ ((s >> 2) & 0x11111111u); }
+
 __device__ __forceinline__ bool ks_flush(uint32_t* lds, const StateLayout& sl, uint64_t* __restrict__ state, uint32_t lane, uint4* __restrict__ slot, uint32_t n_rows_used)
 {
     const uint64_t lb = sl.lane_base(lane);
@@ -79,7 +88,8 @@ __device__ __forceinline__ bool ks_flush(uint32_t* lds, const StateLayout& sl, u
         const uint32_t v = lds[KS_TRIP + i];
         if (!v) continue;
         lds[KS_TRIP + i] = 0;
-        const uint32_t grp = i >> 8, f3 = (i >> 6) & 3u, f2 = (i >> 4) & 3u, f1 = (i >> 2) & 3u, f0 = i & 3u;
+        const uint32_t ix = ks_trip_bin(i); // (the layout is its own inverse)
+        const uint32_t grp = i >> 8, f3 = (ix >> 6) & 3u, f2 = (ix >> 4) & 3u, f1 = (ix >> 2) & 3u, f0 = ix & 3u;
         uint32_t ctx, base;
         if (grp < 2u) { ctx = (f3 << 4) | (f2 << 2) | f0; base = f1; }                               // forward: as is
         else { ctx = ((3u - f0) << 4) | ((3u - f2) << 2) | (3u - f3); base = 3u - f1; }                // reverse: complement, mirrored
@@ -199,6 +209,8 @@ __device__ __forceinline__ void lut_byte(uint32_t (&d)[KS_ND], const uint32_t* e
     for (int q = 0; q < KS_ND / 4; ++q) { const uint4 v = *(const uint4*)(e + 4 * q); d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w; }
 }
 
+template <bool S> struct KsTile { static constexpr bool seg = S; }; // kind of a wave's tile (reads / triplet segments), as a type
+
 // raw data of the NEXT group, in flight while the current one is computed: KS_NH + 1 dwords of packed bases (the window may start
 // up to two nibbles into them), KS_ND dwords of qualities, KS_NH + 1 dwords of reference nibbles
 struct Pre { uint32_t s[KS_NH + 1], q[KS_ND], e[KS_NH + 1]; uint32_t m0, pp, w5; };
@@ -234,7 +246,9 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
     for (uint32_t i = threadIdx.x; i < KS_WORDS; i += blockDim.x) lds[i] = 0;
     block_sync();
     const uint32_t M = 0x11111111u;
-    const uint32_t ln = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // (wave index through readfirstlane: the compiler does not know threadIdx.x >> 6 to be wave-uniform, and would compile the tile
+    // and group loops, whose trip counts derive from it, with divergent exits that copy every loop-carried register per iteration)
+    const uint32_t ln = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const BatchDesc desc = *b.desc; // written by the batch's k_build_plan
     const uint32_t W = desc.fast_w, rpw = 64u / W;
     const uint32_t slot = ln / W, w = ln % W, wnb = KS_NB * w;
@@ -405,11 +419,15 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
         // per-read statistics of the tile's reads, while the first group's data is on its way
         if ((parts & 8u) && __ballot(stat)) read_stats(b, sl, state, refs, err, lds + KS_RS, stat ? r : 0u, stat, stat);
         __builtin_amdgcn_s_setprio(0);
+        // A tile holds reads or triplet segments, never both (padding entries only fill the last group of the chunk's segment
+        // part, behind at least one segment), so the group loop is compiled once per kind: read tiles always update the per-cycle
+        // registers, segment tiles never touch them, and no group decides that again at run time.
+        auto groups = [&](auto tile_kind) __attribute__((always_inline)) {
+        constexpr bool SEG = decltype(tile_kind)::seg; // a tile of triplet segments: triplets only
         for (uint32_t g = 0; g < n_groups; ++g) {
             const uint32_t k = g * rpw + slot; // this lane's record (lanes behind the last slot: unused)
             const uint32_t m0 = cur.m0, w5 = cur.w5, L = (m0 >> 20) & 0xFFu; // L = 0 unless the record reaches get_count
             const bool rc = m0 & 0x10u;
-            const bool segg = (uint32_t)__builtin_amdgcn_readfirstlane((int)m0) & KM_SEG; // a group of triplet segments: triplets only
             const uint32_t nv = (uint32_t)min(max((int32_t)L - (int32_t)wnb, 0), KS_NB);   // valid cycles of this lane
             const uint32_t nvq = (m0 & BQC_FLAG_NO_QUAL) ? 0u : nv;
             uint32_t xm[KS_NH], qm[KS_ND];
@@ -461,7 +479,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
 #pragma unroll
             for (int h = 0; h < KS_NH; ++h) P[h] = planes_of(X[h]);
             // ---- per-cycle counters (this lane's mate is fixed: one register set)
-            if ((parts & 1u) && !segg) {
+            if ((parts & 1u) && !SEG) {
                 cyc_add(A, P, Q);
                 if (++n1 == 15u) { if (lane_used) cyc_spill(A, lds, mate, w); n1 = 0; }
                 if (++n2 == 255u) { if (lane_used) cyc_qflush(A, lds, mate, w); n2 = 0; }
@@ -499,7 +517,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
                 nb[h] = P[h].n | (~xm[h] & M); // literal N or past the end of the read: blocks 8-mer windows and triplet flanks
             }
             // ---- 8-mers: windows starting at the lane's cycles
-            if ((parts & 2u) && !segg) {
+            if ((parts & 2u) && !SEG) {
                 uint32_t S[KS_NH / 2 + 1]; // 2-bit codes of 16 cycles per register, first cycle in the top two bits; then the next lane's
 #pragma unroll
                 for (int j = 0; j < KS_NH / 2; ++j) S[j] = vperm(squeeze2(cn[2 * j]), squeeze2(cn[2 * j + 1]), 0x05040100u);
@@ -586,17 +604,20 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
                     uint32_t* tbin = lds + KS_TRIP + ((rc ? 2u : 0u) + ((m0 & 0x40u) ? 0u : 1u)) * 256u; // fwd1st fwd2nd rev1st rev2nd
 #pragma unroll
                     for (int h = 0; h < KS_NH; ++h) {
-                        if (!ok[h]) continue;
-                        const uint32_t SA = alignbit(I[h], I[h + 1], 6), SB = alignbit(I[h + 1], I[h + 2], 22);
+                        if (!ok[h]) continue; // (lanes without a counted position in this half skip all 8 atomics)
+                        // (after the flank tests above, which read the plain stream)
+                        const uint32_t SA = ks_trip_stream(alignbit(I[h], I[h + 1], 6)), SB = ks_trip_stream(alignbit(I[h + 1], I[h + 2], 22));
 #pragma unroll
-                        for (int t = 0; t < 8; ++t) { // bin = c(j-1) r(j) c(j) r(j+1): 8 contiguous bits of the [r c] stream
+                        for (int t = 0; t < 8; ++t) { // bin = c(j-1) r(j) c(j) r(j+1): 8 contiguous bits of the [r c] stream (ks_trip_bin layout)
                             const uint32_t ix = t < 6 ? bfe(SA, 20 - 4 * t, 8) : bfe(SB, 12 - 4 * (t - 6), 8);
-                            if (ok[h] & (1u << (28 - 4 * t))) atomicAdd(tbin + ix, 1u);
+                            atomicAdd(tbin + ix, bfe(ok[h], 28 - 4 * t, 1)); // branch-free: a position that does not count adds 0
                         }
                     }
                 }
             }
         }
+        };
+        if (seg_tile) groups(KsTile<true>{}); else groups(KsTile<false>{});
         asm volatile("" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         // ---- phase C: lane per read — per-read histograms from the sums left in the records (QualityCheck.hpp:157-165)

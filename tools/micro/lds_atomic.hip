@@ -6,6 +6,9 @@
 //             2 random dwords in 1 KB (the triplet bins)                   3 random among 64 dwords of 1 KB (bins used in practice)
 //             4 all lanes one address                                       5 random dwords in 64 KB, bank = lane (no bank conflict, distinct addresses)
 //             6 random in 64 KB, 31 of 64 lanes active                      7 random in 64 KB, 8 of 64 lanes active
+//             8 / 9 k_short's triplet bins, old / new layout: 6 reads x 10 lanes (4 lanes idle), each read's table (fwd1st fwd2nd
+//               rev1st rev2nd, 256 dwords each) drawn per read and slot, every lane a random hot bin c(j-1) r(j) c(j) r(j+1) with
+//               r(j) = c(j); 8 stores bin ix at ix, 9 at ix ^ ((ix >> 2) & 0x11) (k_short.hip, ks_trip_bin)
 //   build: hipcc --offload-arch=gfx950 -O3 -o lds_atomic lds_atomic.hip      run: ./lds_atomic
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -27,7 +30,7 @@ template <int PAT, bool RTN> __global__ __launch_bounds__(1024) void k_atom(unsi
     __syncthreads();
     const unsigned lane = threadIdx.x & 63u;
     unsigned acc = 0;
-    const bool active = PAT == 6 ? (lane & 1u) != 0u && lane < 63u : PAT == 7 ? (lane & 7u) == 0u : true;
+    const bool active = PAT == 6 ? (lane & 1u) != 0u && lane < 63u : PAT == 7 ? (lane & 7u) == 0u : PAT >= 8 ? lane < 60u : true;
     // the addresses of round 0; every round moves them by a lane-dependent step that keeps the pattern (two VALU instructions per atomic)
     unsigned a[16], step[16];
 #pragma unroll
@@ -38,9 +41,16 @@ template <int PAT, bool RTN> __global__ __launch_bounds__(1024) void k_atom(unsi
         else if (PAT == 2) { a[s] = r & 255u; step[s] = q & 255u; }
         else if (PAT == 3) { a[s] = (r & 63u) * 4u; step[s] = (q & 63u) * 4u; }
         else if (PAT == 4) { a[s] = (unsigned)s * 64u; step[s] = 1u; }
+        else if (PAT >= 8) { // the same addresses every round: the bank pattern of one instruction is what is measured
+            const unsigned grp = mix(seed + (threadIdx.x >> 6) * 131u + (lane / 10u) * 17u + (unsigned)s * 1009u + blockIdx.x * 7919u) & 3u;
+            const unsigned c1 = r & 3u, c0 = (r >> 2) & 3u, r1 = (r >> 4) & 3u;
+            unsigned ix = (c1 << 6) | (c0 << 4) | (c0 << 2) | r1;
+            if (PAT == 9) ix ^= (ix >> 2) & 0x11u;
+            a[s] = grp * 256u + ix; step[s] = 0u; // (KS_TRIP, where k_short has them, is a multiple of 32 words too)
+        }
         else { a[s] = ((r & 511u) * 32u + (lane & 31u)) & 16383u; step[s] = (q & 511u) * 32u; }
     }
-    const unsigned amask = PAT == 2 || PAT == 3 ? 255u : 16383u;
+    const unsigned amask = PAT == 2 || PAT == 3 ? 255u : PAT >= 8 ? 0xFFFFFFFFu : 16383u;
     const unsigned long long t0 = __builtin_readcyclecounter();
     for (int it = 0; it < ITER; ++it) {
         if (active) {
@@ -121,6 +131,7 @@ int main()
         ONE(3, false, "random among 64 dwords") ONE(4, false, "all lanes one address")
         ONE(5, false, "random in 64 KB, bank = lane") ONE(5, true, "random in 64 KB, bank = lane")
         ONE(6, false, "random in 64 KB, 31 lanes") ONE(7, false, "random in 64 KB, 8 lanes")
+        ONE(8, false, "triplet bins, 6 reads x 10 lanes, old layout") ONE(9, false, "triplet bins, 6 reads x 10 lanes, new layout")
         printf("W=%2d address arithmetic alone: %.1f ticks per round of 16\n", waves, base / ITER);
     }
     return 0;
