@@ -7,6 +7,9 @@ Each rank owns its own batch (records shard by read batch: weak scaling, no data
 at the end of the job the flat uint64 state vectors are summed onto rank 0 with one RCCL reduce.
 Prints ONE JSON line on rank 0 (`ms_per_step`: wall milliseconds of one timed step).  `--dump-outputs DIR` also writes the counts the
 timed steps left as .npy files, so that two builds can be compared on the same seeded inputs.
+A plain run does only what that line's headline figure needs: set-up, warm-up, the timed steps, the dump if asked for, the line.
+`--full` adds the legs that take runs of their own: the CPU oracle baseline, the extra device timings, the BAM-file legs through
+bin/bamqualcheck and config 3's recorded figure (`--no-cpu`, `--no-extra`, `--no-e2e`, `--no-large` leave single legs out of it).
 """
 import argparse
 import json
@@ -32,18 +35,24 @@ def main():
     ap.add_argument("--reads", type=int, default=None, help="reads per GPU per step (default: 10 M for config2, 100 k for config5)")
     ap.add_argument("--read-len", type=int, default=None)
     ap.add_argument("--sketch", action="store_true", help="steps include the k-mer sketch of the program's default options (-k 32 -q 17)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline's timed steps: cpu_baseline (the CPU oracle, which also checks the GPU result on a prefix), "
+                         "extra device timings, the BAM-file legs through bin/bamqualcheck (e2e, e2e_large, e2e_shard_proxy; e2e_sharded at --gpus N > 1) "
+                         "and e2e_config3 (config 3's recorded figure); the --no-* options below leave single legs out of it")
     ap.add_argument("--cpu-sample", type=int, default=3_000_000, help="reads timed on the CPU oracle (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the BAM file -> bin/bamqualcheck -> .bamqc leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra device timings (default options with sketch; long reads)")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the CPU oracle baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) skip the BAM file -> bin/bamqualcheck -> .bamqc legs")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the extra device timings (default options with sketch; long reads)")
     ap.add_argument("--e2e-prefix", type=int, default=1_000_000, help="reads of the e2e input checked against the oracle")
-    ap.add_argument("--no-large", action="store_true", help="skip e2e_large (100 M reads over 24 GRCh38-length contigs as a 10 GB file) and e2e_shard_proxy (one worker's eighth of config 3)")
+    ap.add_argument("--no-large", action="store_true", help="(--full) skip e2e_large (100 M reads over 24 GRCh38-length contigs as a 10 GB file) and e2e_shard_proxy (one worker's eighth of config 3)")
     ap.add_argument("--large-reads", type=int, default=100_000_000)
     ap.add_argument("--only-large", action="store_true", help="(development) only e2e_large and e2e_shard_proxy, printed as one JSON object")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the counts they left (what Aggregator.finalize returns to a caller of the timed path) "
                          "as DIR/lane<i>.<name>.npy in float64; the inputs are seeded, so two builds can be compared array for array")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line, nothing besides
+        args.no_cpu = args.no_e2e = args.no_extra = args.no_large = True
     if args.workload == "config3":
         return config3_line(args)
     if args.only_large:
@@ -186,7 +195,7 @@ def main():
         out = {
             "metric": "BAM records/sec (and GB/s vs HBM roofline), 150 bp PE, 1/2/4/8 MI355X",
             "value": value, "unit": "reads/s",
-            "value_kind": "device-resident kernel step (inputs in HBM when the clock starts: the contract's `value`); BAM-file throughput of the program is e2e.reads_per_s",
+            "value_kind": "device-resident kernel step (inputs in HBM when the clock starts: the contract's `value`); BAM-file throughput of the program is e2e.reads_per_s (--full)",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8/u32/u64 integer", "data": "synthetic",
@@ -210,16 +219,17 @@ def main():
         del cols
         if world == 1 and not args.no_extra and not long_reads and not args.sketch:
             out["extra"] = extra_timings(refs)
-        try:  # the headline WGS configuration as a FILE: measured by tools/run_config_file.py under gpurun (generating its 54 GB input takes 3 minutes;
-            # `--workload config3` measures it live), copied here with its source named
-            c3name = next(f for f in ("r4_config3_file.json", "r3_config3_file.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
-            c3 = json.load(open(os.path.join(ROOT, "profiles", c3name)))
-            out["e2e_config3"] = {"source": "profiles/%s (tools/run_config_file.py --config 3; not re-measured in this run)" % c3name, "reads": c3["reads"],
-                                  "bam_GB": c3["bam_bytes"] / 1e9, "wall_s": c3["program_wall_s"], "reads_per_s": c3["reads_per_s"], "compressed_GB_per_s": c3["compressed_GB_per_s"],
-                                  "reader": c3["reader"], "which": c3["which"], "host_reader_reads_per_s": c3["host_reader"]["reads_per_s"],
-                                  "prefix_matches_oracle": c3.get("prefix_matches_oracle")}
-        except Exception:
-            pass
+        if args.full:
+            try:  # the headline WGS configuration as a FILE: measured by tools/run_config_file.py (generating its 54 GB input takes 3 minutes;
+                # `--workload config3` measures it live), copied here with its source named
+                c3name = next(f for f in ("r4_config3_file.json", "r3_config3_file.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
+                c3 = json.load(open(os.path.join(ROOT, "profiles", c3name)))
+                out["e2e_config3"] = {"source": "profiles/%s (tools/run_config_file.py --config 3; not re-measured in this run)" % c3name, "reads": c3["reads"],
+                                      "bam_GB": c3["bam_bytes"] / 1e9, "wall_s": c3["program_wall_s"], "reads_per_s": c3["reads_per_s"], "compressed_GB_per_s": c3["compressed_GB_per_s"],
+                                      "reader": c3["reader"], "which": c3["which"], "host_reader_reads_per_s": c3["host_reader"]["reads_per_s"],
+                                      "prefix_matches_oracle": c3.get("prefix_matches_oracle")}
+            except Exception:
+                pass
         if e2e_big:
             out.update(e2e_big)
             px, c3 = e2e_big.get("e2e_shard_proxy"), out.get("e2e_config3")
