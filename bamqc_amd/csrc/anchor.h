@@ -22,7 +22,8 @@ struct AnchorState {
     uint32_t prev_bp;
 };
 
-// what the host needs from a batch besides the anchors themselves
+// what the host needs from a batch besides the anchors themselves (a context with several read groups: the per-read-group part is the
+// AnchorLane[n_lanes] array behind it in the same buffer, and `before`, `after`, `last_rel`, `n_pending`, `first_certain` are unused)
 struct AnchorSummary {
     uint32_t n_cand;        // reads that enter coverage()
     uint32_t n_breaks;      // candidates that are not < 1000 positions behind the candidate before them on the same chromosome
@@ -35,8 +36,19 @@ struct AnchorSummary {
     int32_t rid_min, rid_max; // range of the reference ids in [0, n_refs) the batch holds (rid_min > rid_max: none)
     uint32_t n_pending;     // candidates set aside (the first n_pending of the batch's candidates: a shard_tail context)
     uint32_t first_certain; // candidate index of the first read that resets whatever the state (0xFFFFFFFF: none; only looked for while setting aside)
+    uint32_t n_bad;         // several read groups: reads whose lane is >= n_lanes (they end the run on the card: k_prep's check 2)
+    uint32_t pad;
     unsigned long long seq_bytes, qual_bytes, cigar_words; // payload sizes: sums of ceil(l_seq / 2), l_seq, n_cigar
     AnchorState before, after;
+};
+// one read group of a context with several (k_an_chain<true>): its window state, its reads, where its candidates and its first_of segment lie
+struct AnchorLane {
+    AnchorState before, after;
+    uint32_t n_cand, n_reads; // candidates / all reads of the read group in the batch
+    uint32_t cand_off;        // its first candidate in the compaction (the candidates grouped by read group, stream order inside a group)
+    uint32_t first_off;       // its segment of first_of: last_rel + 1 entries (none when n_cand == 0), the groups' back to back
+    uint32_t last_rel;        // window (relative to before.win) of its last candidate
+    uint32_t pad;
 };
 #define AN_FLAG_TOO_MANY_BREAKS 1u // not anchored: the state is untouched, the caller takes the host's recurrence for this batch
 #define AN_FLAG_BOUND_OVERFLOW  2u // never expected (the list is sized for every candidate)
@@ -55,7 +67,9 @@ struct AnchorRun {
 };
 
 // breaks a batch may hold for the card's chain (ONE thread walks them, ~0.2 us each: 3 ms at this limit, what the host's pass over a
-// million reads takes); a batch with more — sparse data: every other read is a break — is left to the host
+// million reads takes); a batch with more — sparse data: every other read is a break — is left to the host.  With several read groups
+// the limit is over the whole batch, not per group: the breaks of all groups share bj[] / runs[], and the groups' walks run side by
+// side, so that no walk is longer than the one-group walk at this limit
 #define AN_MAX_BREAKS 16384u
 
 struct AnchorPart { // what a workgroup of k_an_count (1024 reads) knows; summed by k_an_scan
@@ -66,22 +80,32 @@ struct AnchorPart { // what a workgroup of k_an_count (1024 reads) knows; summed
 
 struct AnchorArgs {
     uint32_t n, n_refs, n_lanes, no_fast;
+    uint32_t lane_bits;         // several read groups: ballots that tell the read groups apart (ceil(log2(n_lanes)))
     const uint16_t* flag; const uint8_t* lane; const int32_t* rid; const int32_t* pos; const uint32_t* l_seq; const uint16_t* n_cigar;
     const uint8_t* main_chrom;
     CovEntry* cov_out;          // [n]
     AnchorState* state;         // the read group's state: read by the chain, replaced when the batch is anchored
     AnchorSummary* sum;
+    AnchorLane* lanes;          // several read groups: [n_lanes] (state is then [n_lanes] too)
     // first_of[rel] = the first read (index in the batch) whose window is `rel`, written by the candidate whose window differs from its
     // predecessor's (windows only grow along the candidates, by one per slide and two per reset: rel <= 2 n_cand + 2); preset to AN_NO_READ.
     // (Round 4, first version: a list appended to with an atomic counter — ~5 000 returning atomics on ONE word per million reads,
     // 60 of k_an_apply's 83 us.)
+    // Several read groups: one such table per read group present, at lanes[l].first_off; indices stay stream-order read indices.
     uint32_t* first_of; uint32_t first_cap;
     // scratch
-    uint32_t* cpos; int32_t* crid; uint32_t* cidx; uint32_t* crun; // [n] candidates in stream order
+    uint32_t* cpos; int32_t* crid; uint32_t* cidx; uint32_t* crun; // [n] candidates in stream order (several read groups: grouped by read group)
+    uint8_t* clane;             // [n] several read groups: the candidate's read group
     uint32_t* bj;               // [AN_MAX_BREAKS] candidate index of every break
     AnchorRun* runs;            // [AN_MAX_BREAKS]
     uint32_t* blk_a; uint32_t* blk_b; // [n / 1024 + 2] block counts / offsets of the two compactions
     AnchorPart* parts;          // [n / 1024 + 2]
+    uint32_t* blk_c;            // several read groups: [n_lanes][n / 1024 + 2] candidates per read group and workgroup (scanned in place)
+    uint32_t* blk_r;            // ... [n_lanes + 1][n / 1024 + 2] reads per workgroup and bin (bin 0: lane >= n_lanes, bin l + 1: read group l)
 };
 
 extern "C" void bqc_launch_anchor(const AnchorArgs& a, hipStream_t s);
+// the processing order of a batch with several read groups, on the card: reads with a lane >= n_lanes first, then read group 0, 1, ...,
+// stream order inside each (bqc_pipeline.cpp: host_pass builds the same permutation on the host); tmp: lane_order_tmp_words() words
+extern "C" void bqc_launch_lane_order(const uint8_t* lane, uint32_t n, uint32_t n_lanes, uint32_t* order, uint32_t* tmp, hipStream_t s);
+static inline size_t lane_order_tmp_words(uint32_t n, uint32_t n_lanes) { return ((size_t)n + 1023) / 1024 * ((size_t)n_lanes + 1) + 64; }

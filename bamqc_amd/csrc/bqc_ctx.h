@@ -59,6 +59,7 @@ struct BatchMem {
     uint64_t* d_add_val = nullptr;
     uint32_t n_add = 0;
     uint32_t* d_rsum = nullptr;          // [n_reads][3] per-read sums of the long-read kernel
+    uint32_t* d_order_tmp = nullptr;     // an anchored batch with several read groups: scratch of bqc_launch_lane_order (its order is made on the card)
     ErrRec* d_err = nullptr;
     uint64_t algo_bytes = 0;
     uint32_t n_slow = 0, max_len_slow = 0, n_chunks_slow_ub = 0, t8_lane = 0;
@@ -111,6 +112,7 @@ struct Slot { // one batch in flight through bqc_submit / bqc_submit_async
 // bqc_anchor_complete run in the thread that decodes the batches, bqc_submit_anchored in the one that submits them.
 struct bqc_anchored {
     AnchorSummary* h_sum = nullptr;   // page-locked: the batch's summary ...
+    AnchorLane* h_lanes = nullptr;    // ... with several read groups, its per-group part behind it (n_lanes entries) ...
     uint32_t* h_bound = nullptr;      // ... and the first kInline entries of first_of[] (anchor.h)
     std::vector<uint32_t> rest;       // the entries behind them (sparse data), fetched by bqc_anchor_complete
     std::vector<int32_t> pend_rid;    // a shard_tail context: the reads set aside (the batch's first n_pending candidates) ...
@@ -123,8 +125,8 @@ struct bqc_anchored {
 };
 struct AnchorEngine {
     std::atomic<int> mode{0};         // 0: not used yet, 1: the card keeps the state, 2: off for the rest of the stream (the host keeps it)
-    AnchorState* d_state = nullptr;
-    AnchorSummary* d_sum = nullptr;
+    AnchorState* d_state = nullptr;   // [n_lanes] one window state per read group
+    AnchorSummary* d_sum = nullptr;   // the summary, and with several read groups AnchorLane[n_lanes] behind it
     uint32_t* d_bound = nullptr;
     void* d_scratch = nullptr;
     size_t cap_n = 0;                 // reads the scratch buffers are sized for

@@ -146,6 +146,43 @@ struct CovPlanner {
 // ---------------------------------------------------------------------------------------------------
 // host pass: sizes, read groups, coverage anchors
 // ---------------------------------------------------------------------------------------------------
+// From H.lane_count (reads per read group): the read group with the most reads, whether the batch is mixed, and its stretches and
+// super-windows in processing order — reads whose lane is out of range first, then read group 0, 1, ... (the permutation itself,
+// H.order, is host_pass's, or for an anchored batch the card's: bqc_launch_lane_order).  Returns the number of reads out of range.
+static uint64_t plan_read_groups(HostPass& H, uint32_t n, uint32_t nl)
+{
+    uint32_t lanes_present = 0;
+    H.t8_lane = 0;
+    for (uint32_t l = 0; l < nl; ++l) {
+        if (H.lane_count[l]) ++lanes_present;
+        if (H.lane_count[l] > H.lane_count[H.t8_lane]) H.t8_lane = l;
+    }
+    uint64_t in_lanes = 0;
+    for (uint32_t l = 0; l < nl; ++l) in_lanes += H.lane_count[l];
+    // (a read whose lane is out of range ends the run on the device — check 2 — and the batch then contributes nothing; such
+    // reads still need a place in the decomposition: they go in front of read group 0)
+    const uint64_t n_bad = n - in_lanes;
+    H.multi_lane = lanes_present > 1 || (n_bad > 0 && in_lanes > 0);
+    H.stretches.clear(); H.sws.clear();
+    auto add_stretch = [&](uint32_t lane, uint32_t begin, uint32_t count) {
+        if (!count) return;
+        Stretch S{lane, (uint32_t)H.sws.size(), 0, 0};
+        for (uint32_t p = 0; p < count; p += BQC_SW_READS)
+            H.sws.push_back(SuperWindow{lane, begin + p, std::min<uint32_t>(BQC_SW_READS, count - p), (uint32_t)H.stretches.size()});
+        S.sw_end = (uint32_t)H.sws.size();
+        H.stretches.push_back(S);
+    };
+    if (!H.multi_lane) {
+        uint32_t lane = 0;
+        for (uint32_t l = 0; l < nl; ++l) if (H.lane_count[l]) lane = l;
+        add_stretch(lane, 0, n);
+    } else {
+        uint64_t at = n_bad;
+        for (uint32_t l = 0; l < nl; ++l) { add_stretch(l, (uint32_t)(l == 0 ? 0 : at), (uint32_t)(H.lane_count[l] + (l == 0 ? n_bad : 0))); at += H.lane_count[l]; }
+    }
+    return n_bad;
+}
+
 static int host_pass(bqc_ctx* c, const bqc_batch* b, HostPass& H)
 {
     const uint32_t n = b->n_reads, nl = c->opt.n_lanes;
@@ -175,44 +212,18 @@ static int host_pass(bqc_ctx* c, const bqc_batch* b, HostPass& H)
         H.n_slow += part[t].n_slow; H.max_len_slow = std::max(H.max_len_slow, part[t].max_slow);
         for (uint32_t l = 0; l < nl; ++l) H.lane_count[l] += part[t].lanes[l];
     }
-    uint32_t lanes_present = 0;
-    H.t8_lane = 0;
-    for (uint32_t l = 0; l < nl; ++l) {
-        if (H.lane_count[l]) ++lanes_present;
-        if (H.lane_count[l] > H.lane_count[H.t8_lane]) H.t8_lane = l;
-    }
-    uint64_t in_lanes = 0;
-    for (uint32_t l = 0; l < nl; ++l) in_lanes += H.lane_count[l];
-    // (a read whose lane is out of range ends the run on the device — check 2 — and the batch then contributes nothing; such
-    // reads still need a place in the decomposition: they go in front of read group 0)
-    const uint64_t n_bad = n - in_lanes;
-    H.multi_lane = lanes_present > 1 || (n_bad > 0 && in_lanes > 0);
     // (b) processing order: reads grouped by read group (stable); lane stretches and super-windows
-    H.stretches.clear(); H.sws.clear();
-    auto add_stretch = [&](uint32_t lane, uint32_t begin, uint32_t count) {
-        if (!count) return;
-        Stretch S{lane, (uint32_t)H.sws.size(), 0, 0};
-        for (uint32_t p = 0; p < count; p += BQC_SW_READS)
-            H.sws.push_back(SuperWindow{lane, begin + p, std::min<uint32_t>(BQC_SW_READS, count - p), (uint32_t)H.stretches.size()});
-        S.sw_end = (uint32_t)H.sws.size();
-        H.stretches.push_back(S);
-    };
-    if (!H.multi_lane) {
-        H.order.clear();
-        uint32_t lane = 0;
-        for (uint32_t l = 0; l < nl; ++l) if (H.lane_count[l]) lane = l;
-        add_stretch(lane, 0, n);
-    } else {
+    const uint64_t n_bad = plan_read_groups(H, n, nl);
+    if (H.multi_lane) {
         std::vector<uint64_t> w(nl); // where the next read of each read group goes
         uint64_t at = n_bad, w_bad = 0;
         for (uint32_t l = 0; l < nl; ++l) { w[l] = at; at += H.lane_count[l]; }
-        for (uint32_t l = 0; l < nl; ++l) add_stretch(l, (uint32_t)(l == 0 ? 0 : w[l]), (uint32_t)(H.lane_count[l] + (l == 0 ? n_bad : 0)));
         { const size_t cap = H.order.capacity(); H.order.resize(n); if (H.order.capacity() != cap) advise_huge(H.order); }
         for (uint32_t i = 0; i < n; ++i) {
             const uint32_t lane = b->lane[i];
             if (lane < nl) H.order[w[lane]++] = i; else H.order[w_bad++] = i;
         }
-    }
+    } else H.order.clear();
     // (c) the order-dependent part of OverallNumbers::coverage, in stream order (CovPlanner)
     { const size_t cap = H.cov.capacity(); H.cov.resize(n); if (H.cov.capacity() != cap) advise_huge(H.cov); }
     CovPlanner plan(c, H, n);
@@ -297,12 +308,58 @@ static int host_pass(bqc_ctx* c, const bqc_batch* b, HostPass& H)
 
 // The same for a batch that was anchored on the card (k_anchor.hip): no pass over the reads — the batch's sizes, the read group's
 // state before and behind it and the reads at which the window index changes come with the summary; the tiles follow from those.
+// (first_of[] of a read group: the card's table from `off` on, `total` entries — the inline part and the rest bqc_anchor_complete fetched)
+static int first_from_table(bqc_ctx* c, const bqc_anchored* a, size_t off, size_t total, std::vector<uint32_t>& first)
+{
+    // first[k] = the first read whose window is >= k: the card's first_of[] (the first read whose window IS k, AN_NO_READ where a
+    // reset skipped k), filled from the back
+    if (off + total > bqc_anchored::kInline + a->rest.size()) return bqc_fail(c, BQC_ERR_DEVICE, "internal error: the anchors' window table is shorter than the last window");
+    first.assign(total, AN_NO_READ);
+    uint32_t cur = AN_NO_READ;
+    for (size_t k = total; k-- > 0;) {
+        const size_t at = off + k;
+        const uint32_t v = at < bqc_anchored::kInline ? a->h_bound[at] : a->rest[at - bqc_anchored::kInline];
+        if (v != AN_NO_READ) cur = v;
+        first[k] = cur;
+    }
+    if (first[total - 1] == AN_NO_READ) return bqc_fail(c, BQC_ERR_DEVICE, "internal error: the anchors' window table does not end at the last window");
+    return 0;
+}
+
 static int host_pass_anchored(bqc_ctx* c, uint32_t n, const bqc_anchored* a, HostPass& H)
 {
     const AnchorSummary& S = *a->h_sum;
     H.n = n;
     H.seq_bytes = S.seq_bytes; H.qual_bytes = S.qual_bytes; H.cigar_words = S.cigar_words;
     H.n_slow = S.n_slow; H.max_len_slow = S.max_len_slow;
+    const uint32_t nl = c->opt.n_lanes;
+    if (nl > 1) { // several read groups: every group's counts, states and window table come with the summary's per-group part
+        const AnchorLane* AL = a->h_lanes;
+        H.lane_count.assign(nl, 0);
+        for (uint32_t l = 0; l < nl; ++l) H.lane_count[l] = AL[l].n_reads;
+        if (plan_read_groups(H, n, nl) != S.n_bad) return bqc_fail(c, BQC_ERR_DEVICE, "internal error: the anchors' read counts do not add up");
+        H.order.clear(); // (made on the card: submit_impl)
+        H.n_pending = 0;
+        for (uint32_t l = 0; l < nl; ++l) { // every group's state in front of the batch, as the planner wants to find it
+            const AnchorState& B = AL[l].before;
+            LaneCov& lc = c->cov[l];
+            lc.first = B.first != 0; lc.id = B.id; lc.shift = B.shift; lc.win = B.win;
+        }
+        CovPlanner plan(c, H, n);
+        for (uint32_t l = 0; l < nl; ++l) {
+            if (!AL[l].n_cand) continue;
+            int rc = first_from_table(c, a, AL[l].first_off, (size_t)AL[l].last_rel + 1, H.lane_first[l]);
+            if (rc) return rc;
+            plan.last_rel[l] = AL[l].last_rel;
+        }
+        for (uint32_t l = 0; l < nl; ++l) {
+            const AnchorState& A = AL[l].after;
+            LaneCov& lc = c->cov[l];
+            lc.first = A.first != 0; lc.id = A.id; lc.shift = A.shift; lc.win = A.win; // (batch_base: set by the planner, advanced by finish())
+        }
+        plan.finish();
+        return 0;
+    }
     H.lane_count.assign(1, n);
     H.t8_lane = 0;
     H.multi_lane = false;
@@ -330,20 +387,9 @@ static int host_pass_anchored(bqc_ctx* c, uint32_t n, const bqc_anchored* a, Hos
     lc.first = S.before.first != 0; lc.id = S.before.id; lc.shift = S.before.shift; lc.win = S.before.win;
     CovPlanner plan(c, H, n);
     if (S.n_cand > S.n_pending) {
-        // first[k] = the first read whose window is >= k: the card's first_of[] (the first read whose window IS k, AN_NO_READ where a
-        // reset skipped k), filled from the back
-        const size_t total = (size_t)S.last_rel + 1, inl = std::min<size_t>(total, bqc_anchored::kInline);
-        if (total > inl + a->rest.size()) return bqc_fail(c, BQC_ERR_DEVICE, "internal error: the anchors' window table is shorter than the last window");
-        std::vector<uint32_t>& first = H.lane_first[0];
-        first.assign(total, AN_NO_READ);
-        uint32_t cur = AN_NO_READ;
-        for (size_t k = total; k-- > 0;) {
-            const uint32_t v = k < inl ? a->h_bound[k] : a->rest[k - inl];
-            if (v != AN_NO_READ) cur = v;
-            first[k] = cur;
-        }
+        const int rc = first_from_table(c, a, 0, (size_t)S.last_rel + 1, H.lane_first[0]);
+        if (rc) return rc;
         plan.last_rel[0] = S.last_rel;
-        if (first[total - 1] == AN_NO_READ) return bqc_fail(c, BQC_ERR_DEVICE, "internal error: the anchors' window table does not end at the last window");
     }
     lc.first = S.after.first != 0; lc.id = S.after.id; lc.shift = S.after.shift; lc.win = S.after.win; // (batch_base: set by the planner, advanced by finish())
     plan.finish();
@@ -363,7 +409,9 @@ struct Carver {
 // carve m.dmem (allocating / growing it) for a batch of the given sizes and fill in the DevBatch / PrepArgs pointers
 // in_place (an anchored batch: every column and the anchors live in the caller's device memory until the batch's kernels are through):
 // the image holds no copy of them — the kernels read them where they are (250 MB per million reads that used to be copied once more)
-static int layout_batch(bqc_ctx* c, BatchMem& m, const bqc_batch* b, const HostPass& H, bool from_pool, const CovEntry* in_place = nullptr)
+// order_on_device (an anchored batch with several read groups): the processing order is made on the card (bqc_launch_lane_order), into
+// the image's order table, with scratch of its own behind the image
+static int layout_batch(bqc_ctx* c, BatchMem& m, const bqc_batch* b, const HostPass& H, bool from_pool, const CovEntry* in_place = nullptr, bool order_on_device = false)
 {
     const uint64_t n = H.n;
     const uint32_t nl = c->opt.n_lanes;
@@ -393,7 +441,7 @@ static int layout_batch(bqc_ctx* c, BatchMem& m, const bqc_batch* b, const HostP
                  o_perm = cv.take(4 * perm_cap), o_cf = cv.take(sizeof(Chunk) * cf_cap), o_cs = cv.take(sizeof(Chunk) * cs_cap),
                  o_desc = cv.take(sizeof(BatchDesc)), o_err = cv.take(sizeof(ErrRec)), o_cursave = cv.take(8), o_bsz = cv.take(24 * nblk), o_btgt = cv.take(8 * nblk),
                  o_bmf = cv.take(8 * nblk), o_swc = cv.take(sizeof(SwCounts) * n_sw), o_swp = cv.take(sizeof(SwPlan) * n_sw),
-                 o_rsum = cv.take(H.n_slow ? 12 * n : 0);
+                 o_rsum = cv.take(H.n_slow ? 12 * n : 0), o_otmp = cv.take(order_on_device && H.multi_lane ? 4 * lane_order_tmp_words((uint32_t)n, nl) : 0);
     const size_t need = cv.off + 256;
     if (m.dcap < need) {
         if (m.dmem) { (void)hipFree(m.dmem); m.dmem = nullptr; m.dcap = 0; }
@@ -452,6 +500,7 @@ static int layout_batch(bqc_ctx* c, BatchMem& m, const bqc_batch* b, const HostP
     m.d_lane_mask = (uint8_t*)(base + m.o_mask); m.d_started_after = (uint8_t*)(base + m.o_started);
     m.d_add_idx = (uint64_t*)(base + m.o_aidx); m.d_add_val = (uint64_t*)(base + m.o_aval); m.n_add = (uint32_t)H.add_idx.size();
     m.d_rsum = H.n_slow ? (uint32_t*)(base + o_rsum) : nullptr;
+    m.d_order_tmp = order_on_device && H.multi_lane ? (uint32_t*)(base + o_otmp) : nullptr;
     m.d_err = p.err;
     m.algo_bytes = 48ull * n + H.seq_bytes + H.qual_bytes + 4 * H.cigar_words; // A(L,n) of SURVEY.md §8d summed over the batch
     m.n_slow = H.n_slow; m.max_len_slow = H.max_len_slow; m.n_chunks_slow_ub = (uint32_t)cs_cap; m.t8_lane = H.t8_lane;
@@ -473,7 +522,7 @@ static void fill_tables(const BatchMem& m, const bqc_batch* b, const HostPass& H
     auto at = [&](size_t off) { return img + (off - img_begin); };
     if (b->n_nm_extra) { memcpy(at(m.o_xr), b->nm_extra_read, 4ull * b->n_nm_extra); memcpy(at(m.o_xv), b->nm_extra_val, 4ull * b->n_nm_extra); }
     if (!anchors_on_device) memcpy(at(m.o_cov_in), H.cov.data(), sizeof(CovEntry) * (size_t)H.n);
-    if (H.multi_lane) memcpy(at(m.o_order), H.order.data(), 4ull * H.n);
+    if (H.multi_lane && !anchors_on_device) memcpy(at(m.o_order), H.order.data(), 4ull * H.n); // (an anchored batch: made on the card)
     memcpy(at(m.o_sws), H.sws.data(), sizeof(SuperWindow) * H.sws.size());
     memcpy(at(m.o_stretch), H.stretches.data(), sizeof(Stretch) * H.stretches.size());
     if (!H.tiles.empty()) memcpy(at(m.o_tiles), H.tiles.data(), sizeof(CovTile) * H.tiles.size());
@@ -713,7 +762,7 @@ static int submit_impl(bqc_ctx* c, const bqc_batch* b, bool pinned_columns, uint
     const double t_pass = secs_since(t0) - t_wait;
     static const bool copy_anyway = getenv("BQC_ANCHORED_COPY") && getenv("BQC_ANCHORED_COPY")[0] == '1'; // (A/B: the columns copied into the image as bqc_submit_async does)
     const bool in_place = anchored && !copy_anyway;
-    if ((rc = layout_batch(c, s.m, b, H, false, in_place ? anchored->d_cov : nullptr))) return poison(c, rc);
+    if ((rc = layout_batch(c, s.m, b, H, false, in_place ? anchored->d_cov : nullptr, anchored != nullptr))) return poison(c, rc);
     s.in_place = in_place;
     BatchMem& m = s.m;
     if (H.n_pending) { // shard mode: the covered runs of the reads set aside stay on the device until bqc_shard_resolve
@@ -768,6 +817,9 @@ static int submit_impl(bqc_ctx* c, const bqc_batch* b, bool pinned_columns, uint
     if (he == hipSuccess) he = hipEventRecord(s.ev_h2d, c->copy_stream);
     if (he == hipSuccess) he = hipStreamWaitEvent(c->stream, s.ev_h2d, 0);
     if (he != hipSuccess) { poison(c, BQC_ERR_DEVICE); return bqc_fail(c, BQC_ERR_DEVICE, "upload failed: %s", hipGetErrorString(he)); }
+    // an anchored batch with several read groups: its processing order from its lane column, on the card, behind the image's copy (which
+    // holds no order) — the host pass's permutation, made where the column is
+    if (m.d_order_tmp) bqc_launch_lane_order(m.d.lane, b->n_reads, c->opt.n_lanes, (uint32_t*)((char*)m.dmem + m.o_order), m.d_order_tmp, c->stream);
     if ((rc = enqueue_kernels(c, m))) return poison(c, rc);
     HIPCHK(c, hipMemcpyAsync(s.h_err, m.d_err, sizeof(ErrRec), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(s.ev_done, c->stream));
@@ -818,9 +870,10 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     if (!c || !b || !out || (b->n_reads && !d_cov)) return -BQC_ERR_ARG;
     *out = nullptr;
     AnchorEngine& E = c->anchor;
-    // one read group, and the whole stream from its first batch on (a shard that starts inside the stream sets its first reads aside on
-    // the card as the host's pass would: AnchorState::pending)
-    if (c->opt.n_lanes != 1 || (c->shard.tail && c->shard.resolved) || E.mode.load() == 2) return 1;
+    // the whole stream from its first batch on (a shard that starts inside the stream sets its first reads aside on the card as the host's
+    // pass would — AnchorState::pending — with one read group; with several, such a shard is the host's)
+    const uint32_t nl = c->opt.n_lanes;
+    if ((c->shard.tail && (c->shard.resolved || nl > 1)) || E.mode.load() == 2) return 1;
     {   // (one batch at a time: the scratch buffers hold the summary and window table of the one enqueued before until it is completed)
         std::lock_guard<std::mutex> lk(E.m);
         if (E.outstanding) { E.err = "bqc_anchor_enqueue: the batch enqueued before has not been completed or discarded"; return -BQC_ERR_STATE; }
@@ -828,19 +881,24 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     if (hipSetDevice(c->device) != hipSuccess) return anchor_fail(c, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = b->n_reads;
-    if (!E.d_state) {
-        if (hipMalloc((void**)&E.d_state, sizeof(AnchorState)) != hipSuccess || hipMalloc((void**)&E.d_sum, sizeof(AnchorSummary)) != hipSuccess) return anchor_fail(c, "out of device memory");
+    const size_t sum_bytes = sizeof(AnchorSummary) + (nl > 1 ? sizeof(AnchorLane) * nl : 0); // (the per-group part: only with several)
+    if (!E.d_state) { // one window state per read group
+        if (hipMalloc((void**)&E.d_state, sizeof(AnchorState) * nl) != hipSuccess || hipMalloc((void**)&E.d_sum, sum_bytes) != hipSuccess) return anchor_fail(c, "out of device memory");
         AnchorState s0{};
         s0.first = 1;
         s0.pending = c->shard.tail ? 1u : 0u;
-        if (hipMemcpy(E.d_state, &s0, sizeof s0, hipMemcpyHostToDevice) != hipSuccess) return anchor_fail(c, "copy failed");
+        const std::vector<AnchorState> s0s(nl, s0);
+        if (hipMemcpy(E.d_state, s0s.data(), sizeof(AnchorState) * nl, hipMemcpyHostToDevice) != hipSuccess) return anchor_fail(c, "copy failed");
     }
-    if (E.cap_n < n) { // scratch: [cpos crid cidx crun](4 B x n) [bound](8 B x n) [bj][runs][blk_a][blk_b]
+    // (first_of: 2 n + 16 entries; with several read groups 2 per candidate and 2 per group present, at most 2 n + 2 n_lanes + 16)
+    const size_t first_extra = nl > 1 ? 2 * (size_t)nl + 16 : 16;
+    if (E.cap_n < n) { // scratch: [cpos crid cidx crun](4 B x n) [bound](8 B x n + extra) [bj][runs][blk_a][blk_b][parts] and, with several read groups, [blk_c][blk_r][clane]
         if (hipStreamSynchronize(st) != hipSuccess) return anchor_fail(c, "stream failed");
         if (E.d_scratch) (void)hipFree(E.d_scratch);
         E.d_scratch = nullptr; E.cap_n = 0;
-        const size_t cap = std::max<size_t>(n + n / 8, 1u << 20);
-        const size_t bytes = cap * 24 + 64 + AN_MAX_BREAKS * (4 + sizeof(AnchorRun)) + (cap / 1024 + 4) * (2 * 4 + sizeof(AnchorPart)) + 4096;
+        const size_t cap = std::max<size_t>(n + n / 8, 1u << 20), nbk = cap / 1024 + 4;
+        const size_t bytes = cap * 24 + 4 * first_extra + 64 + AN_MAX_BREAKS * (4 + sizeof(AnchorRun)) + nbk * (2 * 4 + sizeof(AnchorPart)) + 4096 +
+                             (nl > 1 ? 4 * nbk * (2 * (size_t)nl + 1) + cap + 1024 : 0);
         if (hipMalloc(&E.d_scratch, bytes) != hipSuccess) return anchor_fail(c, "out of device memory");
         E.cap_n = cap;
     }
@@ -851,35 +909,41 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     }
     if (!a) {
         a = new bqc_anchored();
-        if (hipHostMalloc((void**)&a->h_sum, sizeof(AnchorSummary), hipHostMallocDefault) != hipSuccess ||
+        if (hipHostMalloc((void**)&a->h_sum, sum_bytes, hipHostMallocDefault) != hipSuccess ||
             hipHostMalloc((void**)&a->h_bound, sizeof(uint32_t) * bqc_anchored::kInline, hipHostMallocDefault) != hipSuccess) {
             if (a->h_sum) (void)hipHostFree(a->h_sum);
             delete a;
             return anchor_fail(c, "out of page-locked memory");
         }
+        a->h_lanes = nl > 1 ? (AnchorLane*)(a->h_sum + 1) : nullptr;
         std::lock_guard<std::mutex> lk(E.m);
         E.all.push_back(a);
     }
     a->rest.clear(); a->pend_rid.clear(); a->pend_bp.clear(); a->completed = false; a->n = (uint32_t)n; a->d_cov = (const CovEntry*)d_cov;
     AnchorArgs A{};
-    A.n = (uint32_t)n; A.n_refs = c->opt.n_refs; A.n_lanes = 1; A.no_fast = c->no_fast ? 1u : 0u;
+    A.n = (uint32_t)n; A.n_refs = c->opt.n_refs; A.n_lanes = nl; A.no_fast = c->no_fast ? 1u : 0u;
     A.flag = b->flag; A.lane = b->lane; A.rid = b->rid; A.pos = b->pos; A.l_seq = b->l_seq; A.n_cigar = b->n_cigar;
     A.main_chrom = c->d_main;
-    A.cov_out = (CovEntry*)d_cov; A.state = E.d_state; A.sum = E.d_sum;
+    A.cov_out = (CovEntry*)d_cov; A.state = E.d_state; A.sum = E.d_sum; A.lanes = nl > 1 ? (AnchorLane*)(E.d_sum + 1) : nullptr;
     char* q = (char*)E.d_scratch;
-    const size_t cap = E.cap_n;
+    const size_t cap = E.cap_n, nbk = cap / 1024 + 4;
     A.cpos = (uint32_t*)q; q += 4 * cap; A.crid = (int32_t*)q; q += 4 * cap; A.cidx = (uint32_t*)q; q += 4 * cap; A.crun = (uint32_t*)q; q += 4 * cap;
-    A.first_of = (uint32_t*)q; q += 8 * cap + 64; A.first_cap = (uint32_t)std::min<size_t>(2 * cap + 16, 0xFFFFFFFFu);
+    A.first_of = (uint32_t*)q; q += 8 * cap + 4 * first_extra + 64; A.first_cap = (uint32_t)std::min<size_t>(2 * cap + first_extra, 0xFFFFFFFFu);
     A.bj = (uint32_t*)q; q += 4 * AN_MAX_BREAKS; A.runs = (AnchorRun*)q; q += sizeof(AnchorRun) * AN_MAX_BREAKS;
     q = (char*)(((uintptr_t)q + 255) & ~(uintptr_t)255);
     A.blk_a = (uint32_t*)q; q += 4 * (cap / 1024 + 4); A.blk_b = (uint32_t*)q; q += 4 * (cap / 1024 + 4);
     q = (char*)(((uintptr_t)q + 255) & ~(uintptr_t)255);
     A.parts = (AnchorPart*)q;
+    if (nl > 1) {
+        q += sizeof(AnchorPart) * nbk;
+        q = (char*)(((uintptr_t)q + 255) & ~(uintptr_t)255);
+        A.blk_c = (uint32_t*)q; q += 4 * nbk * nl; A.blk_r = (uint32_t*)q; q += 4 * nbk * ((size_t)nl + 1); A.clane = (uint8_t*)q;
+    }
     E.d_bound = A.first_of;
-    const size_t n_first = std::min<size_t>(2 * n + 16, A.first_cap); // (windows a batch of n reads can reach)
+    const size_t n_first = std::min<size_t>(2 * n + first_extra, A.first_cap); // (windows a batch of n reads can reach)
     if (hipMemsetAsync(A.first_of, 0xFF, 4 * n_first, st) != hipSuccess) { anchor_release(E, a); return anchor_fail(c, "memset failed"); }
     bqc_launch_anchor(A, st);
-    if (hipMemcpyAsync(a->h_sum, E.d_sum, sizeof(AnchorSummary), hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (hipMemcpyAsync(a->h_sum, E.d_sum, sum_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(a->h_bound, A.first_of, sizeof(uint32_t) * std::min<size_t>(bqc_anchored::kInline, n_first), hipMemcpyDeviceToHost, st) != hipSuccess) {
         anchor_release(E, a);
         return anchor_fail(c, "copy failed");
@@ -909,6 +973,19 @@ extern "C" int bqc_anchor_complete(bqc_ctx* c, bqc_anchored* a, bqc_anchor_info*
         anchor_release(E, a);
         return 1;
     }
+    if (c->opt.n_lanes > 1) { // several read groups: their window tables (back to back, group by group) behind the inline entries
+        const uint32_t nl = c->opt.n_lanes;
+        const size_t K = bqc_anchored::kInline;
+        size_t end = 0;
+        for (uint32_t l = 0; l < nl; ++l)
+            if (a->h_lanes[l].n_cand) end = std::max(end, (size_t)a->h_lanes[l].first_off + a->h_lanes[l].last_rel + 1);
+        if (end > 2 * E.cap_n + 2 * (size_t)nl + 16) return anchor_fail(c, "internal error: a window table lies outside the anchors' scratch");
+        if (end > K) {
+            a->rest.resize(end - K);
+            if (hipSetDevice(c->device) != hipSuccess ||
+                hipMemcpy(a->rest.data(), E.d_bound + K, sizeof(uint32_t) * a->rest.size(), hipMemcpyDeviceToHost) != hipSuccess) return anchor_fail(c, "copy failed");
+        }
+    } else
     if (S.n_cand > S.n_pending && (size_t)S.last_rel + 1 > bqc_anchored::kInline) { // (sparse data: the rest of the table, before the next batch's kernels reuse the buffer)
         a->rest.resize((size_t)S.last_rel + 1 - bqc_anchored::kInline);
         if (hipSetDevice(c->device) != hipSuccess ||

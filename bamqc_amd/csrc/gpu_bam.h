@@ -45,6 +45,7 @@ public:
     // shard in the middle of a stream, no batch handed over to the host decoder so far).  Without it: columns on the host, as ever.
     void set_anchor_context(bqc_ctx* ctx) { anchor_ctx_ = ctx; }
     uint64_t batches_anchored() const { return n_anchored_; }
+    uint64_t batches() const { return n_batches_; } // batches of records the card has decoded (those handed over to the host decoder included)
     double seconds_reading() const { return t_read_; } // time spent in pread, summed over the reader threads
     double seconds_waiting_for_runs() const { return t_wait_run_; } // time the consumer waited for the next inflated run (file, copy or inflate behind)
     double seconds_producer_waiting_for_chunks() const { return t_wait_chunk_; } // time the producer waited for the ring's reader threads
@@ -57,7 +58,7 @@ private:
     Impl* p_ = nullptr;
     BamHeader hdr_;
     std::vector<uint8_t> main_;
-    uint64_t nrec_ = 0, n_handed_over_ = 0, n_anchored_ = 0;
+    uint64_t nrec_ = 0, n_handed_over_ = 0, n_anchored_ = 0, n_batches_ = 0;
     std::atomic<bqc_ctx*> anchor_ctx_{nullptr};
     bool anchors_ok_ = true; // (decode thread)
     double t_read_ = 0, t_wait_run_ = 0, t_wait_chunk_ = 0;

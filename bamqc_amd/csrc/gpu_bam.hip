@@ -1283,12 +1283,13 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         memset(&dv, 0, sizeof dv);
         dv.n_reads = (uint32_t)N; dv.flag = C.flag; dv.mapq = C.mapq; dv.lane = C.lane; dv.rid = C.rid; dv.pos = C.pos; dv.tlen = C.tlen; dv.nm = C.nm; dv.as = C.as;
         dv.l_seq = C.l_seq; dv.n_cigar = C.n_cigar; dv.seq = pay + o_seq; dv.qual = pay + o_qual; dv.cigar = (const uint32_t*)(pay + o_cig);
+        ++n_batches_;
         bqc_anchored* ah = nullptr;
         bqc_ctx* const actx = anchor_ctx_.load();
         if (actx && anchors_ok_) {
             const int arc = bqc_anchor_enqueue(actx, &dv, pay + o_cov, I.s, &ah);
             if (arc < 0) return fail_dev(bqc_anchor_error(actx));
-            if (arc > 0) { anchors_ok_ = false; ah = nullptr; } // (several read groups, a shard in the middle of the stream, or the host has kept the state so far)
+            if (arc > 0) { anchors_ok_ = false; ah = nullptr; } // (a shard in the middle of the stream with several read groups, or the host has kept the state so far)
         }
         auto columns_to_host = [&]() -> hipError_t {
             o.flag.resize(N); o.mapq.resize(N); o.lane.resize(N); o.rid.resize(N); o.pos.resize(N); o.tlen.resize(N);

@@ -1,4 +1,4 @@
-// k_anchor.hip — the order-dependent part of OverallNumbers::coverage (OverallNumbers.hpp:84-110) on the card, for ONE read group.
+// k_anchor.hip — the order-dependent part of OverallNumbers::coverage (OverallNumbers.hpp:84-110) on the card.
 //
 // The reference keeps, per read group, two live windows of 1000 positions: `shift` (where the first one starts), the chromosome
 // `id`, and — in this library's virtual coordinates — `win`, the number of windows flushed so far.  A read that enters coverage()
@@ -23,8 +23,15 @@
 //                                           (flag in the summary; the state is not touched)
 //   k_an_apply                              every candidate: closed form from its run's entry -> {window, offset}; the candidates at
 //                                           which the window changes go to the boundary list the host builds the coverage tiles from
+// Several read groups (the <true> instances and the *_g kernels): the reference keeps one such state per read group, and a read's
+// predecessor in the recurrence is the previous candidate OF ITS GROUP.  So the candidates are compacted grouped by read group (a
+// counting sort: per-workgroup per-group counts, one scan, a scatter with stable ranks — eight ballots over the lane byte give the
+// "same group" mask of a wave), which makes every group's candidates one contiguous segment in stream order; a break is then also the
+// first candidate of a segment; k_an_chain_g walks each group's breaks from that group's state, one workgroup per group; and each
+// group gets its own first_of segment (k_an_first_offs: back to back, sized by the group's last window).  One read group keeps the kernels above unchanged (no grouping to pay for).
 // Checked against the host's recurrence (bqc_pipeline.cpp: CovPlanner) read by read on sorted, sparse, unsorted and wild inputs
-// (tests/test_gpu_anchor.py), and through every test that runs the program with the reader on the card.
+// (tests/test_gpu_anchor.py, tests/test_gpu_anchor_read_groups.py), and through every test that runs the program with the reader on
+// the card.
 #include "kernels_common.h"
 #include "anchor.h"
 
@@ -50,6 +57,60 @@ __device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* wsum /* [4]
     return off;
 }
 
+// exclusive scan of blk[0, len) in place by one workgroup of 1024 threads (wsum: [16]); returns the total
+__device__ __forceinline__ uint32_t scan_excl_1024(uint32_t* blk, uint32_t len, uint32_t* wsum)
+{
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < len; base += 1024u) { // (one round for batches of up to 4 M reads and one read group)
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < len ? blk[i] : 0u;
+        const uint32_t inc = wave_scan_incl(v);
+        block_sync();
+        if (lane_id() == WAVE - 1) wsum[threadIdx.x >> 6] = inc;
+        block_sync();
+        uint32_t off = inc - v, tot = 0;
+        for (uint32_t w = 0; w < 16u; ++w) { if (w < (threadIdx.x >> 6)) off += wsum[w]; tot += wsum[w]; }
+        if (i < len) blk[i] = carry + off;
+        carry += tot;
+    }
+    return carry;
+}
+
+// Several read groups: the place of this thread's item among the workgroup's items with the same key (< 2^nbits, at most 256 + 1 keys),
+// in thread order, behind base[key] — which is advanced past them.  The "same key" mask of the wave from nbits ballots over the key's
+// bits; cnt[w][key] (zero on entry, zero again on return) carries each wave's count to the waves behind it.  Every thread of the
+// 256-thread workgroup calls this (barriers).
+__device__ __forceinline__ uint32_t stable_slot(bool valid, uint32_t key, uint32_t nbits, uint32_t* base, uint32_t (*cnt)[257])
+{
+    uint64_t m = __ballot(valid);
+    for (uint32_t b = 0; b < nbits; ++b) {
+        const bool bit = (key >> b) & 1u;
+        const uint64_t q = __ballot(bit);
+        m &= bit ? q : ~q;
+    }
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t below = (uint32_t)__popcll(m & ((1ull << lane_id()) - 1ull));
+    const bool leader = valid && below == 0;
+    if (leader) cnt[w][key] = (uint32_t)__popcll(m);
+    block_sync();
+    uint32_t pos = 0;
+    if (valid) { pos = base[key] + below; for (uint32_t v = 0; v < w; ++v) pos += cnt[v][key]; }
+    block_sync();
+    if (leader) { atomicAdd(&base[key], cnt[w][key]); cnt[w][key] = 0; }
+    block_sync();
+    return pos;
+}
+
+// sum of v over the 256-thread workgroup (red: [4]); every thread gets it
+__device__ __forceinline__ uint32_t block_sum256(uint32_t v, uint32_t* red)
+{
+    v = wave_sum(v);
+    block_sync();
+    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
+    block_sync();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
 // a read's state inside its run: x = beginPos - shift at the run's entry (for a stuck run: - beginPos of the read that reset)
 __device__ __forceinline__ void an_closed(uint32_t x, uint32_t& delta, uint32_t& slides)
 {
@@ -68,16 +129,31 @@ __device__ __forceinline__ void an_in_run(const AnchorRun& r, uint32_t b, uint32
 } // namespace
 
 // ---- candidates ------------------------------------------------------------------------------------------------------------
+// <true>: several read groups — also the workgroup's candidates per read group (blk_c) and reads per bin (blk_r: bin 0 for a lane out
+// of range, bin l + 1 for read group l)
+template <bool G>
 __global__ __launch_bounds__(256) void k_an_count(AnchorArgs a)
 {
     __shared__ uint32_t wsum[4];
+    __shared__ uint32_t hc[256], hr[257];
     const uint32_t i0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (G) {
+        hc[threadIdx.x] = 0; hr[threadIdx.x] = 0;
+        if (threadIdx.x == 0) hr[256] = 0;
+        block_sync();
+    }
     uint32_t c = 0, n_slow = 0, max_slow = 0, n_noqual = 0, s1 = 0, s2 = 0, s3 = 0;
     int32_t rmin = INT32_MAX, rmax = -1;
     for (uint32_t k = 0; k < 4u; ++k) {
         const uint32_t i = i0 + k;
         if (i >= a.n) break;
-        c += an_candidate(a, i) ? 1u : 0u;
+        const bool cand = an_candidate(a, i);
+        c += cand ? 1u : 0u;
+        if (G) {
+            const uint32_t ln = a.lane[i];
+            atomicAdd(&hr[ln < a.n_lanes ? ln + 1u : 0u], 1u);
+            if (cand) atomicAdd(&hc[ln], 1u);
+        }
         const uint32_t L = a.l_seq[i], f = a.flag[i];
         s1 += (L + 1u) / 2u; s2 += L; s3 += a.n_cigar[i]; // (four reads per thread: far below 2^32; summed in 64 bits from the wave on)
         if (a.no_fast || L > BQC_FAST_MAXLEN) { ++n_slow; max_slow = max(max_slow, L); }
@@ -86,8 +162,13 @@ __global__ __launch_bounds__(256) void k_an_count(AnchorArgs a)
         if ((uint32_t)rid < a.n_refs) { rmin = min(rmin, rid); rmax = max(rmax, rid); }
     }
     uint32_t total;
-    (void)block_excl(c, wsum, total);
+    (void)block_excl(c, wsum, total); // (its barriers also close the histograms)
     if (threadIdx.x == 0) a.blk_a[blockIdx.x] = total;
+    if (G) {
+        const uint32_t nblk = gridDim.x;
+        for (uint32_t l = threadIdx.x; l < a.n_lanes; l += 256u) a.blk_c[(size_t)l * nblk + blockIdx.x] = hc[l];
+        for (uint32_t l = threadIdx.x; l <= a.n_lanes; l += 256u) a.blk_r[(size_t)l * nblk + blockIdx.x] = hr[l];
+    }
     // the batch's other facts: the workgroup's partial results (thousands of waves adding to the same few words took longer than the
     // rest of the kernel; k_an_scan sums the workgroups')
     __shared__ unsigned long long part[4][8];
@@ -121,10 +202,11 @@ __global__ __launch_bounds__(256) void k_an_count(AnchorArgs a)
     }
 }
 
-// exclusive scan of up to 4096 block counts by one workgroup of 1024 threads; the total goes to *total_out
-// (which: 0 = the candidates' counts — it also starts the batch's summary and sums the workgroups' partial facts into it; 1 = the
+// exclusive scan of the nscan block counts blk[] by one workgroup of 1024 threads; the total goes to *total_out; nblk: workgroups of
+// k_an_count (their partial facts in parts[])
+// (which: 0 = the candidates' counts (several read groups: [n_lanes][nblk], group-major) — it also starts the batch's summary and sums the workgroups' partial facts into it; 1 = the
 // breaks' counts — and the first certain reset, when a shard is still setting reads aside)
-__global__ __launch_bounds__(1024) void k_an_scan(uint32_t* __restrict__ blk, uint32_t nblk, AnchorSummary* __restrict__ sum, AnchorPart* __restrict__ parts, int which)
+__global__ __launch_bounds__(1024) void k_an_scan(uint32_t* __restrict__ blk, uint32_t nscan, uint32_t nblk, AnchorSummary* __restrict__ sum, AnchorPart* __restrict__ parts, int which)
 {
     __shared__ uint32_t wsum[16];
     __shared__ unsigned long long red[16][8];
@@ -164,20 +246,29 @@ __global__ __launch_bounds__(1024) void k_an_scan(uint32_t* __restrict__ blk, ui
         if (lane_id() == 0 && fc != 0xFFFFFFFFu) atomicMin(&sum->first_certain, fc); // (sixteen waves)
     }
     uint32_t* const total_out = which == 0 ? &sum->n_cand : &sum->n_breaks;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nblk; base += 1024u) { // (one round for batches of up to 4 M reads)
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < nblk ? blk[i] : 0u;
-        const uint32_t inc = wave_scan_incl(v);
-        block_sync();
-        if (lane_id() == WAVE - 1) wsum[threadIdx.x >> 6] = inc;
-        block_sync();
-        uint32_t off = inc - v, tot = 0;
-        for (uint32_t w = 0; w < 16u; ++w) { if (w < (threadIdx.x >> 6)) off += wsum[w]; tot += wsum[w]; }
-        if (i < nblk) blk[i] = carry + off;
-        carry += tot;
+    const uint32_t total = scan_excl_1024(blk, nscan, wsum);
+    if (threadIdx.x == 0) *total_out = total;
+}
+
+// several read groups: the candidates compacted grouped by read group, stream order inside a group (workgroup = k_an_count's 1024
+// reads, taken 256 at a time so that thread order is stream order)
+__global__ __launch_bounds__(256) void k_an_scatter_g(AnchorArgs a)
+{
+    __shared__ uint32_t base[257], cnt[4][257];
+    const uint32_t nblk = gridDim.x;
+    for (uint32_t l = threadIdx.x; l < 257u; l += 256u) {
+        base[l] = l < a.n_lanes ? a.blk_c[(size_t)l * nblk + blockIdx.x] : 0u;
+        cnt[0][l] = cnt[1][l] = cnt[2][l] = cnt[3][l] = 0;
     }
-    if (threadIdx.x == 0) *total_out = carry;
+    block_sync();
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t i = blockIdx.x * 1024u + k * 256u + threadIdx.x;
+        const bool in = i < a.n, cand = in && an_candidate(a, i);
+        const uint32_t ln = in ? a.lane[i] : 0u;
+        const uint32_t j = stable_slot(cand, ln, a.lane_bits, base, cnt);
+        if (cand) { a.cpos[j] = (uint32_t)a.pos[i]; a.crid[j] = a.rid[i]; a.cidx[j] = i; a.clane[j] = (uint8_t)ln; }
+        else if (in) a.cov_out[i] = CovEntry{BQC_COV_NONE, 0u};
+    }
 }
 
 __global__ __launch_bounds__(256) void k_an_scatter(AnchorArgs a)
@@ -199,22 +290,25 @@ __global__ __launch_bounds__(256) void k_an_scatter(AnchorArgs a)
 
 // ---- breaks ------------------------------------------------------------------------------------------------------------------
 namespace {
+template <bool G>
 __device__ __forceinline__ bool an_break(const AnchorArgs& a, uint32_t j)
 {
     if (j == 0) return true; // the batch's first candidate: its state comes from the batch before
+    if (G && a.clane[j] != a.clane[j - 1]) return true; // a read group's first candidate: its state comes from the batch before too
     return a.crid[j] != a.crid[j - 1] || a.cpos[j] - a.cpos[j - 1] >= BQC_VSIZE; // (unsigned: a read in front of its predecessor is a break)
 }
 }
+template <bool G>
 __global__ __launch_bounds__(256) void k_an_bcount(AnchorArgs a)
 {
     __shared__ uint32_t wsum[4];
     const uint32_t nc = a.sum->n_cand, j0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
     uint32_t c = 0;
-    for (uint32_t k = 0; k < 4u; ++k) c += (j0 + k < nc && an_break(a, j0 + k)) ? 1u : 0u;
+    for (uint32_t k = 0; k < 4u; ++k) c += (j0 + k < nc && an_break<G>(a, j0 + k)) ? 1u : 0u;
     uint32_t total;
     (void)block_excl(c, wsum, total);
     if (threadIdx.x == 0) a.blk_b[blockIdx.x] = total;
-    if (a.state->pending) { // a shard in the middle of the stream: the first read that resets the windows whatever their state
+    if (!G && a.state->pending) { // a shard in the middle of the stream: the first read that resets the windows whatever their state
         uint32_t fc = 0xFFFFFFFFu;
         for (uint32_t k = 0; k < 4u && fc == 0xFFFFFFFFu; ++k) {
             const uint32_t j = j0 + k;
@@ -229,13 +323,14 @@ __global__ __launch_bounds__(256) void k_an_bcount(AnchorArgs a)
         if (lane_id() == 0 && fc != 0xFFFFFFFFu) atomicMin(&a.parts[blockIdx.x].first_certain, fc); // (the workgroup's four waves; k_an_scan takes the minimum)
     }
 }
+template <bool G>
 __global__ __launch_bounds__(256) void k_an_bscatter(AnchorArgs a)
 {
     __shared__ uint32_t wsum[4];
     const uint32_t nc = a.sum->n_cand, j0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
     bool br[4];
     uint32_t c = 0;
-    for (uint32_t k = 0; k < 4u; ++k) { br[k] = j0 + k < nc && an_break(a, j0 + k); c += br[k] ? 1u : 0u; }
+    for (uint32_t k = 0; k < 4u; ++k) { br[k] = j0 + k < nc && an_break<G>(a, j0 + k); c += br[k] ? 1u : 0u; }
     uint32_t total;
     uint32_t r = a.blk_b[blockIdx.x] + block_excl(c, wsum, total); // breaks in front of this thread's first candidate
     for (uint32_t k = 0; k < 4u; ++k) {
@@ -325,6 +420,78 @@ __global__ __launch_bounds__(256) void k_an_chain(AnchorArgs a)
     }
 }
 
+// several read groups: one workgroup per read group walks the breaks of its segment from its own state, as k_an_chain does for one
+// (the limit of breaks is the batch's: over it, every workgroup leaves its group's state alone)
+__global__ __launch_bounds__(256) void k_an_chain_g(AnchorArgs a)
+{
+    __shared__ uint32_t s_j[256], s_b[256], s_bl[256], s_jn[256], red[4];
+    __shared__ int32_t s_rid[256];
+    const uint32_t l = blockIdx.x, nl = a.n_lanes, nb = a.sum->n_breaks, nc_all = a.sum->n_cand, nblk = (a.n + 1023u) / 1024u;
+    // the group's reads (workgroup 0: also those out of range), where its candidates lie, and how many groups in front of it have any
+    uint32_t r = 0, bad = 0;
+    for (uint32_t k = threadIdx.x; k < nblk; k += 256u) { r += a.blk_r[(size_t)(l + 1) * nblk + k]; if (l == 0) bad += a.blk_r[k]; }
+    auto cand_at = [&](uint32_t g) { return nblk == 0 ? 0u : g < nl ? a.blk_c[(size_t)g * nblk] : nc_all; };
+    const uint32_t c0 = cand_at(l), c1 = cand_at(l + 1);
+    r = block_sum256(r, red);
+    bad = block_sum256(bad, red);
+    const AnchorState st = a.state[l];
+    if (threadIdx.x == 0) {
+        AnchorLane L{};
+        L.before = st; L.after = st; L.n_cand = c1 - c0; L.n_reads = r; L.cand_off = c0; L.first_off = 0; L.last_rel = 0; // (first_off: k_an_first_offs)
+        a.lanes[l] = L;
+        if (l == 0) a.sum->n_bad = bad;
+    }
+    if (nb > AN_MAX_BREAKS) { if (threadIdx.x == 0) atomicOr(&a.sum->flags, AN_FLAG_TOO_MANY_BREAKS); return; }
+    if (c1 == c0) return;
+    uint32_t first = st.first, s = (uint32_t)st.shift, rel = 0;
+    int32_t id = st.id;
+    AnchorRun run{};
+    const uint32_t b_lo = a.crun[c0], b_hi = a.crun[c1 - 1] + 1u; // (the group's first candidate is a break: its breaks are [b_lo, b_hi))
+    for (uint32_t base = b_lo; base < b_hi; base += 256u) {
+        block_sync();
+        {
+            const uint32_t k = base + threadIdx.x;
+            if (k < b_hi) {
+                const uint32_t j = a.bj[k];
+                s_j[threadIdx.x] = j; s_b[threadIdx.x] = a.cpos[j]; s_rid[threadIdx.x] = a.crid[j];
+                s_bl[threadIdx.x] = j > c0 ? a.cpos[j - 1] : 0u;        // the last read of the run before
+                s_jn[threadIdx.x] = k + 1 < b_hi ? a.bj[k + 1] : c1;    // where this run ends
+            }
+        }
+        block_sync();
+        if (threadIdx.x == 0) {
+            const uint32_t m = min(256u, b_hi - base);
+            for (uint32_t t = 0; t < m; ++t) {
+                const uint32_t j = s_j[t], b = s_b[t];
+                const int32_t rid = s_rid[t];
+                if (j != c0) {
+                    uint32_t r2, d2;
+                    an_in_run(run, s_bl[t], r2, d2);
+                    rel = r2; s = s_bl[t] - d2;
+                }
+                if (first) { first = 0; id = rid; s = b; }
+                if (id != rid || b - s > 2u * BQC_VSIZE) { id = rid; rel += 2u; s = b; }
+                uint32_t p = b - s;
+                if (p > BQC_VSIZE && p < 2u * BQC_VSIZE) { rel += 1u; s += BQC_VSIZE; p -= BQC_VSIZE; }
+                run.b_e = b; run.s_e = s; run.rel_e = rel; run.stuck = p == 2u * BQC_VSIZE ? 1u : 0u; run.b_star = b;
+                if (run.stuck)
+                    for (uint32_t q = j + 1; q < s_jn[t]; ++q) { const uint32_t bq = a.cpos[q]; if (bq != b) { run.b_star = bq; break; } }
+                a.runs[base + t] = run;
+            }
+        }
+    }
+    if (threadIdx.x == 0) { // behind the group's last candidate
+        uint32_t r2, d2;
+        const uint32_t bl = a.cpos[c1 - 1];
+        an_in_run(run, bl, r2, d2);
+        AnchorState out = st;
+        out.first = 0; out.id = id; out.shift = (int32_t)(bl - d2); out.pad = 0; out.win = st.win + r2;
+        a.state[l] = out;
+        a.lanes[l].after = out;
+        a.lanes[l].last_rel = r2;
+    }
+}
+
 // ---- every candidate's anchor ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_an_apply(AnchorArgs a)
 {
@@ -348,16 +515,119 @@ __global__ __launch_bounds__(256) void k_an_apply(AnchorArgs a)
     }
 }
 
-extern "C" void bqc_launch_anchor(const AnchorArgs& a, hipStream_t s)
+// several read groups: where each group's first_of segment lies — its last_rel + 1 entries, back to back in group order, so that the
+// host's inline copy of the table's head holds every group's windows of a dense batch (one workgroup, a thread per group)
+__global__ __launch_bounds__(256) void k_an_first_offs(AnchorArgs a)
 {
+    __shared__ uint32_t wsum[4];
+    const uint32_t l = threadIdx.x;
+    const uint32_t v = l < a.n_lanes && a.lanes[l].n_cand ? a.lanes[l].last_rel + 1u : 0u;
+    uint32_t total;
+    const uint32_t off = block_excl(v, wsum, total);
+    if (l < a.n_lanes) a.lanes[l].first_off = off;
+}
+
+// several read groups: the window of a candidate relative to ITS group's window at batch entry; first_of per group
+__global__ __launch_bounds__(256) void k_an_apply_g(AnchorArgs a)
+{
+    if (a.sum->flags & AN_FLAG_TOO_MANY_BREAKS) return;
+    const uint32_t nc = a.sum->n_cand, j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= nc) return;
+    const uint32_t i = a.cidx[j];
+    const AnchorLane& L = a.lanes[a.clane[j]];
+    const uint32_t c0 = L.cand_off;
+    uint32_t rel, delta;
+    an_in_run(a.runs[a.crun[j]], a.cpos[j], rel, delta);
+    a.cov_out[i] = CovEntry{rel, delta};
+    bool boundary = j == c0;
+    if (j != c0) {
+        uint32_t relp, dp;
+        an_in_run(a.runs[a.crun[j - 1]], a.cpos[j - 1], relp, dp);
+        boundary = relp != rel;
+    }
+    if (boundary) {
+        const uint32_t at = L.first_off + rel;
+        if (rel <= L.last_rel && at < a.first_cap) a.first_of[at] = i;
+        else atomicOr(&a.sum->flags, AN_FLAG_BOUND_OVERFLOW);
+    }
+}
+
+// ---- the processing order of a batch with several read groups ------------------------------------------------------------------
+// tmp[bin][blk] = reads of workgroup blk (1024 reads) in bin (0: lane >= n_lanes, l + 1: read group l)
+__global__ __launch_bounds__(256) void k_lo_count(const uint8_t* __restrict__ lane, uint32_t n, uint32_t nl, uint32_t* __restrict__ tmp)
+{
+    __shared__ uint32_t h[257];
+    h[threadIdx.x] = 0;
+    if (threadIdx.x == 0) h[256] = 0;
+    block_sync();
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t i = blockIdx.x * 1024u + k * 256u + threadIdx.x;
+        if (i < n) { const uint32_t ln = lane[i]; atomicAdd(&h[ln < nl ? ln + 1u : 0u], 1u); }
+    }
+    block_sync();
+    for (uint32_t b = threadIdx.x; b <= nl; b += 256u) tmp[(size_t)b * gridDim.x + blockIdx.x] = h[b];
+}
+__global__ __launch_bounds__(1024) void k_lo_scan(uint32_t* __restrict__ tmp, uint32_t len)
+{
+    __shared__ uint32_t wsum[16];
+    (void)scan_excl_1024(tmp, len, wsum);
+}
+__global__ __launch_bounds__(256) void k_lo_scatter(const uint8_t* __restrict__ lane, uint32_t n, uint32_t nl, uint32_t nbits, const uint32_t* __restrict__ tmp,
+                                                    uint32_t* __restrict__ order)
+{
+    __shared__ uint32_t base[257], cnt[4][257];
+    for (uint32_t b = threadIdx.x; b < 257u; b += 256u) {
+        base[b] = b <= nl ? tmp[(size_t)b * gridDim.x + blockIdx.x] : 0u;
+        cnt[0][b] = cnt[1][b] = cnt[2][b] = cnt[3][b] = 0;
+    }
+    block_sync();
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t i = blockIdx.x * 1024u + k * 256u + threadIdx.x;
+        const uint32_t ln = i < n ? lane[i] : 0u;
+        const uint32_t at = stable_slot(i < n, ln < nl ? ln + 1u : 0u, nbits, base, cnt);
+        if (i < n) order[at] = i;
+    }
+}
+
+static uint32_t bits_for(uint32_t max_key) { return max_key ? 32u - (uint32_t)__builtin_clz(max_key) : 0u; }
+
+extern "C" void bqc_launch_lane_order(const uint8_t* lane, uint32_t n, uint32_t nl, uint32_t* order, uint32_t* tmp, hipStream_t s)
+{
+    if (!n) return;
+    const uint32_t nblk = (n + 1023u) / 1024u;
+    hipLaunchKernelGGL(k_lo_count, dim3(nblk), dim3(256), 0, s, lane, n, nl, tmp);
+    hipLaunchKernelGGL(k_lo_scan, dim3(1), dim3(1024), 0, s, tmp, nblk * (nl + 1u));
+    hipLaunchKernelGGL(k_lo_scatter, dim3(nblk), dim3(256), 0, s, lane, n, nl, bits_for(nl), tmp, order);
+}
+
+extern "C" void bqc_launch_anchor(const AnchorArgs& a_in, hipStream_t s)
+{
+    AnchorArgs a = a_in;
     const uint32_t nblk = (a.n + 1023u) / 1024u; // (also the grid of the candidates' passes: n_cand <= n is only known on the card)
-    if (a.n) hipLaunchKernelGGL(k_an_count, dim3(nblk), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_a, nblk, a.sum, a.parts, 0); // (starts the summary)
+    if (a.n_lanes > 1) { // several read groups
+        a.lane_bits = bits_for(a.n_lanes - 1u);
+        if (a.n) hipLaunchKernelGGL(k_an_count<true>, dim3(nblk), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_c, nblk * a.n_lanes, nblk, a.sum, a.parts, 0); // (starts the summary)
+        if (a.n) {
+            hipLaunchKernelGGL(k_an_scatter_g, dim3(nblk), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_an_bcount<true>, dim3(nblk), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_b, nblk, nblk, a.sum, a.parts, 1);
+            hipLaunchKernelGGL(k_an_bscatter<true>, dim3(nblk), dim3(256), 0, s, a);
+        }
+        hipLaunchKernelGGL(k_an_chain_g, dim3(a.n_lanes), dim3(256), 0, s, a);
+        if (a.n) {
+            hipLaunchKernelGGL(k_an_first_offs, dim3(1), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_an_apply_g, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
+        }
+        return;
+    }
+    if (a.n) hipLaunchKernelGGL(k_an_count<false>, dim3(nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_a, nblk, nblk, a.sum, a.parts, 0); // (starts the summary)
     if (!a.n) { hipLaunchKernelGGL(k_an_chain, dim3(1), dim3(256), 0, s, a); return; }
     hipLaunchKernelGGL(k_an_scatter, dim3(nblk), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_an_bcount, dim3(nblk), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_b, nblk, a.sum, a.parts, 1);
-    hipLaunchKernelGGL(k_an_bscatter, dim3(nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_an_bcount<false>, dim3(nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_b, nblk, nblk, a.sum, a.parts, 1);
+    hipLaunchKernelGGL(k_an_bscatter<false>, dim3(nblk), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_an_chain, dim3(1), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_an_apply, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
 }

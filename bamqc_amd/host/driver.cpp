@@ -1171,7 +1171,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     }
     if (timing && refs_beside_loop) fprintf(stderr, "[timing] references uploaded beside the record loop; the submitting thread waited %.3f s for them\n", t_wait_refs);
     if (timing && lazy_refs) fprintf(stderr, "[timing] %u of %u contigs loaded, when their first reads arrived: %.3f s\n", n_lazy_refs, n_refs, t_lazy_refs);
-    if (timing && use_gpu_reader) fprintf(stderr, "[timing] %llu batches anchored on the card (fixed columns never on the host)\n", (unsigned long long)gpu_rd.batches_anchored());
+    if (timing && use_gpu_reader) fprintf(stderr, "[timing] %llu batches anchored on the card (fixed columns never on the host) of %llu batches\n", (unsigned long long)gpu_rd.batches_anchored(), (unsigned long long)gpu_rd.batches());
     if (timing && use_gpu_reader)
         fprintf(stderr, "[timing] reader on the card: pread %.2f s summed over its reader threads, the producer waited %.2f s for them, the decode thread waited %.2f s for inflated runs\n",
                 gpu_rd.seconds_reading(), gpu_rd.seconds_producer_waiting_for_chunks(), gpu_rd.seconds_waiting_for_runs());
