@@ -559,43 +559,77 @@ __global__ __launch_bounds__(1024) void k_build_plan(PrepArgs a)
     }
 }
 
-// entries of one super-window: read groups (first-mate slots | other slots, missing ones null), segment entries, generic reads
+// exclusive sums of four values over the workgroup's threads in thread order (in place); tot: the sums over all threads.  `sh`: 4 * waves words
+__device__ __forceinline__ void block_scan_excl4(uint32_t v[4], uint32_t* sh, uint32_t tot[4])
+{
+    const uint32_t w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint32_t inc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) inc[k] = wave_scan_incl(v[k]);
+    block_sync();
+    if (lane_id() == WAVE - 1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sh[4 * w + k] = inc[k];
+    }
+    block_sync();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t base = 0, t = 0;
+        for (uint32_t q = 0; q < nw; ++q) { const uint32_t x = sh[4 * q + k]; if (q < w) base += x; t += x; }
+        tot[k] = t;
+        v[k] = base + inc[k] - v[k];
+    }
+}
+
+// entries of one super-window: read groups (first-mate slots | other slots, missing ones null), segment entries, generic reads.
+// Thread t owns the positions [SC_PER * t, + SC_PER) of the super-window: their classes are requested together (two 16-byte loads
+// in stream order), ranked by ONE workgroup scan of four counts, and placed from registers; the read groups leave LDS coalesced.
+// (Round 5: a thread walked its positions twice, one dependent class load and store after another: latency-bound, 0.9 TB/s.)
+#define SC_PER (BQC_SW_READS / PR_THREADS)
+#define SC_ENT (3 * BQC_SW_READS + 128) // groups * rpw <= (count / h + 1) * rpw with rpw / h <= 2.5 (rpw = 5: 3 + 2 slots)
 __global__ __launch_bounds__(PR_THREADS) void k_build_scatter(PrepArgs a)
 {
-    __shared__ uint32_t ent[3 * BQC_SW_READS + 128]; // groups * rpw <= (count / h + 1) * rpw with rpw / h <= 2.5 (rpw = 5: 3 + 2 slots)
-    __shared__ uint32_t sh[2 * (PR_THREADS / 64)];
+    __shared__ uint32_t ent[SC_ENT];
+    __shared__ uint32_t sh[4 * (PR_THREADS / 64)];
     const SuperWindow sw = a.sws[blockIdx.x];
     const SwPlan pl = a.sw_plan[blockIdx.x];
     const uint32_t fast_w = a.desc->fast_w, rpw = 64u / fast_w, h0 = (rpw + 1) / 2, h1 = rpw / 2;
     const uint32_t n_ent = pl.n_groups * rpw;
-    if (n_ent > 3 * BQC_SW_READS + 128) { if (threadIdx.x == 0) atomicOr(&a.err->flags, BQC_DEVERR_INTERNAL); return; }
+    if (n_ent > SC_ENT) { if (threadIdx.x == 0) atomicOr(&a.err->flags, BQC_DEVERR_INTERNAL); return; }
     for (uint32_t k = threadIdx.x; k < n_ent; k += PR_THREADS) ent[k] = 0xFFFFFFFFu;
-    // thread t owns the positions [t * per, (t + 1) * per) of the super-window: ranks inside its run, then across threads
-    const uint32_t per = (sw.count + PR_THREADS - 1) / PR_THREADS;
-    const uint32_t lo = min(sw.count, threadIdx.x * per), hi = min(sw.count, lo + per);
-    uint32_t c[4] = {0, 0, 0, 0};
-    for (uint32_t p = lo; p < hi; ++p) {
-        const uint32_t r = a.order ? a.order[sw.begin + p] : sw.begin + p;
-        uint32_t ns;
-        const uint32_t cl = read_class(a, r, &ns);
-        c[cl] += 1; c[3] += ns;
+    // the reads and their classes (class << 8 | segments; 3 << 8: no read)
+    uint32_t r[SC_PER], v[SC_PER];
+    const uint32_t p0 = SC_PER * threadIdx.x;
+    if (!a.order && p0 + SC_PER <= sw.count && ((sw.begin + p0) & 7u) == 0u) {
+        const uint4 x = *(const uint4*)(a.cls + sw.begin + p0), y = *(const uint4*)(a.cls + sw.begin + p0 + 8);
+        const uint32_t wd[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+#pragma unroll
+        for (int k = 0; k < SC_PER; ++k) { r[k] = sw.begin + p0 + k; v[k] = (wd[k >> 1] >> (16 * (k & 1))) & 0xFFFFu; }
+    } else {
+#pragma unroll
+        for (int k = 0; k < SC_PER; ++k) { const uint32_t p = p0 + k; r[k] = p < sw.count ? (a.order ? a.order[sw.begin + p] : sw.begin + p) : 0xFFFFFFFFu; }
+#pragma unroll
+        for (int k = 0; k < SC_PER; ++k) v[k] = r[k] != 0xFFFFFFFFu ? a.cls[r[k]] : 3u << 8;
     }
-    uint32_t base[4], tot;
-    for (int k = 0; k < 4; ++k) base[k] = block_scan_excl(c[k], sh, &tot);
-    block_sync();
-    for (uint32_t p = lo; p < hi; ++p) {
-        const uint32_t r = a.order ? a.order[sw.begin + p] : sw.begin + p;
-        uint32_t ns;
-        const uint32_t cl = read_class(a, r, &ns);
-        const uint32_t k = base[cl]++;
-        if (cl == 0u) ent[(k / h0) * rpw + k % h0] = r;
-        else if (cl == 1u) ent[(k / h1) * rpw + h0 + k % h1] = r;
-        else a.perm[pl.slow_base + k] = r;
-        if (ns) {
-            const uint32_t co = a.cigar_off[r];
-            for (uint32_t j = 0; j < ns; ++j) a.perm[pl.seg_base + base[3] + j] = BQC_ENTRY_SEG | (co + j);
-            base[3] += ns;
-        }
+    uint32_t c[4] = {0, 0, 0, 0}; // first-mate fast reads, other fast reads, generic reads, segment entries
+#pragma unroll
+    for (int k = 0; k < SC_PER; ++k) {
+        const uint32_t cl = v[k] >> 8;
+        c[0] += cl == 0u; c[1] += cl == 1u; c[2] += cl == 2u; c[3] += cl < 3u ? v[k] & 0xFFu : 0u;
+    }
+    uint32_t co[SC_PER]; // CIGAR offsets of the reads with segments (rare), requested before the scan
+#pragma unroll
+    for (int k = 0; k < SC_PER; ++k) co[k] = (v[k] >> 8) < 3u && (v[k] & 0xFFu) ? a.cigar_off[r[k]] : 0u;
+    uint32_t tot[4];
+    block_scan_excl4(c, sh, tot); // c: this thread's first ranks (its barriers also order the null entries before the placement)
+    uint32_t k0 = c[0], k1 = c[1], k2 = c[2], k3 = c[3];
+#pragma unroll
+    for (int k = 0; k < SC_PER; ++k) {
+        const uint32_t cl = v[k] >> 8, ns = v[k] & 0xFFu;
+        if (cl == 0u) { ent[(k0 / h0) * rpw + k0 % h0] = r[k]; ++k0; }
+        else if (cl == 1u) { ent[(k1 / h1) * rpw + h0 + k1 % h1] = r[k]; ++k1; }
+        else if (cl == 2u) a.perm[pl.slow_base + k2++] = r[k];
+        if (cl < 3u && ns) { for (uint32_t j = 0; j < ns; ++j) a.perm[pl.seg_base + k3 + j] = BQC_ENTRY_SEG | (co[k] + j); k3 += ns; }
     }
     block_sync();
     for (uint32_t k = threadIdx.x; k < n_ent; k += PR_THREADS) a.perm[pl.group_base + k] = ent[k];
