@@ -1,16 +1,44 @@
 // anchor.h — the order-dependent part of OverallNumbers::coverage (OverallNumbers.hpp:84-110) ON THE CARD (k_anchor.hip), for
 // batches whose fixed columns already live in device memory (the reader on the card, gpu_bam.hip): the columns then never come back
-// to the host, which only sees a summary of a few hundred bytes and the list of reads at which the window index changes.
+// to the host, which only sees a summary of a few hundred bytes and the list of reads at which the window index changes.  Also the
+// two functions that ARE the rule — which reads enter coverage() and what one of them does to a read group's windows — for every
+// place that applies it, on the host and on the card.
 #pragma once
 #include <stdint.h>
 
+#include "../../include/bamqc.h"
 #include "device_types.h"
+
+// THE RULE, stated once for the host's pass (bqc_pipeline.cpp) and the card's kernels (k_anchor.hip); plain C++, no device pass needed.
+#if defined(__HIP__) || defined(__HIPCC__)
+#define AN_RULE __host__ __device__ __forceinline__
+#else
+#define AN_RULE inline
+#endif
+// which reads enter coverage(): a primary record with a first / last flag, mapped, not a duplicate, on a main chromosome, of a read
+// group the context has (bamqualcheck.cpp:318-327,392,430-433)
+AN_RULE bool an_is_candidate(uint32_t flag, int32_t rid, uint32_t n_refs, const uint8_t* main_chrom, uint32_t lane, uint32_t n_lanes)
+{
+    return !((flag & 0xD04u) || !(flag & 0xC0u) || (uint32_t)rid >= n_refs || !main_chrom[rid] || lane >= n_lanes);
+}
+// one read at beginPos b of chromosome rid enters coverage() (OverallNumbers.hpp:84-110): moves {first, id, shift} and adds the windows
+// flushed to `win` (a reset flushes two, a slide one); returns the read's position in the two live windows, 0 .. 2000.  Unsigned
+// 32-bit arithmetic as the reference's: a read in front of `shift` resets.
+template <class Win>
+AN_RULE uint32_t an_step(bool& first, int32_t& id, uint32_t& shift, Win& win, int32_t rid, uint32_t b)
+{
+    if (first) { first = false; id = rid; shift = b; }
+    if (id != rid || b - shift > 2u * BQC_VSIZE) { id = rid; shift = b; win += 2; }
+    uint32_t p = b - shift;
+    if (p > BQC_VSIZE && p < 2u * BQC_VSIZE) { shift += BQC_VSIZE; p -= BQC_VSIZE; win += 1; }
+    return p;
+}
 
 // the window state machine of one read group between two reads (host mirror: LaneCov, bqc_ctx.h)
 struct AnchorState {
     uint32_t first;   // no read has entered coverage() yet
     int32_t id;       // chromosome of the live windows
-    int32_t shift;    // position of the first live window's first base
+    uint32_t shift;   // position of the first live window's first base
     uint32_t pad;
     uint64_t win;     // absolute index (flush order) of the first live window
     // A shard that starts inside the stream (bqc_options.shard_tail): its reads are SET ASIDE (BQC_COV_PENDING) up to the first one
@@ -22,31 +50,30 @@ struct AnchorState {
     uint32_t prev_bp;
 };
 
-// what the host needs from a batch besides the anchors themselves (a context with several read groups: the per-read-group part is the
-// AnchorLane[n_lanes] array behind it in the same buffer, and `before`, `after`, `last_rel`, `n_pending`, `first_certain` are unused)
+// what the host needs from a batch besides the anchors themselves: the batch's facts here, and behind it in the same buffer one
+// AnchorLane per read group (n_lanes of them)
 struct AnchorSummary {
     uint32_t n_cand;        // reads that enter coverage()
     uint32_t n_breaks;      // candidates that are not < 1000 positions behind the candidate before them on the same chromosome
-    uint32_t n_bound;       // (unused since round 4: the boundary list is the dense array AnchorArgs::first_of)
     uint32_t flags;         // AN_FLAG_*
     uint32_t n_slow;        // reads of the generic path (longer than BQC_FAST_MAXLEN, or every read with no_fast)
     uint32_t max_len_slow;
     uint32_t n_noqual;      // primary first / last records without qualities (check_read_len's message, QualityCheck.hpp:70-79)
-    uint32_t last_rel;      // window (relative to before.win) of the last candidate
     int32_t rid_min, rid_max; // range of the reference ids in [0, n_refs) the batch holds (rid_min > rid_max: none)
+    // (setting aside exists for one read group only: these are lanes[0]'s)
     uint32_t n_pending;     // candidates set aside (the first n_pending of the batch's candidates: a shard_tail context)
     uint32_t first_certain; // candidate index of the first read that resets whatever the state (0xFFFFFFFF: none; only looked for while setting aside)
-    uint32_t n_bad;         // several read groups: reads whose lane is >= n_lanes (they end the run on the card: k_prep's check 2)
+    uint32_t n_bad;         // reads whose lane is >= n_lanes (they end the run on the card: k_prep's check 2); counted with several read groups only
     uint32_t pad;
     unsigned long long seq_bytes, qual_bytes, cigar_words; // payload sizes: sums of ceil(l_seq / 2), l_seq, n_cigar
-    AnchorState before, after;
 };
-// one read group of a context with several (k_an_chain<true>): its window state, its reads, where its candidates and its first_of segment lie
+// one read group's part (k_an_chain): its window state, its reads, where its candidates and its first_of segment lie.  One read group:
+// lanes[0] with cand_off = first_off = 0 and n_reads = n (a lane out of range is not looked for: n_bad = 0)
 struct AnchorLane {
     AnchorState before, after;
     uint32_t n_cand, n_reads; // candidates / all reads of the read group in the batch
     uint32_t cand_off;        // its first candidate in the compaction (the candidates grouped by read group, stream order inside a group)
-    uint32_t first_off;       // its segment of first_of: last_rel + 1 entries (none when n_cand == 0), the groups' back to back
+    uint32_t first_off;       // its segment of first_of: last_rel + 1 entries (none when it has no anchored candidate), the groups' back to back
     uint32_t last_rel;        // window (relative to before.win) of its last candidate
     uint32_t pad;
 };
@@ -84,9 +111,9 @@ struct AnchorArgs {
     const uint16_t* flag; const uint8_t* lane; const int32_t* rid; const int32_t* pos; const uint32_t* l_seq; const uint16_t* n_cigar;
     const uint8_t* main_chrom;
     CovEntry* cov_out;          // [n]
-    AnchorState* state;         // the read group's state: read by the chain, replaced when the batch is anchored
+    AnchorState* state;         // [n_lanes] the read groups' states: read by the chain, replaced when the batch is anchored
     AnchorSummary* sum;
-    AnchorLane* lanes;          // several read groups: [n_lanes] (state is then [n_lanes] too)
+    AnchorLane* lanes;          // [n_lanes]
     // first_of[rel] = the first read (index in the batch) whose window is `rel`, written by the candidate whose window differs from its
     // predecessor's (windows only grow along the candidates, by one per slide and two per reset: rel <= 2 n_cand + 2); preset to AN_NO_READ.
     // (Round 4, first version: a list appended to with an atomic counter — ~5 000 returning atomics on ONE word per million reads,

@@ -348,12 +348,7 @@ extern "C" int bqc_reset(bqc_ctx* c)
     if (c->sketch) sketch_reset(c->sketch, c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
-    if (c->anchor.d_state) { // (anchors made on the card: the read group's state starts over as well)
-        AnchorState s0{};
-        s0.first = 1;
-        s0.pending = c->shard.tail && !c->shard.resolved ? 1u : 0u;
-        HIPCHK(c, hipMemcpy(c->anchor.d_state, &s0, sizeof s0, hipMemcpyHostToDevice));
-    }
+    if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
     c->anchor.mode = 0;
     c->state_seq = 0;
     c->flushed = false;

@@ -21,7 +21,7 @@
 struct LaneCov { // host side of OverallNumbers' window state machine (OverallNumbers.hpp:84-110)
     bool first = true;
     int32_t id = 0;
-    int32_t shift = 0;
+    uint32_t shift = 0;      // (unsigned as the reference's arithmetic: anchor.h, an_step)
     uint64_t win = 0;        // absolute index (flush order) of the window currently held in v1
     uint64_t batch_base = 0; // absolute window index that is batch-relative window 0 (= carry windows 0,1)
 };
@@ -112,7 +112,7 @@ struct Slot { // one batch in flight through bqc_submit / bqc_submit_async
 // bqc_anchor_complete run in the thread that decodes the batches, bqc_submit_anchored in the one that submits them.
 struct bqc_anchored {
     AnchorSummary* h_sum = nullptr;   // page-locked: the batch's summary ...
-    AnchorLane* h_lanes = nullptr;    // ... with several read groups, its per-group part behind it (n_lanes entries) ...
+    AnchorLane* h_lanes = nullptr;    // ... its per-group part behind it (n_lanes entries) ...
     uint32_t* h_bound = nullptr;      // ... and the first kInline entries of first_of[] (anchor.h)
     std::vector<uint32_t> rest;       // the entries behind them (sparse data), fetched by bqc_anchor_complete
     std::vector<int32_t> pend_rid;    // a shard_tail context: the reads set aside (the batch's first n_pending candidates) ...
@@ -126,7 +126,7 @@ struct bqc_anchored {
 struct AnchorEngine {
     std::atomic<int> mode{0};         // 0: not used yet, 1: the card keeps the state, 2: off for the rest of the stream (the host keeps it)
     AnchorState* d_state = nullptr;   // [n_lanes] one window state per read group
-    AnchorSummary* d_sum = nullptr;   // the summary, and with several read groups AnchorLane[n_lanes] behind it
+    AnchorSummary* d_sum = nullptr;   // the summary, and AnchorLane[n_lanes] behind it
     uint32_t* d_bound = nullptr;
     void* d_scratch = nullptr;
     size_t cap_n = 0;                 // reads the scratch buffers are sized for
@@ -226,6 +226,7 @@ int bqc_copy_stream(bqc_ctx* c);
 int bqc_report_errors(bqc_ctx* c, const ErrRec& e); // what the device found wrong with a batch -> error code + message (0: nothing)
 int bqc_drain(bqc_ctx* c);                 // wait for every batch in flight; returns the first error of the stream (context poisoned)
 void bqc_pipeline_destroy(bqc_ctx* c);     // frees slots and pooled buffers
+hipError_t bqc_anchor_fresh_state(bqc_ctx* c); // every read group's window state on the card back to "no read yet" (d_state exists)
 void bqc_anchor_destroy(bqc_ctx* c);       // frees the anchor engine's buffers and handles
 // Every reader of d_state goes through this: the packed 8-mer rows of k_short are summed into the state vector first.
 void bqc_state_ready(bqc_ctx* c);

@@ -87,14 +87,7 @@ struct CovPlanner {
     void step(uint32_t i, uint32_t lane, int32_t rid, uint32_t beginpos, uint64_t& rel, uint32_t& pos)
     {
         LaneCov& s = c->cov[lane];
-        if (s.first) { s.first = false; s.id = rid; s.shift = (int32_t)beginpos; }
-        if (s.id != rid || (uint32_t)(beginpos - (uint32_t)s.shift) > 2u * BQC_VSIZE) { // reset: two windows flushed
-            s.id = rid; s.win += 2; s.shift = (int32_t)beginpos;
-        }
-        pos = beginpos - (uint32_t)s.shift;
-        if (pos > BQC_VSIZE && pos < 2u * BQC_VSIZE) { // slide: one window flushed
-            s.win += 1; s.shift += BQC_VSIZE; pos = beginpos - (uint32_t)s.shift;
-        }
+        pos = an_step(s.first, s.id, s.shift, s.win, rid, beginpos);
         rel = s.win - s.batch_base;
         if (rel > 0xFFFFFFF0ull) return;
         std::vector<uint32_t>& first = H.lane_first[lane]; // first[k] = first read of the lane whose window is >= k
@@ -251,15 +244,9 @@ static int host_pass(bqc_ctx* c, const bqc_batch* b, HostPass& H)
         for (uint32_t i = 0; i < n; ++i) {
             const uint32_t flag = flags[i], lane = lanes[i];
             const int32_t rid = rids[i];
-            // primary record with a first / last flag, on a main chromosome, mapped, not a duplicate (bamqualcheck.cpp:318-327,392,430-433)
-            if ((flag & 0xD04u) || !(flag & 0xC0u) || (uint32_t)rid >= n_refs || !main_chrom[rid] || lane >= nl) { out[i] = CovEntry{BQC_COV_NONE, 0}; continue; }
+            if (!an_is_candidate(flag, rid, n_refs, main_chrom, lane, nl)) { out[i] = CovEntry{BQC_COV_NONE, 0}; continue; }
             LaneCov& st = one ? local : cov[lane];
-            const uint32_t beginpos = (uint32_t)poss[i];
-            // CovPlanner::step, inlined (OverallNumbers.hpp:84-110)
-            if (st.first) { st.first = false; st.id = rid; st.shift = (int32_t)beginpos; }
-            if (st.id != rid || (uint32_t)(beginpos - (uint32_t)st.shift) > 2u * BQC_VSIZE) { st.id = rid; st.win += 2; st.shift = (int32_t)beginpos; } // reset: two windows flushed
-            uint32_t pos = beginpos - (uint32_t)st.shift;
-            if (pos > BQC_VSIZE && pos < 2u * BQC_VSIZE) { st.win += 1; st.shift += BQC_VSIZE; pos = beginpos - (uint32_t)st.shift; } // slide: one window flushed
+            const uint32_t pos = an_step(st.first, st.id, st.shift, st.win, rid, (uint32_t)poss[i]);
             const uint64_t rel = st.win - st.batch_base;
             if (rel > 0xFFFFFFF0ull) { too_many = true; break; }
             std::vector<uint32_t>& first = lane_first[lane]; // first[k] = first read of the lane whose window is >= k
@@ -273,10 +260,7 @@ static int host_pass(bqc_ctx* c, const bqc_batch* b, HostPass& H)
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t flag = b->flag[i], lane = b->lane[i];
         const int32_t rid = b->rid[i];
-        // primary record with a first / last flag, on a main chromosome, mapped, not a duplicate (bamqualcheck.cpp:318-327,392,430-433)
-        const bool cand = !(flag & 0x900u) && (flag & 0xC0u) && !(flag & 0x4u) && !(flag & 0x400u) && rid >= 0 && (uint32_t)rid < n_refs && main_chrom[rid] &&
-                          lane < nl;
-        if (!cand) { H.cov[i] = CovEntry{BQC_COV_NONE, 0}; continue; }
+        if (!an_is_candidate(flag, rid, n_refs, main_chrom, lane, nl)) { H.cov[i] = CovEntry{BQC_COV_NONE, 0}; continue; }
         const uint32_t beginpos = (uint32_t)b->pos[i];
         if (set_aside && sh.pending[lane]) {
             // Does the state machine reset at this read WHATEVER its state?  Its position in the live windows is
@@ -306,6 +290,23 @@ static int host_pass(bqc_ctx* c, const bqc_batch* b, HostPass& H)
     return 0;
 }
 
+// Test hook (host only, no GPU call; tests/test_anchor_rule.py): the candidate test and the step of anchor.h over n reads in stream
+// order for n_lanes states, as host_pass and the card's chain apply them.  win[i]: the read's window (absolute — states[].win counts
+// on) or ~0 for a read that does not enter coverage(); off[i]: its position in the live windows.
+extern "C" void bqc_anchor_rule(uint32_t n, const uint16_t* flag, const int32_t* rid, const int32_t* pos, const uint8_t* lane, uint32_t n_refs,
+                                const uint8_t* main_chrom, uint32_t n_lanes, AnchorState* states, uint64_t* win, uint32_t* off)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        win[i] = ~0ull; off[i] = 0;
+        if (!an_is_candidate(flag[i], rid[i], n_refs, main_chrom, lane[i], n_lanes)) continue;
+        AnchorState& s = states[lane[i]];
+        bool first = s.first != 0;
+        off[i] = an_step(first, s.id, s.shift, s.win, rid[i], (uint32_t)pos[i]);
+        s.first = first;
+        win[i] = s.win;
+    }
+}
+
 // The same for a batch that was anchored on the card (k_anchor.hip): no pass over the reads — the batch's sizes, the read group's
 // state before and behind it and the reads at which the window index changes come with the summary; the tiles follow from those.
 // (first_of[] of a read group: the card's table from `off` on, `total` entries — the inline part and the rest bqc_anchor_complete fetched)
@@ -326,51 +327,22 @@ static int first_from_table(bqc_ctx* c, const bqc_anchored* a, size_t off, size_
     return 0;
 }
 
+// (a read group has windows in the table when it has candidates that were not set aside — setting aside exists for one group only)
+static bool lane_anchored(const AnchorSummary& S, const AnchorLane* AL, uint32_t l) { return AL[l].n_cand > (l == 0 ? S.n_pending : 0u); }
+static void load_state(LaneCov& lc, const AnchorState& s) { lc.first = s.first != 0; lc.id = s.id; lc.shift = s.shift; lc.win = s.win; } // (batch_base: the planner's)
+
 static int host_pass_anchored(bqc_ctx* c, uint32_t n, const bqc_anchored* a, HostPass& H)
 {
     const AnchorSummary& S = *a->h_sum;
+    const AnchorLane* AL = a->h_lanes; // every group's counts, states and window table come with the summary's per-group part
+    const uint32_t nl = c->opt.n_lanes;
     H.n = n;
     H.seq_bytes = S.seq_bytes; H.qual_bytes = S.qual_bytes; H.cigar_words = S.cigar_words;
     H.n_slow = S.n_slow; H.max_len_slow = S.max_len_slow;
-    const uint32_t nl = c->opt.n_lanes;
-    if (nl > 1) { // several read groups: every group's counts, states and window table come with the summary's per-group part
-        const AnchorLane* AL = a->h_lanes;
-        H.lane_count.assign(nl, 0);
-        for (uint32_t l = 0; l < nl; ++l) H.lane_count[l] = AL[l].n_reads;
-        if (plan_read_groups(H, n, nl) != S.n_bad) return bqc_fail(c, BQC_ERR_DEVICE, "internal error: the anchors' read counts do not add up");
-        H.order.clear(); // (made on the card: submit_impl)
-        H.n_pending = 0;
-        for (uint32_t l = 0; l < nl; ++l) { // every group's state in front of the batch, as the planner wants to find it
-            const AnchorState& B = AL[l].before;
-            LaneCov& lc = c->cov[l];
-            lc.first = B.first != 0; lc.id = B.id; lc.shift = B.shift; lc.win = B.win;
-        }
-        CovPlanner plan(c, H, n);
-        for (uint32_t l = 0; l < nl; ++l) {
-            if (!AL[l].n_cand) continue;
-            int rc = first_from_table(c, a, AL[l].first_off, (size_t)AL[l].last_rel + 1, H.lane_first[l]);
-            if (rc) return rc;
-            plan.last_rel[l] = AL[l].last_rel;
-        }
-        for (uint32_t l = 0; l < nl; ++l) {
-            const AnchorState& A = AL[l].after;
-            LaneCov& lc = c->cov[l];
-            lc.first = A.first != 0; lc.id = A.id; lc.shift = A.shift; lc.win = A.win; // (batch_base: set by the planner, advanced by finish())
-        }
-        plan.finish();
-        return 0;
-    }
-    H.lane_count.assign(1, n);
-    H.t8_lane = 0;
-    H.multi_lane = false;
-    H.order.clear();
-    H.stretches.clear(); H.sws.clear();
-    {
-        Stretch St{0, 0, 0, 0};
-        for (uint32_t p = 0; p < n; p += BQC_SW_READS) H.sws.push_back(SuperWindow{0, p, std::min<uint32_t>(BQC_SW_READS, n - p), 0});
-        St.sw_end = (uint32_t)H.sws.size();
-        H.stretches.push_back(St);
-    }
+    H.lane_count.assign(nl, 0);
+    for (uint32_t l = 0; l < nl; ++l) H.lane_count[l] = AL[l].n_reads;
+    if (plan_read_groups(H, n, nl) != S.n_bad) return bqc_fail(c, BQC_ERR_DEVICE, "internal error: the anchors' read counts do not add up");
+    H.order.clear(); // (made on the card: submit_impl)
     H.n_pending = 0;
     if (S.n_pending) { // a shard in the middle of the stream: the reads set aside go to the pending log, as host_pass would have put them there
         ShardCtx& sh = c->shard;
@@ -381,17 +353,20 @@ static int host_pass_anchored(bqc_ctx* c, uint32_t n, const bqc_anchored* a, Hos
         pb.bp = a->pend_bp;
         H.n_pending = S.n_pending;
     }
-    if (c->shard.tail) { c->shard.pending[0] = S.after.pending ? 1 : 0; c->shard.has_prev[0] = S.after.has_prev ? 1 : 0; c->shard.prev_rid[0] = S.after.prev_rid; c->shard.prev_bp[0] = S.after.prev_bp; }
-    // the read group's state in front of the batch, as the planner wants to find it
-    LaneCov& lc = c->cov[0];
-    lc.first = S.before.first != 0; lc.id = S.before.id; lc.shift = S.before.shift; lc.win = S.before.win;
-    CovPlanner plan(c, H, n);
-    if (S.n_cand > S.n_pending) {
-        const int rc = first_from_table(c, a, 0, (size_t)S.last_rel + 1, H.lane_first[0]);
-        if (rc) return rc;
-        plan.last_rel[0] = S.last_rel;
+    if (c->shard.tail) { // (anchored on the card with one read group only)
+        const AnchorState& A = AL[0].after;
+        c->shard.pending[0] = A.pending ? 1 : 0; c->shard.has_prev[0] = A.has_prev ? 1 : 0; c->shard.prev_rid[0] = A.prev_rid; c->shard.prev_bp[0] = A.prev_bp;
     }
-    lc.first = S.after.first != 0; lc.id = S.after.id; lc.shift = S.after.shift; lc.win = S.after.win; // (batch_base: set by the planner, advanced by finish())
+    // every group's state in front of the batch, as the planner wants to find it; its window table; its state behind the batch
+    for (uint32_t l = 0; l < nl; ++l) load_state(c->cov[l], AL[l].before);
+    CovPlanner plan(c, H, n);
+    for (uint32_t l = 0; l < nl; ++l) {
+        if (!lane_anchored(S, AL, l)) continue;
+        const int rc = first_from_table(c, a, AL[l].first_off, (size_t)AL[l].last_rel + 1, H.lane_first[l]);
+        if (rc) return rc;
+        plan.last_rel[l] = AL[l].last_rel;
+    }
+    for (uint32_t l = 0; l < nl; ++l) load_state(c->cov[l], AL[l].after);
     plan.finish();
     return 0;
 }
@@ -865,6 +840,19 @@ static void anchor_release_locked(AnchorEngine& E, bqc_anchored* a)
 static void anchor_release(AnchorEngine& E, bqc_anchored* a) { std::lock_guard<std::mutex> lk(E.m); anchor_release_locked(E, a); }
 extern "C" const char* bqc_anchor_error(const bqc_ctx* c) { return c ? c->anchor.err.c_str() : ""; }
 
+// the window state of every read group on the card as a stream finds it at its first read (bqc_anchor_enqueue's first batch, bqc_reset)
+hipError_t bqc_anchor_fresh_state(bqc_ctx* c)
+{
+    AnchorState s0{};
+    s0.first = 1;
+    s0.pending = c->shard.tail && !c->shard.resolved ? 1u : 0u;
+    const std::vector<AnchorState> s0s(c->opt.n_lanes, s0);
+    return hipMemcpy(c->anchor.d_state, s0s.data(), sizeof(AnchorState) * s0s.size(), hipMemcpyHostToDevice);
+}
+// entries of first_of[] beyond two per read: a window changes at most twice per candidate, and every read group present ends with one
+// entry and may start two behind the table's first (2 n + 2 n_lanes + 16 entries in all)
+static size_t anchor_first_extra(uint32_t nl) { return 2 * (size_t)nl + 16; }
+
 extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, void* stream, bqc_anchored** out)
 {
     if (!c || !b || !out || (b->n_reads && !d_cov)) return -BQC_ERR_ARG;
@@ -881,17 +869,12 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     if (hipSetDevice(c->device) != hipSuccess) return anchor_fail(c, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = b->n_reads;
-    const size_t sum_bytes = sizeof(AnchorSummary) + (nl > 1 ? sizeof(AnchorLane) * nl : 0); // (the per-group part: only with several)
+    const size_t sum_bytes = sizeof(AnchorSummary) + sizeof(AnchorLane) * nl; // (the summary and its per-group part)
     if (!E.d_state) { // one window state per read group
         if (hipMalloc((void**)&E.d_state, sizeof(AnchorState) * nl) != hipSuccess || hipMalloc((void**)&E.d_sum, sum_bytes) != hipSuccess) return anchor_fail(c, "out of device memory");
-        AnchorState s0{};
-        s0.first = 1;
-        s0.pending = c->shard.tail ? 1u : 0u;
-        const std::vector<AnchorState> s0s(nl, s0);
-        if (hipMemcpy(E.d_state, s0s.data(), sizeof(AnchorState) * nl, hipMemcpyHostToDevice) != hipSuccess) return anchor_fail(c, "copy failed");
+        if (bqc_anchor_fresh_state(c) != hipSuccess) return anchor_fail(c, "copy failed");
     }
-    // (first_of: 2 n + 16 entries; with several read groups 2 per candidate and 2 per group present, at most 2 n + 2 n_lanes + 16)
-    const size_t first_extra = nl > 1 ? 2 * (size_t)nl + 16 : 16;
+    const size_t first_extra = anchor_first_extra(nl);
     if (E.cap_n < n) { // scratch: [cpos crid cidx crun](4 B x n) [bound](8 B x n + extra) [bj][runs][blk_a][blk_b][parts] and, with several read groups, [blk_c][blk_r][clane]
         if (hipStreamSynchronize(st) != hipSuccess) return anchor_fail(c, "stream failed");
         if (E.d_scratch) (void)hipFree(E.d_scratch);
@@ -915,7 +898,7 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
             delete a;
             return anchor_fail(c, "out of page-locked memory");
         }
-        a->h_lanes = nl > 1 ? (AnchorLane*)(a->h_sum + 1) : nullptr;
+        a->h_lanes = (AnchorLane*)(a->h_sum + 1);
         std::lock_guard<std::mutex> lk(E.m);
         E.all.push_back(a);
     }
@@ -924,7 +907,7 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     A.n = (uint32_t)n; A.n_refs = c->opt.n_refs; A.n_lanes = nl; A.no_fast = c->no_fast ? 1u : 0u;
     A.flag = b->flag; A.lane = b->lane; A.rid = b->rid; A.pos = b->pos; A.l_seq = b->l_seq; A.n_cigar = b->n_cigar;
     A.main_chrom = c->d_main;
-    A.cov_out = (CovEntry*)d_cov; A.state = E.d_state; A.sum = E.d_sum; A.lanes = nl > 1 ? (AnchorLane*)(E.d_sum + 1) : nullptr;
+    A.cov_out = (CovEntry*)d_cov; A.state = E.d_state; A.sum = E.d_sum; A.lanes = (AnchorLane*)(E.d_sum + 1);
     char* q = (char*)E.d_scratch;
     const size_t cap = E.cap_n, nbk = cap / 1024 + 4;
     A.cpos = (uint32_t*)q; q += 4 * cap; A.crid = (int32_t*)q; q += 4 * cap; A.cidx = (uint32_t*)q; q += 4 * cap; A.crun = (uint32_t*)q; q += 4 * cap;
@@ -973,23 +956,18 @@ extern "C" int bqc_anchor_complete(bqc_ctx* c, bqc_anchored* a, bqc_anchor_info*
         anchor_release(E, a);
         return 1;
     }
-    if (c->opt.n_lanes > 1) { // several read groups: their window tables (back to back, group by group) behind the inline entries
-        const uint32_t nl = c->opt.n_lanes;
-        const size_t K = bqc_anchored::kInline;
-        size_t end = 0;
-        for (uint32_t l = 0; l < nl; ++l)
-            if (a->h_lanes[l].n_cand) end = std::max(end, (size_t)a->h_lanes[l].first_off + a->h_lanes[l].last_rel + 1);
-        if (end > 2 * E.cap_n + 2 * (size_t)nl + 16) return anchor_fail(c, "internal error: a window table lies outside the anchors' scratch");
-        if (end > K) {
-            a->rest.resize(end - K);
-            if (hipSetDevice(c->device) != hipSuccess ||
-                hipMemcpy(a->rest.data(), E.d_bound + K, sizeof(uint32_t) * a->rest.size(), hipMemcpyDeviceToHost) != hipSuccess) return anchor_fail(c, "copy failed");
-        }
-    } else
-    if (S.n_cand > S.n_pending && (size_t)S.last_rel + 1 > bqc_anchored::kInline) { // (sparse data: the rest of the table, before the next batch's kernels reuse the buffer)
-        a->rest.resize((size_t)S.last_rel + 1 - bqc_anchored::kInline);
+    // the read groups' window tables lie back to back, group by group: what is behind the inline entries (sparse data) is fetched here,
+    // before the next batch's kernels reuse the buffer
+    const uint32_t nl = c->opt.n_lanes;
+    const size_t K = bqc_anchored::kInline;
+    size_t end = 0;
+    for (uint32_t l = 0; l < nl; ++l)
+        if (lane_anchored(S, a->h_lanes, l)) end = std::max(end, (size_t)a->h_lanes[l].first_off + a->h_lanes[l].last_rel + 1);
+    if (end > 2 * E.cap_n + anchor_first_extra(nl)) return anchor_fail(c, "internal error: a window table lies outside the anchors' scratch");
+    if (end > K) {
+        a->rest.resize(end - K);
         if (hipSetDevice(c->device) != hipSuccess ||
-            hipMemcpy(a->rest.data(), E.d_bound + bqc_anchored::kInline, sizeof(uint32_t) * a->rest.size(), hipMemcpyDeviceToHost) != hipSuccess) return anchor_fail(c, "copy failed");
+            hipMemcpy(a->rest.data(), E.d_bound + K, sizeof(uint32_t) * a->rest.size(), hipMemcpyDeviceToHost) != hipSuccess) return anchor_fail(c, "copy failed");
     }
     if (S.n_pending) { // the reads set aside: chromosome and position of the batch's first n_pending candidates (the scratch's crid / cpos)
         a->pend_rid.resize(S.n_pending); a->pend_bp.resize(S.n_pending);
@@ -1094,7 +1072,7 @@ extern "C" int bqc_shard_export(bqc_ctx* c, void* out)
     memcpy(w, head, 8); w += 8;
     for (uint32_t l = 0; l < nl; ++l) {
         const LaneCov& s = c->cov[l];
-        const LaneWire lw{(uint8_t)s.first, started[l], 0, 0, s.id, s.shift};
+        const LaneWire lw{(uint8_t)s.first, started[l], 0, 0, s.id, (int32_t)s.shift};
         memcpy(w, &lw, sizeof lw); w += sizeof lw;
         HIPCHK(c, hipMemcpy(w, c->d_carry + ((size_t)l * 2 + (parity[l] & 1u)) * 2 * BQC_VSIZE, 2 * BQC_VSIZE * 4, hipMemcpyDeviceToHost));
         w += 2 * BQC_VSIZE * 4;
@@ -1133,7 +1111,7 @@ extern "C" int bqc_shard_resolve(bqc_ctx* c, const void* pred)
         LaneWire lw;
         memcpy(&lw, r, sizeof lw); r += sizeof lw;
         LaneCov s;
-        s.first = lw.first != 0; s.id = lw.id; s.shift = lw.shift; s.win = 0; s.batch_base = 0;
+        s.first = lw.first != 0; s.id = lw.id; s.shift = (uint32_t)lw.shift; s.win = 0; s.batch_base = 0;
         c->cov[l] = s;
         started_in[l] = lw.started;
         memcpy(carry_in.data() + carry_lane * l, r, 2 * BQC_VSIZE * 4); r += 2 * BQC_VSIZE * 4; // live half -> half 0

@@ -18,17 +18,19 @@
 //                                           without qualities, range of chromosomes) on the way
 //   k_an_bcount / k_an_scan / k_an_bscatter the breaks among them, listed; every candidate learns the number of its run
 //   k_an_chain                              ONE thread walks the breaks (their operands loaded into LDS by the workgroup, 256 at a
-//                                           time): state at the end of the run before, transition of the recurrence, state the new run
-//                                           starts with.  More than AN_MAX_BREAKS breaks: the batch is left to the host's recurrence
-//                                           (flag in the summary; the state is not touched)
+//                                           time): state at the end of the run before, transition of the recurrence (anchor.h: an_step,
+//                                           the one the host's pass uses), state the new run starts with.  More than AN_MAX_BREAKS
+//                                           breaks: the batch is left to the host's recurrence (flag in the summary; the state is not
+//                                           touched)
 //   k_an_apply                              every candidate: closed form from its run's entry -> {window, offset}; the candidates at
 //                                           which the window changes go to the boundary list the host builds the coverage tiles from
-// Several read groups (the <true> instances and the *_g kernels): the reference keeps one such state per read group, and a read's
-// predecessor in the recurrence is the previous candidate OF ITS GROUP.  So the candidates are compacted grouped by read group (a
+// Several read groups (the <true> instances, k_an_scatter_g and k_an_first_offs): the reference keeps one such state per read group, and
+// a read's predecessor in the recurrence is the previous candidate OF ITS GROUP.  So the candidates are compacted grouped by read group (a
 // counting sort: per-workgroup per-group counts, one scan, a scatter with stable ranks — eight ballots over the lane byte give the
 // "same group" mask of a wave), which makes every group's candidates one contiguous segment in stream order; a break is then also the
-// first candidate of a segment; k_an_chain_g walks each group's breaks from that group's state, one workgroup per group; and each
-// group gets its own first_of segment (k_an_first_offs: back to back, sized by the group's last window).  One read group keeps the kernels above unchanged (no grouping to pay for).
+// first candidate of a segment; k_an_chain<true> walks each group's breaks from that group's state, one workgroup per group — the same
+// walk (an_walk) over other bounds; and each group gets its own first_of segment (k_an_first_offs: back to back, sized by the group's
+// last window).  With one read group the <false> instances run: no grouping to pay for, the group's part of the summary is lanes[0].
 // Checked against the host's recurrence (bqc_pipeline.cpp: CovPlanner) read by read on sorted, sparse, unsorted and wild inputs
 // (tests/test_gpu_anchor.py, tests/test_gpu_anchor_read_groups.py), and through every test that runs the program with the reader on
 // the card.
@@ -38,10 +40,7 @@
 namespace {
 __device__ __forceinline__ bool an_candidate(const AnchorArgs& a, uint32_t i)
 {
-    const uint32_t flag = a.flag[i];
-    const int32_t rid = a.rid[i];
-    // primary record with a first / last flag, on a main chromosome, mapped, not a duplicate (bamqualcheck.cpp:318-327,392,430-433)
-    return !((flag & 0xD04u) || !(flag & 0xC0u) || (uint32_t)rid >= a.n_refs || !a.main_chrom[rid] || a.lane[i] >= a.n_lanes);
+    return an_is_candidate(a.flag[i], a.rid[i], a.n_refs, a.main_chrom, a.lane[i], a.n_lanes);
 }
 
 // exclusive prefix of `v` over the workgroup's 256 threads, and the workgroup's total
@@ -342,111 +341,21 @@ __global__ __launch_bounds__(256) void k_an_bscatter(AnchorArgs a)
 }
 
 // ---- the chain over the breaks -----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_an_chain(AnchorArgs a)
+namespace {
+// The breaks [b_lo, b_hi) of a segment of candidates that ends in front of c1, walked from the state `st` in front of the segment's
+// first anchored candidate j_first (the break b_lo): the workgroup loads the breaks' operands into LDS, 256 at a time, and thread 0
+// runs, per break, state at the end of the run before -> step of the recurrence -> the AnchorRun the new run starts with.  Every
+// thread of the workgroup calls this (barriers); THREAD 0 gets the state behind the segment's last candidate and that candidate's
+// window relative to st.win.
+__device__ __forceinline__ AnchorState an_walk(const AnchorArgs& a, uint32_t c1, uint32_t b_lo, uint32_t b_hi, uint32_t j_first, const AnchorState& st, uint32_t& last_rel)
 {
     __shared__ uint32_t s_j[256], s_b[256], s_bl[256], s_jn[256];
     __shared__ int32_t s_rid[256];
-    const uint32_t nc = a.sum->n_cand, nb = a.sum->n_breaks;
-    AnchorState st = *a.state;
-    if (threadIdx.x == 0) { a.sum->before = st; a.sum->after = st; a.sum->last_rel = 0; a.sum->n_pending = 0; }
-    if (nb > AN_MAX_BREAKS) { if (threadIdx.x == 0) atomicOr(&a.sum->flags, AN_FLAG_TOO_MANY_BREAKS); return; }
-    if (nc == 0) return;
-    // setting aside: the candidates in front of the first certain reset are pending; the chain starts AT that read — a break — from the
-    // context's own state (a stream that begins there)
-    uint32_t k0 = 0, j_first = 0;
-    if (st.pending) {
-        const uint32_t fc = a.sum->first_certain;
-        j_first = fc == 0xFFFFFFFFu ? nc : fc;
-        if (threadIdx.x == 0) a.sum->n_pending = j_first;
-        if (j_first == nc) { // every candidate of the batch is set aside
-            if (threadIdx.x == 0) {
-                AnchorState out = st;
-                out.has_prev = 1; out.prev_rid = a.crid[nc - 1]; out.prev_bp = a.cpos[nc - 1];
-                *a.state = out;
-                a.sum->after = out;
-            }
-            return;
-        }
-        k0 = a.crun[j_first];
-    }
     // the state between two reads: first / id / absolute shift / windows flushed in this batch, and the run it belongs to
-    uint32_t first = st.first, s = (uint32_t)st.shift, rel = 0;
+    bool first = st.first != 0;
+    uint32_t s = st.shift, rel = 0;
     int32_t id = st.id;
     AnchorRun run{};
-    for (uint32_t base = k0; base < nb; base += 256u) {
-        block_sync();
-        {
-            const uint32_t k = base + threadIdx.x;
-            if (k < nb) {
-                const uint32_t j = a.bj[k];
-                s_j[threadIdx.x] = j; s_b[threadIdx.x] = a.cpos[j]; s_rid[threadIdx.x] = a.crid[j];
-                s_bl[threadIdx.x] = j ? a.cpos[j - 1] : 0u;            // the last read of the run before
-                s_jn[threadIdx.x] = k + 1 < nb ? a.bj[k + 1] : nc;      // where this run ends
-            }
-        }
-        block_sync();
-        if (threadIdx.x == 0) {
-            const uint32_t m = min(256u, nb - base);
-            for (uint32_t t = 0; t < m; ++t) {
-                const uint32_t j = s_j[t], b = s_b[t];
-                const int32_t rid = s_rid[t];
-                if (j != j_first) { // where the run before has got to at its last read (the first read of all: the state that came in)
-                    uint32_t r2, d2;
-                    an_in_run(run, s_bl[t], r2, d2);
-                    rel = r2; s = s_bl[t] - d2;
-                }
-                // the recurrence itself (OverallNumbers.hpp:84-110)
-                if (first) { first = 0; id = rid; s = b; }
-                if (id != rid || b - s > 2u * BQC_VSIZE) { id = rid; rel += 2u; s = b; }
-                uint32_t p = b - s;
-                if (p > BQC_VSIZE && p < 2u * BQC_VSIZE) { rel += 1u; s += BQC_VSIZE; p -= BQC_VSIZE; }
-                run.b_e = b; run.s_e = s; run.rel_e = rel; run.stuck = p == 2u * BQC_VSIZE ? 1u : 0u; run.b_star = b;
-                if (run.stuck) // the first read of the run further right (reads at the same position come first: the run is sorted)
-                    for (uint32_t q = j + 1; q < s_jn[t]; ++q) { const uint32_t bq = a.cpos[q]; if (bq != b) { run.b_star = bq; break; } }
-                a.runs[base + t] = run;
-            }
-        }
-    }
-    if (threadIdx.x == 0) { // behind the batch's last candidate
-        uint32_t r2, d2;
-        const uint32_t bl = a.cpos[nc - 1];
-        an_in_run(run, bl, r2, d2);
-        AnchorState out = st;
-        out.first = 0; out.id = id; out.shift = (int32_t)(bl - d2); out.pad = 0; out.win = st.win + r2;
-        if (st.pending) { out.pending = 0; out.has_prev = 1; out.prev_rid = a.crid[j_first]; out.prev_bp = a.cpos[j_first]; }
-        *a.state = out;
-        a.sum->after = out;
-        a.sum->last_rel = r2;
-    }
-}
-
-// several read groups: one workgroup per read group walks the breaks of its segment from its own state, as k_an_chain does for one
-// (the limit of breaks is the batch's: over it, every workgroup leaves its group's state alone)
-__global__ __launch_bounds__(256) void k_an_chain_g(AnchorArgs a)
-{
-    __shared__ uint32_t s_j[256], s_b[256], s_bl[256], s_jn[256], red[4];
-    __shared__ int32_t s_rid[256];
-    const uint32_t l = blockIdx.x, nl = a.n_lanes, nb = a.sum->n_breaks, nc_all = a.sum->n_cand, nblk = (a.n + 1023u) / 1024u;
-    // the group's reads (workgroup 0: also those out of range), where its candidates lie, and how many groups in front of it have any
-    uint32_t r = 0, bad = 0;
-    for (uint32_t k = threadIdx.x; k < nblk; k += 256u) { r += a.blk_r[(size_t)(l + 1) * nblk + k]; if (l == 0) bad += a.blk_r[k]; }
-    auto cand_at = [&](uint32_t g) { return nblk == 0 ? 0u : g < nl ? a.blk_c[(size_t)g * nblk] : nc_all; };
-    const uint32_t c0 = cand_at(l), c1 = cand_at(l + 1);
-    r = block_sum256(r, red);
-    bad = block_sum256(bad, red);
-    const AnchorState st = a.state[l];
-    if (threadIdx.x == 0) {
-        AnchorLane L{};
-        L.before = st; L.after = st; L.n_cand = c1 - c0; L.n_reads = r; L.cand_off = c0; L.first_off = 0; L.last_rel = 0; // (first_off: k_an_first_offs)
-        a.lanes[l] = L;
-        if (l == 0) a.sum->n_bad = bad;
-    }
-    if (nb > AN_MAX_BREAKS) { if (threadIdx.x == 0) atomicOr(&a.sum->flags, AN_FLAG_TOO_MANY_BREAKS); return; }
-    if (c1 == c0) return;
-    uint32_t first = st.first, s = (uint32_t)st.shift, rel = 0;
-    int32_t id = st.id;
-    AnchorRun run{};
-    const uint32_t b_lo = a.crun[c0], b_hi = a.crun[c1 - 1] + 1u; // (the group's first candidate is a break: its breaks are [b_lo, b_hi))
     for (uint32_t base = b_lo; base < b_hi; base += 256u) {
         block_sync();
         {
@@ -454,7 +363,7 @@ __global__ __launch_bounds__(256) void k_an_chain_g(AnchorArgs a)
             if (k < b_hi) {
                 const uint32_t j = a.bj[k];
                 s_j[threadIdx.x] = j; s_b[threadIdx.x] = a.cpos[j]; s_rid[threadIdx.x] = a.crid[j];
-                s_bl[threadIdx.x] = j > c0 ? a.cpos[j - 1] : 0u;        // the last read of the run before
+                s_bl[threadIdx.x] = j > j_first ? a.cpos[j - 1] : 0u;  // the last read of the run before
                 s_jn[threadIdx.x] = k + 1 < b_hi ? a.bj[k + 1] : c1;    // where this run ends
             }
         }
@@ -463,55 +372,81 @@ __global__ __launch_bounds__(256) void k_an_chain_g(AnchorArgs a)
             const uint32_t m = min(256u, b_hi - base);
             for (uint32_t t = 0; t < m; ++t) {
                 const uint32_t j = s_j[t], b = s_b[t];
-                const int32_t rid = s_rid[t];
-                if (j != c0) {
+                if (j != j_first) { // where the run before has got to at its last read (the first read of all: the state that came in)
                     uint32_t r2, d2;
                     an_in_run(run, s_bl[t], r2, d2);
                     rel = r2; s = s_bl[t] - d2;
                 }
-                if (first) { first = 0; id = rid; s = b; }
-                if (id != rid || b - s > 2u * BQC_VSIZE) { id = rid; rel += 2u; s = b; }
-                uint32_t p = b - s;
-                if (p > BQC_VSIZE && p < 2u * BQC_VSIZE) { rel += 1u; s += BQC_VSIZE; p -= BQC_VSIZE; }
+                const uint32_t p = an_step(first, id, s, rel, s_rid[t], b);
                 run.b_e = b; run.s_e = s; run.rel_e = rel; run.stuck = p == 2u * BQC_VSIZE ? 1u : 0u; run.b_star = b;
-                if (run.stuck)
+                if (run.stuck) // the first read of the run further right (reads at the same position come first: the run is sorted)
                     for (uint32_t q = j + 1; q < s_jn[t]; ++q) { const uint32_t bq = a.cpos[q]; if (bq != b) { run.b_star = bq; break; } }
                 a.runs[base + t] = run;
             }
         }
     }
-    if (threadIdx.x == 0) { // behind the group's last candidate
-        uint32_t r2, d2;
-        const uint32_t bl = a.cpos[c1 - 1];
-        an_in_run(run, bl, r2, d2);
-        AnchorState out = st;
-        out.first = 0; out.id = id; out.shift = (int32_t)(bl - d2); out.pad = 0; out.win = st.win + r2;
+    uint32_t d2;
+    const uint32_t bl = a.cpos[c1 - 1];
+    an_in_run(run, bl, last_rel, d2);
+    AnchorState out = st;
+    out.first = 0; out.id = id; out.shift = bl - d2; out.pad = 0; out.win = st.win + last_rel;
+    return out;
+}
+} // namespace
+
+// <false>: one workgroup for the batch's one read group — with the set-aside prologue and epilogue of a shard in the middle of the
+// stream; also launched alone for an empty batch.  <true>: one workgroup per read group walks the breaks of its segment from its own
+// state (the limit of breaks is the batch's: over it, every workgroup leaves its group's state alone).  Both fill the group's
+// AnchorLane on every path: the host reads its before / after whatever happened.
+template <bool G>
+__global__ __launch_bounds__(256) void k_an_chain(AnchorArgs a)
+{
+    const uint32_t l = G ? blockIdx.x : 0u, nb = a.sum->n_breaks, nc_all = a.sum->n_cand;
+    uint32_t c0 = 0, c1 = nc_all, n_reads = a.n;
+    if (G) { // the group's reads (workgroup 0: also those out of range) and where its candidates lie
+        __shared__ uint32_t red[4];
+        const uint32_t nl = a.n_lanes, nblk = (a.n + 1023u) / 1024u;
+        uint32_t r = 0, bad = 0;
+        for (uint32_t k = threadIdx.x; k < nblk; k += 256u) { r += a.blk_r[(size_t)(l + 1) * nblk + k]; if (l == 0) bad += a.blk_r[k]; }
+        auto cand_at = [&](uint32_t g) { return nblk == 0 ? 0u : g < nl ? a.blk_c[(size_t)g * nblk] : nc_all; };
+        c0 = cand_at(l); c1 = cand_at(l + 1);
+        n_reads = block_sum256(r, red);
+        bad = block_sum256(bad, red);
+        if (l == 0 && threadIdx.x == 0) a.sum->n_bad = bad;
+    }
+    const AnchorState st = a.state[l];
+    if (threadIdx.x == 0) {
+        AnchorLane L{};
+        L.before = st; L.after = st; L.n_cand = c1 - c0; L.n_reads = n_reads; L.cand_off = c0; // (first_off: 0, or k_an_first_offs)
+        a.lanes[l] = L;
+    }
+    if (nb > AN_MAX_BREAKS) { if (threadIdx.x == 0) atomicOr(&a.sum->flags, AN_FLAG_TOO_MANY_BREAKS); return; }
+    if (c1 == c0) return;
+    // setting aside: the candidates in front of the first certain reset are pending; the chain starts AT that read — a break — from the
+    // context's own state (a stream that begins there)
+    uint32_t j_first = c0;
+    if (!G && st.pending) {
+        const uint32_t fc = a.sum->first_certain;
+        j_first = fc == 0xFFFFFFFFu ? c1 : fc;
+        if (threadIdx.x == 0) a.sum->n_pending = j_first;
+        if (j_first == c1) { // every candidate of the batch is set aside
+            if (threadIdx.x == 0) {
+                AnchorState out = st;
+                out.has_prev = 1; out.prev_rid = a.crid[c1 - 1]; out.prev_bp = a.cpos[c1 - 1];
+                a.state[l] = out;
+                a.lanes[l].after = out;
+            }
+            return;
+        }
+    }
+    // (a segment's first candidate and a certain reset are breaks: the segment's anchored breaks are [crun[j_first], crun[c1 - 1]])
+    uint32_t last_rel;
+    AnchorState out = an_walk(a, c1, a.crun[j_first], a.crun[c1 - 1] + 1u, j_first, st, last_rel);
+    if (threadIdx.x == 0) {
+        if (!G && st.pending) { out.pending = 0; out.has_prev = 1; out.prev_rid = a.crid[j_first]; out.prev_bp = a.cpos[j_first]; }
         a.state[l] = out;
         a.lanes[l].after = out;
-        a.lanes[l].last_rel = r2;
-    }
-}
-
-// ---- every candidate's anchor ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_an_apply(AnchorArgs a)
-{
-    if (a.sum->flags & AN_FLAG_TOO_MANY_BREAKS) return;
-    const uint32_t nc = a.sum->n_cand, j = blockIdx.x * 256u + threadIdx.x;
-    if (j >= nc) return;
-    const uint32_t i = a.cidx[j], np = a.sum->n_pending;
-    if (j < np) { a.cov_out[i] = CovEntry{BQC_COV_PENDING, j}; return; } // set aside: its place in the batch's pending log
-    uint32_t rel, delta;
-    an_in_run(a.runs[a.crun[j]], a.cpos[j], rel, delta);
-    a.cov_out[i] = CovEntry{rel, delta};
-    bool boundary = j == np;
-    if (j != np) {
-        uint32_t relp, dp;
-        an_in_run(a.runs[a.crun[j - 1]], a.cpos[j - 1], relp, dp);
-        boundary = relp != rel;
-    }
-    if (boundary) {
-        if (rel < a.first_cap) a.first_of[rel] = i;
-        else atomicOr(&a.sum->flags, AN_FLAG_BOUND_OVERFLOW);
+        a.lanes[l].last_rel = last_rel;
     }
 }
 
@@ -527,15 +462,19 @@ __global__ __launch_bounds__(256) void k_an_first_offs(AnchorArgs a)
     if (l < a.n_lanes) a.lanes[l].first_off = off;
 }
 
-// several read groups: the window of a candidate relative to ITS group's window at batch entry; first_of per group
-__global__ __launch_bounds__(256) void k_an_apply_g(AnchorArgs a)
+// ---- every candidate's anchor ------------------------------------------------------------------------------------------------
+// closed form from its run's entry -> {window relative to ITS group's window at batch entry, offset}; the candidates at which the
+// window changes go to their group's first_of segment
+template <bool G>
+__global__ __launch_bounds__(256) void k_an_apply(AnchorArgs a)
 {
     if (a.sum->flags & AN_FLAG_TOO_MANY_BREAKS) return;
     const uint32_t nc = a.sum->n_cand, j = blockIdx.x * 256u + threadIdx.x;
     if (j >= nc) return;
     const uint32_t i = a.cidx[j];
-    const AnchorLane& L = a.lanes[a.clane[j]];
-    const uint32_t c0 = L.cand_off;
+    const AnchorLane& L = a.lanes[G ? a.clane[j] : 0u];
+    const uint32_t c0 = G ? L.cand_off : a.sum->n_pending; // the group's first anchored candidate
+    if (!G && j < c0) { a.cov_out[i] = CovEntry{BQC_COV_PENDING, j}; return; } // set aside: its place in the batch's pending log
     uint32_t rel, delta;
     an_in_run(a.runs[a.crun[j]], a.cpos[j], rel, delta);
     a.cov_out[i] = CovEntry{rel, delta};
@@ -600,34 +539,28 @@ extern "C" void bqc_launch_lane_order(const uint8_t* lane, uint32_t n, uint32_t 
     hipLaunchKernelGGL(k_lo_scatter, dim3(nblk), dim3(256), 0, s, lane, n, nl, bits_for(nl), tmp, order);
 }
 
+template <bool G>
+static void launch_anchor(const AnchorArgs& a, hipStream_t s)
+{
+    const uint32_t nblk = (a.n + 1023u) / 1024u; // (also the grid of the candidates' passes: n_cand <= n is only known on the card)
+    if (a.n) hipLaunchKernelGGL(k_an_count<G>, dim3(nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, G ? a.blk_c : a.blk_a, G ? nblk * a.n_lanes : nblk, nblk, a.sum, a.parts, 0); // (starts the summary)
+    if (a.n) {
+        hipLaunchKernelGGL(G ? k_an_scatter_g : k_an_scatter, dim3(nblk), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_an_bcount<G>, dim3(nblk), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_b, nblk, nblk, a.sum, a.parts, 1);
+        hipLaunchKernelGGL(k_an_bscatter<G>, dim3(nblk), dim3(256), 0, s, a);
+    }
+    hipLaunchKernelGGL(k_an_chain<G>, dim3(G ? a.n_lanes : 1u), dim3(256), 0, s, a); // (an empty batch: fills the groups' state fields)
+    if (a.n) {
+        if (G) hipLaunchKernelGGL(k_an_first_offs, dim3(1), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_an_apply<G>, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
+    }
+}
+
 extern "C" void bqc_launch_anchor(const AnchorArgs& a_in, hipStream_t s)
 {
     AnchorArgs a = a_in;
-    const uint32_t nblk = (a.n + 1023u) / 1024u; // (also the grid of the candidates' passes: n_cand <= n is only known on the card)
-    if (a.n_lanes > 1) { // several read groups
-        a.lane_bits = bits_for(a.n_lanes - 1u);
-        if (a.n) hipLaunchKernelGGL(k_an_count<true>, dim3(nblk), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_c, nblk * a.n_lanes, nblk, a.sum, a.parts, 0); // (starts the summary)
-        if (a.n) {
-            hipLaunchKernelGGL(k_an_scatter_g, dim3(nblk), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_an_bcount<true>, dim3(nblk), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_b, nblk, nblk, a.sum, a.parts, 1);
-            hipLaunchKernelGGL(k_an_bscatter<true>, dim3(nblk), dim3(256), 0, s, a);
-        }
-        hipLaunchKernelGGL(k_an_chain_g, dim3(a.n_lanes), dim3(256), 0, s, a);
-        if (a.n) {
-            hipLaunchKernelGGL(k_an_first_offs, dim3(1), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_an_apply_g, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
-        }
-        return;
-    }
-    if (a.n) hipLaunchKernelGGL(k_an_count<false>, dim3(nblk), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_a, nblk, nblk, a.sum, a.parts, 0); // (starts the summary)
-    if (!a.n) { hipLaunchKernelGGL(k_an_chain, dim3(1), dim3(256), 0, s, a); return; }
-    hipLaunchKernelGGL(k_an_scatter, dim3(nblk), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_an_bcount<false>, dim3(nblk), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_an_scan, dim3(1), dim3(1024), 0, s, a.blk_b, nblk, nblk, a.sum, a.parts, 1);
-    hipLaunchKernelGGL(k_an_bscatter<false>, dim3(nblk), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_an_chain, dim3(1), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_an_apply, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
+    if (a.n_lanes > 1) { a.lane_bits = bits_for(a.n_lanes - 1u); launch_anchor<true>(a, s); } // several read groups
+    else launch_anchor<false>(a, s);
 }

@@ -8,33 +8,10 @@ import numpy as np
 import pytest
 
 from bamqc_amd import Aggregator, BamQCError, _abi, _lib, synth
+from tests.anchor_recurrence import reference_anchors
 from tests.hipmem import Hip
 
 pytestmark = pytest.mark.gpu
-
-
-def reference_anchors(cols, state, n_refs, main):
-    """the recurrence itself, one read at a time: returns (win relative to the batch's first window or 0xFFFFFFFF, offset) per read"""
-    n = len(cols["flag"])
-    win = np.full(n, 0xFFFFFFFF, np.uint64)
-    off = np.zeros(n, np.uint32)
-    first, sid, shift, w = state
-    base = w
-    M = 1 << 32
-    for i in range(n):
-        f, rid = int(cols["flag"][i]), int(cols["rid"][i])
-        if (f & 0xD04) or not (f & 0xC0) or not (0 <= rid < n_refs) or not main[rid] or int(cols["lane"][i]) >= 1:
-            continue
-        b = int(cols["pos"][i]) % M
-        if first:
-            first, sid, shift = False, rid, b
-        if sid != rid or (b - shift) % M > 2000:
-            sid, shift, w = rid, b, w + 2
-        p = (b - shift) % M
-        if 1000 < p < 2000:
-            w, shift, p = w + 1, (shift + 1000) % M, p - 1000
-        win[i], off[i] = w - base, p
-    return win, off, (first, sid, shift, w)
 
 
 def device_batch(hip, cols):

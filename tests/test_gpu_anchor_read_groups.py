@@ -13,6 +13,7 @@ import pytest
 
 from bamqc_amd import Aggregator, BamQCError, _abi, _lib, hostio, synth
 from tests import synth as tsynth
+from tests.anchor_recurrence import NO_WIN, per_group_anchors
 from tests.cli_oracle import oracle_bamqualcheck
 from tests.hipmem import Hip
 from tests.parity import run_oracle
@@ -21,34 +22,6 @@ from tests.test_gpu_anchor import device_batch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "bin", "bamqualcheck")
-NO_WIN = 0xFFFFFFFF
-
-
-def per_group_anchors(cols, states, n_lanes, n_refs):
-    """the recurrence one read at a time, a state (first, chromosome, shift, window) per read group: returns (window relative to the
-    read's group's window at batch entry, or NO_WIN; offset) per read, and the states behind the batch"""
-    n = len(cols["flag"])
-    win = np.full(n, NO_WIN, np.uint64)
-    off = np.zeros(n, np.uint32)
-    states = [list(s) for s in states]
-    base = [s[3] for s in states]
-    M = 1 << 32
-    for i in range(n):
-        f, rid, lane = int(cols["flag"][i]), int(cols["rid"][i]), int(cols["lane"][i])
-        if (f & 0xD04) or not (f & 0xC0) or not (0 <= rid < n_refs) or lane >= n_lanes:
-            continue
-        first, sid, shift, w = states[lane]
-        b = int(cols["pos"][i]) % M
-        if first:
-            first, sid, shift = False, rid, b
-        if sid != rid or (b - shift) % M > 2000:
-            sid, shift, w = rid, b, w + 2
-        p = (b - shift) % M
-        if 1000 < p < 2000:
-            w, shift, p = w + 1, (shift + 1000) % M, p - 1000
-        states[lane] = [first, sid, shift, w]
-        win[i], off[i] = w - base[lane], p
-    return win, off, states
 
 
 def enqueue(lib, agg, hip, cols):
@@ -283,6 +256,42 @@ def test_too_many_breaks_in_one_group_leave_every_group_to_the_host():
         assert not diffs, diffs[:10]
         dev.close()
         host.close()
+    finally:
+        hip.free()
+
+
+def test_reset_starts_every_read_group_over_on_the_card():
+    """three read groups: an anchored batch that leaves every group on the second contig, bqc_reset, then a second anchored stream that
+    starts on the first contig — every group's first read is a FIRST read again (not a reset out of the windows of the stream before:
+    two windows flushed too many), so anchors and final counts equal those of a fresh context given only the second stream"""
+    lib = _lib.load()
+    refs = refs_for(17)
+    before = synth.batch(17, 30_000, LENS, refs, n_lanes=3)
+    stream = split(synth.batch(18, 40_000, LENS, refs, n_lanes=3), 2)
+    hip = Hip()
+    try:
+        used, fresh = contexts(refs, 3)
+        rc, rc2, b, h, _ = enqueue(lib, used, hip, before)
+        assert (rc, rc2) == (0, 0), (lib.bqc_anchor_error(used.h) or b"").decode()
+        assert lib.bqc_submit_anchored(used.h, C.byref(b), h, None) == 0
+        used.sync()
+        used.reset()
+        for agg in (used, fresh):
+            states = [(True, 0, 0, 0)] * 3
+            for cols in stream:
+                rc, rc2, b, h, cov = enqueue(lib, agg, hip, cols)
+                assert (rc, rc2) == (0, 0), (lib.bqc_anchor_error(agg.h) or b"").decode()
+                win, off, states = per_group_anchors(cols, states, 3, len(refs))
+                got = cov[:, 0].astype(np.uint64)
+                assert np.array_equal(got, win), (agg is used, np.flatnonzero(got != win)[:10])
+                cand = win != NO_WIN
+                assert np.array_equal(cov[cand, 1], off[cand])
+                assert lib.bqc_submit_anchored(agg.h, C.byref(b), h, None) == 0, (lib.bqc_last_error(agg.h) or b"").decode()
+                agg.sync()
+        diffs = _abi.diff_counts(fresh.finalize(), used.finalize())
+        assert not diffs, diffs[:10]
+        used.close()
+        fresh.close()
     finally:
         hip.free()
 

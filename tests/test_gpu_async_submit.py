@@ -14,7 +14,8 @@ from bamqc_amd import Aggregator, _abi, _lib, synth
 from tests import synth as tsynth
 from tests.hipmem import Hip
 from tests.parity import run_oracle, split
-from tests.test_gpu_anchor import device_batch, reference_anchors, with_positions
+from tests.anchor_recurrence import reference_anchors
+from tests.test_gpu_anchor import device_batch, with_positions
 from tests.test_gpu_fuzz import wild_batch
 
 pytestmark = pytest.mark.gpu
