@@ -60,9 +60,9 @@ struct AnchorSummary {
     uint32_t max_len_slow;
     uint32_t n_noqual;      // primary first / last records without qualities (check_read_len's message, QualityCheck.hpp:70-79)
     int32_t rid_min, rid_max; // range of the reference ids in [0, n_refs) the batch holds (rid_min > rid_max: none)
-    // (setting aside exists for one read group only: these are lanes[0]'s)
-    uint32_t n_pending;     // candidates set aside (the first n_pending of the batch's candidates: a shard_tail context)
-    uint32_t first_certain; // candidate index of the first read that resets whatever the state (0xFFFFFFFF: none; only looked for while setting aside)
+    uint32_t n_pending;     // candidates set aside, all read groups together (a shard_tail context): the length of the batch's pending log
+    uint32_t first_certain; // one read group: candidate index of the first read that resets whatever the state (0xFFFFFFFF: none; only
+                            // looked for while setting aside).  Several: every group has its own (AnchorArgs::lane_fc)
     uint32_t n_bad;         // reads whose lane is >= n_lanes (they end the run on the card: k_prep's check 2); counted with several read groups only
     uint32_t pad;
     unsigned long long seq_bytes, qual_bytes, cigar_words; // payload sizes: sums of ceil(l_seq / 2), l_seq, n_cigar
@@ -75,6 +75,11 @@ struct AnchorLane {
     uint32_t cand_off;        // its first candidate in the compaction (the candidates grouped by read group, stream order inside a group)
     uint32_t first_off;       // its segment of first_of: last_rel + 1 entries (none when it has no anchored candidate), the groups' back to back
     uint32_t last_rel;        // window (relative to before.win) of its last candidate
+    // a shard_tail context whose read group is still setting aside (before.pending): the group's first n_pending candidates are set
+    // aside — those in front of ITS first certain reset —, and their entries of the batch's pending log are pend_base .. pend_base +
+    // n_pending - 1, in stream order (the groups' parts back to back in group order; resolve steps one state per group, so any log
+    // that keeps a group's reads in stream order is the stream's)
+    uint32_t n_pending, pend_base;
     uint32_t pad;
 };
 #define AN_FLAG_TOO_MANY_BREAKS 1u // not anchored: the state is untouched, the caller takes the host's recurrence for this batch
@@ -108,6 +113,7 @@ struct AnchorPart { // what a workgroup of k_an_count (1024 reads) knows; summed
 struct AnchorArgs {
     uint32_t n, n_refs, n_lanes, no_fast;
     uint32_t lane_bits;         // several read groups: ballots that tell the read groups apart (ceil(log2(n_lanes)))
+    uint32_t set_aside;         // several read groups: a shard_tail context that is not resolved — some state[] may be pending
     const uint16_t* flag; const uint8_t* lane; const int32_t* rid; const int32_t* pos; const uint32_t* l_seq; const uint16_t* n_cigar;
     const uint8_t* main_chrom;
     CovEntry* cov_out;          // [n]
@@ -129,6 +135,10 @@ struct AnchorArgs {
     AnchorPart* parts;          // [n / 1024 + 2]
     uint32_t* blk_c;            // several read groups: [n_lanes][n / 1024 + 2] candidates per read group and workgroup (scanned in place)
     uint32_t* blk_r;            // ... [n_lanes + 1][n / 1024 + 2] reads per workgroup and bin (bin 0: lane >= n_lanes, bin l + 1: read group l)
+    // several read groups, set_aside: every group's first certain reset (candidate index; 0xFFFFFFFF: none), and the batch's pending log
+    // (chromosome, beginPos and read group of the reads set aside, by their index in the log)
+    uint32_t* lane_fc;          // [n_lanes]
+    int32_t* plog_rid; uint32_t* plog_bp; uint8_t* plog_lane; // [n]
 };
 
 extern "C" void bqc_launch_anchor(const AnchorArgs& a, hipStream_t s);

@@ -115,8 +115,9 @@ struct bqc_anchored {
     AnchorLane* h_lanes = nullptr;    // ... its per-group part behind it (n_lanes entries) ...
     uint32_t* h_bound = nullptr;      // ... and the first kInline entries of first_of[] (anchor.h)
     std::vector<uint32_t> rest;       // the entries behind them (sparse data), fetched by bqc_anchor_complete
-    std::vector<int32_t> pend_rid;    // a shard_tail context: the reads set aside (the batch's first n_pending candidates) ...
-    std::vector<uint32_t> pend_bp;    // ... chromosome and beginPos, for the pending log (bqc_shard_resolve)
+    std::vector<int32_t> pend_rid;    // a shard_tail context: the reads set aside (the batch's pending log, AnchorLane::pend_base) ...
+    std::vector<uint32_t> pend_bp;    // ... chromosome and beginPos, for the pending log (bqc_shard_resolve) ...
+    std::vector<uint8_t> pend_lane;   // ... and with several read groups the read group
     const CovEntry* d_cov = nullptr;  // the caller's device buffer with the anchors of the batch's reads
     uint32_t n = 0;
     bool completed = false;
@@ -129,6 +130,7 @@ struct AnchorEngine {
     AnchorSummary* d_sum = nullptr;   // the summary, and AnchorLane[n_lanes] behind it
     uint32_t* d_bound = nullptr;
     void* d_scratch = nullptr;
+    const uint32_t* d_plog_bp = nullptr; const int32_t* d_plog_rid = nullptr; const uint8_t* d_plog_lane = nullptr; // the outstanding batch's pending log (in the scratch)
     size_t cap_n = 0;                 // reads the scratch buffers are sized for
     std::mutex m;                     // the free list and `outstanding` (handles come back from the submitting thread)
     std::vector<bqc_anchored*> free_list, all;

@@ -327,8 +327,8 @@ static int first_from_table(bqc_ctx* c, const bqc_anchored* a, size_t off, size_
     return 0;
 }
 
-// (a read group has windows in the table when it has candidates that were not set aside — setting aside exists for one group only)
-static bool lane_anchored(const AnchorSummary& S, const AnchorLane* AL, uint32_t l) { return AL[l].n_cand > (l == 0 ? S.n_pending : 0u); }
+// (a read group has windows in the table when it has candidates that were not set aside)
+static bool lane_anchored(const AnchorLane* AL, uint32_t l) { return AL[l].n_cand > AL[l].n_pending; }
 static void load_state(LaneCov& lc, const AnchorState& s) { lc.first = s.first != 0; lc.id = s.id; lc.shift = s.shift; lc.win = s.win; } // (batch_base: the planner's)
 
 static int host_pass_anchored(bqc_ctx* c, uint32_t n, const bqc_anchored* a, HostPass& H)
@@ -345,23 +345,24 @@ static int host_pass_anchored(bqc_ctx* c, uint32_t n, const bqc_anchored* a, Hos
     H.order.clear(); // (made on the card: submit_impl)
     H.n_pending = 0;
     if (S.n_pending) { // a shard in the middle of the stream: the reads set aside go to the pending log, as host_pass would have put them there
-        ShardCtx& sh = c->shard;
+        ShardCtx& sh = c->shard; // (the card's log is grouped by read group, stream order inside a group: resolve steps one state per group)
         sh.batches.emplace_back();
         PendBatch& pb = sh.batches.back();
-        pb.lane.assign(S.n_pending, 0);
+        if (nl > 1) pb.lane = a->pend_lane; else pb.lane.assign(S.n_pending, 0);
         pb.rid = a->pend_rid;
         pb.bp = a->pend_bp;
         H.n_pending = S.n_pending;
     }
-    if (c->shard.tail) { // (anchored on the card with one read group only)
-        const AnchorState& A = AL[0].after;
-        c->shard.pending[0] = A.pending ? 1 : 0; c->shard.has_prev[0] = A.has_prev ? 1 : 0; c->shard.prev_rid[0] = A.prev_rid; c->shard.prev_bp[0] = A.prev_bp;
-    }
+    if (c->shard.tail) // every group's set-aside state behind the batch: the host's pass finds it current if it has to take over
+        for (uint32_t l = 0; l < nl; ++l) {
+            const AnchorState& A = AL[l].after;
+            c->shard.pending[l] = A.pending ? 1 : 0; c->shard.has_prev[l] = A.has_prev ? 1 : 0; c->shard.prev_rid[l] = A.prev_rid; c->shard.prev_bp[l] = A.prev_bp;
+        }
     // every group's state in front of the batch, as the planner wants to find it; its window table; its state behind the batch
     for (uint32_t l = 0; l < nl; ++l) load_state(c->cov[l], AL[l].before);
     CovPlanner plan(c, H, n);
     for (uint32_t l = 0; l < nl; ++l) {
-        if (!lane_anchored(S, AL, l)) continue;
+        if (!lane_anchored(AL, l)) continue;
         const int rc = first_from_table(c, a, AL[l].first_off, (size_t)AL[l].last_rel + 1, H.lane_first[l]);
         if (rc) return rc;
         plan.last_rel[l] = AL[l].last_rel;
@@ -859,9 +860,10 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     *out = nullptr;
     AnchorEngine& E = c->anchor;
     // the whole stream from its first batch on (a shard that starts inside the stream sets its first reads aside on the card as the host's
-    // pass would — AnchorState::pending — with one read group; with several, such a shard is the host's)
+    // pass would, read group by read group — AnchorState::pending)
     const uint32_t nl = c->opt.n_lanes;
-    if ((c->shard.tail && (c->shard.resolved || nl > 1)) || E.mode.load() == 2) return 1;
+    if ((c->shard.tail && c->shard.resolved) || E.mode.load() == 2) return 1;
+    const bool log_groups = c->shard.tail && nl > 1; // the pending log of a batch with several read groups: made by k_an_apply
     {   // (one batch at a time: the scratch buffers hold the summary and window table of the one enqueued before until it is completed)
         std::lock_guard<std::mutex> lk(E.m);
         if (E.outstanding) { E.err = "bqc_anchor_enqueue: the batch enqueued before has not been completed or discarded"; return -BQC_ERR_STATE; }
@@ -876,12 +878,13 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
     }
     const size_t first_extra = anchor_first_extra(nl);
     if (E.cap_n < n) { // scratch: [cpos crid cidx crun](4 B x n) [bound](8 B x n + extra) [bj][runs][blk_a][blk_b][parts] and, with several read groups, [blk_c][blk_r][clane]
+                       // — and for a shard that sets aside, [lane_fc](4 B x n_lanes) and the pending log [bp rid](4 B x n) [lane](n)
         if (hipStreamSynchronize(st) != hipSuccess) return anchor_fail(c, "stream failed");
         if (E.d_scratch) (void)hipFree(E.d_scratch);
         E.d_scratch = nullptr; E.cap_n = 0;
         const size_t cap = std::max<size_t>(n + n / 8, 1u << 20), nbk = cap / 1024 + 4;
         const size_t bytes = cap * 24 + 4 * first_extra + 64 + AN_MAX_BREAKS * (4 + sizeof(AnchorRun)) + nbk * (2 * 4 + sizeof(AnchorPart)) + 4096 +
-                             (nl > 1 ? 4 * nbk * (2 * (size_t)nl + 1) + cap + 1024 : 0);
+                             (nl > 1 ? 4 * nbk * (2 * (size_t)nl + 1) + cap + 1024 : 0) + (log_groups ? 4 * (size_t)nl + 9 * cap + 1024 : 0);
         if (hipMalloc(&E.d_scratch, bytes) != hipSuccess) return anchor_fail(c, "out of device memory");
         E.cap_n = cap;
     }
@@ -902,7 +905,7 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
         std::lock_guard<std::mutex> lk(E.m);
         E.all.push_back(a);
     }
-    a->rest.clear(); a->pend_rid.clear(); a->pend_bp.clear(); a->completed = false; a->n = (uint32_t)n; a->d_cov = (const CovEntry*)d_cov;
+    a->rest.clear(); a->pend_rid.clear(); a->pend_bp.clear(); a->pend_lane.clear(); a->completed = false; a->n = (uint32_t)n; a->d_cov = (const CovEntry*)d_cov;
     AnchorArgs A{};
     A.n = (uint32_t)n; A.n_refs = c->opt.n_refs; A.n_lanes = nl; A.no_fast = c->no_fast ? 1u : 0u;
     A.flag = b->flag; A.lane = b->lane; A.rid = b->rid; A.pos = b->pos; A.l_seq = b->l_seq; A.n_cigar = b->n_cigar;
@@ -921,6 +924,16 @@ extern "C" int bqc_anchor_enqueue(bqc_ctx* c, const bqc_batch* b, void* d_cov, v
         q += sizeof(AnchorPart) * nbk;
         q = (char*)(((uintptr_t)q + 255) & ~(uintptr_t)255);
         A.blk_c = (uint32_t*)q; q += 4 * nbk * nl; A.blk_r = (uint32_t*)q; q += 4 * nbk * ((size_t)nl + 1); A.clane = (uint8_t*)q;
+    }
+    E.d_plog_bp = A.cpos; E.d_plog_rid = A.crid; E.d_plog_lane = nullptr; // (one read group: the first candidates ARE the log)
+    if (log_groups) {
+        q += cap;
+        q = (char*)(((uintptr_t)q + 255) & ~(uintptr_t)255);
+        A.set_aside = 1;
+        A.lane_fc = (uint32_t*)q; q += 4 * (size_t)nl;
+        q = (char*)(((uintptr_t)q + 255) & ~(uintptr_t)255);
+        A.plog_bp = (uint32_t*)q; q += 4 * cap; A.plog_rid = (int32_t*)q; q += 4 * cap; A.plog_lane = (uint8_t*)q;
+        E.d_plog_bp = A.plog_bp; E.d_plog_rid = A.plog_rid; E.d_plog_lane = A.plog_lane;
     }
     E.d_bound = A.first_of;
     const size_t n_first = std::min<size_t>(2 * n + first_extra, A.first_cap); // (windows a batch of n reads can reach)
@@ -962,18 +975,20 @@ extern "C" int bqc_anchor_complete(bqc_ctx* c, bqc_anchored* a, bqc_anchor_info*
     const size_t K = bqc_anchored::kInline;
     size_t end = 0;
     for (uint32_t l = 0; l < nl; ++l)
-        if (lane_anchored(S, a->h_lanes, l)) end = std::max(end, (size_t)a->h_lanes[l].first_off + a->h_lanes[l].last_rel + 1);
+        if (lane_anchored(a->h_lanes, l)) end = std::max(end, (size_t)a->h_lanes[l].first_off + a->h_lanes[l].last_rel + 1);
     if (end > 2 * E.cap_n + anchor_first_extra(nl)) return anchor_fail(c, "internal error: a window table lies outside the anchors' scratch");
     if (end > K) {
         a->rest.resize(end - K);
         if (hipSetDevice(c->device) != hipSuccess ||
             hipMemcpy(a->rest.data(), E.d_bound + K, sizeof(uint32_t) * a->rest.size(), hipMemcpyDeviceToHost) != hipSuccess) return anchor_fail(c, "copy failed");
     }
-    if (S.n_pending) { // the reads set aside: chromosome and position of the batch's first n_pending candidates (the scratch's crid / cpos)
+    if (S.n_pending) { // the reads set aside: the batch's pending log — chromosome, position and, with several read groups, the group
+        if (S.n_pending > a->n) return anchor_fail(c, "internal error: more reads set aside than the batch holds");
         a->pend_rid.resize(S.n_pending); a->pend_bp.resize(S.n_pending);
-        const char* q = (const char*)E.d_scratch;
-        if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(a->pend_bp.data(), q, 4ull * S.n_pending, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(a->pend_rid.data(), q + 4 * E.cap_n, 4ull * S.n_pending, hipMemcpyDeviceToHost) != hipSuccess) return anchor_fail(c, "copy failed");
+        if (E.d_plog_lane) a->pend_lane.resize(S.n_pending);
+        if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(a->pend_bp.data(), E.d_plog_bp, 4ull * S.n_pending, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(a->pend_rid.data(), E.d_plog_rid, 4ull * S.n_pending, hipMemcpyDeviceToHost) != hipSuccess ||
+            (E.d_plog_lane && hipMemcpy(a->pend_lane.data(), E.d_plog_lane, S.n_pending, hipMemcpyDeviceToHost) != hipSuccess)) return anchor_fail(c, "copy failed");
     }
     a->completed = true;
     return 0;

@@ -1289,7 +1289,7 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         if (actx && anchors_ok_) {
             const int arc = bqc_anchor_enqueue(actx, &dv, pay + o_cov, I.s, &ah);
             if (arc < 0) return fail_dev(bqc_anchor_error(actx));
-            if (arc > 0) { anchors_ok_ = false; ah = nullptr; } // (a shard in the middle of the stream with several read groups, or the host has kept the state so far)
+            if (arc > 0) { anchors_ok_ = false; ah = nullptr; } // (the host has kept the state so far, or the context is a resolved shard)
         }
         auto columns_to_host = [&]() -> hipError_t {
             o.flag.resize(N); o.mapq.resize(N); o.lane.resize(N); o.rid.resize(N); o.pos.resize(N); o.tlen.resize(N);

@@ -31,8 +31,12 @@
 // first candidate of a segment; k_an_chain<true> walks each group's breaks from that group's state, one workgroup per group — the same
 // walk (an_walk) over other bounds; and each group gets its own first_of segment (k_an_first_offs: back to back, sized by the group's
 // last window).  With one read group the <false> instances run: no grouping to pay for, the group's part of the summary is lanes[0].
+// A shard that starts inside the stream (AnchorState::pending) sets each group's candidates aside up to THAT GROUP's first certain reset:
+// k_an_bcount looks for it inside every pending group's segment, k_an_chain starts the group's walk there, k_an_first_offs gives every
+// group its part of the batch's pending log, and k_an_apply writes the log (BQC_COV_PENDING anchors; chromosome, position and group of
+// each).  The groups leave the pending state independently, in different batches or never.
 // Checked against the host's recurrence (bqc_pipeline.cpp: CovPlanner) read by read on sorted, sparse, unsorted and wild inputs
-// (tests/test_gpu_anchor.py, tests/test_gpu_anchor_read_groups.py), and through every test that runs the program with the reader on
+// (tests/test_gpu_anchor.py, tests/test_gpu_anchor_read_groups.py, tests/test_gpu_anchor_shard_read_groups.py), and through every test that runs the program with the reader on
 // the card.
 #include "kernels_common.h"
 #include "anchor.h"
@@ -139,6 +143,7 @@ __global__ __launch_bounds__(256) void k_an_count(AnchorArgs a)
     if (G) {
         hc[threadIdx.x] = 0; hr[threadIdx.x] = 0;
         if (threadIdx.x == 0) hr[256] = 0;
+        if (a.set_aside && blockIdx.x == 0 && threadIdx.x < a.n_lanes) a.lane_fc[threadIdx.x] = 0xFFFFFFFFu; // (k_an_bcount takes the minimum)
         block_sync();
     }
     uint32_t c = 0, n_slow = 0, max_slow = 0, n_noqual = 0, s1 = 0, s2 = 0, s3 = 0;
@@ -321,6 +326,36 @@ __global__ __launch_bounds__(256) void k_an_bcount(AnchorArgs a)
         for (int o = 32; o > 0; o >>= 1) fc = min(fc, (uint32_t)__shfl_xor((int)fc, o));
         if (lane_id() == 0 && fc != 0xFFFFFFFFu) atomicMin(&a.parts[blockIdx.x].first_certain, fc); // (the workgroup's four waves; k_an_scan takes the minimum)
     }
+    if (G && a.set_aside) { // the same per read group, for the groups that are still setting aside: the predecessor is the candidate before
+                            // it in the group's segment, or for the segment's first the one the group's state remembers
+        uint32_t fg = 0xFFFFFFFFu, fj = 0xFFFFFFFFu; // this thread's first certain reset, and its group
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t j = j0 + k;
+            if (j >= nc) break;
+            const uint32_t g = a.clane[j];
+            if (g == fg) continue; // (only a group's first counts)
+            const AnchorState& S = a.state[g];
+            if (!S.pending) continue;
+            const bool inner = j != 0 && a.clane[j - 1] == g;
+            const bool has_prev = inner || S.has_prev != 0;
+            const int32_t prid = inner ? a.crid[j - 1] : S.prev_rid;
+            const uint32_t d = a.cpos[j] - (inner ? a.cpos[j - 1] : S.prev_bp);
+            if (!(has_prev && (a.crid[j] != prid || (d > 2u * BQC_VSIZE && d <= 0xFFFFFFFFu - 2u * BQC_VSIZE)))) continue;
+            if (fj != 0xFFFFFFFFu) atomicMin(&a.lane_fc[fg], fj); // (a thread whose four candidates span two pending groups)
+            fg = g; fj = j;
+        }
+        // a wave's candidates are nearly always one group's: one atomic for the wave then
+        const uint64_t has = __ballot(fj != 0xFFFFFFFFu);
+        if (has) {
+            const uint32_t g0 = (uint32_t)__shfl((int)fg, __ffsll((long long)has) - 1);
+            if (__ballot(fj != 0xFFFFFFFFu && fg != g0) == 0) {
+                uint32_t m = fj;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, o));
+                if (lane_id() == 0) atomicMin(&a.lane_fc[g0], m);
+            } else if (fj != 0xFFFFFFFFu) atomicMin(&a.lane_fc[fg], fj);
+        }
+    }
 }
 template <bool G>
 __global__ __launch_bounds__(256) void k_an_bscatter(AnchorArgs a)
@@ -394,10 +429,11 @@ __device__ __forceinline__ AnchorState an_walk(const AnchorArgs& a, uint32_t c1,
 }
 } // namespace
 
-// <false>: one workgroup for the batch's one read group — with the set-aside prologue and epilogue of a shard in the middle of the
-// stream; also launched alone for an empty batch.  <true>: one workgroup per read group walks the breaks of its segment from its own
-// state (the limit of breaks is the batch's: over it, every workgroup leaves its group's state alone).  Both fill the group's
-// AnchorLane on every path: the host reads its before / after whatever happened.
+// <false>: one workgroup for the batch's one read group; also launched alone for an empty batch.  <true>: one workgroup per read group
+// walks the breaks of its segment from its own state (the limit of breaks is the batch's: over it, every workgroup leaves its group's
+// state alone, the set-aside fields too).  Both with the set-aside prologue and epilogue of a shard in the middle of the stream, per
+// read group: the groups leave the pending state one by one, at their own first certain reset.  Both fill the group's AnchorLane on
+// every path: the host reads its before / after whatever happened.
 template <bool G>
 __global__ __launch_bounds__(256) void k_an_chain(AnchorArgs a)
 {
@@ -425,10 +461,10 @@ __global__ __launch_bounds__(256) void k_an_chain(AnchorArgs a)
     // setting aside: the candidates in front of the first certain reset are pending; the chain starts AT that read — a break — from the
     // context's own state (a stream that begins there)
     uint32_t j_first = c0;
-    if (!G && st.pending) {
-        const uint32_t fc = a.sum->first_certain;
+    if (st.pending) {
+        const uint32_t fc = G ? a.lane_fc[l] : a.sum->first_certain;
         j_first = fc == 0xFFFFFFFFu ? c1 : fc;
-        if (threadIdx.x == 0) a.sum->n_pending = j_first;
+        if (threadIdx.x == 0) { a.lanes[l].n_pending = j_first - c0; if (!G) a.sum->n_pending = j_first; } // (several groups: k_an_first_offs sums them)
         if (j_first == c1) { // every candidate of the batch is set aside
             if (threadIdx.x == 0) {
                 AnchorState out = st;
@@ -443,23 +479,28 @@ __global__ __launch_bounds__(256) void k_an_chain(AnchorArgs a)
     uint32_t last_rel;
     AnchorState out = an_walk(a, c1, a.crun[j_first], a.crun[c1 - 1] + 1u, j_first, st, last_rel);
     if (threadIdx.x == 0) {
-        if (!G && st.pending) { out.pending = 0; out.has_prev = 1; out.prev_rid = a.crid[j_first]; out.prev_bp = a.cpos[j_first]; }
+        if (st.pending) { out.pending = 0; out.has_prev = 1; out.prev_rid = a.crid[j_first]; out.prev_bp = a.cpos[j_first]; }
         a.state[l] = out;
         a.lanes[l].after = out;
         a.lanes[l].last_rel = last_rel;
     }
 }
 
-// several read groups: where each group's first_of segment lies — its last_rel + 1 entries, back to back in group order, so that the
-// host's inline copy of the table's head holds every group's windows of a dense batch (one workgroup, a thread per group)
+// several read groups: where each group's first_of segment lies — its last_rel + 1 entries (none when every candidate of the group was
+// set aside), back to back in group order, so that the host's inline copy of the table's head holds every group's windows of a dense
+// batch; and where each group's part of the batch's pending log lies — behind the earlier groups' (one workgroup, a thread per group)
 __global__ __launch_bounds__(256) void k_an_first_offs(AnchorArgs a)
 {
     __shared__ uint32_t wsum[4];
     const uint32_t l = threadIdx.x;
-    const uint32_t v = l < a.n_lanes && a.lanes[l].n_cand ? a.lanes[l].last_rel + 1u : 0u;
-    uint32_t total;
+    const bool in = l < a.n_lanes;
+    const uint32_t np = in ? a.lanes[l].n_pending : 0u;
+    const uint32_t v = in && a.lanes[l].n_cand > np ? a.lanes[l].last_rel + 1u : 0u;
+    uint32_t total, n_pending;
     const uint32_t off = block_excl(v, wsum, total);
-    if (l < a.n_lanes) a.lanes[l].first_off = off;
+    const uint32_t pbase = block_excl(np, wsum, n_pending);
+    if (in) { a.lanes[l].first_off = off; a.lanes[l].pend_base = pbase; }
+    if (l == 0) a.sum->n_pending = n_pending;
 }
 
 // ---- every candidate's anchor ------------------------------------------------------------------------------------------------
@@ -473,8 +514,13 @@ __global__ __launch_bounds__(256) void k_an_apply(AnchorArgs a)
     if (j >= nc) return;
     const uint32_t i = a.cidx[j];
     const AnchorLane& L = a.lanes[G ? a.clane[j] : 0u];
-    const uint32_t c0 = G ? L.cand_off : a.sum->n_pending; // the group's first anchored candidate
-    if (!G && j < c0) { a.cov_out[i] = CovEntry{BQC_COV_PENDING, j}; return; } // set aside: its place in the batch's pending log
+    const uint32_t c0 = G ? L.cand_off + L.n_pending : a.sum->n_pending; // the group's first anchored candidate
+    if (j < c0) { // set aside: its place in the batch's pending log (one group: the candidates' arrays are the log)
+        const uint32_t at = G ? L.pend_base + (j - L.cand_off) : j;
+        a.cov_out[i] = CovEntry{BQC_COV_PENDING, at};
+        if (G) { a.plog_rid[at] = a.crid[j]; a.plog_bp[at] = a.cpos[j]; a.plog_lane[at] = a.clane[j]; }
+        return;
+    }
     uint32_t rel, delta;
     an_in_run(a.runs[a.crun[j]], a.cpos[j], rel, delta);
     a.cov_out[i] = CovEntry{rel, delta};

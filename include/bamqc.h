@@ -227,10 +227,10 @@ int bqc_submit_async(bqc_ctx* ctx, const bqc_batch* batch, uint64_t* ticket);
  *                        which the columns are complete); d_cov: 8 bytes per read of device memory for the anchors, valid — like the
  *                        columns — until the batch's ticket is reported uploaded.  Returns 0 and a handle; 1: not available — a
  *                        batch has gone through bqc_submit* / bqc_upload before (the host then keeps the state for the rest of the
- *                        stream), or the context is a shard_tail context with several read groups (such a shard's per-group set-aside
- *                        is the host's); < 0: -BQC_ERR_*.  Any number of read groups (n_lanes) otherwise: one window state per read
- *                        group on the card, and the batch's processing order by read group is made there too.  (A shard_tail context
- *                        with one read group sets its first reads aside on the card exactly as bqc_submit* does on the host.)
+ *                        stream), or the context is a shard_tail context that bqc_shard_resolve has resolved; < 0: -BQC_ERR_*.  Any
+ *                        number of read groups (n_lanes): one window state per read group on the card, and the batch's processing
+ *                        order by read group is made there too.  A shard_tail context sets every read group's first reads aside on
+ *                        the card — up to that group's own first certain reset — exactly as bqc_submit* does on the host.
  *   bqc_anchor_complete  after the caller has synchronised `stream`: 0 = anchored; 1 = not anchored (more position breaks in the batch —
  *                        all read groups together — than the card's chains take: the card has left every group's state untouched; this batch and every later one
  *                        go through bqc_submit* with host columns); < 0: -BQC_ERR_* (bqc_anchor_error).  `info` (optional): what a
