@@ -22,8 +22,8 @@
 // record) is copied in front of the next run's bytes.  Every buffer is allocated in open(): allocations, releases and page-locking
 // behind a running inflate kernel wait for it.
 //
-// Record layout, tag types: the public SAM/BAM specification; the rules applied to a record are those of the host reader
-// (bam_io.cpp: next_batch, citing bamqualcheck.cpp:72-100 getLane, QualityCheck.hpp:201-209 NM, TripletCounting.hpp:113-127 AS).
+// What a record is — the chain's size rule, the test "a record may start here", the scan of the optional fields, the flag annotation —
+// is stated once, in host/bam_record.h, for the kernels here and for the host reader (bam_io.cpp); only the byte sources differ.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -42,6 +42,7 @@
 #include "../../include/bamqc.h"
 #include "gpu_bam.h"
 #include "gpu_inflate.h"
+#include "../host/bam_record.h"
 #include "../host/parallel.h"
 
 hipStream_t bqc_pool_stream(int device, int rank); // bqc_api.cpp: a stream bqc_warmup has made ahead (rank: the order of need), or a new one
@@ -65,29 +66,11 @@ struct GbLanes { const uint8_t* blob; const uint32_t* off; const uint32_t* len; 
 typedef uint32_t __attribute__((aligned(1))) gb_u32_u;
 typedef uint32_t gb_u32x4 __attribute__((ext_vector_type(4)));
 typedef gb_u32x4 __attribute__((aligned(1))) gb_u32x4_u;
-typedef uint16_t __attribute__((aligned(1))) gb_u16_u;
 
 namespace {
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *(const gb_u32_u*)p; }
-__device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return *(const gb_u16_u*)p; }
-
-// host/bam_io.cpp: plausible_record
-__device__ bool gb_plausible(const uint8_t* base, uint64_t avail, uint64_t p, int32_t n_ref, uint64_t& next)
-{
-    if (p + 36 > avail) return false;
-    const uint32_t bs = ld32(base + p);
-    if (bs < 32u || bs > (1u << 28)) return false;
-    const uint8_t* r = base + p + 4;
-    const int32_t rid = (int32_t)ld32(r), pos = (int32_t)ld32(r + 4), rnext = (int32_t)ld32(r + 20), pnext = (int32_t)ld32(r + 24);
-    if (rid < -1 || rid >= n_ref || rnext < -1 || rnext >= n_ref || pos < -1 || pnext < -1) return false;
-    const uint32_t l_name = r[8], n_cig = ld16(r + 12), l_seq = ld32(r + 16);
-    if (l_name == 0 || l_seq > (1u << 28)) return false;
-    const uint64_t var = 32ull + l_name + 4ull * n_cig + (l_seq + 1u) / 2u + l_seq;
-    if (var > bs) return false;
-    if (p + 4 + 32 + l_name <= avail && r[32 + l_name - 1] != 0) return false; // read name is NUL-terminated
-    next = p + 4 + bs;
-    return true;
-}
+// a walk's answer to one step of the chain (bam_record.h: br_check)
+__device__ __forceinline__ uint32_t gb_walk_flag(BrCheck c) { return c == BR_INCOMPLETE ? GB_INCOMPLETE : c == BR_OK ? 0u : GB_CORRUPT; }
 } // namespace
 
 // lane per segment: first record start (segment 0: the window's start, which is one), then the chain up to the segment's end
@@ -101,6 +84,7 @@ __global__ __launch_bounds__(64) void k_gb_walk(const uint8_t* __restrict__ base
     const uint32_t s = seg0 + blockIdx.x * 64 + threadIdx.x;
     if (s >= seg0 + nseg) return;
     const uint64_t a = (uint64_t)s * GB_SEG, b = min(avail, a + GB_SEG);
+    const BrBytes src{base};
     GbSeg S{};
     const bool known = s == seg0 && exact != UINT64_MAX;
     uint64_t p = known ? exact : a;
@@ -108,7 +92,7 @@ __global__ __launch_bounds__(64) void k_gb_walk(const uint8_t* __restrict__ base
         const uint64_t stop = min(b, limit);
         for (; p < stop; ++p) {
             uint64_t q1, q2, q3;
-            if (gb_plausible(base, avail, p, n_ref, q1) && gb_plausible(base, avail, q1, n_ref, q2) && gb_plausible(base, avail, q2, n_ref, q3)) break;
+            if (br_plausible(src, avail, p, n_ref, q1) && br_plausible(src, avail, q1, n_ref, q2) && br_plausible(src, avail, q2, n_ref, q3)) break;
         }
         if (p >= stop) { S.first = S.exit = 0xFFFFFFFFu; S.flags = GB_NO_START; segs[s] = S; return; }
     }
@@ -122,19 +106,14 @@ __global__ __launch_bounds__(64) void k_gb_walk(const uint8_t* __restrict__ base
     uint32_t ahead = 0;
     const uint64_t last_line = avail >= 4 ? avail - 4 : 0;
     while (p < b && p < limit) {
-        if (p + 36 > avail) { S.flags |= GB_INCOMPLETE; break; }
         ahead ^= ld32(base + min(p + 1536u, last_line));
-        const uint32_t bs = ld32(base + p);
-        if (bs < 32u) { S.flags |= GB_CORRUPT; break; }
-        const uint8_t* r = base + p + 4;
-        const uint32_t l_name = r[8], n_cig = ld16(r + 12), l_seq = ld32(r + 16);
-        const uint64_t var = 32ull + l_name + 4ull * n_cig + ((uint64_t)l_seq + 1u) / 2u + l_seq;
-        if (var > bs) { S.flags |= GB_CORRUPT; break; }
-        if (p + 4 + bs > avail) { S.flags |= GB_INCOMPLETE; break; }
+        BrHead h;
+        const BrCheck c = br_step(src, avail, p, h);
+        if (c != BR_OK) { S.flags |= gb_walk_flag(c); break; }
         out[n] = GbRec{(uint32_t)p, so, qo, co};
-        so += (l_seq + 1u) / 2u; qo += l_seq; co += n_cig;
+        so += (h.l_seq + 1u) / 2u; qo += h.l_seq; co += h.n_cig;
         ++n;
-        p += 4ull + bs;
+        p += 4ull + h.bs;
     }
     S.exit = (uint32_t)min(p, (uint64_t)0xFFFFFFFEu);
     S.count = n; S.seq_bytes = so; S.qual_bytes = qo; S.cigar_words = co;
@@ -149,10 +128,10 @@ __global__ __launch_bounds__(64) void k_gb_walk(const uint8_t* __restrict__ base
 // loads; the guess tests 64 candidate starts at a time (ballot: the first one that holds), and the chain reads a record's header
 // from LDS — every lane the same addresses, a broadcast — ~150 clocks per record instead of a memory latency.  What lies beyond the
 // staged bytes (the records a plausibility test follows past the segment's end) is read from memory as before.  Same results, field
-// for field: tests/test_gpu_reader.py compares both with the host reader's walk.
+// for field: tests/test_gpu_reader.py reads the files of tests/bam_sweeps.py with each of the two kernels and compares the columns.
 #define GBW_STAGE (GB_SEG + 192u)
 namespace {
-struct GbwView {
+struct GbwView { // a byte source (bam_record.h) over the window
     const uint32_t* buf;   // LDS copy of base[a, a + staged)
     const uint8_t* base;
     uint64_t a, staged;
@@ -167,23 +146,9 @@ struct GbwView {
         return ld32(base + p);
     }
     __device__ __forceinline__ uint32_t u8(uint64_t p) const { return p >= a && p < a + staged ? (buf[(uint32_t)(p - a) >> 2] >> (8u * ((uint32_t)(p - a) & 3u))) & 255u : base[p]; }
+    __device__ __forceinline__ uint32_t u16(uint64_t p) const { return u8(p) | (u8(p + 1) << 8); }
+    __device__ __forceinline__ uint64_t find0(uint64_t from, uint64_t end) const { while (from < end && u8(from)) ++from; return from; }
 };
-// gb_plausible over a view
-__device__ __forceinline__ bool gbw_plausible(const GbwView& V, uint64_t avail, uint64_t p, int32_t n_ref, uint64_t& next)
-{
-    if (p + 36 > avail) return false;
-    const uint32_t bs = V.u32(p);
-    if (bs < 32u || bs > (1u << 28)) return false;
-    const int32_t rid = (int32_t)V.u32(p + 4), pos = (int32_t)V.u32(p + 8), rnext = (int32_t)V.u32(p + 24), pnext = (int32_t)V.u32(p + 28);
-    if (rid < -1 || rid >= n_ref || rnext < -1 || rnext >= n_ref || pos < -1 || pnext < -1) return false;
-    const uint32_t w12 = V.u32(p + 12), l_name = w12 & 255u, n_cig = V.u32(p + 16) & 0xFFFFu, l_seq = V.u32(p + 20);
-    if (l_name == 0 || l_seq > (1u << 28)) return false;
-    const uint64_t var = 32ull + l_name + 4ull * n_cig + (l_seq + 1u) / 2u + l_seq;
-    if (var > bs) return false;
-    if (p + 4 + 32 + l_name <= avail && V.u8(p + 4 + 32 + l_name - 1) != 0) return false; // read name is NUL-terminated
-    next = p + 4 + bs;
-    return true;
-}
 } // namespace
 
 __global__ __launch_bounds__(64) void k_gb_walk_wave(const uint8_t* __restrict__ base, uint64_t avail, uint32_t seg0, uint32_t nseg, uint64_t exact, uint64_t limit, int32_t n_ref,
@@ -224,7 +189,7 @@ __global__ __launch_bounds__(64) void k_gb_walk_wave(const uint8_t* __restrict__
         for (uint64_t r0 = a; r0 < stop && !found; r0 += 64u) {
             const uint64_t c = r0 + lane;
             uint64_t q1, q2, q3;
-            const bool ok = c < stop && gbw_plausible(V, avail, c, n_ref, q1) && gbw_plausible(V, avail, q1, n_ref, q2) && gbw_plausible(V, avail, q2, n_ref, q3);
+            const bool ok = c < stop && br_plausible(V, avail, c, n_ref, q1) && br_plausible(V, avail, q1, n_ref, q2) && br_plausible(V, avail, q2, n_ref, q3);
             const uint64_t m = __ballot(ok);
             if (m) { p = r0 + (uint64_t)(__ffsll((unsigned long long)m) - 1); found = true; }
         }
@@ -246,22 +211,18 @@ __global__ __launch_bounds__(64) void k_gb_walk_wave(const uint8_t* __restrict__
     const uint32_t avail_r = (uint32_t)min(avail - a, (uint64_t)0x7FFFFFFFu), staged_r = (uint32_t)staged;
     uint32_t r = p >= a && p - a < (uint64_t)stop_r ? (uint32_t)(p - a) : 0xFFFFFFFFu;        // (outside: nothing to walk; p stays what it is)
     while (r < stop_r) {
-        if (r + 36u > avail_r) { S.flags |= GB_INCOMPLETE; break; }
-        uint32_t bs, w12, w16, l_seq;
+        BrHead h{0, 0, 0, 0}; // (br_check looks at it only when the header's 36 bytes are there)
         if (r + 24u <= staged_r) {
             const uint32_t w = r >> 2, sh = r & 3u;
             const uint32_t x0 = buf[w], x1 = buf[w + 1], x3 = buf[w + 3], x4 = buf[w + 4], x5 = buf[w + 5], x6 = buf[w + 6]; // (buf has a spare word behind the staged bytes)
-            bs = __builtin_amdgcn_alignbyte(x1, x0, sh); w12 = __builtin_amdgcn_alignbyte(x4, x3, sh);
-            w16 = __builtin_amdgcn_alignbyte(x5, x4, sh); l_seq = __builtin_amdgcn_alignbyte(x6, x5, sh);
-        } else { const uint64_t q = a + r; bs = V.u32(q); w12 = V.u32(q + 12); w16 = V.u32(q + 16); l_seq = V.u32(q + 20); } // (the last record of the data at hand)
-        if (bs < 32u) { S.flags |= GB_CORRUPT; break; }
-        const uint32_t l_name = w12 & 255u, n_cig = w16 & 0xFFFFu;
-        const uint64_t var = 32ull + l_name + 4ull * n_cig + ((uint64_t)l_seq + 1u) / 2u + l_seq;
-        if (var > bs) { S.flags |= GB_CORRUPT; break; }
-        const uint64_t next = (uint64_t)r + 4u + bs; // (64 bits: a block_size near 2^32 must not wrap into the segment)
-        if (next > avail - a) { S.flags |= GB_INCOMPLETE; break; }
+            h = BrHead{__builtin_amdgcn_alignbyte(x1, x0, sh), __builtin_amdgcn_alignbyte(x4, x3, sh) & 255u, __builtin_amdgcn_alignbyte(x5, x4, sh) & 0xFFFFu,
+                       __builtin_amdgcn_alignbyte(x6, x5, sh)};
+        } else if (r + 36u <= avail_r) h = br_head(V, a + r); // (the last record of the data at hand)
+        const BrCheck c = br_check(h, avail - a - r);
+        if (c != BR_OK) { S.flags |= gb_walk_flag(c); break; }
+        const uint64_t next = (uint64_t)r + 4u + h.bs; // (64 bits: a block_size near 2^32 must not wrap into the segment)
         if (lane == (n & 63u)) mine = GbRec{(uint32_t)(a + r), so, qo, co};
-        so += (l_seq + 1u) / 2u; qo += l_seq; co += n_cig;
+        so += (h.l_seq + 1u) / 2u; qo += h.l_seq; co += h.n_cig;
         ++n;
         if ((n & 63u) == 0u) out[n - 64u + lane] = mine;
         if (next >= stop_r) { r = 0xFFFFFFFFu; p = a + next; break; } // the walk leaves the segment (or the data to look at)
@@ -276,8 +237,33 @@ __global__ __launch_bounds__(64) void k_gb_walk_wave(const uint8_t* __restrict__
     }
 }
 
-// workgroup per taken segment, thread per record: the fixed columns and the tag scan of host/bam_io.cpp
+// workgroup per taken segment, thread per record: the fixed columns and the scan of the optional fields (bam_record.h)
 #define GBD_STAGE 64u // bytes of a record's optional fields staged in LDS (k_gb_decode)
+namespace {
+struct GbdStage { // a byte source over a record's optional fields: the first GBD_STAGE bytes from LDS, the rest from memory
+    const uint32_t* tb; // (a spare word behind the stage)
+    const uint8_t* tg0;
+    __device__ __forceinline__ uint32_t u8(uint64_t o) const { return o < GBD_STAGE ? (tb[(uint32_t)o >> 2] >> (8u * ((uint32_t)o & 3u))) & 255u : (uint32_t)tg0[o]; }
+    __device__ __forceinline__ uint32_t u16(uint64_t o) const { return u8(o) | (u8(o + 1) << 8); }
+    __device__ __forceinline__ uint32_t u32(uint64_t o) const
+    {
+        if (o + 4 <= GBD_STAGE) { const uint32_t w = (uint32_t)o >> 2, sh = (uint32_t)o & 3u; return __builtin_amdgcn_alignbyte(tb[w + 1], tb[w], sh); }
+        return u8(o) | (u8(o + 1) << 8) | (u8(o + 2) << 16) | (u8(o + 3) << 24);
+    }
+    __device__ __forceinline__ uint64_t find0(uint64_t from, uint64_t end) const { while (from < end && u8(from)) ++from; return from; }
+};
+// what the scan of a record's optional fields means for the batch (any bit: the host reader decodes it), by the host reader's order of checks
+__device__ __forceinline__ uint32_t gb_exceptions(const BrTags& T, int lane, uint32_t lane_count)
+{
+    uint32_t x = 0;
+    if (T.flags & BR_TAGS_CORRUPT) x |= GBX_TAGS;
+    if (T.flags & BR_RG_NOT_Z) x |= GBX_RG_TYPE;
+    if (!(T.flags & BR_RG_SEEN)) x |= GBX_RG_MISSING;
+    else if ((uint32_t)lane >= lane_count) x |= GBX_LANE;
+    if ((T.flags & BR_NM_SEEN) && T.nm == BQC_NM_ABSENT) x |= GBX_NM_VALUE;
+    return x;
+}
+} // namespace
 __global__ __launch_bounds__(64) void k_gb_decode(const uint8_t* __restrict__ base, const GbSeg* __restrict__ segs, const GbRec* __restrict__ recs,
                                                    const GbBase* __restrict__ bases, GbCols C, GbLanes LN, const uint8_t* __restrict__ main_chrom, uint32_t n_main,
                                                    uint32_t* __restrict__ status)
@@ -291,108 +277,43 @@ __global__ __launch_bounds__(64) void k_gb_decode(const uint8_t* __restrict__ ba
     for (uint32_t slot = threadIdx.x; slot < count; slot += 64) {
         const GbRec R = recs[(size_t)s * GB_MAXR + slot];
         const uint32_t i = B.rec + slot;
-        const uint8_t* r = base + R.off + 4;
-        const uint32_t bs = ld32(r - 4);
-        const int32_t rid = (int32_t)ld32(r), pos = (int32_t)ld32(r + 4);
-        const uint32_t l_name = r[8], mapq = r[9], n_cig = ld16(r + 12), flag = ld16(r + 14), l_seq = ld32(r + 16);
-        const int32_t rnext = (int32_t)ld32(r + 20), tlen = (int32_t)ld32(r + 28);
-        const uint8_t* ql = r + 32 + l_name + 4ull * n_cig + (l_seq + 1u) / 2u;
-        const uint8_t* const tg0 = ql + l_seq;
-        const uint8_t* te = r + bs;
-        int lane = -1;
-        bool rg_seen = false, as_seen = false, nm_seen = false;
-        int32_t nm = BQC_NM_ABSENT, as = BQC_AS_ABSENT;
+        const BrBytes rec{base + R.off};
+        const BrHead h = br_head(rec, 0);
+        // (the fixed fields are asked for here, with the header: read where they are stored, behind the scan, each was a round trip of its own)
+        const int32_t rid = (int32_t)rec.u32(4), pos = (int32_t)rec.u32(8), rnext = (int32_t)rec.u32(24), tlen = (int32_t)rec.u32(32);
+        const uint32_t mapq = rec.u8(13), flag = rec.u16(18);
+        const uint8_t* const tg0 = rec.p + br_tags_off(h);
         // The optional fields are walked byte by byte, every byte the address of the next: from memory that was a chain of dependent
         // loads (the kernel's whole time).  Round 4: a record's first GBD_STAGE bytes of fields come into LDS with four 16-byte loads
         // issued together (what lies behind them, if anything, is read from memory as before; the buffer's slack covers the over-read).
-        const uint64_t tlen_all = te > tg0 ? (uint64_t)(te - tg0) : 0;
+        const uint64_t tlen_all = 4ull + h.bs > br_tags_off(h) ? 4ull + h.bs - br_tags_off(h) : 0;
         uint32_t* const tb = tagbuf[threadIdx.x];
+        uint32_t first_qual;
         {
             gb_u32x4 v[GBD_STAGE / 16];
 #pragma unroll
             for (uint32_t k = 0; k < GBD_STAGE / 16; ++k) v[k] = 16u * k < tlen_all ? *(const gb_u32x4_u*)(tg0 + 16u * k) : gb_u32x4{0, 0, 0, 0};
+            first_qual = rec.u8(h.l_seq ? br_qual_off(h) : 0); // (with the stage's loads; without bases any byte: br_flag does not look at it)
 #pragma unroll
             for (uint32_t k = 0; k < GBD_STAGE / 16; ++k) { tb[4 * k] = v[k].x; tb[4 * k + 1] = v[k].y; tb[4 * k + 2] = v[k].z; tb[4 * k + 3] = v[k].w; }
         }
-        auto t8 = [&](uint64_t o) -> uint32_t { return o < GBD_STAGE ? (tb[(uint32_t)o >> 2] >> (8u * ((uint32_t)o & 3u))) & 255u : (uint32_t)tg0[o]; };
-        auto t16 = [&](uint64_t o) -> uint32_t { return t8(o) | (t8(o + 1) << 8); };
-        auto t32 = [&](uint64_t o) -> uint32_t {
-            if (o + 4 <= GBD_STAGE) { const uint32_t w = (uint32_t)o >> 2, sh = (uint32_t)o & 3u; return __builtin_amdgcn_alignbyte(tb[w + 1], tb[w], sh); } // (a spare word behind the stage)
-            return t8(o) | (t8(o + 1) << 8) | (t8(o + 2) << 16) | (t8(o + 3) << 24);
-        };
-        uint64_t tg = 0; // offset of the next field from tg0
-        while (tg + 3 <= tlen_all) {
-            const char k0 = (char)t8(tg), k1 = (char)t8(tg + 1), ty = (char)t8(tg + 2);
-            const uint64_t v = tg + 3;
-            uint64_t len = 0;
-            switch (ty) {
-            case 'A': case 'c': case 'C': len = 1; break;
-            case 's': case 'S': len = 2; break;
-            case 'i': case 'I': case 'f': len = 4; break;
-            case 'Z': case 'H': {
-                uint64_t z = v;
-                while (z < tlen_all && t8(z)) ++z;
-                len = z < tlen_all ? (z - v) + 1 : tlen_all - v;
-                break;
+        const GbdStage tags{tb, tg0};
+        const BrTags T = br_scan_tags(tags, tlen_all, [&](int32_t) { exc |= GBX_NM_EXTRA; });
+        int lane = -1;
+        if ((T.flags & BR_RG_SEEN) && !(T.flags & BR_RG_NOT_Z)) {
+            for (uint32_t l = 0; l < LN.n && lane < 0; ++l) {
+                if (LN.len[l] != T.rg_len) continue;
+                const uint8_t* id = LN.blob + LN.off[l];
+                uint32_t k = 0;
+                while (k < T.rg_len && id[k] == tags.u8(T.rg_off + k)) ++k;
+                if (k == T.rg_len) lane = (int)LN.index[l];
             }
-            case 'B': {
-                if (v + 5 > tlen_all) { len = tlen_all - v; break; }
-                const char st = (char)t8(v);
-                const uint64_t cnt = t32(v + 1);
-                const uint64_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-                len = 5 + cnt * es;
-                break;
-            }
-            default: len = tlen_all - v; break;
-            }
-            if (len > tlen_all - v) { exc |= GBX_TAGS; break; }
-            if (k0 == 'R' && k1 == 'G' && !rg_seen) {
-                rg_seen = true;
-                if (ty == 'Z') {
-                    const uint32_t idl = len ? (uint32_t)len - 1 : 0;
-                    for (uint32_t l = 0; l < LN.n && lane < 0; ++l) {
-                        if (LN.len[l] != idl) continue;
-                        const uint8_t* id = LN.blob + LN.off[l];
-                        uint32_t k = 0;
-                        while (k < idl && id[k] == t8(v + k)) ++k;
-                        if (k == idl) lane = (int)LN.index[l];
-                    }
-                    if (lane < 0) { exc |= GBX_RG_UNKNOWN; lane = 0; }
-                } else exc |= GBX_RG_TYPE;
-            } else if (k0 == 'N' && k1 == 'M' && (ty == 'c' || ty == 'C' || ty == 's' || ty == 'S' || ty == 'i' || ty == 'I')) {
-                uint32_t x;
-                switch (ty) {
-                case 'c': x = (uint32_t)(int32_t)(int8_t)t8(v); break;
-                case 'C': x = t8(v); break;
-                case 's': x = (uint32_t)(int32_t)(int16_t)t16(v); break;
-                case 'S': x = t16(v); break;
-                default: x = t32(v); break;
-                }
-                if (!nm_seen) { nm = (int32_t)x; nm_seen = true; }
-                else exc |= GBX_NM_EXTRA;
-            } else if (k0 == 'A' && k1 == 'S' && !as_seen) {
-                as_seen = true;
-                switch (ty) {
-                case 'A': as = (int32_t)(char)t8(v); break;
-                case 'c': as = (int8_t)t8(v); break;
-                case 'C': as = (int32_t)t8(v); break;
-                case 's': as = (int16_t)t16(v); break;
-                case 'S': as = (int32_t)t16(v); break;
-                case 'i': case 'I': as = (int32_t)t32(v); break;
-                case 'f': as = (int32_t)__uint_as_float(t32(v)); break;
-                default: as = BQC_AS_ABSENT; break;
-                }
-            }
-            tg = v + len;
+            if (lane < 0) { exc |= GBX_RG_UNKNOWN; lane = 0; }
         }
-        if (!rg_seen) exc |= GBX_RG_MISSING;
-        else if ((uint32_t)lane >= LN.lane_count) exc |= GBX_LANE;
-        if (nm_seen && nm == BQC_NM_ABSENT) exc |= GBX_NM_VALUE;
-        uint32_t f = flag & 0x0FFFu;
-        if (rnext >= 0 && (uint32_t)rnext < n_main && main_chrom[rnext]) f |= BQC_FLAG_MATE_MAIN;
-        if (l_seq > 0 && ql[0] == 0xFF) f |= BQC_FLAG_NO_QUAL;
-        C.flag[i] = (uint16_t)f; C.mapq[i] = (uint8_t)mapq; C.lane[i] = (uint8_t)(lane < 0 ? 0 : lane); C.rid[i] = rid; C.pos[i] = pos; C.tlen[i] = tlen;
-        C.nm[i] = nm; C.as[i] = as; C.l_seq[i] = l_seq; C.n_cigar[i] = (uint16_t)n_cig;
+        exc |= gb_exceptions(T, lane, LN.lane_count);
+        C.flag[i] = (uint16_t)br_flag(flag, rnext, main_chrom, n_main, h.l_seq, first_qual);
+        C.mapq[i] = (uint8_t)mapq; C.lane[i] = (uint8_t)(lane < 0 ? 0 : lane); C.rid[i] = rid; C.pos[i] = pos;
+        C.tlen[i] = tlen; C.nm[i] = T.nm; C.as[i] = T.as; C.l_seq[i] = h.l_seq; C.n_cigar[i] = (uint16_t)h.n_cig;
         C.rec_off[i] = R.off; C.so[i] = B.so + R.so; C.qo[i] = B.qo + R.qo; C.co[i] = B.co + R.co;
     }
     if (exc) atomicOr(status, exc);
@@ -408,11 +329,10 @@ __global__ __launch_bounds__(256) void k_gb_copy(const uint8_t* __restrict__ bas
 {
     const uint32_t i = blockIdx.x * 16 + (threadIdx.x >> 4), gl = threadIdx.x & 15u;
     if (i >= n) return;
-    const uint8_t* r = base + C.rec_off[i] + 4;
-    const uint32_t l_name = r[8], n_cig = C.n_cigar[i], l_seq = C.l_seq[i];
-    const uint8_t* cg = r + 32 + l_name;
-    const uint8_t* sq = cg + 4ull * n_cig;
-    const uint8_t* ql = sq + (l_seq + 1u) / 2u;
+    const uint8_t* r = base + C.rec_off[i];
+    const uint32_t n_cig = C.n_cigar[i], l_seq = C.l_seq[i];
+    const BrHead h{0, r[12], n_cig, l_seq}; // (block_size plays no part in where the arrays lie)
+    const uint8_t *cg = r + br_cigar_off(h), *sq = r + br_seq_off(h), *ql = r + br_qual_off(h);
     uint8_t* dc = cigar + 4ull * C.co[i];
     uint8_t* ds = seq + C.so[i];
     uint8_t* dq = qual + C.qo[i];
@@ -1334,12 +1254,10 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
             recs.reserve(N);
             size_t hso = 0, hqo = 0, hco = 0;
             for (uint64_t q = 0; q + 36 <= pos && recs.size() < N;) {
-                const uint8_t* r = I.handover_raw.data() + q;
-                const uint32_t bs = r[0] | (r[1] << 8) | (r[2] << 16) | ((uint32_t)r[3] << 24);
-                const uint32_t n_cig = r[16] | (r[17] << 8), l_seq = r[20] | (r[21] << 8) | (r[22] << 16) | ((uint32_t)r[23] << 24);
-                recs.push_back(BamRec{(size_t)q, bs, l_seq, n_cig, hso, hqo, hco, nrec_ + recs.size()});
-                hso += (l_seq + 1u) / 2u; hqo += l_seq; hco += n_cig;
-                q += 4ull + bs;
+                const BrHead h = br_head(BrBytes{I.handover_raw.data()}, q);
+                recs.push_back(BamRec{(size_t)q, h.bs, h.l_seq, h.n_cig, hso, hqo, hco, nrec_ + recs.size()});
+                hso += (h.l_seq + 1u) / 2u; hqo += h.l_seq; hco += h.n_cig;
+                q += 4ull + h.bs;
             }
             if (recs.size() != N || hso != so || hqo != qo || hco != co) return unsupported("the record walk could not be verified");
             o.d_seq = o.d_qual = nullptr; o.d_cigar = nullptr; // (a host batch; its device buffer stays for the next one)
@@ -1363,8 +1281,8 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         t_read_ = I.t_read; t_wait_run_ = I.t_wait_run; t_wait_chunk_ = I.t_wait_chunk;
         t_dec = now_s() - td;
         if (I.timing)
-            fprintf(stderr, "[gpu reader] batch of %zu records (%.1f MB): %.1f ms = next run %.1f + walk %.1f + decode %.1f (reading so far %.3f s, waiting for runs %.3f s, rewalked %llu) at %.3f\n", N,
-                    pos / 1e6, (now_s() - t0) * 1e3, t_adv * 1e3, t_walk * 1e3, t_dec * 1e3, I.t_read, I.t_wait_run, (unsigned long long)I.n_rewalk, now_s());
+            fprintf(stderr, "[gpu reader] batch of %zu records (%.1f MB): %.1f ms = next run %.1f + walk %.1f (a %s per segment) + decode %.1f (reading so far %.3f s, waiting for runs %.3f s, rewalked %llu) at %.3f\n", N,
+                    pos / 1e6, (now_s() - t0) * 1e3, t_adv * 1e3, t_walk * 1e3, walk_by_lanes ? "lane" : "wave", t_dec * 1e3, I.t_read, I.t_wait_run, (unsigned long long)I.n_rewalk, now_s());
         return 1;
     }
 }

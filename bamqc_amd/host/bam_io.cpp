@@ -1,5 +1,7 @@
-// bam_io.cpp — see bam_io.h
+// bam_io.cpp — see bam_io.h.  What a BAM record is (size rule, plausibility test, optional-field scan, flag annotation) is stated in
+// bam_record.h, for this reader and the one on the card (csrc/gpu_bam.hip).
 #include "bam_io.h"
+#include "bam_record.h"
 #include "parallel.h"
 
 #include <algorithm>
@@ -32,7 +34,6 @@ void HostBatch::clear()
 }
 
 static inline uint32_t rd32(const uint8_t* p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
-static inline uint16_t rd16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 
 bool BamReader::fill(size_t need, std::string& err)
 {
@@ -117,10 +118,18 @@ bool BamReader::open(const char* path, std::string& err, bool header_first)
     return true;
 }
 
-// One record's variable part, decoded by parse_record.
 namespace {
 struct RecErr { size_t index = SIZE_MAX; std::string msg; int code = 0; };
-
+// what the scan of record i's optional fields (bam_record.h) means for the run, by the reference's order of checks
+void rec_error(RecErr& E, size_t i, const BrTags& T, int lane, unsigned lane_count, uint64_t nrec)
+{
+    if (T.flags & BR_TAGS_CORRUPT) { E.index = i; E.msg = "corrupt BAM tags"; E.code = BQC_ERR_IO; }
+    else if (T.flags & BR_RG_NOT_Z) { E.index = i; E.msg = "Read does not have Z"; E.code = BQC_ERR_ARG; }
+    else if (!(T.flags & BR_RG_SEEN)) { // DEFINED: the reference falls off the end of getLane() (undefined behaviour)
+        E.index = i; E.msg = "ERROR: read without RG tag (record " + std::to_string(nrec) + ")"; E.code = BQC_ERR_ARG;
+    } else if ((unsigned)lane >= lane_count) { E.index = i; E.msg = "ERROR: read group index out of range (no @RG lines in the header?)"; E.code = BQC_ERR_ARG; }
+    else if ((T.flags & BR_NM_SEEN) && T.nm == BQC_NM_ABSENT) { E.index = i; E.msg = "NM tag value 0xFFFFFFFF is not representable"; E.code = BQC_ERR_RANGE; }
+}
 } // namespace
 
 // ---- parallel record walk ---------------------------------------------------------------------------------------------
@@ -128,24 +137,7 @@ struct RecErr { size_t index = SIZE_MAX; std::string msg; int code = 0; };
 // buffer it is split into segments walked by several threads: every thread but the first has to GUESS where a record
 // starts in its segment (the first offset at which three records in a row look like records) — a guess that is only used
 // if the walk of the previous segment ends exactly there; otherwise that segment is walked again from the known position.
-// The result is the serial walk's, whatever the data.
-static inline bool plausible_record(const uint8_t* base, size_t avail, size_t p, int32_t n_ref, size_t& next)
-{
-    if (p + 36 > avail) return false;
-    const uint32_t bs = rd32(base + p);
-    if (bs < 32 || bs > (1u << 28)) return false;
-    const uint8_t* r = base + p + 4;
-    const int32_t rid = (int32_t)rd32(r), pos = (int32_t)rd32(r + 4), rnext = (int32_t)rd32(r + 20), pnext = (int32_t)rd32(r + 24);
-    if (rid < -1 || rid >= n_ref || rnext < -1 || rnext >= n_ref || pos < -1 || pnext < -1) return false;
-    const uint32_t l_name = r[8], n_cig = rd16(r + 12), l_seq = rd32(r + 16);
-    if (l_name == 0 || l_seq > (1u << 28)) return false;
-    const size_t var = 32 + (size_t)l_name + 4ull * n_cig + (l_seq + 1) / 2 + l_seq;
-    if (var > bs) return false;
-    if (p + 4 + 32 + l_name <= avail && r[32 + l_name - 1] != 0) return false; // read name is NUL-terminated
-    next = p + 4 + (size_t)bs;
-    return true;
-}
-
+// The result is the serial walk's, whatever the data.  (The test, and the chain's size rule: bam_record.h.)
 bool BamReader::open_range(const char* path, uint64_t begin_hint, uint64_t end_hint, std::string& err)
 {
     if (!open(path, err)) return false; // header (from the file's start)
@@ -188,14 +180,14 @@ bool BamReader::locate_first_record(std::string& err)
     (void)fill(4u << 20, e); // best effort: a small shard has less
     if (!e.empty()) { err = e; return false; }
     const size_t avail = buf_.size() - cur_;
-    const uint8_t* base = buf_.data() + cur_;
+    const BrBytes src{buf_.data() + cur_};
     const int32_t n_ref = (int32_t)hdr_.ref_names.size();
     static const bool skew = getenv("BQC_TEST_SHARD_SKEW") != nullptr; // tests: a wrong guess (the second record found), to exercise the fallback
     for (size_t p = 0; p < avail; ++p) {
         if (beyond_range(p)) break; // no record starts inside this shard
-        size_t q1, q2, q3;
-        const bool hit = plausible_record(base, avail, p, n_ref, q1) &&
-                         (q1 >= avail || (plausible_record(base, avail, q1, n_ref, q2) && (q2 >= avail || plausible_record(base, avail, q2, n_ref, q3))));
+        uint64_t q1, q2, q3;
+        const bool hit = br_plausible(src, avail, p, n_ref, q1) &&
+                         (q1 >= avail || (br_plausible(src, avail, q1, n_ref, q2) && (q2 >= avail || br_plausible(src, avail, q2, n_ref, q3))));
         if (!hit) continue;
         if (skew && q1 < avail) p = q1;
         range_first_ = p;
@@ -212,32 +204,28 @@ void BamReader::walk_segment(const uint8_t* base, size_t avail, size_t a, size_t
 {
     out.recs.clear();
     out.n_all = 0;
+    const BrBytes src{base};
     size_t p = a;
     if (!exact_start) {
         const int32_t n_ref = (int32_t)hdr_.ref_names.size();
         for (; p < b; ++p) {
-            size_t q1, q2, q3;
-            if (plausible_record(base, avail, p, n_ref, q1) && plausible_record(base, avail, q1, n_ref, q2) && plausible_record(base, avail, q2, n_ref, q3)) break;
+            uint64_t q1, q2, q3;
+            if (br_plausible(src, avail, p, n_ref, q1) && br_plausible(src, avail, q1, n_ref, q2) && br_plausible(src, avail, q2, n_ref, q3)) break;
         }
         static const bool skew = getenv("BQC_TEST_WALK_SKEW") != nullptr; // tests: make every guess wrong (start at the second record found)
-        if (skew && p < b) { size_t q; if (plausible_record(base, avail, p, n_ref, q)) p = q; }
+        if (skew && p < b) { uint64_t q; if (br_plausible(src, avail, p, n_ref, q)) p = q; }
         if (p >= b) { out.first = out.end = SIZE_MAX; return; }
     }
     out.first = p;
     while (p < b) {
-        if (p + 36 > avail) break;
-        const uint32_t bs = rd32(base + p);
-        if (bs < 32) break; // (the serial walk reports it when it gets here)
-        const uint8_t* r = base + p + 4;
-        const int32_t rid = (int32_t)rd32(r);
-        const uint32_t l_name = r[8], n_cig = rd16(r + 12), l_seq = rd32(r + 16);
-        const size_t var = 32 + (size_t)l_name + 4ull * n_cig + (l_seq + 1) / 2 + l_seq;
-        if (var > bs || p + 4 + (size_t)bs > avail) break;
+        BrHead h;
+        if (br_step(src, avail, p, h) != BR_OK) break; // (the serial walk reports it when it gets here)
+        const int32_t rid = (int32_t)src.u32(p + 4);
         bool keep = true;
         if (filter_) keep = rid < 0 ? keep_unplaced_ : ((size_t)rid < keep_.size() && keep_[rid]);
-        if (keep) out.recs.push_back(BamRec{p, bs, l_seq, n_cig, 0, 0, 0, out.n_all});
+        if (keep) out.recs.push_back(BamRec{p, h.bs, h.l_seq, h.n_cig, 0, 0, 0, out.n_all});
         ++out.n_all;
-        p += 4 + (size_t)bs;
+        p += 4 + (size_t)h.bs;
     }
     out.end = p;
 }
@@ -343,21 +331,20 @@ int BamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, std:
             const uint32_t bs0 = rd32(buf_.data() + cur_ + rel);
             if (bs0 < 32 || !fill(rel + 4 + (size_t)bs0, e)) { err = e.empty() ? "truncated BAM record" : e; io_error = true; break; }
         }
-        const uint8_t* r = buf_.data() + cur_ + rel + 4;
-        const uint32_t bs = rd32(r - 4);
-        if (bs < 32) { err = "truncated BAM record"; io_error = true; break; }
-        const int32_t rid = (int32_t)rd32(r);
-        const uint32_t l_name = r[8], n_cig = rd16(r + 12), l_seq = rd32(r + 16);
-        const size_t var = 32 + (size_t)l_name + 4ull * n_cig + (l_seq + 1) / 2 + l_seq;
-        if (var > bs) { err = "corrupt BAM record"; io_error = true; break; }
+        // (all of the record is there now, or its block_size is below 32)
+        const BrBytes src{buf_.data() + cur_};
+        BrHead h;
+        const BrCheck c = br_step(src, buf_.size() - cur_, rel, h);
+        if (c != BR_OK) { err = c == BR_CORRUPT ? "corrupt BAM record" : "truncated BAM record"; io_error = true; break; }
+        const int32_t rid = (int32_t)src.u32(rel + 4);
         bool keep = true;
         if (filter_) keep = rid < 0 ? keep_unplaced_ : ((size_t)rid < keep_.size() && keep_[rid]);
         if (keep) {
-            recs.push_back(BamRec{rel, bs, l_seq, n_cig, so, qo, co, nrec_});
-            so += (l_seq + 1) / 2; qo += l_seq; co += n_cig;
-            bases += l_seq;
+            recs.push_back(BamRec{rel, h.bs, h.l_seq, h.n_cig, so, qo, co, nrec_});
+            so += (h.l_seq + 1) / 2; qo += h.l_seq; co += h.n_cig;
+            bases += h.l_seq;
         }
-        rel += 4 + (size_t)bs;
+        rel += 4 + (size_t)h.bs;
         ++nrec_;
     }
     if (nrec_ > nrec_at_start) {
@@ -411,96 +398,30 @@ bool bam_decode_records(const uint8_t* base, const std::vector<BamRec>& recs, Ba
         bool have_last = false;
         for (size_t i = lo; i < hi; ++i) {
             const BamRec& R = recs[i];
-            const uint8_t* r = base + R.off + 4;
-            const int32_t rid = (int32_t)rd32(r), pos = (int32_t)rd32(r + 4);
-            const uint32_t l_name = r[8], mapq = r[9];
-            const uint32_t n_cig = R.n_cig, flag = rd16(r + 14), l_seq = R.l_seq;
-            const int32_t rnext = (int32_t)rd32(r + 20), tlen = (int32_t)rd32(r + 28);
-            const uint8_t* cig = r + 32 + l_name;
-            const uint8_t* sq = cig + 4ull * n_cig;
-            const uint8_t* ql = sq + (l_seq + 1) / 2;
-            const uint8_t* tg = ql + l_seq;
-            const uint8_t* te = r + R.bs;
-            // one linear tag scan: RG (getLane, bamqualcheck.cpp:72-100), every integer NM (QualityCheck.hpp:201-209),
-            // first AS (TripletCounting.hpp:113-127)
-            int lane = -1;
-            bool rg_seen = false, rg_bad = false, as_seen = false, nm_seen = false, bad_tags = false;
-            int32_t nm = BQC_NM_ABSENT, as = BQC_AS_ABSENT;
-            while (tg + 3 <= te) {
-                const char k0 = (char)tg[0], k1 = (char)tg[1], ty = (char)tg[2];
-                const uint8_t* v = tg + 3;
-                size_t len = 0;
-                switch (ty) {
-                case 'A': case 'c': case 'C': len = 1; break;
-                case 's': case 'S': len = 2; break;
-                case 'i': case 'I': case 'f': len = 4; break;
-                case 'Z': case 'H': { const void* z = memchr(v, 0, (size_t)(te - v)); len = z ? (size_t)((const uint8_t*)z - v) + 1 : (size_t)(te - v); break; }
-                case 'B': {
-                    if (v + 5 > te) { len = (size_t)(te - v); break; }
-                    const char st = (char)v[0];
-                    const size_t cnt = rd32(v + 1);
-                    const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-                    len = 5 + cnt * es;
-                    break;
+            const BrBytes rec{base + R.off};
+            const BrHead h{R.bs, rec.u8(12), R.n_cig, R.l_seq};
+            const uint8_t *cig = rec.p + br_cigar_off(h), *sq = rec.p + br_seq_off(h), *ql = rec.p + br_qual_off(h);
+            const uint64_t tags_at = br_tags_off(h), rec_end = 4ull + R.bs;
+            const BrBytes tags{rec.p + tags_at};
+            const BrTags T = br_scan_tags(tags, rec_end > tags_at ? rec_end - tags_at : 0, [&](int32_t x) { extra[t].emplace_back((uint32_t)i, x); });
+            int lane = -1; // RG -> lane through the header's table (getLane, bamqualcheck.cpp:72-100)
+            if ((T.flags & BR_RG_SEEN) && !(T.flags & BR_RG_NOT_Z)) {
+                const uint8_t* v = tags.p + T.rg_off;
+                if (have_last && last_id.size() == T.rg_len && memcmp(last_id.data(), v, T.rg_len) == 0) lane = last_lane;
+                else {
+                    std::string id((const char*)v, T.rg_len);
+                    auto it = lane_names.find(id);
+                    if (it == lane_names.end()) { unknown_rg[t].emplace_back((uint32_t)i, id); lane = 0; } // operator[] would insert 0 (:86)
+                    else { lane = (int)it->second; last_id.swap(id); last_lane = lane; have_last = true; }
                 }
-                default: len = (size_t)(te - v); break;
-                }
-                if (v + len > te) { bad_tags = true; break; }
-                if (k0 == 'R' && k1 == 'G' && !rg_seen) {
-                    rg_seen = true;
-                    if (ty == 'Z') {
-                        const size_t idl = len ? len - 1 : 0;
-                        if (have_last && last_id.size() == idl && memcmp(last_id.data(), v, idl) == 0) lane = last_lane;
-                        else {
-                            std::string id((const char*)v, idl);
-                            auto it = lane_names.find(id);
-                            if (it == lane_names.end()) { unknown_rg[t].emplace_back((uint32_t)i, id); lane = 0; } // operator[] would insert 0 (:86)
-                            else { lane = (int)it->second; last_id.swap(id); last_lane = lane; have_last = true; }
-                        }
-                    } else rg_bad = true;
-                } else if (k0 == 'N' && k1 == 'M' && (ty == 'c' || ty == 'C' || ty == 's' || ty == 'S' || ty == 'i' || ty == 'I')) {
-                    uint32_t x = 0;
-                    switch (ty) {
-                    case 'c': x = (uint32_t)(int32_t)(int8_t)v[0]; break;
-                    case 'C': x = v[0]; break;
-                    case 's': x = (uint32_t)(int32_t)(int16_t)rd16(v); break;
-                    case 'S': x = rd16(v); break;
-                    default: x = rd32(v); break;
-                    }
-                    if (!nm_seen) { nm = (int32_t)x; nm_seen = true; }
-                    else extra[t].emplace_back((uint32_t)i, (int32_t)x);
-                } else if (k0 == 'A' && k1 == 'S' && !as_seen) {
-                    as_seen = true;
-                    switch (ty) {
-                    case 'A': as = (int32_t)(char)v[0]; break;
-                    case 'c': as = (int8_t)v[0]; break;
-                    case 'C': as = v[0]; break;
-                    case 's': as = (int16_t)rd16(v); break;
-                    case 'S': as = rd16(v); break;
-                    case 'i': case 'I': as = (int32_t)rd32(v); break;
-                    case 'f': { float f; uint32_t u = rd32(v); memcpy(&f, &u, 4); as = (int32_t)f; break; }
-                    default: as = BQC_AS_ABSENT; break; // extractTagValue fails -> "Could not read AS tag"
-                    }
-                }
-                tg = v + len;
             }
-            RecErr& E = errs[t];
-            if (E.index == SIZE_MAX) { // the first failing record of this range, by the reference's order of checks
-                if (bad_tags) { E.index = i; E.msg = "corrupt BAM tags"; E.code = BQC_ERR_IO; }
-                else if (rg_bad) { E.index = i; E.msg = "Read does not have Z"; E.code = BQC_ERR_ARG; }
-                else if (!rg_seen) { // DEFINED: the reference falls off the end of getLane() (undefined behaviour)
-                    E.index = i; E.msg = "ERROR: read without RG tag (record " + std::to_string(R.nrec) + ")"; E.code = BQC_ERR_ARG;
-                } else if ((unsigned)lane >= hdr.lane_count) { E.index = i; E.msg = "ERROR: read group index out of range (no @RG lines in the header?)"; E.code = BQC_ERR_ARG; }
-                else if (nm_seen && nm == BQC_NM_ABSENT) { E.index = i; E.msg = "NM tag value 0xFFFFFFFF is not representable"; E.code = BQC_ERR_RANGE; }
-            }
-            uint32_t f = flag & 0x0FFFu;
-            if (rnext >= 0 && (size_t)rnext < main_chrom.size() && main_chrom[rnext]) f |= BQC_FLAG_MATE_MAIN;
-            if (l_seq > 0 && ql[0] == 0xFF) f |= BQC_FLAG_NO_QUAL;
-            o.flag[i] = (uint16_t)f; o.mapq[i] = (uint8_t)mapq; o.lane[i] = (uint8_t)(lane < 0 ? 0 : lane); o.rid[i] = rid;
-            o.pos[i] = pos; o.tlen[i] = tlen; o.nm[i] = nm; o.as[i] = as; o.l_seq[i] = l_seq; o.n_cigar[i] = (uint16_t)n_cig;
-            if (n_cig) memcpy(o.cigar.data() + R.co, cig, 4ull * n_cig);
-            memcpy(o.seq.data() + R.so, sq, (l_seq + 1) / 2);
-            memcpy(o.qual.data() + R.qo, ql, l_seq);
+            if (errs[t].index == SIZE_MAX) rec_error(errs[t], i, T, lane, hdr.lane_count, R.nrec); // the first failing record of this range
+            o.flag[i] = (uint16_t)br_flag(rec.u16(18), (int32_t)rec.u32(24), main_chrom.data(), main_chrom.size(), h.l_seq, h.l_seq ? ql[0] : 0u);
+            o.mapq[i] = (uint8_t)rec.u8(13); o.lane[i] = (uint8_t)(lane < 0 ? 0 : lane); o.rid[i] = (int32_t)rec.u32(4);
+            o.pos[i] = (int32_t)rec.u32(8); o.tlen[i] = (int32_t)rec.u32(32); o.nm[i] = T.nm; o.as[i] = T.as; o.l_seq[i] = h.l_seq; o.n_cigar[i] = (uint16_t)h.n_cig;
+            if (h.n_cig) memcpy(o.cigar.data() + R.co, cig, 4ull * h.n_cig);
+            memcpy(o.seq.data() + R.so, sq, (h.l_seq + 1) / 2);
+            memcpy(o.qual.data() + R.qo, ql, h.l_seq);
         }
     });
     // unknown read groups, in record order: the first use inserts the id with lane 0

@@ -239,3 +239,113 @@ def test_gpu_reader_on_adversarial_bgzf_members(tmp_path, monkeypatch):
             got = [dict((k, np.array(v, copy=True)) for k, v in x.items() if isinstance(v, np.ndarray)) for x in b.batches(1234)]
             b.close()
         same(want, {k: np.concatenate([c[k] for c in got]) for k in got[0]})
+
+
+# ---- the record rules (host/bam_record.h) on the card: the sweep files of tests/bam_sweeps.py ------------------------------------
+def _digest(cols):
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(cols):
+        h.update(np.ascontiguousarray(cols[k]).tobytes())
+    return h.hexdigest()
+
+
+def _sweep_columns(path, batch_reads, **kw):
+    """(columns, batches handed over) of a sweep file, every reference a main chromosome as in pybam.columns"""
+    b = hostio.BamFile(path, **kw)
+    b.set_main_chrom(np.ones(2, np.uint8))
+    got = [dict((k, np.array(v, copy=True)) for k, v in x.items() if isinstance(v, np.ndarray)) for x in b.batches(batch_reads)]
+    handed = b.batches_handed_over if "gpu" in kw else 0
+    info = b.range_info
+    b.close()
+    return {k: np.concatenate([c[k] for c in got]) for k in got[0]}, handed, info
+
+
+@pytest.fixture(scope="module")
+def sweeps(tmp_path_factory):
+    """{name: (path, columns by the independent decoder, columns by the host reader)}"""
+    from tests import bam_sweeps, pybam
+    d = tmp_path_factory.mktemp("sweeps")
+    out = {}
+    for name, write in (("tags", bam_sweeps.tag_sweep), ("sizes", bam_sweeps.size_sweep)):
+        p = str(d / (name + ".bam"))
+        write(p)
+        out[name] = (p, pybam.columns(p)[0], _sweep_columns(p, 1 << 20)[0])
+    return out
+
+
+@pytest.mark.parametrize("name", ["tags", "sizes"])
+def test_sweep_files_through_the_reader_on_the_card(sweeps, name):
+    """Every column as the independent decoder and the host reader have it — decoded on the card: no batch went through the host decoder."""
+    path, want, host = sweeps[name]
+    for batch_reads in (257, 1 << 20):
+        gpu, handed, _ = _sweep_columns(path, batch_reads, gpu=0)
+        assert handed == 0
+        same(want, gpu)
+        same(host, gpu)
+
+
+def test_tag_sweep_with_a_second_nm_is_handed_over(tmp_path):
+    """One second NM tag, in a record whose fields cross the end of the card's stage: that batch goes to the host decoder, with the
+    host reader's columns and extra values."""
+    from tests import bam_sweeps
+    path = str(tmp_path / "nm2.bam")
+    bam_sweeps.tag_sweep(path, second_nm=True)
+    host, _, _ = _sweep_columns(path, 1 << 20)
+    assert len(host["nm_extra_read"]) == 1 and host["nm_extra_val"][0] == 77
+    gpu, handed, _ = _sweep_columns(path, 1 << 20, gpu=0)
+    assert handed == 1
+    same(host, gpu)
+
+
+def test_tag_sweep_with_a_field_cut_short_is_the_same_error(tmp_path):
+    from tests import bam_sweeps
+    path = str(tmp_path / "cut.bam")
+    bam_sweeps.tag_sweep(path, cut_last=True)
+    said = []
+    for kw in ({}, {"gpu": 0}):
+        with pytest.raises(IOError) as e:
+            _sweep_columns(path, 1 << 20, **kw)
+        said.append(str(e.value))
+    assert said[0] == said[1] and "corrupt BAM tags" in said[0]
+
+
+def test_size_sweep_in_three_shards(sweeps):
+    """Shards that start in the middle of the file: the card guesses their first record (k_gb_walk*: exact == UINT64_MAX) where the
+    host range reader does; same columns, same chain words."""
+    path, want, _ = sweeps["sizes"]
+    parts = []
+    for lo, hi in _shard_hints(path, 3):
+        h, _, hinfo = _sweep_columns(path, 1 << 20, begin_hint=lo, end_hint=hi)
+        g, handed, ginfo = _sweep_columns(path, 257, begin_hint=lo, end_hint=hi, gpu=0)
+        assert handed == 0 and ginfo == hinfo, (lo, hi)
+        same(h, g)
+        parts.append(g)
+    same(want, {k: np.concatenate([p[k] for p in parts]) for k in parts[0]})
+
+
+def test_lane_per_segment_walk_kernel_reads_the_sweep_files_alike(sweeps):
+    """BQC_GB_WALK=lane (k_gb_walk, a lane per segment) in a fresh process — the switch is read once per process — against the
+    default kernel (k_gb_walk_wave) here: the same bytes in every column of both files.  Which kernel walked is what the reader's
+    BQC_GB_TIMING line says of every batch."""
+    import os, subprocess, sys, textwrap
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    paths = [sweeps[name][0] for name in ("tags", "sizes")]
+    prog = textwrap.dedent("""
+        import sys
+        sys.path.insert(0, %r)
+        from tests.test_gpu_reader import _digest, _sweep_columns
+        for path in %r:
+            for batch_reads in (257, 1 << 20):
+                cols, handed, _ = _sweep_columns(path, batch_reads, gpu=0)
+                print(_digest(cols), handed)
+        """) % (root, paths)
+    r = subprocess.run([sys.executable, "-c", prog], env=dict(os.environ, BQC_GB_WALK="lane", BQC_GB_TIMING="1"), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stderr.count("(a lane per segment)") >= 4 and "(a wave per segment)" not in r.stderr, r.stderr
+    here = []
+    for path in paths:
+        for batch_reads in (257, 1 << 20):
+            cols, handed, _ = _sweep_columns(path, batch_reads, gpu=0)
+            here.append("%s %d" % (_digest(cols), handed))
+    assert r.stdout.split("\n")[:-1] == here and all(x.endswith(" 0") for x in here)

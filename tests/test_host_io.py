@@ -292,6 +292,55 @@ def test_adversarial_bgzf_members_through_the_host_reader(tmp_path):
             assert np.array_equal(np.concatenate([b[k] for b in got]), want[k]), (k, threads)
 
 
+@pytest.fixture(scope="module")
+def sweep_files(tmp_path_factory):
+    """tests/bam_sweeps.py: {name: (path, columns by the independent decoder)}"""
+    from tests import bam_sweeps
+    d = tmp_path_factory.mktemp("sweeps")
+    out = {}
+    for name, write in (("tags", bam_sweeps.tag_sweep), ("sizes", bam_sweeps.size_sweep)):
+        p = str(d / (name + ".bam"))
+        n = write(p)
+        out[name] = (p, pybam.columns(p)[0])
+        assert len(out[name][1]["flag"]) == n
+    return out
+
+
+def _digests(cols):
+    import hashlib
+    return {k: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() for k, v in cols.items()}
+
+
+@pytest.mark.parametrize("threads", ["1", "4"])
+def test_sweep_files_through_the_host_reader(sweep_files, threads):
+    """The optional-field scan, the flag annotation and the serial block_size walk (host/bam_record.h) on every byte position the
+    sweep files reach, through the host reader: every column as the independent decoder has it.  BQC_IO_THREADS is read once per
+    process, so each thread count reads the files in a child process of its own, which prints a SHA-256 per column.  (Files this
+    small stay below the thresholds of the parallel record walk and of the parallel decode: the thread count reaches the BGZF
+    inflate only.  The guessing walk is test_parallel_record_walk_equals_the_serial_walk's.)"""
+    import json, sys, textwrap
+    prog = textwrap.dedent("""
+        import sys, json, numpy as np
+        sys.path.insert(0, %r)
+        from bamqc_amd import hostio
+        from tests.test_host_io import _digests
+        out = []
+        for path in %r:
+            for batch_reads in (257, 1 << 20):
+                f = hostio.BamFile(path)
+                f.set_main_chrom(np.ones(2, np.uint8))
+                got = list(f.batches(max_reads=batch_reads))
+                f.close()
+                out.append(_digests({k: np.concatenate([b[k] for b in got]) for k in got[0]}))
+        print(json.dumps(out))
+        """) % (ROOT, [sweep_files[name][0] for name in ("tags", "sizes")])
+    r = subprocess.run([sys.executable, "-c", prog], env=dict(os.environ, BQC_IO_THREADS=threads), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    got = json.loads(r.stdout.strip().split("\n")[-1])
+    want = [_digests(sweep_files[name][1]) for name in ("tags", "sizes") for _ in range(2)]
+    assert got == want
+
+
 def test_parallel_record_walk_equals_the_serial_walk(tmp_path):
     """Batches of a 120 MB stream read with one thread (serial block_size walk), with several (segments walked in parallel from
     guessed record starts) and with every guess forced wrong (each segment walked again from the position the chain
