@@ -100,6 +100,8 @@ extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
     c->ref_len.assign(nr, 0);
     const char* v = getenv("BQC_NO_FAST");
     c->no_fast = v && v[0] == '1';
+    const char* cs = getenv("BQC_COV_STREAM");
+    c->cov_side = !(cs && cs[0] == '0');
 #define CCHK(call)                                                                                            \
     do {                                                                                                      \
         hipError_t e_ = (call);                                                                               \
@@ -206,6 +208,12 @@ hipStream_t bqc_pool_stream(int device, int rank)
         }
     }
     hipStream_t s = nullptr;
+    if (rank == BQC_STREAM_RANK_COV) { // the context's coverage stream: it must not take the card from the compute stream's next kernel
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = 0; }
+        if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        return s;
+    }
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     return s;
 }
@@ -251,6 +259,7 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    if (c->cov_stream) (void)hipStreamSynchronize(c->cov_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     bqc_pipeline_destroy(c);
     bqc_anchor_destroy(c);
@@ -266,6 +275,9 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     for (auto e : c->ev) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    if (c->cov_stream) (void)hipStreamDestroy(c->cov_stream);
+    if (c->ev_cov_fork) (void)hipEventDestroy(c->ev_cov_fork);
+    if (c->ev_cov_join) (void)hipEventDestroy(c->ev_cov_join);
     delete c;
 }
 

@@ -147,6 +147,11 @@ struct bqc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;      // compute: every kernel of the context, in batch order
     hipStream_t copy_stream = nullptr; // host-to-device copies of the batches in flight
+    // coverage beside the chunk plan (bqc_pipeline.cpp, enqueue_kernels): k_cov and its companions of a batch run on a stream of lower
+    // priority between two events of the compute stream — forked behind k_prep_reads, joined before the batch's last launch
+    hipStream_t cov_stream = nullptr;  // (made when the first batch needs it)
+    bool cov_side = true;              // BQC_COV_STREAM=0: the coverage launches on the compute stream, behind k_long (as before round 8)
+    hipEvent_t ev_cov_fork = nullptr, ev_cov_join = nullptr;
     uint32_t n_cu = 256;
     uint64_t* d_state = nullptr;
     ErrRec* d_err0 = nullptr;          // error record of work outside a batch (final flush)
@@ -220,7 +225,9 @@ int bqc_fail(bqc_ctx* c, int code, const char* fmt, ...);
         if (e_ != hipSuccess) return bqc_fail(c, BQC_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
-// bqc_api.cpp: a non-blocking stream on `device` — one of those bqc_warmup has made ahead, or a new one (nullptr: creation failed)
+// bqc_api.cpp: a non-blocking stream on `device` — one of those bqc_warmup has made ahead, or a new one (nullptr: creation failed);
+// rank BQC_STREAM_RANK_COV: never made ahead, and of the lowest priority the device has
+#define BQC_STREAM_RANK_COV 4
 hipStream_t bqc_pool_stream(int device, int rank);
 // the context's copy stream, taken when the first batch needs it (0: ok)
 int bqc_copy_stream(bqc_ctx* c);

@@ -24,7 +24,7 @@ void bqc_launch_nm_extra(const DevBatch&, const StateLayout&, uint64_t*, const D
 void bqc_launch_long(const DevBatch&, const StateLayout&, uint64_t*, const DevRefs&, uint32_t*, uint32_t*, uint32_t max_len_ub, uint32_t max_read_len, uint32_t, uint32_t, uint32_t* t8rows, uint32_t* t8_used, uint32_t t8_lane, uint32_t* cyc_tiles, uint32_t* cyc_used, uint32_t slot_cap, hipStream_t);
 uint32_t bqc_long_slots(uint32_t max_len_ub, uint32_t max_read_len, uint32_t n_chunks_ub, uint32_t n_cu);
 void bqc_launch_cov(const DevBatch&, const StateLayout&, uint64_t*, uint32_t* carry, uint32_t* parity, const uint8_t* lane_mask, uint8_t* started,
-                    const uint8_t* started_after, uint32_t n_lanes, hipStream_t);
+                    const uint8_t* started_after, uint32_t n_lanes, uint32_t cov_extra_cap, hipStream_t);
 void bqc_launch_add_words(uint64_t* state, const uint64_t* idx, const uint64_t* val, uint32_t n, hipStream_t);
 void bqc_launch_or_bytes(uint8_t* dst, const uint8_t* src, uint32_t n, hipStream_t);
 void bqc_launch_short(const DevBatch&, const StateLayout&, uint64_t*, const DevRefs&, uint32_t*, uint32_t grid, uint32_t* t8rows, uint32_t* t8_used, hipStream_t);
@@ -415,7 +415,7 @@ static int layout_batch(bqc_ctx* c, BatchMem& m, const bqc_batch* b, const HostP
     const size_t o_flag2 = cv.take(2 * n), o_soff = cv.take(4 * n), o_qoff = cv.take(4 * n), o_cgoff = cv.take(4 * n), o_cov = cv.take(sizeof(CovEntry) * n),
                  o_covx = cv.take(sizeof(CovExtra) * cx_cap), o_cls = cv.take(2 * n), o_segs = cv.take(sizeof(TripSeg) * (H.cigar_words + 1)),
                  o_perm = cv.take(4 * perm_cap), o_cf = cv.take(sizeof(Chunk) * cf_cap), o_cs = cv.take(sizeof(Chunk) * cs_cap),
-                 o_desc = cv.take(sizeof(BatchDesc)), o_err = cv.take(sizeof(ErrRec)), o_cursave = cv.take(8), o_bsz = cv.take(24 * nblk), o_btgt = cv.take(8 * nblk),
+                 o_desc = cv.take(sizeof(BatchDesc)), o_err = cv.take(sizeof(ErrRec)), o_cursave = cv.take(8), o_bsz = cv.take(24 * nblk), o_gsz = cv.take(24 * ((nblk + PR_GROUP - 1) / PR_GROUP)), o_btgt = cv.take(8 * nblk),
                  o_bmf = cv.take(8 * nblk), o_swc = cv.take(sizeof(SwCounts) * n_sw), o_swp = cv.take(sizeof(SwPlan) * n_sw),
                  o_rsum = cv.take(H.n_slow ? 12 * n : 0), o_otmp = cv.take(order_on_device && H.multi_lane ? 4 * lane_order_tmp_words((uint32_t)n, nl) : 0);
     const size_t need = cv.off + 256;
@@ -471,7 +471,7 @@ static int layout_batch(bqc_ctx* c, BatchMem& m, const bqc_batch* b, const HostP
     p.chunks_slow = (Chunk*)(base + o_cs); p.chunks_slow_cap = (uint32_t)cs_cap;
     p.desc = (BatchDesc*)(base + o_desc); p.err = (ErrRec*)(base + o_err);
     p.cursor = c->d_cursor; p.cursor_save = (int32_t*)(base + o_cursave);
-    p.blk_sizes = (unsigned long long*)(base + o_bsz); p.blk_tgt = (uint32_t*)(base + o_btgt); p.blk_maxfast = (uint32_t*)(base + o_bmf);
+    p.blk_sizes = (unsigned long long*)(base + o_bsz); p.grp_sizes = (unsigned long long*)(base + o_gsz); p.blk_tgt = (uint32_t*)(base + o_btgt); p.blk_maxfast = (uint32_t*)(base + o_bmf);
     p.sw_counts = (SwCounts*)(base + o_swc); p.sw_plan = (SwPlan*)(base + o_swp);
     m.d_lane_mask = (uint8_t*)(base + m.o_mask); m.d_started_after = (uint8_t*)(base + m.o_started);
     m.d_add_idx = (uint64_t*)(base + m.o_aidx); m.d_add_val = (uint64_t*)(base + m.o_aval); m.n_add = (uint32_t)H.add_idx.size();
@@ -527,18 +527,51 @@ static void tick(bqc_ctx* c, const char* name)
     c->n_timed++;
 }
 
-static int enqueue_kernels(bqc_ctx* c, BatchMem& m)
+// What a batch adds to the coverage state: k_cov (or, without tiles, the read groups that have started), then the host's words.
+// Inputs: cov[], cov_extra[], desc->n_cov_extra (final behind k_prep_reads) and the host's tables; output: poscov words, by atomics.
+static void launch_coverage(bqc_ctx* c, BatchMem& m, hipStream_t s)
+{
+    const DevBatch& d = m.d;
+    if (!d.n_cov_tiles) bqc_launch_or_bytes(c->d_started, m.d_started_after, c->opt.n_lanes, s); // (else: k_cov's epilogue)
+    else bqc_launch_cov(d, c->sl, c->d_state, c->d_carry, c->d_parity, m.d_lane_mask, c->d_started, m.d_started_after, c->opt.n_lanes, m.prep.cov_extra_cap, s);
+    bqc_launch_add_words(c->d_state, m.d_add_idx, m.d_add_val, m.n_add, s);
+}
+
+// the compute stream waits for the coverage stream's work of this batch
+static int cov_join(bqc_ctx* c, bool& forked)
+{
+    if (!forked) return 0;
+    forked = false;
+    HIPCHK(c, hipEventRecord(c->ev_cov_join, c->cov_stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_cov_join, 0));
+    return 0;
+}
+
+// The launches of a batch.  The compute stream orders the batches and everything else the context does (bqc_sync, bqc_reset, exports,
+// the slots' ev_done, bqc_dbatch_free wait for it alone): whatever runs on the coverage stream lies between a fork behind k_prep_reads
+// and a join in front of the batch's last launch, and EVERY return behind the fork joins (enqueue_kernels).
+static int enqueue_batch(bqc_ctx* c, BatchMem& m, bool& forked)
 {
     DevRefs refs{(const uint8_t* const*)c->d_ref_ptrs, c->d_ref_len, c->d_main, c->opt.n_refs, (const uint32_t* const*)c->d_refn_ptrs};
     uint32_t* err = &m.d_err->flags;
     const DevBatch& d = m.d;
-    if (d.n_reads == 0) { if (c->timing) { c->n_timed = 0; c->tnames.clear(); } return 0; }
+    const bool side = c->cov_side && (d.n_cov_tiles || m.n_add);
+    if (side && !c->ev_cov_join) { // the first batch that needs them
+        if (!c->cov_stream) c->cov_stream = bqc_pool_stream(c->device, BQC_STREAM_RANK_COV);
+        if (!c->cov_stream) return bqc_fail(c, BQC_ERR_DEVICE, "hipStreamCreate failed");
+        if (!c->ev_cov_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_cov_fork, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_cov_join, hipEventDisableTiming));
+    }
     if (c->timing) { c->n_timed = 0; c->tnames.clear(); (void)hipEventRecord(c->ev[0], c->stream); }
     m.prep.replay = m.processed ? 1u : 0u;
-    bqc_launch_prep(m.prep, refs, c->stream);
+    bqc_launch_prep(m.prep, refs, c->stream, side ? c->ev_cov_fork : nullptr); // (the plan's one workgroup is queued before the coverage stream's work)
     m.processed = true;
     tick(c, "k_prep");
-    if (!d.n_cov_tiles) bqc_launch_or_bytes(c->d_started, m.d_started_after, c->opt.n_lanes, c->stream); // (else: k_cov's epilogue)
+    if (side) {
+        HIPCHK(c, hipStreamWaitEvent(c->cov_stream, c->ev_cov_fork, 0));
+        forked = true;
+        launch_coverage(c, m, c->cov_stream);
+    } else if (!d.n_cov_tiles) bqc_launch_or_bytes(c->d_started, m.d_started_after, c->opt.n_lanes, c->stream);
     if (d.n_reads > m.n_slow) { // reads on the short-read fast path
         const uint32_t grid = c->n_cu; // one workgroup per CU (the chunk count is on the device); every workgroup owns a slot of scratch rows
         if (!(bqc_short_parts() & 8u)) { // (profiling only: per-read statistics of the fast chunks as a separate kernel)
@@ -569,13 +602,29 @@ static int enqueue_kernels(bqc_ctx* c, BatchMem& m)
         tick(c, "k_long");
     }
     if (d.n_nm_extra) bqc_launch_nm_extra(d, c->sl, c->d_state, refs, err, c->stream);
-    if (d.n_cov_tiles) bqc_launch_cov(d, c->sl, c->d_state, c->d_carry, c->d_parity, m.d_lane_mask, c->d_started, m.d_started_after, c->opt.n_lanes, c->stream);
-    bqc_launch_add_words(c->d_state, m.d_add_idx, m.d_add_val, m.n_add, c->stream);
-    tick(c, "k_cov");
+    if (!side) {
+        if (d.n_cov_tiles) launch_coverage(c, m, c->stream);
+        else bqc_launch_add_words(c->d_state, m.d_add_idx, m.d_add_val, m.n_add, c->stream);
+        tick(c, "k_cov");
+    }
     if (c->sketch) { sketch_process(c->sketch, d, c->stream); tick(c, "k_sketch"); }
+    if (side) { // the join, behind everything the compute stream has of this batch but its last launch
+        const int rc = cov_join(c, forked);
+        if (rc) return rc;
+        tick(c, "k_cov"); // (on the coverage stream: what the compute stream WAITS for it at the join, not the kernel's time)
+    }
     bqc_launch_err_merge(c->d_err0, m.d_err, c->stream); // the first batch with an error defines the stream's error
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+
+static int enqueue_kernels(bqc_ctx* c, BatchMem& m)
+{
+    if (m.d.n_reads == 0) { if (c->timing) { c->n_timed = 0; c->tnames.clear(); } return 0; }
+    bool forked = false;
+    const int rc = enqueue_batch(c, m, forked);
+    if (forked) (void)cov_join(c, forked); // (a return in the middle of the batch: the context is poisoned, and the compute stream still orders everything)
+    return rc;
 }
 
 // what the device found wrong with a batch -> error code and message (the reference prints a message and exits 1)
@@ -1181,7 +1230,7 @@ extern "C" int bqc_shard_resolve(bqc_ctx* c, const void* pred)
         d.n_reads = n; d.lane = (const uint8_t*)(base + o_lane); d.cov = (const CovEntry*)(base + o_cov); d.cov_extra = (const CovExtra*)(base + o_covx);
         d.desc = (const BatchDesc*)(base + o_desc); d.cov_tiles = (const CovTile*)(base + o_tiles); d.n_cov_tiles = (uint32_t)H.tiles.size();
         if (!d.n_cov_tiles) bqc_launch_or_bytes(c->d_started, (const uint8_t*)(base + o_started), nl, c->stream);
-        else bqc_launch_cov(d, c->sl, c->d_state, c->d_carry, c->d_parity, (const uint8_t*)(base + o_mask), c->d_started, (const uint8_t*)(base + o_started), nl, c->stream);
+        else bqc_launch_cov(d, c->sl, c->d_state, c->d_carry, c->d_parity, (const uint8_t*)(base + o_mask), c->d_started, (const uint8_t*)(base + o_started), nl, pb.extra_cap, c->stream);
         bqc_launch_add_words(c->d_state, (const uint64_t*)(base + o_aidx), (const uint64_t*)(base + o_aval), (uint32_t)H.add_idx.size(), c->stream);
         HIPCHK(c, hipStreamSynchronize(c->stream)); // (img and the tables are reused by the next batch)
         (void)hipFree(pb.dmem);

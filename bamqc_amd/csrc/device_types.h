@@ -126,7 +126,7 @@ struct DevBatch {
     const int32_t* as_;
     const uint32_t* l_seq;
     const uint16_t* n_cigar;
-    const uint32_t* seq_off;   // payload offsets: prefix sums over the reads (k_prep_sizes / _scan / _reads)
+    const uint32_t* seq_off;   // payload offsets: prefix sums over the reads (k_prep_sizes / _reads)
     const uint32_t* qual_off;
     const uint32_t* cigar_off;
     // variable-length payload

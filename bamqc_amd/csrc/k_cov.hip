@@ -14,7 +14,7 @@
 __global__ __launch_bounds__(256) void k_cov(DevBatch b, StateLayout sl, uint64_t* __restrict__ state,
                                                 uint32_t* __restrict__ carry /* [lane][2][2000] */, uint32_t* parity /* [n_lanes], then a counter */,
                                                 const uint8_t* __restrict__ lane_mask, uint8_t* __restrict__ started,
-                                                const uint8_t* __restrict__ started_after, uint32_t n_lanes)
+                                                const uint8_t* __restrict__ started_after, uint32_t n_lanes, uint32_t cov_extra_cap)
 {
     // 256 threads x 16 positions >= BQC_COV_TILE + 1; position p lives at KC_AT(p): 4 words of padding after every 64, so that the
     // 16-byte accesses of the scan (thread t: words 16 t ..) of 16 neighbouring threads fall on 64 different banks
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void k_cov(DevBatch b, StateLayout sl, uint64_
         if (i0 < t.list_end) e0 = load(t, i0);
         if (i1 < t.list_end) e1 = load(t, i1);
     }
-    const uint32_t n_extra = b.desc->n_cov_extra;
+    const uint32_t n_extra = min(b.desc->n_cov_extra, cov_extra_cap); // (k_build_plan clamps the descriptor's; this kernel may run before it)
     // persistent workgroups: the depth histogram stays in LDS across tiles and is flushed once per lane
     for (uint32_t ti = blockIdx.x;; ti += gridDim.x) {
         const bool done = ti >= b.n_cov_tiles;
@@ -190,11 +190,11 @@ __global__ void k_err_merge(ErrRec* __restrict__ dst, const ErrRec* __restrict__
 extern "C" void bqc_launch_err_merge(ErrRec* dst, const ErrRec* src, hipStream_t s) { hipLaunchKernelGGL(k_err_merge, dim3(1), dim3(1), 0, s, dst, src); }
 
 extern "C" void bqc_launch_cov(const DevBatch& b, const StateLayout& sl, uint64_t* state, uint32_t* carry, uint32_t* parity, const uint8_t* lane_mask,
-                               uint8_t* started, const uint8_t* started_after, uint32_t n_lanes, hipStream_t s)
+                               uint8_t* started, const uint8_t* started_after, uint32_t n_lanes, uint32_t cov_extra_cap, hipStream_t s)
 {
     if (b.n_cov_tiles == 0) return;
     const uint32_t grid = b.n_cov_tiles < 2048u ? b.n_cov_tiles : 2048u; // persistent workgroups, ~8 per CU
-    hipLaunchKernelGGL(k_cov, dim3(grid), dim3(256), 0, s, b, sl, state, carry, parity, lane_mask, started, started_after, n_lanes);
+    hipLaunchKernelGGL(k_cov, dim3(grid), dim3(256), 0, s, b, sl, state, carry, parity, lane_mask, started, started_after, n_lanes, cov_extra_cap);
 }
 
 extern "C" void bqc_launch_cov_final(const StateLayout& sl, uint64_t* state, const uint32_t* carry, const uint32_t* parity,

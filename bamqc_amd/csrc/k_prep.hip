@@ -1,7 +1,9 @@
 // k_prep.hip — the per-read pre-pass and the work decomposition of a batch, on the device.
 //
 // What the reference does record by record before its counters see a read is done here for a whole batch:
-//   k_prep_sizes / k_prep_scan   payload offsets of every read (prefix sums of ceil(L/2), L, n_cigar)
+//   k_prep_sizes                 sums of ceil(L/2), L, n_cigar per block of 1024 reads, in two levels: inside groups of PR_GROUP blocks, and
+//                                per group (prep.h); k_prep_reads adds the groups before its own — the payload offsets of every read
+//                                without a serial scan between the two launches
 //   k_prep_reads                 lane per read: quality-missing flag, checkFlagsAndQuality (TripletCounting.hpp:136-168)
 //                                incl. the forward-only FASTA scan (:254-259) inside a block, the covered interval(s) of
 //                                OverallNumbers::coverage (OverallNumbers.hpp:112-131) from the host's anchor (win, pos), the triplet
@@ -13,6 +15,7 @@
 //                                every lane of k_short only ever sees one mate.
 // Only the O(1)-per-read coverage anchor recurrence (OverallNumbers.hpp:84-110) stays on the host (bqc_pipeline.cpp).
 #include <algorithm>
+#include <vector>
 #include "kernels_common.h"
 #include "prep.h"
 
@@ -57,6 +60,10 @@ __device__ __forceinline__ uint32_t block_scan_excl_max(uint32_t v, uint32_t* sh
     const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x138 /* wave_shr:1 */, 0xF, 0xF, true); // inclusive value of the lane before
     return max(base, prev);
 }
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) // a value every lane holds, into scalar registers
+{
+    return (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)v) | (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32;
+}
 __device__ __forceinline__ void err_key(ErrRec* e, uint32_t read, uint32_t order)
 {
     atomicMin(&e->first_key, ((unsigned long long)read << 3) | order);
@@ -65,64 +72,60 @@ __device__ __forceinline__ void err_key(ErrRec* e, uint32_t read, uint32_t order
 // ---------------------------------------------------------------------------------------------------
 // payload sizes -> offsets
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PR_THREADS) void k_prep_sizes(PrepArgs a)
+// One workgroup per group of PR_GROUP blocks, a wave per block (16 waves, PR_GROUP / 16 blocks each): lane l of the wave owns the reads
+// 256 j + 4 l .. + 3 of the block, j = 0 .. 3 — the loads of k_prep_reads.  Every load of a wave is requested before the first sum.
+#define PS_THREADS 1024
+#define PS_PER (PR_GROUP / (PS_THREADS / 64))
+__global__ __launch_bounds__(PS_THREADS) void k_prep_sizes(PrepArgs a)
 {
-    __shared__ unsigned long long sh[3 * (PR_THREADS / 64)];
+    __shared__ unsigned long long sh[3 * PR_GROUP];
     if (blockIdx.x == 0 && threadIdx.x == 0) { // first kernel of the batch: its records start empty; a replayed batch starts from its own cursor
         a.err->first_key = BQC_ERRKEY_NONE; a.err->flags = 0; a.err->aux0 = a.err->aux1 = 0;
         a.desc->n_cov_extra = 0;
         if (a.pend_extra_n) *a.pend_extra_n = 0;
         if (a.replay) *a.cursor = *a.cursor_save; else *a.cursor_save = *a.cursor;
     }
-    for (uint32_t k = blockIdx.x * PR_THREADS + threadIdx.x; k < a.n_sw; k += gridDim.x * PR_THREADS) a.sw_counts[k] = SwCounts{0, 0, 0, 0};
-    const uint32_t b0 = blockIdx.x * PR_BLOCK;
-    unsigned long long s1 = 0, s2 = 0, s3 = 0;
+    for (uint32_t k = blockIdx.x * PS_THREADS + threadIdx.x; k < a.n_sw; k += gridDim.x * PS_THREADS) a.sw_counts[k] = SwCounts{0, 0, 0, 0};
+    const uint32_t nblk = (a.n + PR_BLOCK - 1) / PR_BLOCK, bg0 = blockIdx.x * PR_GROUP, nb = min((uint32_t)PR_GROUP, nblk - bg0);
+    const uint32_t w = threadIdx.x >> 6, l = lane_id();
+    uint4 vl[PS_PER][4];
+    uint2 vc[PS_PER][4];
 #pragma unroll
-    for (int j = 0; j < PR_PER_THREAD; ++j) {
-        const uint32_t i = b0 + j * PR_THREADS + threadIdx.x;
-        if (i < a.n) { const uint32_t L = a.l_seq[i]; s1 += (L + 1) / 2; s2 += L; s3 += a.n_cigar[i]; }
-    }
+    for (int q = 0; q < PS_PER; ++q) {
+        const uint32_t bl = w + (PS_THREADS / 64) * q;
+        const unsigned long long i0 = (unsigned long long)(bg0 + bl) * PR_BLOCK;
+        const bool whole = bl < nb && i0 + PR_BLOCK <= a.n;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); s3 += __shfl_xor(s3, o); }
-    if (lane_id() == 0) { const uint32_t w = threadIdx.x >> 6; sh[3 * w] = s1; sh[3 * w + 1] = s2; sh[3 * w + 2] = s3; }
-    block_sync();
-    if (threadIdx.x < 3) {
-        unsigned long long t = 0;
-        for (uint32_t w = 0; w < PR_THREADS / 64; ++w) t += sh[3 * w + threadIdx.x];
-        a.blk_sizes[3ull * blockIdx.x + threadIdx.x] = t;
-    }
-}
-
-// one workgroup: block sums -> exclusive bases, in place; a batch whose payload does not fit 32-bit offsets is an error
-__global__ __launch_bounds__(1024) void k_prep_scan(PrepArgs a)
-{
-    __shared__ unsigned long long sh[3 * 1024];
-    const uint32_t nblk = (a.n + PR_BLOCK - 1) / PR_BLOCK;
-    const uint32_t per = (nblk + blockDim.x - 1) / blockDim.x;
-    const uint32_t lo = min(nblk, threadIdx.x * per), hi = min(nblk, lo + per);
-    unsigned long long t[3] = {0, 0, 0};
-    for (uint32_t b = lo; b < hi; ++b)
-        for (int k = 0; k < 3; ++k) t[k] += a.blk_sizes[3ull * b + k];
-    for (int k = 0; k < 3; ++k) sh[3 * threadIdx.x + k] = t[k];
-    block_sync();
-    for (uint32_t d = 1; d < blockDim.x; d <<= 1) { // Hillis-Steele over the thread totals
-        unsigned long long v[3] = {0, 0, 0};
-        if (threadIdx.x >= d) for (int k = 0; k < 3; ++k) v[k] = sh[3 * (threadIdx.x - d) + k];
-        block_sync();
-        for (int k = 0; k < 3; ++k) sh[3 * threadIdx.x + k] += v[k];
-        block_sync();
-    }
-    unsigned long long run[3];
-    for (int k = 0; k < 3; ++k) run[k] = sh[3 * threadIdx.x + k] - t[k];
-    for (uint32_t b = lo; b < hi; ++b) {
-        bool over = false;
-        for (int k = 0; k < 3; ++k) {
-            const unsigned long long s = a.blk_sizes[3ull * b + k];
-            a.blk_sizes[3ull * b + k] = run[k];
-            run[k] += s;
-            over |= run[k] > 0xFFFFFFFFull;
+        for (int j = 0; j < 4; ++j) {
+            vl[q][j] = make_uint4(0, 0, 0, 0); vc[q][j] = make_uint2(0, 0);
+            if (whole) { const uint32_t i = (uint32_t)i0 + 256u * j + 4u * l; vl[q][j] = *(const uint4*)(a.l_seq + i); vc[q][j] = *(const uint2*)(a.n_cigar + i); }
         }
-        if (over) err_key(a.err, b * PR_BLOCK, 3);
+    }
+#pragma unroll
+    for (int q = 0; q < PS_PER; ++q) {
+        const uint32_t bl = w + (PS_THREADS / 64) * q;
+        const unsigned long long i0 = (unsigned long long)(bg0 + bl) * PR_BLOCK;
+        unsigned long long s1 = 0, s2 = 0, s3 = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint4 v = vl[q][j];
+            s1 += (unsigned long long)((v.x + 1) / 2) + (v.y + 1) / 2 + (v.z + 1) / 2 + (v.w + 1) / 2;
+            s2 += (unsigned long long)v.x + v.y + v.z + v.w;
+            s3 += (vc[q][j].x & 0xFFFFu) + (vc[q][j].x >> 16) + (vc[q][j].y & 0xFFFFu) + (vc[q][j].y >> 16);
+        }
+        if (bl < nb && i0 + PR_BLOCK > a.n) // the batch's last block
+            for (unsigned long long i = i0 + l; i < a.n; i += WAVE) { const uint32_t L = a.l_seq[i]; s1 += (L + 1) / 2; s2 += L; s3 += a.n_cigar[i]; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); s3 += __shfl_xor(s3, o); }
+        if (l == 0) { sh[3 * bl] = s1; sh[3 * bl + 1] = s2; sh[3 * bl + 2] = s3; } // (a block past the batch's end: 0)
+    }
+    block_sync();
+    if (threadIdx.x < 3 * PR_GROUP) {
+        const uint32_t bl = threadIdx.x / 3, k = threadIdx.x % 3;
+        unsigned long long t = 0;
+        for (uint32_t j = 0; j < bl; ++j) t += sh[3 * j + k];
+        if (bl < nb) a.blk_sizes[3ull * (bg0 + bl) + k] = t;
+        if (bl == PR_GROUP - 1) a.grp_sizes[3ull * blockIdx.x + k] = t + sh[3 * bl + k];
     }
 }
 
@@ -171,7 +174,7 @@ __device__ __forceinline__ ReadOut prep_one(const PrepArgs& a, const DevRefs& re
     else if (lane >= a.n_lanes) err_key(a.err, i, 2);
     // (BQC_FLAG_NO_QUAL — quality block starting with 0xFF, SURVEY U1 — is a fact of the record's decoding and arrives with the
     // flag column: probing qual[qo] here cost one 128-byte line per read, more than every other byte this kernel reads)
-    if (!offsets_ok) nc = 0; // (the batch fails: k_prep_scan)
+    if (!offsets_ok) nc = 0; // (the batch fails: the block's check in k_prep_reads)
     const bool fast = !a.no_fast && L <= BQC_FAST_MAXLEN;
     uint32_t nseg = 0;
     CovEntry ce = in.ce;
@@ -276,17 +279,51 @@ __global__ __launch_bounds__(PR_THREADS) __attribute__((amdgpu_waves_per_eu(PR_W
 {
     __shared__ uint32_t sh[2 * (PR_THREADS / 64)];
     __shared__ uint32_t red[8];
+    __shared__ unsigned long long gsum[3 * (PR_THREADS / 64) + 6];
     const uint32_t i0 = blockIdx.x * PR_BLOCK + 4u * threadIdx.x;
-    const unsigned long long gs = a.blk_sizes[3ull * blockIdx.x], gq = a.blk_sizes[3ull * blockIdx.x + 1], gc = a.blk_sizes[3ull * blockIdx.x + 2];
     if (threadIdx.x < 8) red[threadIdx.x] = threadIdx.x == 0 ? 0xFFFFFFFFu : 0u;
+    // The block's bases: the totals of the groups before this block's (thread t: groups t, t + 256, ..) and the sums inside the group up
+    // to this block, without and with it (threads 0 .. 5, a word each).  Requested in front of the columns — loads return in the order of their requests —
+    // and summed while the columns are in flight: no round trip in front of them, and none behind.
+    const uint32_t grp = blockIdx.x / PR_GROUP, nblk = gridDim.x;
+    unsigned long long grp_before[3] = {0, 0, 0}, grp_more[3] = {0, 0, 0}, in_grp = 0;
+    for (uint32_t g = threadIdx.x + 2 * PR_THREADS; g < grp; g += PR_THREADS) { // (more than 512 groups, batches of more than 16 M reads: waited for here)
+        const unsigned long long* p = (const unsigned long long*)((const char*)a.grp_sizes + 24u * g); // (a 32-bit offset from a scalar base)
+        for (int k = 0; k < 3; ++k) grp_before[k] += p[k];
+    }
+    if (threadIdx.x < grp) {
+        const unsigned long long* p = (const unsigned long long*)((const char*)a.grp_sizes + 24u * threadIdx.x);
+        for (int k = 0; k < 3; ++k) grp_before[k] += p[k];
+    }
+    if (threadIdx.x + PR_THREADS < grp) {
+        const unsigned long long* p = (const unsigned long long*)((const char*)a.grp_sizes + 24u * (threadIdx.x + PR_THREADS));
+        for (int k = 0; k < 3; ++k) grp_more[k] = p[k];
+    }
+    if (threadIdx.x < 6) { // (a word per lane: loads the wave does not wait for here, as it would for scalar ones)
+        const bool grp_last = (blockIdx.x + 1) % PR_GROUP == 0 || blockIdx.x + 1 == nblk;
+        const unsigned long long* incl_p = grp_last ? a.grp_sizes + 3ull * grp : a.blk_sizes + 3ull * (blockIdx.x + 1);
+        in_grp = threadIdx.x < 3 ? a.blk_sizes[3ull * blockIdx.x + threadIdx.x] : incl_p[threadIdx.x - 3];
+    }
+    auto sum_groups = [&] { // over the workgroup, into LDS: read behind the barriers of the scans below
+        for (int k = 0; k < 3; ++k) grp_before[k] += grp_more[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+            for (int k = 0; k < 3; ++k) grp_before[k] += __shfl_xor(grp_before[k], o);
+        if (lane_id() == 0) for (int k = 0; k < 3; ++k) gsum[3 * (threadIdx.x >> 6) + k] = grp_before[k];
+        if (threadIdx.x < 6) gsum[3 * (PR_THREADS / 64) + threadIdx.x] = in_grp;
+    };
     ReadIn in[4];
     const uint32_t nlive = i0 >= a.n ? 0u : min(4u, a.n - i0);
-    if (nlive == 4u) {
+    if ((unsigned long long)(blockIdx.x + 1) * PR_BLOCK <= a.n) { // (every block but a batch's last: the same for all its threads, so that they can sum together inside)
         const uint4 vl = *(const uint4*)(a.l_seq + i0);
         const uint2 vc = *(const uint2*)(a.n_cigar + i0), vf = *(const uint2*)(a.flag_in + i0);
         const uint32_t vlane = *(const uint32_t*)(a.lane + i0), vmq = *(const uint32_t*)(a.mapq + i0);
         const int4 vr = *(const int4*)(a.rid + i0), vp = *(const int4*)(a.pos + i0), va = *(const int4*)(a.as_ + i0);
         const uint4 c01 = *(const uint4*)(a.cov_in + i0), c23 = *(const uint4*)(a.cov_in + i0 + 2);
+        // (the sums are taken HERE, while the columns are in flight: without this the compiler adds the two loaded halves, and waits
+        // for them, in front of the column loads)
+        asm volatile("" : "+v"(grp_before[0]), "+v"(grp_before[1]), "+v"(grp_before[2]));
+        sum_groups();
         const uint32_t Ls[4] = {vl.x, vl.y, vl.z, vl.w}, ncs[4] = {vc.x & 0xFFFFu, vc.x >> 16, vc.y & 0xFFFFu, vc.y >> 16};
         const uint32_t fs[4] = {vf.x & 0xFFFFu, vf.x >> 16, vf.y & 0xFFFFu, vf.y >> 16};
         const int32_t rs[4] = {vr.x, vr.y, vr.z, vr.w}, ps[4] = {vp.x, vp.y, vp.z, vp.w}, as[4] = {va.x, va.y, va.z, va.w};
@@ -294,6 +331,7 @@ __global__ __launch_bounds__(PR_THREADS) __attribute__((amdgpu_waves_per_eu(PR_W
 #pragma unroll
         for (int j = 0; j < 4; ++j) in[j] = ReadIn{Ls[j], ncs[j], fs[j], (vlane >> (8 * j)) & 0xFFu, (vmq >> (8 * j)) & 0xFFu, rs[j], ps[j], as[j], cs[j]};
     } else {
+        sum_groups();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             in[j] = ReadIn{0, 0, 0x900u, 0, 0, -1, 0, 0, CovEntry{BQC_COV_NONE, 0}};
@@ -305,7 +343,16 @@ __global__ __launch_bounds__(PR_THREADS) __attribute__((amdgpu_waves_per_eu(PR_W
 #pragma unroll
     for (int j = 0; j < 4; ++j) { ls[j] = ts; lq[j] = tq; lc[j] = tc; ts += (in[j].L + 1) / 2; tq += in[j].L; tc += in[j].nc; }
     uint32_t tot;
-    const unsigned long long bs = gs + block_scan_excl(ts, sh, &tot), bq = gq + block_scan_excl(tq, sh, &tot), bc = gc + block_scan_excl(tc, sh, &tot);
+    const uint32_t xs = block_scan_excl(ts, sh, &tot), xq = block_scan_excl(tq, sh, &tot), xc = block_scan_excl(tc, sh, &tot);
+    unsigned long long excl[3], incl[3];
+    for (int k = 0; k < 3; ++k) { // (behind the scans' barriers; the same in every lane: scalar registers)
+        unsigned long long t = 0;
+        for (uint32_t w = 0; w < PR_THREADS / 64; ++w) t += gsum[3 * w + k];
+        grp_before[k] = uniform64(t); excl[k] = uniform64(gsum[3 * (PR_THREADS / 64) + k]); incl[k] = uniform64(gsum[3 * (PR_THREADS / 64) + 3 + k]);
+    }
+    unsigned long long base[3];
+    if (prep_block_bases(grp_before, excl, incl, base) && threadIdx.x == 0) err_key(a.err, blockIdx.x * PR_BLOCK, 3);
+    const unsigned long long bs = base[0] + xs, bq = base[1] + xq, bc = base[2] + xc;
     ReadOut out[4];
     // what the four reads need from memory besides their columns, all of it requested before the first read is looked at
     CigarView cv[4];
@@ -636,16 +683,43 @@ __global__ __launch_bounds__(PR_THREADS) void k_build_scatter(PrepArgs a)
 }
 
 // the unordered flags of the hot kernels and the keyed first error, for the host (one small copy per batch)
-extern "C" void bqc_launch_prep(const PrepArgs& a, const DevRefs& refs, hipStream_t s)
+// after_reads (or nullptr): recorded behind k_prep_reads — cov[], cov_extra[] and desc->n_cov_extra are final there (k_cov's inputs)
+extern "C" void bqc_launch_prep(const PrepArgs& a, const DevRefs& refs, hipStream_t s, hipEvent_t after_reads)
 {
     if (a.n == 0) return;
     const uint32_t nblk = (a.n + PR_BLOCK - 1) / PR_BLOCK;
-    hipLaunchKernelGGL(k_prep_sizes, dim3(nblk), dim3(PR_THREADS), 0, s, a);
-    hipLaunchKernelGGL(k_prep_scan, dim3(1), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(k_prep_sizes, dim3((nblk + PR_GROUP - 1) / PR_GROUP), dim3(PS_THREADS), 0, s, a);
     hipLaunchKernelGGL(k_prep_reads, dim3(nblk), dim3(PR_THREADS), 0, s, a, refs);
+    if (after_reads) (void)hipEventRecord(after_reads, s);
     if (a.order) hipLaunchKernelGGL(k_build_count, dim3(a.n_sw), dim3(PR_THREADS), 0, s, a);
     hipLaunchKernelGGL(k_build_plan, dim3(1), dim3(1024), 0, s, a);
     hipLaunchKernelGGL(k_build_scatter, dim3(a.n_sw), dim3(PR_THREADS), 0, s, a);
+}
+
+// The offsets' arithmetic on the host, step by step as the two kernels do it (tests: a batch with 4 GB of payload cannot be one).
+extern "C" uint32_t bqc_prep_group(void) { return PR_GROUP; }
+extern "C" uint32_t bqc_prep_bases(const uint64_t* blk_totals, uint32_t n_blocks, uint64_t* bases)
+{
+    const uint32_t n_groups = (n_blocks + PR_GROUP - 1) / PR_GROUP;
+    std::vector<unsigned long long> blk(3ull * n_blocks), grp(3ull * n_groups);
+    for (uint32_t g = 0; g < n_groups; ++g) // k_prep_sizes
+        for (int k = 0; k < 3; ++k) {
+            unsigned long long t = 0;
+            for (uint32_t b = g * PR_GROUP; b < std::min(n_blocks, (g + 1) * PR_GROUP); ++b) { blk[3ull * b + k] = t; t += blk_totals[3ull * b + k]; }
+            grp[3ull * g + k] = t;
+        }
+    uint32_t first_bad = 0xFFFFFFFFu;
+    for (uint32_t b = 0; b < n_blocks; ++b) { // k_prep_reads
+        const uint32_t g = b / PR_GROUP;
+        const bool grp_last = (b + 1) % PR_GROUP == 0 || b + 1 == n_blocks;
+        const unsigned long long* incl = grp_last ? &grp[3ull * g] : &blk[3ull * (b + 1)];
+        unsigned long long before[3] = {0, 0, 0}, base[3];
+        for (uint32_t g2 = 0; g2 < g; ++g2)
+            for (int k = 0; k < 3; ++k) before[k] += grp[3ull * g2 + k];
+        if (prep_block_bases(before, &blk[3ull * b], incl, base)) first_bad = std::min(first_bad, b);
+        for (int k = 0; k < 3; ++k) bases[3ull * b + k] = base[k];
+    }
+    return first_bad;
 }
 
 // ---------------------------------------------------------------------------------------------------
