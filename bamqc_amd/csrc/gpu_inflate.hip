@@ -24,7 +24,11 @@
 //
 // Format: RFC 1951 (public); acceptance rules as the host decoder's (bamqc_amd/host/inflate_fast.cpp): over-subscribed or
 // incomplete code sets, a missing end-of-block code, distances before the block's start, output other than ISIZE bytes, input
-// beyond the block are errors — a corrupt file is reported, never followed out of bounds.
+// beyond the block are errors — a corrupt file is reported, never followed out of bounds.  Both halves of that sentence are tested
+// on streams built bit by bit (tests/deflate_build.py, tests/test_gpu_inflate_handbuilt.py), not only on what zlib's encoder writes:
+// distances up to 32 768 (the 15 bits of a match description), 15-bit length and distance codes in one symbol (48 bits between two
+// refills), code sets with 336 of GW_LX's 352 second-level entries, one-code and empty distance sets, a header at every bit
+// alignment; and each of the rejections above made by construction, in every kernel variant.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

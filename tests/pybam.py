@@ -184,15 +184,21 @@ def write_bam(path, header_text, refs, records, block=40000, rng=None):
 
 
 MEMBER_KINDS = ("stored", "fixed", "level9", "flush_split", "level1", "empty")
+HANDBUILT_KINDS = ("handbuilt", "handbuilt", "handbuilt", "empty")  # (for write_bam_adversarial's `kinds`)
 
 
 def _bgzf_member(payload, kind, rng):
     """One BGZF member whose DEFLATE stream is of the given kind: `stored` (level 0: stored blocks only), `fixed` (Z_FIXED: fixed
     Huffman codes), `level9` / `level1` (dynamic codes), `flush_split` (the payload compressed in 2-5 pieces with Z_FULL_FLUSH
-    between them: several deflate blocks, an empty stored block after each, no match reaches back over a flush point).
-    Returns None when the member would not fit BGZF's 64 KiB."""
+    between them: several deflate blocks, an empty stored block after each, no match reaches back over a flush point), `handbuilt`
+    (no zlib encoder: tests/deflate_build.py's member_stream — farthest matches up to distance 32 768, 15-bit codes, one-code and
+    empty distance sets, several deflate blocks).  Returns None when the member would not fit BGZF's 64 KiB."""
     import zlib
-    if kind == "stored":
+    if kind == "handbuilt":
+        import random
+        from tests import deflate_build
+        comp = deflate_build.member_stream(payload, random.Random(int(rng.integers(0, 1 << 30))))
+    elif kind == "stored":
         c = zlib.compressobj(0, zlib.DEFLATED, -15)
         comp = c.compress(payload) + c.flush()
     elif kind == "fixed":
@@ -216,9 +222,9 @@ def _bgzf_member(payload, kind, rng):
             struct.pack("<II", zlib.crc32(payload) & 0xFFFFFFFF, len(payload)))
 
 
-def write_bam_adversarial(path, header_text, refs, records, rng, tiny_until=0.5):
+def write_bam_adversarial(path, header_text, refs, records, rng, tiny_until=0.5, kinds=MEMBER_KINDS):
     """The same records as a BGZF file no writer in the field produces but every reader must take: members alternate between the kinds
-    of MEMBER_KINDS (empty members in the middle of the file included); the first `tiny_until` of the stream is cut into payloads of
+    of `kinds` (empty members in the middle of the file included); the first `tiny_until` of the stream is cut into payloads of
     1..200 bytes (every record of that part straddles at least one member boundary, most straddle several), the rest into payloads
     of 1..65 280 bytes with the extremes (1, 65 280) forced in.  Returns the list of (kind, payload bytes) written."""
     out = _bam_bytes(header_text, refs, records)
@@ -227,7 +233,7 @@ def write_bam_adversarial(path, header_text, refs, records, rng, tiny_until=0.5)
     with open(path, "wb") as f:
         p, k = 0, 0
         while p < len(out):
-            kind = MEMBER_KINDS[k % len(MEMBER_KINDS)]
+            kind = kinds[k % len(kinds)]
             k += 1
             if kind == "empty":
                 f.write(_bgzf_member(b"", "level1", rng))

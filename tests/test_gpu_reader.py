@@ -241,6 +241,38 @@ def test_gpu_reader_on_adversarial_bgzf_members(tmp_path, monkeypatch):
         same(want, {k: np.concatenate([c[k] for c in got]) for k in got[0]})
 
 
+def test_gpu_reader_on_handbuilt_deflate_members(tmp_path, monkeypatch):
+    """The reader on the card on members whose DEFLATE streams no zlib encoder writes (tests/pybam.py kind `handbuilt`, through
+    tests/deflate_build.py: farthest matches up to distance 32 768, dynamic codes up to 15 bits over skewed frequencies, one-code and
+    empty distance sets, several deflate blocks per member, empty members between them): the columns of tests/pybam.columns
+    (gzip + struct) and of the host reader, by the default kernels and a lane per block, decoded on the card (no batch handed over)."""
+    from tests import pybam
+    from tests.test_host_io import _wild_bam
+    path = str(tmp_path / "hand.bam")
+    _wild_bam(path, 43, 2000, extra_nm=False, adversarial=True, pad_header=300, kinds=pybam.HANDBUILT_KINDS, tiny_until=0.05)
+    want, refs, _, _ = pybam.columns(path, [1, 1, 1])
+    assert len(want["flag"]) == 2000
+    h = hostio.BamFile(path)
+    h.set_main_chrom(np.ones(3, np.uint8))
+    host = [dict((k, np.array(v, copy=True)) for k, v in x.items() if isinstance(v, np.ndarray)) for x in h.batches(1234)]
+    h.close()
+    host = {k: np.concatenate([c[k] for c in host]) for k in host[0]}
+    same(want, host)
+    for env in ({}, {"BQC_GI_WAVE": "0"}):
+        with monkeypatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            b = hostio.BamFile(path, gpu=0)
+            b.set_main_chrom(np.ones(3, np.uint8))
+            got = [dict((k, np.array(v, copy=True)) for k, v in x.items() if isinstance(v, np.ndarray)) for x in b.batches(1234)]
+            handed = b.batches_handed_over
+            b.close()
+        got = {k: np.concatenate([c[k] for c in got]) for k in got[0]}
+        same(want, got)
+        same(host, got)
+        assert handed == 0, env
+
+
 # ---- the record rules (host/bam_record.h) on the card: the sweep files of tests/bam_sweeps.py ------------------------------------
 def _digest(cols):
     import hashlib

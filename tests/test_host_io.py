@@ -193,7 +193,7 @@ def test_sam_text_decodes_to_the_same_batches(synth_files, tmp_path):
         assert np.array_equal(gb[k], gs[k]), k
 
 
-def _wild_bam(path, seed, n_reads, extra_nm=True, adversarial=False, pad_header=0):
+def _wild_bam(path, seed, n_reads, extra_nm=True, adversarial=False, pad_header=0, kinds=None, tiny_until=0.5):
     """Wild records (tests/test_gpu_fuzz.py) as a BAM with every tag type around the three tags the decoder looks for."""
     from tests.test_gpu_fuzz import wild_batch
     from tests import pybam
@@ -240,7 +240,7 @@ def _wild_bam(path, seed, n_reads, extra_nm=True, adversarial=False, pad_header=
         so += (L + 1) // 2; qo += L; co += nc
     text += "".join("@CO\tpadding line %d of a long header\n" % i for i in range(pad_header))
     if adversarial:  # members of every DEFLATE kind, payloads of 1 .. 65 280 bytes, every record of the first half across member boundaries
-        pybam.write_bam_adversarial(path, text, [("chr%d" % (i + 1), len(r)) for i, r in enumerate(refs)], recs, rng)
+        pybam.write_bam_adversarial(path, text, [("chr%d" % (i + 1), len(r)) for i, r in enumerate(refs)], recs, rng, tiny_until, kinds or pybam.MEMBER_KINDS)
     else:
         pybam.write_bam(path, text, [("chr%d" % (i + 1), len(r)) for i, r in enumerate(refs)], recs, rng=rng)
     return cols, exp_extra
@@ -280,6 +280,27 @@ def test_adversarial_bgzf_members_through_the_host_reader(tmp_path):
     p = str(tmp_path / "adv.bam")
     _wild_bam(p, 31, 4000, extra_nm=False, adversarial=True, pad_header=4000)
     want, refs, _, _ = pybam.columns(p, [1, 1, 1])
+    for threads in ("1", "4"):
+        os.environ["BQC_IO_THREADS"] = threads
+        try:
+            f = hostio.BamFile(p)
+            f.set_main_chrom(np.ones(3, np.uint8))
+            got = list(f.batches(max_reads=999))
+        finally:
+            del os.environ["BQC_IO_THREADS"]
+        for k in ("flag", "mapq", "lane", "rid", "pos", "tlen", "nm", "as_", "l_seq", "n_cigar", "seq", "qual", "cigar"):
+            assert np.array_equal(np.concatenate([b[k] for b in got]), want[k]), (k, threads)
+
+
+def test_handbuilt_deflate_members_through_the_host_reader(tmp_path):
+    """A BGZF file whose members' DEFLATE streams no zlib encoder writes (tests/pybam.py kind `handbuilt`: farthest matches up to
+    distance 32 768, dynamic codes up to 15 bits over skewed frequencies, one-code and empty distance sets, several deflate blocks
+    per member; empty members between them; the first twentieth of the file in payloads of 1..200 bytes): the host reader's columns against the independent decoder's (gzip + struct)."""
+    from tests import pybam
+    p = str(tmp_path / "hand.bam")
+    _wild_bam(p, 41, 2000, extra_nm=False, adversarial=True, pad_header=300, kinds=pybam.HANDBUILT_KINDS, tiny_until=0.05)
+    want, refs, _, _ = pybam.columns(p, [1, 1, 1])
+    assert len(want["flag"]) == 2000
     for threads in ("1", "4"):
         os.environ["BQC_IO_THREADS"] = threads
         try:
