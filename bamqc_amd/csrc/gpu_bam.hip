@@ -41,6 +41,7 @@
 
 #include "../../include/bamqc.h"
 #include "gpu_bam.h"
+#include "gpu_batch.h"
 #include "gpu_inflate.h"
 #include "../host/bam_record.h"
 #include "../host/parallel.h"
@@ -57,12 +58,6 @@ enum { GBX_TAGS = 1 << 8, GBX_RG_MISSING = 1 << 9, GBX_RG_TYPE = 1 << 10, GBX_RG
 struct GbSeg { uint32_t first, exit, count, flags, seq_bytes, qual_bytes, cigar_words, pad; }; // offsets relative to the window
 struct GbRec { uint32_t off, so, qo, co; };                                                     // payload prefix inside the segment
 struct GbBase { uint64_t so, qo, co; uint32_t rec, take; };                                    // where a taken segment's records / payload start in the batch
-struct GbCols { // device copies of the fixed columns + per-record payload placement
-    uint16_t* flag; uint8_t* mapq; uint8_t* lane; int32_t* rid; int32_t* pos; int32_t* tlen; int32_t* nm; int32_t* as; uint32_t* l_seq; uint16_t* n_cigar;
-    uint32_t* rec_off; uint64_t* so; uint64_t* qo; uint64_t* co;
-};
-struct GbLanes { const uint8_t* blob; const uint32_t* off; const uint32_t* len; const uint32_t* index; uint32_t n, lane_count; };
-
 typedef uint32_t __attribute__((aligned(1))) gb_u32_u;
 typedef uint32_t gb_u32x4 __attribute__((ext_vector_type(4)));
 typedef gb_u32x4 __attribute__((aligned(1))) gb_u32x4_u;
@@ -360,36 +355,6 @@ __global__ __launch_bounds__(256) void k_gb_copy(const uint8_t* __restrict__ bas
 // host side
 // ---------------------------------------------------------------------------------------------------
 namespace {
-template <typename T> struct DevBuf { // grows, never shrinks
-    T* p = nullptr;
-    size_t cap = 0;
-    bool need(size_t n, bool exact = false)
-    {
-        if (cap >= n) return true;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t c = exact ? n : n + n / 4 + 64;
-        if (hipMalloc((void**)&p, c * sizeof(T)) != hipSuccess) { p = nullptr; return false; }
-        cap = c;
-        return true;
-    }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-template <typename T> struct PinBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    bool need(size_t n)
-    {
-        if (cap >= n) return true;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        const size_t c = n + n / 4 + 64;
-        if (hipHostMalloc((void**)&p, c * sizeof(T), hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-        cap = c;
-        return true;
-    }
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
 // The batches' payload buffers: allocated when a reader opens (before its first kernel runs: hipMalloc and hipFree behind a running
 // 30 ms inflate kernel were measured to wait for it), all of one size, handed back here when a batch object dies.
 struct PayloadPool {
@@ -435,9 +400,11 @@ struct PayloadPool {
     }
 };
 PayloadPool g_pool;
-void dev_free_hook(void* p) { g_pool.give(p); }
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 } // namespace
+void gb_pool_fill(size_t bytes, int n) { g_pool.fill(bytes, n); }
+void* gb_pool_take(size_t need, size_t& cap) { void* p = g_pool.take(need); cap = p ? g_pool.cap : 0; return p; }
+void gb_pool_give(void* p) { g_pool.give(p); }
 
 // One run of BGZF blocks in flight: its own stream, page-locked input buffer and device buffers.  The uncompressed bytes land behind
 // `head` spare bytes, which take the unfinished record of the run before (the record stream is walked run by run).
@@ -682,7 +649,7 @@ bool GpuBamReader::open(const char* path, int device, const BamHeader& hdr, uint
         if (!ok) { err = "GPU reader: out of device memory"; return false; }
         const size_t typical = std::min<size_t>(reads * 400, batch_bases / 2 * 3 + reads * 40 + (64u << 20)) + (1u << 20);
         const double t_c = now_s();
-        g_pool.fill(typical, 10); // (a batch's buffer comes back when its kernels are through: three in the pipeline, three queued, the decoder's, spares)
+        gb_pool_fill(typical, 10); // (a batch's buffer comes back when its kernels are through: three in the pipeline, three queued, the decoder's, spares)
         buffers_allocated = true; // (the caller creates its context from here on: side by side with these allocations the two were measured to hold each other up)
         if (I.timing) fprintf(stderr, "[gpu reader] open: run buffers %.1f, walk buffers %.1f, batch pool %.1f ms\n", (t_b - t_a) * 1e3, (t_c - t_b) * 1e3, (now_s() - t_c) * 1e3);
     }
@@ -1160,86 +1127,20 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         if (n > 0xFFFFFFF0ull) return unsupported("batch too large");
         t_walk += now_s() - ta;
         const double td = now_s();
-        // columns
+        // columns: the batch's buffer, the decode kernels, then anchors or fixed columns and the status word (gpu_batch.h)
         const size_t N = (size_t)n;
-        // scratch columns of the copy kernel: [so qo co](8 B) [rec_off](4 B) per record
-        const size_t Np = (N + 63) & ~(size_t)63, Np_cap = std::max(Np, (std::min<size_t>(max_reads, 1u << 22) + 63 + GB_MAXR) & ~(size_t)63);
-        if (!I.d_cols.need(Np_cap * (3 * 8 + 4) + 256)) return fail_dev("out of device memory");
-        // the batch's own buffer on the device: [seq][qual][cigar] (512 spare bytes behind each: the kernels' vector loads), then the fixed
-        // columns [rid pos tlen nm as l_seq](4 B) [flag n_cigar](2 B) [mapq lane](1 B) and 8 bytes per read for the coverage anchors — a
-        // batch that is anchored on the card (bqc_anchor_*) is submitted from here without its columns ever visiting the host
-        const size_t o_seq = 512, o_qual = (o_seq + so + 512 + 255) & ~(size_t)255, o_cig = o_qual + ((qo + 512 + 255) & ~(size_t)255),
-                     o_fix = (o_cig + 4 * co + 512 + 255) & ~(size_t)255, o_cov = o_fix + Np * (6 * 4 + 2 * 2 + 2), total = o_cov + 8 * Np + 256;
-        if (o.dev_cap < total) {
-            if (o.dev_mem) dev_free_hook(o.dev_mem);
-            o.dev_mem = g_pool.take(total);
-            o.dev_cap = o.dev_mem ? g_pool.cap : 0;
-            if (!o.dev_mem) { // larger than the pool's buffers (or the pool is empty): its own allocation
-                const size_t cap = total + total / 8 + 4096;
-                if (hipMalloc(&o.dev_mem, cap) != hipSuccess) { o.dev_mem = nullptr; return fail_dev("out of device memory"); }
-                o.dev_cap = cap;
-            }
-            o.dev_free = dev_free_hook;
-        }
-        uint8_t* pay = (uint8_t*)o.dev_mem;
-        GbCols C;
-        {
-            uint8_t* q = I.d_cols.p;
-            C.so = (uint64_t*)q; q += Np * 8; C.qo = (uint64_t*)q; q += Np * 8; C.co = (uint64_t*)q; q += Np * 8; C.rec_off = (uint32_t*)q;
-            q = pay + o_fix;
-            C.rid = (int32_t*)q; q += Np * 4; C.pos = (int32_t*)q; q += Np * 4; C.tlen = (int32_t*)q; q += Np * 4; C.nm = (int32_t*)q; q += Np * 4;
-            C.as = (int32_t*)q; q += Np * 4; C.l_seq = (uint32_t*)q; q += Np * 4;
-            C.flag = (uint16_t*)q; q += Np * 2; C.n_cigar = (uint16_t*)q; q += Np * 2;
-            C.mapq = q; q += Np; C.lane = q;
-        }
+        GbBatch L;
+        if (const char* what = gb_batch_layout(o, I.d_cols, N, max_reads, GB_MAXR, so, qo, co, L)) return fail_dev(what);
+        const GbCols& C = L.C;
         GbLanes LN{I.d_lane_blob.p, I.d_lane_tab.p, I.d_lane_tab.p + I.n_lane_ids, I.d_lane_tab.p + 2 * (size_t)I.n_lane_ids, I.n_lane_ids, I.lane_count};
         hipError_t he = hipMemcpyAsync(I.d_base.p, I.h_base.p, (size_t)last_taken * sizeof(GbBase), hipMemcpyHostToDevice, I.s);
         if (he != hipSuccess) return fail_dev("copy failed");
         hipLaunchKernelGGL(k_gb_decode, dim3(last_taken), dim3(64), 0, I.s, base, I.d_seg.p, I.d_rec.p, I.d_base.p, C, LN, I.d_main.p, I.n_main, I.d_status);
-        hipLaunchKernelGGL(k_gb_copy, dim3((uint32_t)((N + 15) / 16)), dim3(256), 0, I.s, base, C, (uint32_t)N, pay + o_seq, pay + o_qual, pay + o_cig);
-        // The anchors of the coverage statistic on the card (k_anchor.hip), when the program has handed its context over and the stream
-        // allows it: the fixed columns then stay here, and a summary comes back instead of 26 bytes per read
-        bqc_batch dv;
-        memset(&dv, 0, sizeof dv);
-        dv.n_reads = (uint32_t)N; dv.flag = C.flag; dv.mapq = C.mapq; dv.lane = C.lane; dv.rid = C.rid; dv.pos = C.pos; dv.tlen = C.tlen; dv.nm = C.nm; dv.as = C.as;
-        dv.l_seq = C.l_seq; dv.n_cigar = C.n_cigar; dv.seq = pay + o_seq; dv.qual = pay + o_qual; dv.cigar = (const uint32_t*)(pay + o_cig);
+        hipLaunchKernelGGL(k_gb_copy, dim3((uint32_t)((N + 15) / 16)), dim3(256), 0, I.s, base, C, (uint32_t)N, L.seq, L.qual, L.cigar);
         ++n_batches_;
-        bqc_anchored* ah = nullptr;
-        bqc_ctx* const actx = anchor_ctx_.load();
-        if (actx && anchors_ok_) {
-            const int arc = bqc_anchor_enqueue(actx, &dv, pay + o_cov, I.s, &ah);
-            if (arc < 0) return fail_dev(bqc_anchor_error(actx));
-            if (arc > 0) { anchors_ok_ = false; ah = nullptr; } // (the host has kept the state so far, or the context is a resolved shard)
-        }
-        auto columns_to_host = [&]() -> hipError_t {
-            o.flag.resize(N); o.mapq.resize(N); o.lane.resize(N); o.rid.resize(N); o.pos.resize(N); o.tlen.resize(N);
-            o.nm.resize(N); o.as.resize(N); o.l_seq.resize(N); o.n_cigar.resize(N);
-            hipError_t e = hipMemcpyAsync(o.flag.data(), C.flag, N * 2, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.n_cigar.data(), C.n_cigar, N * 2, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.mapq.data(), C.mapq, N, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.lane.data(), C.lane, N, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.rid.data(), C.rid, N * 4, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.pos.data(), C.pos, N * 4, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.tlen.data(), C.tlen, N * 4, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.nm.data(), C.nm, N * 4, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.as.data(), C.as, N * 4, hipMemcpyDeviceToHost, I.s);
-            if (e == hipSuccess) e = hipMemcpyAsync(o.l_seq.data(), C.l_seq, N * 4, hipMemcpyDeviceToHost, I.s);
-            return e;
-        };
-        he = ah ? hipSuccess : columns_to_host();
-        if (he == hipSuccess) he = hipMemcpyAsync(I.h_status, I.d_status, 4, hipMemcpyDeviceToHost, I.s);
-        if (he != hipSuccess || !I.sync()) return fail_dev("decode failed");
-        if (ah) {
-            bqc_anchor_info info{};
-            // a batch the host decoder takes (below), or one with more breaks than the card's chain walks: the host keeps the window
-            // state from this batch on (it is current there: every anchored batch before this one is submitted before it)
-            const int arc = *I.h_status ? 1 : bqc_anchor_complete(actx, ah, &info);
-            if (*I.h_status) bqc_anchor_discard(actx, ah);
-            if (arc < 0) return fail_dev(bqc_anchor_error(actx));
-            if (arc > 0) {
-                anchors_ok_ = false; ah = nullptr;
-                if (!*I.h_status && (columns_to_host() != hipSuccess || !I.sync())) return fail_dev("decode failed");
-            } else { o.anchored = ah; o.dev = dv; o.n_noqual = info.n_noqual; o.rid_min = info.rid_min; o.rid_max = info.rid_max; ++n_anchored_; }
+        {
+            std::string aerr;
+            if (const char* what = gb_batch_finish(o, L, anchor_ctx_.load(), anchors_ok_, n_anchored_, I.s, I.ev, I.d_status, I.h_status, aerr)) return fail_dev(what);
         }
         if (*I.h_status) {
             // A record the card does not decode (a read group that is not in the header, a second NM tag, no RG tag, ...): THIS
@@ -1272,7 +1173,6 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
             if (I.timing) fprintf(stderr, "[gpu reader] batch of %zu records handed over to the host decoder (%.1f ms)\n", N, (now_s() - t0) * 1e3);
             return fine ? 1 : -1;
         }
-        o.d_seq = pay + o_seq; o.d_qual = pay + o_qual; o.d_cigar = (const uint32_t*)(pay + o_cig);
         I.cur += pos;
         if (over) end_of_range(I.abs_of(I.cur));
         nrec_ += n;

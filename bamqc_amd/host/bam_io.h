@@ -3,7 +3,9 @@
 // BamTagsDict (reference src/bamqualcheck.cpp:44-100, 252-267, 303-315; QualityCheck.hpp:201-209;
 // TripletCounting.hpp:110-130).  Formats: public SAM/BAM specification.
 #pragma once
+#include <cctype>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <utility>
@@ -133,6 +135,26 @@ private:
 // SAM text from a stream (the reference reads SAM from stdin when the input is "-": bamqualcheck.cpp:252-260,
 // CommandLineParser.hpp:92-107).  Fills the same batch as BamReader: same tag rules, POS - 1, QUAL '*' -> 0xFF bytes.
 // Format: public SAM specification.
+// The two alphabets of SAM text, stated once for the host parser and the reader on the card (csrc/gpu_sam.hip): a CIGAR operation's
+// letter -> its code, a base's letter (upper-cased; anything else is N = 15) -> its 4-bit code.
+static const char kSamOps[] = "MIDNSHP=X";
+static const char kSamNib[] = "=ACMGRSVTWYHKDBN";
+inline uint32_t sam_base_code(unsigned char ch) { const char* z = strchr(kSamNib, toupper(ch)); return z && ch ? (uint32_t)(z - kSamNib) : 15u; }
+
+// a line as split at '\n' (NUL bytes and all: DESIGN section 2), without one '\r' in front of the '\n' it ended with
+void sam_take_line(const char* p, size_t n, bool newline, std::string& line);
+// one '@' line of the header: appended to the text; @SQ -> reference names, lengths and the name index (a duplicate name: the later one wins)
+void sam_header_line(const std::string& line, BamHeader& hdr, std::map<std::string, int32_t>& ref_index);
+// The record rules of SAM text, one line at a time (SamReader::next_batch, and a batch the reader on the card hands over).
+struct SamLineParser {
+    BamHeader& hdr;
+    const std::map<std::string, int32_t>& ref_index;
+    const std::vector<uint8_t>& main_chrom;
+    uint64_t& nrec;
+    std::vector<std::string> fields;
+    int parse(const std::string& line, HostBatch& o, std::string& err, int& err_code);
+};
+
 class SamReader : public RecordReader {
 public:
     bool open(FILE* f, std::string& err); // reads the header (@ lines)

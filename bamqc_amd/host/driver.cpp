@@ -32,6 +32,7 @@
 #include "inflate_fast.h"
 #include "host_tools.h"
 #include "../csrc/gpu_bam.h"
+#include "../csrc/gpu_sam.h"
 #include <hip/hip_runtime_api.h>
 
 // ---------------------------------------------------------------------------------------------------
@@ -272,8 +273,9 @@ struct bqc_bam {
     bool is_sam = false;
     FILE* sam_file = nullptr;
     std::unique_ptr<GpuBamReader> gpu; // bqc_bam_open_gpu: records decoded on the card
+    std::unique_ptr<GpuSamReader> gsam; // bqc_bam_open_gpu of SAM text: the same
     uint64_t g_b0 = 0, g_b1 = UINT64_MAX; // bqc_bam_open_gpu_range: the shard's block boundaries
-    RecordReader& rd() { return gpu ? static_cast<RecordReader&>(*gpu) : is_sam ? static_cast<RecordReader&>(sam) : static_cast<RecordReader&>(bam); }
+    RecordReader& rd() { return gpu ? static_cast<RecordReader&>(*gpu) : gsam ? static_cast<RecordReader&>(*gsam) : is_sam ? static_cast<RecordReader&>(sam) : static_cast<RecordReader&>(bam); }
     const BamHeader& hdr() const { return const_cast<bqc_bam*>(this)->rd().header(); }
     ~bqc_bam() { if (sam_file && sam_file != stdin) fclose(sam_file); }
     HostBatch hb;
@@ -288,12 +290,16 @@ struct bqc_bam {
     }
 };
 
+static bool is_sam_path(const char* path) // SAM text: stdin or a file
+{
+    const size_t n = strlen(path);
+    return strcmp(path, "-") == 0 || (n > 4 && strcmp(path + n - 4, ".sam") == 0);
+}
 extern "C" int bqc_bam_open(const char* path, bqc_bam** out)
 {
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
-    const size_t n = strlen(path);
-    if (strcmp(path, "-") == 0 || (n > 4 && strcmp(path + n - 4, ".sam") == 0)) { // SAM text: stdin or a file
+    if (is_sam_path(path)) {
         b->is_sam = true;
         b->sam_file = strcmp(path, "-") == 0 ? stdin : fopen(path, "r");
         if (!b->sam_file) { b->err = std::string("could not open ") + path; *out = b; return BQC_ERR_IO; }
@@ -308,6 +314,16 @@ extern "C" int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out)
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
     *out = b;
+    if (is_sam_path(path)) { // SAM text: the reader takes the descriptor from its first byte
+        const int fd = strcmp(path, "-") == 0 ? 0 : open(path, O_RDONLY);
+        if (fd < 0) { b->err = std::string("could not open ") + path; return BQC_ERR_IO; }
+        b->gsam.reset(new GpuSamReader());
+        if (!b->gsam->start(fd, 0, b->err)) { b->gsam.reset(); return BQC_ERR_IO; }
+        if (!b->gsam->open(device, 1u << 20, 256u << 20, b->err)) { b->gsam.reset(); return BQC_ERR_DEVICE; }
+        b->gsam->allow_kernels();
+        b->refresh_lanes();
+        return 0;
+    }
     if (!b->bam.open(path, b->err, true)) return BQC_ERR_IO; // the header, on the host
     b->gpu.reset(new GpuBamReader());
     const uint64_t first_record = b->bam.stream_pos();
@@ -340,6 +356,7 @@ extern "C" int bqc_bam_open_gpu_range(const char* path, int device, uint64_t beg
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
     *out = b;
+    if (is_sam_path(path)) { b->err = "SAM text cannot be read in shards"; return BQC_ERR_ARG; }
     if (!shard_blocks(path, begin_hint, end_hint, b->g_b0, b->g_b1, b->err)) { if (b->err.empty()) b->err = "empty shard"; return BQC_ERR_ARG; }
     if (!b->bam.open(path, b->err, true)) return BQC_ERR_IO; // the header, on the host
     b->gpu.reset(new GpuBamReader());
@@ -355,7 +372,7 @@ extern "C" uint64_t bqc_bam_range_begin_block(const bqc_bam* b) { return b->gpu 
 extern "C" uint64_t bqc_bam_range_end_block(const bqc_bam* b) { return b->gpu ? b->g_b1 : b->bam.range_end_block(); }
 extern "C" uint64_t bqc_bam_range_first(const bqc_bam* b) { return b->gpu ? b->gpu->range_first() : b->bam.range_first(); }
 extern "C" uint64_t bqc_bam_range_over(const bqc_bam* b) { return b->gpu ? b->gpu->range_over() : b->bam.range_over(); }
-extern "C" uint64_t bqc_bam_batches_handed_over(const bqc_bam* b) { return b && b->gpu ? b->gpu->batches_handed_over() : 0; }
+extern "C" uint64_t bqc_bam_batches_handed_over(const bqc_bam* b) { return b && b->gpu ? b->gpu->batches_handed_over() : b && b->gsam ? b->gsam->batches_handed_over() : 0; }
 extern "C" uint64_t bqc_file_size(const char* path) { return path ? bgzf_file_size(path) : 0; }
 extern "C" void bqc_gpu_inflate_device(int device) { bgzf_gpu_inflate_device(device); }
 extern "C" uint64_t bqc_gpu_inflated_blocks(void) { return bgzf_gpu_inflated_blocks(); }
@@ -384,7 +401,7 @@ extern "C" int bqc_bam_set_main_chrom(bqc_bam* b, const uint8_t* mc)
 extern "C" int bqc_bam_set_rid_filter(bqc_bam* b, const uint8_t* keep, int keep_unplaced)
 {
     if (!b || !keep) return BQC_ERR_ARG;
-    if (b->is_sam) return BQC_ERR_ARG; // (chromosome sharding needs the BAM reader)
+    if (b->is_sam || b->gsam) return BQC_ERR_ARG; // (chromosome sharding needs the BAM reader)
     b->bam.set_rid_filter(std::vector<uint8_t>(keep, keep + b->hdr().ref_names.size()), keep_unplaced != 0);
     return 0;
 }
@@ -394,7 +411,7 @@ extern "C" int bqc_bam_next(bqc_bam* b, uint32_t max_reads, uint64_t max_bases, 
     int code = 0;
     const int rc = b->rd().next_batch(b->hb, max_reads, max_bases, b->err, code);
     if (rc < 0) return code < 0 ? code : -code; // (GpuBamReader::kUnsupported is negative already)
-    if (b->gpu && b->hb.d_seq) { // callers of this wrapper read the columns on the host: fetch the payload
+    if (b->hb.d_seq) { // callers of this wrapper read the columns on the host: fetch the payload
         HostBatch& h = b->hb;
         uint64_t so = 0, qo = 0, co = 0;
         for (size_t i = 0; i < h.n(); ++i) { so += (h.l_seq[i] + 1u) / 2u; qo += h.l_seq[i]; co += h.n_cigar[i]; }
@@ -508,6 +525,57 @@ extern "C" int bqc_bam_write(const char* path, const bqc_batch* b, uint32_t n_re
     std::string err;
     if (!w.open(path, text, names, lens, err, level)) return BQC_ERR_IO;
     return w.write_batch_parallel(*b, lane_ids, first_read_index) && w.close() ? 0 : BQC_ERR_IO;
+}
+
+// The same batch as SAM text: the header's lines, then a line per read (PNEXT 0, RNEXT "=" on a placed read, integer tags as type i).
+extern "C" int bqc_sam_write(const char* path, const bqc_batch* b, uint32_t n_refs, const char* const* ref_names, const uint32_t* ref_lens,
+                             uint32_t n_lanes, uint64_t first_read_index)
+{
+    if (!path || !b || (n_refs && (!ref_names || !ref_lens))) return BQC_ERR_ARG;
+    std::vector<std::string> names, lane_ids;
+    std::vector<uint32_t> lens;
+    for (uint32_t c = 0; c < n_refs; ++c) { names.push_back(ref_names[c]); lens.push_back(ref_lens[c]); }
+    const std::string text = synth_header_text(names, lens, n_lanes, lane_ids);
+    const size_t n = b->n_reads;
+    for (size_t i = 0; i < n; ++i) if (b->lane[i] >= lane_ids.size() || b->rid[i] >= (int32_t)n_refs) return BQC_ERR_ARG;
+    FILE* f = fopen(path, "wb");
+    if (!f) return BQC_ERR_IO;
+    setvbuf(f, nullptr, _IOFBF, 1 << 22);
+    bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    std::vector<uint64_t> so_at(n + 1), qo_at(n + 1), co_at(n + 1);
+    for (size_t i = 0; i < n; ++i) { so_at[i + 1] = so_at[i] + (b->l_seq[i] + 1) / 2; qo_at[i + 1] = qo_at[i] + b->l_seq[i]; co_at[i + 1] = co_at[i] + b->n_cigar[i]; }
+    const size_t slice = 1u << 18; // lines are made by all host threads, a slice at a time, and written in order
+    for (size_t lo = 0; ok && lo < n; lo += slice) {
+        const size_t cnt = std::min(slice, n - lo);
+        const unsigned nt = std::max(1u, bqc_host_threads());
+        std::vector<std::string> part(nt);
+        parallel_ranges(cnt, nt, 4096, [&](unsigned t, size_t a, size_t z) {
+            std::string& o = part[t];
+            char num[32];
+            for (size_t i = lo + a; i < lo + z; ++i) {
+                const uint32_t L = b->l_seq[i], nc = b->n_cigar[i];
+                o += 'r'; o += std::to_string(first_read_index + i); o += '\t';
+                o += std::to_string(b->flag[i] & 0x0FFFu); o += '\t';
+                if (b->rid[i] >= 0) o += names[b->rid[i]]; else o += '*';
+                o += '\t'; o += std::to_string((int64_t)b->pos[i] + 1); o += '\t'; o += std::to_string(b->mapq[i]); o += '\t';
+                if (!nc) o += '*';
+                for (uint32_t k = 0; k < nc; ++k) { const uint32_t w = b->cigar[co_at[i] + k]; snprintf(num, sizeof num, "%u%c", w >> 4, (w & 15u) < 9 ? kSamOps[w & 15u] : '?'); o += num; }
+                o += b->rid[i] >= 0 ? "\t=\t0\t" : "\t*\t0\t";
+                o += std::to_string(b->tlen[i]); o += '\t';
+                if (!L) o += '*';
+                for (uint32_t k = 0; k < L; ++k) { const uint8_t by = b->seq[so_at[i] + k / 2]; o += kSamNib[k & 1 ? by & 15 : by >> 4]; }
+                o += '\t';
+                if (!L || b->qual[qo_at[i]] == 0xFF) o += '*';
+                else for (uint32_t k = 0; k < L; ++k) o += (char)(b->qual[qo_at[i] + k] + 33);
+                o += "\tRG:Z:"; o += lane_ids[b->lane[i]];
+                if (b->nm[i] != BQC_NM_ABSENT) { o += "\tNM:i:"; o += std::to_string(b->nm[i]); }
+                if (b->as[i] != BQC_AS_ABSENT) { o += "\tAS:i:"; o += std::to_string(b->as[i]); }
+                o += '\n';
+            }
+        });
+        for (const std::string& o : part) ok = ok && fwrite(o.data(), 1, o.size(), f) == o.size();
+    }
+    return (fclose(f) == 0) && ok ? 0 : BQC_ERR_IO;
 }
 
 // The plan of bqc_synth_write, streamed: slices of the plan are generated (bqc_synth_slice), serialised into BAM records by
@@ -754,6 +822,9 @@ namespace {
 struct ShardArgs { uint32_t index, count; bqc_shard_hook hook; void* user; };
 }
 
+// SAM text on stdin: streams at least this long go to the card.  Measured (profiles/sam_reader_ab.json): whole-program
+// time, host reader against the card, at 1 / 4 / 16 / 64 MB of text — the card is not slower from 64 MB on (0.19 against 0.29 s).
+static const size_t kSamCardFrom = 64u << 20;
 static int run_program(int argc, const char** argv, const ShardArgs* shard, bool host_reader_only = false)
 {
     ProgramOptions opt;
@@ -784,8 +855,14 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     // "-": SAM text from stdin; everything else is opened as BAM (bamqualcheck.cpp:252-262: a .sam path fails to open there too)
     BamReader bam_rd;
     SamReader sam_rd;
+    GpuSamReader gsam_rd;
     std::string err;
     const bool from_stdin = opt.bamFile == "-";
+    // SAM text on stdin is decoded on the card (csrc/gpu_sam.hip) unless BQC_GPU_DECODE=0: the reader takes the descriptor from its
+    // first byte.  BQC_GPU_DECODE unset: a stream that ends within its first kSamCardFrom bytes (read here, while the runtime starts) is
+    // parsed on the host from memory, and no device reader is set up.
+    const char* const gd_stdin = getenv("BQC_GPU_DECODE");
+    const bool use_gsam = from_stdin && !(gd_stdin && atoi(gd_stdin) == 0);
     // a failure before the hook is reached must still reach it: the other processes wait for this one
     auto shard_abort = [&]() { if (shard) { bqc_shard_info si{}; si.status = 1; bqc_shard_result sr{}; (void)shard->hook(shard->user, &si, &sr); } return 1; };
     if (shard && from_stdin) { fprintf(stderr, "ERROR: a stream on stdin cannot be split between processes\n"); return shard_abort(); }
@@ -794,7 +871,8 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     // function of the hint), so that either reader can take the range
     uint64_t shard_b0 = 0, shard_b1 = UINT64_MAX;
     bool shard_gpu = false;
-    if (from_stdin) opened = sam_rd.open(stdin, err);
+    if (use_gsam) opened = gsam_rd.start(0, gd_stdin ? 0 : kSamCardFrom, err);
+    else if (from_stdin) opened = sam_rd.open(stdin, err);
     else if (shard) { // this process's part of the compressed file
         const uint64_t size = bqc_file_size(opt.bamFile.c_str());
         const uint64_t lo = size / shard->count * shard->index, hi = shard->index + 1 == shard->count ? UINT64_MAX : size / shard->count * (shard->index + 1);
@@ -845,7 +923,8 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         bqc_raw_vector_free_hook = pin_free_hook;
         bqc_raw_vector_pin_hook = pin_hook;
     }
-    RecordReader& rd = from_stdin ? static_cast<RecordReader&>(sam_rd) : use_gpu_reader ? static_cast<RecordReader&>(gpu_rd) : static_cast<RecordReader&>(bam_rd);
+    const bool gsam_card = use_gsam && gsam_rd.header().lane_count != 0 && (gd_stdin || !gsam_rd.stream_ended());
+    RecordReader& rd = use_gsam ? static_cast<RecordReader&>(gsam_rd) : from_stdin ? static_cast<RecordReader&>(sam_rd) : use_gpu_reader ? static_cast<RecordReader&>(gpu_rd) : static_cast<RecordReader&>(bam_rd);
     if (use_gpu_reader) gpu_rd.header() = bam_rd.header(); // (complete once opened, in the decode thread: the device is not up yet)
     if (!shard || shard->index == 0) {
         FILE* of = fopen(opt.outputFile.c_str(), "wb"); // opened (truncated) before the scan, :278-283
@@ -894,6 +973,16 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
                 return;
             }
             gpu_rd.set_main_chrom(main_chrom);
+        }
+        if (gsam_card) {
+            std::string e;
+            const bool ok = gsam_rd.open(opt.device, opt.batch_reads, 256ull << 20, e);
+            gpu_reader_opened = true;
+            if (!ok) {
+                std::lock_guard<std::mutex> lk(Q.m);
+                Q.err = e; Q.err_code = BQC_ERR_DEVICE; Q.done = true; Q.cv.notify_all();
+                return;
+            }
         }
         for (;;) {
             std::unique_ptr<HostBatch> hb;
@@ -989,6 +1078,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         const char* da = getenv("BQC_DEVICE_ANCHORS");
         if (!rc && ctx && !(da && da[0] == '0')) gpu_rd.set_anchor_context(ctx);
         gpu_rd.allow_kernels(); // (the context exists: the card may get busy)
+    });
+    if (gsam_card) allow_thr = std::thread([&gpu_reader_opened, &gsam_rd, ctx, rc] { // (the same for the reader of SAM text)
+        while (!gpu_reader_opened.load()) std::this_thread::sleep_for(std::chrono::microseconds(100));
+        const char* da = getenv("BQC_DEVICE_ANCHORS");
+        if (!rc && ctx && !(da && da[0] == '0')) gsam_rd.set_anchor_context(ctx);
+        gsam_rd.allow_kernels();
     });
     const auto t_create = clk::now();
     if (rc) { fprintf(stderr, "ERROR: %s\n", create_err.c_str()); stop_decoder(); return shard_abort(); }
@@ -1162,7 +1257,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (ref_loader.joinable()) ref_loader.join();
     if (!status && (rc = bqc_sync(ctx))) { fprintf(stderr, "%s\n", bqc_last_error(ctx)); status = 1; } // what the device found in the last batches
     dec.join();
-    if (timing) fprintf(stderr, "[timing] records decoded %s\n", use_gpu_reader ? "on the GPU (csrc/gpu_bam.hip)" : "on the host");
+    if (timing) fprintf(stderr, "[timing] records decoded %s\n", use_gpu_reader ? "on the GPU (csrc/gpu_bam.hip)" : gsam_card ? "on the GPU (csrc/gpu_sam.hip)" : "on the host");
     if (timing) { // (every buffer of the run exists at this point: what is in use now is the run's peak)
         size_t free_b = 0, total_b = 0, pinned = 0;
         { std::lock_guard<std::mutex> lk(g_pins.m); for (auto& kv : g_pins.blocks) pinned += kv.second; }
@@ -1175,6 +1270,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (timing && use_gpu_reader)
         fprintf(stderr, "[timing] reader on the card: pread %.2f s summed over its reader threads, the producer waited %.2f s for them, the decode thread waited %.2f s for inflated runs\n",
                 gpu_rd.seconds_reading(), gpu_rd.seconds_producer_waiting_for_chunks(), gpu_rd.seconds_waiting_for_runs());
+    if (timing && use_gsam) {
+        fprintf(stderr, "[sam reader] %llu batches on the card, %llu handed over, %llu anchored\n", (unsigned long long)gsam_rd.batches(), (unsigned long long)gsam_rd.batches_handed_over(),
+                (unsigned long long)gsam_rd.batches_anchored());
+        fprintf(stderr, "[sam reader] read() %.3f s in the reader thread; the decode thread waited %.3f s for input, copied text for %.3f s, ran kernels for %.3f s\n", gsam_rd.seconds_reading(),
+                gsam_rd.seconds_waiting_for_input(), gsam_rd.seconds_copying(), gsam_rd.seconds_in_kernels());
+    }
     if (timing && use_gpu_reader && gpu_rd.batches_handed_over()) fprintf(stderr, "[timing] %llu batches held records the card does not decode and went through the host decoder\n", (unsigned long long)gpu_rd.batches_handed_over());
     if (timing)
         fprintf(stderr, "[timing] %llu records: decode thread busy %.2f s, submit thread (host pass + enqueue; page-locking %.2f s) %.2f s, waiting for the decoder %.2f s, loop %.2f s\n",

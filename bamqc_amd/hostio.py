@@ -32,7 +32,8 @@ def batch_to_cols(b):
 class BamFile:
     def __init__(self, path, begin_hint=None, end_hint=None, gpu=None):
         """The whole file, or (begin_hint / end_hint: compressed byte offsets) one shard of its record stream.
-        gpu: a device index — the file is inflated and decoded on that GPU (batches are fetched back)."""
+        gpu: a device index — the file is inflated and decoded on that GPU (batches are fetched back); SAM text (a path ending
+        in .sam, or "-") is decoded there too."""
         self.lib = _lib.load()
         self.h = C.c_void_p()
         if gpu is not None and (begin_hint is not None or end_hint is not None):
@@ -159,6 +160,17 @@ def write_bam(path, cols, ref_names, ref_lens, n_lanes=1, first_read_index=0, le
     rc = lib.bqc_bam_write(path.encode(), C.byref(b), len(rl), names, rl.ctypes.data_as(_abi.u32p), n_lanes, first_read_index, level)
     if rc:
         raise IOError("bqc_bam_write failed: %d" % rc)
+
+
+def write_sam(path, cols, ref_names, ref_lens, n_lanes=1, first_read_index=0):
+    """A column dict as SAM text (the header and tags of write_bam)."""
+    lib = _lib.load()
+    b, keep = _abi.make_batch(cols)
+    rl = np.ascontiguousarray(ref_lens, np.uint32)
+    names = (C.c_char_p * len(ref_names))(*[s.encode() for s in ref_names])
+    rc = lib.bqc_sam_write(path.encode(), C.byref(b), len(rl), names, rl.ctypes.data_as(_abi.u32p), n_lanes, first_read_index)
+    if rc:
+        raise IOError("bqc_sam_write failed: %d" % rc)
 
 
 def write_fasta(path, names, codes):

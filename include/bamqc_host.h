@@ -50,6 +50,11 @@ int bqc_synth_stream(const bqc_synth_params* p, const char* const* ref_names, co
 int bqc_bam_write(const char* path, const bqc_batch* b, uint32_t n_refs, const char* const* ref_names, const uint32_t* ref_lens,
                   uint32_t n_lanes, uint64_t first_read_index, int level);
 
+/* The same batch as SAM text, with the same header lines: one line per read, QNAME r<first_read_index + i>, PNEXT 0, RNEXT "=" on a
+ * placed read, tags RG:Z, NM:i, AS:i; reads without qualities get QUAL "*". */
+int bqc_sam_write(const char* path, const bqc_batch* b, uint32_t n_refs, const char* const* ref_names, const uint32_t* ref_lens,
+                  uint32_t n_lanes, uint64_t first_read_index);
+
 /* ---- BAM / FASTA input (replaces SeqAn BamStream / SequenceStream) --------- */
 typedef struct bqc_bam bqc_bam;
 int bqc_bam_open(const char* path, bqc_bam** out);  /* on failure *out still holds the message */
@@ -62,10 +67,15 @@ int bqc_bam_open_range(const char* path, uint64_t begin_hint, uint64_t end_hint,
  * the caller).  A batch that holds a record the card does not decode (a read group missing from the header, a second NM tag, no
  * RG tag, ...) is decoded by the host reader's rules from the bytes on the card (bqc_bam_batches_handed_over counts them);
  * bqc_bam_next returns -1000 when the FILE needs the host reader (a record walk that cannot be verified, a corrupt record, a
- * file that ends inside a record): open it with bqc_bam_open then. */
+ * file that ends inside a record): open it with bqc_bam_open then.
+ * A path that ends in ".sam", and "-" (stdin), is SAM text and is decoded on the card as well (the reader takes the descriptor from
+ * its first byte).  A stream cannot be started over, so -1000 never comes back for it: a batch with a line the card has no rule for
+ * (bqc_bam_batches_handed_over counts them too) is parsed by the host's line parser, whose errors and messages are the ones reported;
+ * the records in front of a failing line are delivered before its error. */
 int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out);
 uint64_t bqc_bam_batches_handed_over(const bqc_bam* b);
-/* A shard (as bqc_bam_open_range) read, inflated and decoded on GPU `device`: only the shard's bytes of the file are touched. */
+/* A shard (as bqc_bam_open_range) read, inflated and decoded on GPU `device`: only the shard's bytes of the file are touched.
+ * SAM text has no shards: BQC_ERR_ARG. */
 int bqc_bam_open_gpu_range(const char* path, int device, uint64_t begin_hint, uint64_t end_hint, bqc_bam** out);
 uint64_t bqc_bam_range_begin_block(const bqc_bam* b);
 uint64_t bqc_bam_range_end_block(const bqc_bam* b);   /* UINT64_MAX: end of the file */
