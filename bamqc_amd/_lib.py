@@ -22,6 +22,7 @@ _SIGNATURES = {
     "bqc_last_error": (C.c_char_p, [C.c_void_p]),
     "bqc_set_reference": (C.c_int, [C.c_void_p, C.c_int32, _abi.u8p, C.c_uint64]),
     "bqc_reserve_references": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),
+    "bqc_move_references": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bqc_submit": (C.c_int, [C.c_void_p, C.POINTER(_abi.Batch)]),
     "bqc_submit_async": (C.c_int, [C.c_void_p, C.POINTER(_abi.Batch), C.POINTER(C.c_uint64)]),
     "bqc_batch_uploaded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int]),
@@ -94,6 +95,9 @@ _SIGNATURES = {
     "bqc_main_shard": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, _abi.SHARD_HOOK, C.c_void_p]),
     "bqc_main_multi": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_int]),
     "bqc_program_args": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_uint64]),
+    "bqc_session_open": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]),
+    "bqc_session_run": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
+    "bqc_session_close": (None, [C.c_void_p]),
     "bqc_calib_read4": (C.c_int, [C.c_uint64, C.c_int]),
     "bqc_inflate_raw": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]),
     "bqc_crc32": (C.c_uint32, [C.c_char_p, C.c_uint64]),

@@ -324,6 +324,28 @@ extern "C" int bqc_set_reference(bqc_ctx* c, int32_t rid, const uint8_t* dna5, u
     return upload_ref_tables(c);
 }
 
+// The contigs of `from` become those of `to` without another upload: the device allocations (and the bqc_reserve_references block they
+// may lie in) change owner.  Same device, same n_refs, `to` has none yet; `from` is only good for bqc_destroy afterwards.
+extern "C" int bqc_move_references(bqc_ctx* from, bqc_ctx* to)
+{
+    if (!from || !to || from == to) return BQC_ERR_ARG;
+    if (from->device != to->device || from->opt.n_refs != to->opt.n_refs) return fail(to, BQC_ERR_ARG, "bqc_move_references: another device or another number of contigs");
+    if (to->ref_arena) return fail(to, BQC_ERR_STATE, "bqc_move_references: the receiving context has references of its own");
+    for (size_t r = 0; r < to->d_ref.size(); ++r) if (to->d_ref[r] || to->d_refn[r]) return fail(to, BQC_ERR_STATE, "bqc_move_references: the receiving context has references of its own");
+    HIPCHK(to, hipSetDevice(to->device));
+    (void)bqc_drain(from); // (nothing of the giving context may still be reading them)
+    HIPCHK(to, hipStreamSynchronize(from->stream));
+    to->d_ref = from->d_ref; to->d_refn = from->d_refn; to->ref_len = from->ref_len;
+    to->ref_arena = from->ref_arena; to->ref_arena_cap = from->ref_arena_cap; to->ref_arena_used = from->ref_arena_used;
+    from->d_ref.assign(from->d_ref.size(), nullptr); from->d_refn.assign(from->d_refn.size(), nullptr); from->ref_len.assign(from->ref_len.size(), 0);
+    from->ref_arena = nullptr; from->ref_arena_cap = from->ref_arena_used = 0;
+    from->poisoned = true; from->poison_code = BQC_ERR_STATE; from->err = "its references were moved to another context";
+    const int rc = upload_ref_tables(to);
+    if (rc) return rc;
+    HIPCHK(to, hipStreamSynchronize(to->stream));
+    return 0;
+}
+
 // Wait for everything submitted and report the first error of the stream (as the reference would have met it): batches of the
 // submit pipeline through their own records, resident batches (bqc_process) through the context's merged record.
 static int sync_and_check(bqc_ctx* c)

@@ -52,6 +52,14 @@ public:
     // set by open() once its device buffers are allocated (also when it fails before that): a caller that creates its own device
     // context in another thread starts doing so from here on
     std::atomic<bool> buffers_allocated{false};
+    // One process, many files.  open() on a reader that has been open before keeps every buffer that is large enough (streams, events,
+    // status words, the page-locked chunk ring, run / walk / column buffers, the batches' payload pool) and grows the others; nothing
+    // shrinks; ranges, counters, lane tables and the anchor state start fresh.  end_file(): the file is over (or given up) — the
+    // reader's threads end, its streams are waited for, the file is closed; call it before the next open() needs the card quiet and
+    // before the two questions below.
+    void end_file();
+    void memory_held(size_t& device_bytes, size_t& pinned_bytes); // what the reader (and the batches' payload pool) holds now
+    const char* buffers_report(); // "new": first open(); "kept": opened again and nothing had to grow since; "grown"
 
 private:
     struct Impl;
@@ -63,5 +71,7 @@ private:
     bool anchors_ok_ = true; // (decode thread)
     double t_read_ = 0, t_wait_run_ = 0, t_wait_chunk_ = 0;
     bool ranged_ = false;
+    bool reopened_ = false;
+    size_t held_before_ = 0; // bytes held when open() took the buffers over
     uint64_t range_b0_ = 0, range_b1_ = UINT64_MAX, range_first_ = 0, range_over_ = 0;
 };

@@ -394,6 +394,13 @@ struct PayloadPool {
         forget(p);
         (void)hipFree(p);
     }
+    size_t held() // bytes of every buffer allocated and not released
+    {
+        std::lock_guard<std::mutex> lk(m);
+        size_t b = 0;
+        for (auto& kv : owned) b += kv.second;
+        return b;
+    }
     void forget(void* p)
     {
         for (size_t i = 0; i < owned.size(); ++i) if (owned[i].first == p) { owned[i] = owned.back(); owned.pop_back(); return; }
@@ -482,7 +489,8 @@ struct GpuBamReader::Impl {
     double avg_rec_bytes = 0, avg_rec_bases = 0;
     uint64_t grow_window = 0;
 
-    ~Impl()
+    // the file is over (or given up): no thread of the reader runs and nothing of it is queued on the card any more
+    void quiesce()
     {
         { std::lock_guard<std::mutex> lk(m); stop = true; }
         cv.notify_all();
@@ -491,20 +499,57 @@ struct GpuBamReader::Impl {
         if (producer.joinable()) producer.join();
         for (std::thread& t : readers) if (t.joinable()) t.join();
         (void)hipSetDevice(device);
-        if (cs) { (void)hipStreamSynchronize(cs); (void)hipStreamDestroy(cs); }
-        if (ps) { (void)hipStreamSynchronize(ps); (void)hipStreamDestroy(ps); }
+        if (cs) (void)hipStreamSynchronize(cs);
+        if (ps) (void)hipStreamSynchronize(ps);
         if (ring_alloc.joinable()) ring_alloc.join();
+        if (s) (void)hipStreamSynchronize(s);
+        if (fd >= 0) { close(fd); fd = -1; }
+    }
+    template <typename B> static void take(B& mine, B& theirs) { std::swap(mine.p, theirs.p); std::swap(mine.cap, theirs.cap); }
+    // The reader is opened again (one process, many files): every BUFFER of the reader before — streams, events, status words, the
+    // page-locked chunk ring, run buffers, walk and column buffers — becomes this one's; everything else of this object is per file
+    // and starts as the constructor left it.  `O` has been quiesced and is only good for its destructor afterwards.
+    void adopt(Impl& O)
+    {
+        std::swap(s, O.s); std::swap(ps, O.ps); std::swap(cs, O.cs); std::swap(ev, O.ev);
+        std::swap(d_status, O.d_status); std::swap(h_status, O.h_status);
+        for (int k = 0; k < kMaxSlots; ++k) { std::swap(slots[k].p, O.slots[k].p); std::swap(slots[k].registered, O.slots[k].registered); std::swap(slots[k].done, O.slots[k].done); }
+        for (int k = 0; k < kRuns; ++k) {
+            GbRun &A = runs[k], &B = O.runs[k];
+            take(A.d_comp, B.d_comp); take(A.d_blocks, B.d_blocks); take(A.d_crc, B.d_crc); take(A.d_out, B.d_out); take(A.d_tok, B.d_tok); take(A.d_ntok, B.d_ntok);
+            A.hb.swap(B.hb); A.hc.swap(B.hc);
+            std::swap(A.ready, B.ready); std::swap(A.copied, B.copied); std::swap(A.d_status, B.d_status);
+        }
+        take(d_seg, O.d_seg); take(h_seg, O.h_seg); take(d_rec, O.d_rec); take(d_base, O.d_base); take(h_base, O.h_base); take(d_cols, O.d_cols);
+        take(d_lane_blob, O.d_lane_blob); take(d_lane_tab, O.d_lane_tab); take(d_main, O.d_main);
+        first_raw.swap(O.first_raw); handover_raw.swap(O.handover_raw); handover_recs.swap(O.handover_recs);
+    }
+    // bytes of device memory / of page-locked host memory this reader holds (the batches' payload pool is counted by the caller)
+    void footprint(size_t& dev, size_t& pinned) const
+    {
+        dev = pinned = 0;
+        for (const GbRun& R : runs) dev += R.d_comp.cap + R.d_blocks.cap * sizeof(GiBlock) + R.d_crc.cap * 4 + R.d_out.cap + R.d_tok.cap * 4 + R.d_ntok.cap * 4;
+        dev += d_seg.cap * sizeof(GbSeg) + d_rec.cap * sizeof(GbRec) + d_base.cap * sizeof(GbBase) + d_cols.cap + d_lane_blob.cap + d_lane_tab.cap * 4 + d_main.cap;
+        pinned += h_seg.cap * sizeof(GbSeg) + h_base.cap * sizeof(GbBase);
+        for (const Slot& C : slots) if (C.p && C.registered) pinned += kHeadroom + chunk_bytes + 64;
+    }
+    bool s_ready = false; // (consumer) the producer's first memset has been waited for
+
+    ~Impl()
+    {
+        quiesce();
+        if (cs) (void)hipStreamDestroy(cs);
+        if (ps) (void)hipStreamDestroy(ps);
         for (Slot& C : slots) { if (C.done) (void)hipEventDestroy(C.done); if (C.p) { if (C.registered) (void)hipHostUnregister(C.p); free(C.p); } }
         for (GbRun& R : runs) {
             if (R.ready) (void)hipEventDestroy(R.ready);
             if (R.copied) (void)hipEventDestroy(R.copied);
             if (R.d_status) (void)hipFree(R.d_status);
         }
-        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+        if (s) (void)hipStreamDestroy(s);
         if (ev) (void)hipEventDestroy(ev);
         if (d_status) (void)hipFree(d_status);
         if (h_status) (void)hipHostFree(h_status);
-        if (fd >= 0) close(fd);
     }
     bool sync() { return hipEventRecord(ev, s) == hipSuccess && hipEventSynchronize(ev) == hipSuccess; }
     // read-group ids -> lane index, column-wise: off[n] len[n] index[n] (again when a batch handed over to the host decoder has met
@@ -572,15 +617,41 @@ void GpuBamReader::allow_kernels()
     p_->cv.notify_all();
 }
 GpuBamReader::~GpuBamReader() { delete p_; }
+void GpuBamReader::end_file() { if (p_) p_->quiesce(); }
+void GpuBamReader::memory_held(size_t& device_bytes, size_t& pinned_bytes)
+{
+    device_bytes = pinned_bytes = 0;
+    if (p_) p_->footprint(device_bytes, pinned_bytes);
+    device_bytes += g_pool.held();
+}
+const char* GpuBamReader::buffers_report()
+{
+    if (!reopened_) return "new";
+    size_t d = 0, h = 0;
+    memory_held(d, h);
+    return d + h > held_before_ ? "grown" : "kept";
+}
 
 bool GpuBamReader::open(const char* path, int device, const BamHeader& hdr, uint64_t first_record_u, size_t batch_reads, size_t batch_bases, std::string& err)
 {
     const double t_open0 = now_s();
     if (&hdr != &hdr_) hdr_ = hdr; // (a caller that has filled header() itself passes it: nothing is written while others read it)
-    delete p_;
+    Impl* const before = p_;
     p_ = new Impl();
     Impl& I = *p_;
     I.device = device;
+    // opened before: the buffers stay (nothing shrinks), the per-file state is this new object's and the counters below
+    reopened_ = false; held_before_ = 0;
+    if (before) {
+        before->quiesce();
+        if (before->device == device && before->dev_ready) { I.adopt(*before); reopened_ = true; size_t d = 0, h = 0; I.footprint(d, h); held_before_ = d + h + g_pool.held(); }
+        delete before;
+    }
+    nrec_ = n_handed_over_ = n_anchored_ = n_batches_ = 0;
+    anchors_ok_ = true;
+    t_read_ = t_wait_run_ = t_wait_chunk_ = 0;
+    range_first_ = range_over_ = 0;
+    buffers_allocated = false;
     I.timing = getenv("BQC_GB_TIMING") != nullptr;
     if (const char* e = getenv("BQC_GB_RUN_MB")) I.run_bytes = (size_t)std::max(1, atoi(e)) << 20;
     if (const char* e = getenv("BQC_GB_READERS")) { I.kReaders = std::min(8, std::max(1, atoi(e))); I.kSlots = 2 * I.kReaders; }
@@ -612,15 +683,16 @@ bool GpuBamReader::open(const char* path, int device, const BamHeader& hdr, uint
         for (int k_ = 0; k_ < I.kSlots; ++k_) {
             Impl::Slot& C = I.slots[k_];
             const size_t bytes = (Impl::kHeadroom + I.chunk_bytes + 64 + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
+            if (C.p) continue; // (the chunk of the file before)
             C.p = (uint8_t*)aligned_alloc((size_t)2 << 20, bytes);
             if (C.p) memset(C.p, 0, bytes); else ok = false;
         }
         ok = ok && hipSetDevice(device) == hipSuccess;
         for (int k_ = 0; ok && k_ < I.kSlots; ++k_) {
             Impl::Slot& C = I.slots[k_];
-            ok = hipHostRegister(C.p, Impl::kHeadroom + I.chunk_bytes + 64, hipHostRegisterDefault) == hipSuccess;
+            if (!C.registered) ok = hipHostRegister(C.p, Impl::kHeadroom + I.chunk_bytes + 64, hipHostRegisterDefault) == hipSuccess;
             C.registered = ok;
-            ok = ok && hipEventCreateWithFlags(&C.done, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
+            if (!C.done) ok = ok && hipEventCreateWithFlags(&C.done, hipEventBlockingSync | hipEventDisableTiming) == hipSuccess;
         }
         { std::lock_guard<std::mutex> lk(I.rm); I.ring_state = ok ? 1 : -1; }
         I.rcv.notify_all();
@@ -655,19 +727,19 @@ bool GpuBamReader::open(const char* path, int device, const BamHeader& hdr, uint
     }
 
     const double t_s0 = now_s();
-    if (he == hipSuccess) { I.ps = bqc_pool_stream(device, 1); if (!I.ps) he = hipErrorOutOfMemory; } // (made ahead by bqc_warmup when the program runs; the consumer's stream: at the first batch)
+    if (he == hipSuccess && !I.ps) { I.ps = bqc_pool_stream(device, 1); if (!I.ps) he = hipErrorOutOfMemory; } // (made ahead by bqc_warmup when the program runs; the consumer's stream: at the first batch)
     const double t_s1 = now_s();
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&I.ev, hipEventBlockingSync | hipEventDisableTiming);
-    if (he == hipSuccess) he = hipMalloc((void**)&I.d_status, 64);
-    if (he == hipSuccess) he = hipHostMalloc((void**)&I.h_status, 64, hipHostMallocDefault);
+    if (he == hipSuccess && !I.ev) he = hipEventCreateWithFlags(&I.ev, hipEventBlockingSync | hipEventDisableTiming);
+    if (he == hipSuccess && !I.d_status) he = hipMalloc((void**)&I.d_status, 64);
+    if (he == hipSuccess && !I.h_status) he = hipHostMalloc((void**)&I.h_status, 64, hipHostMallocDefault);
     if (he == hipSuccess) he = hipMemsetAsync(I.d_status, 0, 64, I.ps);
     // ONE stream for all runs: a process gets a handful of hardware queues, streams beyond them share one, and a 30 ms inflate
     // kernel in a shared queue holds up whatever else is in it
     for (GbRun& R : I.runs) {
         R.s = I.ps;
-        if (he == hipSuccess) he = hipEventCreateWithFlags(&R.ready, hipEventBlockingSync | hipEventDisableTiming);
-        if (he == hipSuccess) he = hipEventCreateWithFlags(&R.copied, hipEventBlockingSync | hipEventDisableTiming);
-        if (he == hipSuccess) he = hipMalloc((void**)&R.d_status, 64);
+        if (he == hipSuccess && !R.ready) he = hipEventCreateWithFlags(&R.ready, hipEventBlockingSync | hipEventDisableTiming);
+        if (he == hipSuccess && !R.copied) he = hipEventCreateWithFlags(&R.copied, hipEventBlockingSync | hipEventDisableTiming);
+        if (he == hipSuccess && !R.d_status) he = hipMalloc((void**)&R.d_status, 64);
     }
     const double t_s2 = now_s();
 
@@ -841,6 +913,7 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
         first_raw.resize(cap + 64);
         const size_t n_pieces = (cap + piece - 1) / piece;
         std::atomic<size_t> next_piece{0};
+        std::atomic<bool> file_ended{false}; // a piece came back short: the file ends in it
         std::vector<size_t> got_of(n_pieces, 0);
         const double t0 = now_s();
         auto read_pieces = [&]() {
@@ -859,7 +932,7 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
                     g += (size_t)r;
                 }
                 got_of[k] = g;
-                if (g < want) { next_piece = n_pieces; return; } // the file ends here
+                if (g < want) { file_ended = true; next_piece = n_pieces; return; } // the file ends here
             }
         };
         {
@@ -871,7 +944,9 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
         size_t got = 0;
         for (size_t k = 0; k < n_pieces; ++k) { got += got_of[k]; if (got_of[k] < std::min(piece, cap - k * piece)) break; }
         t_read += now_s() - t0;
-        if (got < cap) file_eof = true;
+        // (pieces behind the first 64 MB are not started once the device is up — at once, when the reader has been open before: what has
+        // been read is then a prefix of the file, not its end, and the rest comes through the ring)
+        if (file_ended.load()) file_eof = true;
         const size_t p = parse_blocks(R, first_raw.data(), got, 0, nb, utotal, stop_at, out_limit, stopped);
         if (p == SIZE_MAX) { R.rc = -1; return; }
         if (file_eof && !stopped && p != got && utotal + 65536 <= out_limit) { R.err = "truncated BGZF file"; R.rc = -1; return; }
@@ -1001,8 +1076,9 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
     err_code = 0;
     Impl& I = *p_;
     if (hipSetDevice(I.device) != hipSuccess) { err = "GPU reader: device lost"; err_code = BQC_ERR_DEVICE; return -1; }
-    if (!I.s) { // the consumer's stream (the third one the program needs: bqc_pool_stream)
-        I.s = bqc_pool_stream(I.device, 2);
+    if (!I.s_ready) { // the consumer's stream (the third one the program needs: bqc_pool_stream; a reader opened again has it)
+        if (!I.s) I.s = bqc_pool_stream(I.device, 2);
+        I.s_ready = true;
         if (!I.s || hipStreamSynchronize(I.ps) != hipSuccess) { err = "GPU reader: no stream"; err_code = BQC_ERR_DEVICE; return -1; } // (the status word's memset is on the producer's)
     }
     auto fail_dev = [&](const char* what) { err = std::string("GPU reader: ") + what; err_code = BQC_ERR_DEVICE; return -1; };

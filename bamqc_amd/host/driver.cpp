@@ -18,6 +18,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <chrono>
 #include <thread>
@@ -660,6 +661,9 @@ struct ProgramOptions {
     int device = 0;
     uint32_t batch_reads = [] { const char* e = getenv("BQC_BATCH_READS"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 1u << 20; }(); // (the variable: experiments; --batch-reads)
     bool no_sketch = false;
+    // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
+    std::string manifest;
+    std::vector<std::pair<std::string, std::string>> jobs;
 };
 
 const char* kVersion = "dev"; // src/version.h:12
@@ -678,16 +682,68 @@ void usage(FILE* f)
             "    -q, --quality-cutoff STRING\n          Comma-separated list of PHRED quality thresholds. Default: 17.\n"
             "    -e, --error-rate DOUBLE\n          Error rate guaranteed. Default: 0.01.\n"
             "    -s, --seed INT\n          Seed value for the randomness. Default: 1.\n\n"
-            "  MI355X options (not in the reference):\n    --device INT, --max-read-len INT, --hist-cap INT, --batch-reads INT, --no-sketch\n\n"
+            "  MI355X options (not in the reference):\n    --device INT, --max-read-len INT, --hist-cap INT, --batch-reads INT, --no-sketch\n"
+            "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
+            "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
+            "          job's input; in a single run the filename is taken as it is.\n\n"
             "VERSION\n    bamqualcheck version: %s\n    Last update August 2019\n",
             kVersion);
 }
 
+// the positional rule (valid values: "- bam sam" by file extension, CommandLineParser.hpp:59-60), for a path that is not "-"
+bool input_extension_ok(const std::string& path, std::string& err)
+{
+    size_t dot = path.rfind('.');
+    std::string ext = dot == std::string::npos ? "" : path.substr(dot + 1);
+    if (ext != "bam" && ext != "sam") { err = "bamqualcheck: the given path '" + path + "' does not have one of the valid file extensions [*.-, *.bam, *.sam]"; return false; }
+    return true;
+}
+
+// --manifest LIST: one job per line, INPUT<TAB>OUTPUT; empty lines and lines that start with '#' are skipped, a '\r' in front of the
+// '\n' is dropped.  Everything that is wrong with the list is found here, before any job runs or any output file is touched.
+bool read_manifest(const std::string& path, std::vector<std::pair<std::string, std::string>>& jobs, std::string& err)
+{
+    std::string text;
+    {
+        FILE* f = fopen(path.c_str(), "rb");
+        if (!f) { err = "bamqualcheck: the manifest '" + path + "' cannot be read"; return false; }
+        char buf[1 << 16];
+        size_t n;
+        while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+        const bool bad = ferror(f) != 0;
+        fclose(f);
+        if (bad) { err = "bamqualcheck: the manifest '" + path + "' cannot be read"; return false; }
+    }
+    std::set<std::string> outputs;
+    size_t line_no = 0;
+    for (size_t p = 0; p < text.size();) {
+        size_t e = text.find('\n', p);
+        if (e == std::string::npos) e = text.size();
+        std::string line = text.substr(p, e - p);
+        p = e + 1;
+        ++line_no;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::string where = "bamqualcheck: manifest '" + path + "' line " + std::to_string(line_no) + ": ";
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos || line.find('\t', tab + 1) != std::string::npos || tab == 0 || tab + 1 == line.size()) { err = where + "expected INPUT<TAB>OUTPUT"; return false; }
+        const std::string in = line.substr(0, tab), out = line.substr(tab + 1);
+        if (in == "-") { err = where + "a stream on stdin is not a job"; return false; }
+        std::string xerr;
+        if (!input_extension_ok(in, xerr)) { err = where + xerr.substr(strlen("bamqualcheck: ")); return false; }
+        if (!outputs.insert(out).second) { err = where + "the output '" + out + "' is named twice"; return false; }
+        jobs.emplace_back(in, out);
+    }
+    if (jobs.empty()) { err = "bamqualcheck: the manifest '" + path + "' names no job"; return false; }
+    return true;
+}
+
 // returns 0 = ok, 1 = parse error, 2 = help/version printed (exit 0)
-int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err)
+// session_form: the options of a session (bqc_session_open) — the program's without an input, -o and --manifest
+int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err, bool session_form = false)
 {
     std::string kstr = "32", qstr = "17";
-    bool have_r = false, have_o = false;
+    bool have_r = false, have_o = false, have_m = false;
     std::vector<std::string> pos;
     auto need = [&](int& i, const std::string& name, std::string& val, const char* inl) -> bool {
         if (inl) { val = inl; return true; }
@@ -735,17 +791,22 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err)
         else if (key == "--hist-cap") { if (!need(i, key, v, inl)) return 1; o.hist_cap = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
         else if (key == "--batch-reads") { if (!need(i, key, v, inl)) return 1; o.batch_reads = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
         else if (key == "--no-sketch") { o.no_sketch = true; }
+        else if (key == "--manifest") { if (!need(i, key, v, inl)) return 1; o.manifest = v; have_m = true; }
         else if (a[0] == '-') { err = "bamqualcheck: illegal option -- " + a.substr(a.rfind("--", 0) == 0 ? 2 : 1); return 1; }
         else pos.push_back(a);
     }
     if (!have_r) { err = "bamqualcheck: option requires an argument -- r (required option -r/--reference missing)"; return 1; }
-    if (!have_o) { err = "bamqualcheck: option requires an argument -- o (required option -o/--output-file missing)"; return 1; }
-    if (pos.size() != 1) { err = pos.empty() ? "bamqualcheck: Not enough arguments were provided." : "bamqualcheck: Too many arguments were provided!"; return 1; }
-    o.bamFile = pos[0];
-    if (o.bamFile != "-") { // valid values: "- bam sam" (file extension), CommandLineParser.hpp:59-60
-        size_t dot = o.bamFile.rfind('.');
-        std::string ext = dot == std::string::npos ? "" : o.bamFile.substr(dot + 1);
-        if (ext != "bam" && ext != "sam") { err = "bamqualcheck: the given path '" + o.bamFile + "' does not have one of the valid file extensions [*.-, *.bam, *.sam]"; return 1; }
+    if (session_form) {
+        if (have_o || have_m || !pos.empty()) { err = "bamqualcheck: a session takes the program's options without an input, -o and --manifest"; return 1; }
+    } else if (have_m) {
+        if (have_o) { err = "bamqualcheck: --manifest names every job's output: -o cannot be given with it"; return 1; }
+        if (!pos.empty()) { err = "bamqualcheck: --manifest names every job's input: no BAMFILE can be given with it"; return 1; }
+        if (!read_manifest(o.manifest, o.jobs, err)) return 1;
+    } else {
+        if (!have_o) { err = "bamqualcheck: option requires an argument -- o (required option -o/--output-file missing)"; return 1; }
+        if (pos.size() != 1) { err = pos.empty() ? "bamqualcheck: Not enough arguments were provided." : "bamqualcheck: Too many arguments were provided!"; return 1; }
+        o.bamFile = pos[0];
+        if (o.bamFile != "-" && !input_extension_ok(o.bamFile, err)) return 1;
     }
     // comma separated lists, parsed like the reference's stringstream loops (:121-143)
     auto split_nums = [](const std::string& s, auto& out) {
@@ -820,12 +881,71 @@ struct BatchQueue { // decode thread -> submit thread
 
 namespace {
 struct ShardArgs { uint32_t index, count; bqc_shard_hook hook; void* user; };
+
+// What identifies the reference genome a job needs: the FASTA file (path and what stat says of it) and the BAM header's @SQ lines.
+struct RefKey {
+    bool valid = false; // (false: the file could not be examined — never equal to anything)
+    std::string path;
+    uint64_t dev = 0, ino = 0, size = 0;
+    int64_t mtime_s = 0, mtime_ns = 0;
+    std::vector<std::string> sq_names;
+    std::vector<uint32_t> sq_lens;
+    bool operator==(const RefKey& o) const
+    {
+        return valid && o.valid && path == o.path && dev == o.dev && ino == o.ino && size == o.size && mtime_s == o.mtime_s && mtime_ns == o.mtime_ns && sq_names == o.sq_names && sq_lens == o.sq_lens;
+    }
+};
+RefKey make_ref_key(const std::string& fasta, const BamHeader& H)
+{
+    RefKey k;
+    struct stat st;
+    if (stat(fasta.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) return k;
+    k.valid = true; k.path = fasta;
+    k.dev = (uint64_t)st.st_dev; k.ino = (uint64_t)st.st_ino; k.size = (uint64_t)st.st_size; k.mtime_s = (int64_t)st.st_mtim.tv_sec; k.mtime_ns = (int64_t)st.st_mtim.tv_nsec;
+    k.sq_names = H.ref_names; k.sq_lens = H.ref_lens;
+    return k;
 }
+// The options that size a context (bqc_options): equal ones mean bqc_reset instead of bqc_create.
+struct CtxKey {
+    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0;
+    int isize = 0, seed = 0, device = 0;
+    bool sketch = false;
+    double e = 0;
+    std::vector<int32_t> klist;
+    std::vector<uint32_t> qlist;
+    std::vector<uint8_t> main_chrom;
+    bool operator==(const CtxKey& o) const
+    {
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && isize == o.isize && seed == o.seed && device == o.device &&
+               sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
+    }
+};
+}
+
+// One process, many files: what outlives a job.  run_program borrows from it and gives back; without one it
+// creates and destroys as ever.  The runtime itself (bqc_warmup's streams, the pin hooks' registry g_pins) is the process's already.
+struct bqc_session {
+    std::vector<std::string> args; // argv[0] and the options every job runs with
+    bqc_ctx* ctx = nullptr;        // the context of the job before (whatever way that job ended: bqc_reset clears a poisoned one)
+    CtxKey ctx_key;
+    RefKey ref_key;                // the genome whose contigs are on the card, in ctx
+    std::vector<int32_t> fasta_index; // for ref_key: each BAM reference's position in the FASTA file (the cursor rule), -1: not there
+    uint32_t contigs_on_card = 0;
+    GpuBamReader gpu_rd;           // opened again for every file it takes: its buffers stay
+    std::vector<std::unique_ptr<HostBatch>> spare; // the decoder's batch objects: their columns, page locks and device buffers
+    std::atomic<bool> ended{false}; // a HIP error: nothing more is started on the card
+    uint32_t job = 0, n_jobs = 0;  // the job that runs (1-based), and how many there will be if known
+    // a job that starts over with the host reader (GpuBamReader::kUnsupported) reports what its FIRST pass found in place
+    bool started_over = false, first_ctx_kept = false;
+    uint32_t first_contigs = 0;
+    ~bqc_session() { spare.clear(); if (ctx) bqc_destroy(ctx); }
+};
+typedef bqc_session Session;
 
 // SAM text on stdin: streams at least this long go to the card.  Measured (profiles/sam_reader_ab.json): whole-program
 // time, host reader against the card, at 1 / 4 / 16 / 64 MB of text — the card is not slower from 64 MB on (0.19 against 0.29 s).
 static const size_t kSamCardFrom = 64u << 20;
-static int run_program(int argc, const char** argv, const ShardArgs* shard, bool host_reader_only = false)
+static int run_program(int argc, const char** argv, const ShardArgs* shard, bool host_reader_only = false, Session* S = nullptr)
 {
     ProgramOptions opt;
     std::string perr;
@@ -840,6 +960,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         fprintf(stderr, "[timing] %s: %.3f s after launch\n", what, now - atof(getenv("BQC_T0")));
     };
     since_launch("main entered");
+    if (S) { // one option for every job, a genome per directory: "{dir}" in the reference's path stands for the directory of the job's input
+        const size_t slash = opt.bamFile.rfind('/');
+        const std::string dir = slash == std::string::npos ? "." : slash == 0 ? "/" : opt.bamFile.substr(0, slash);
+        for (size_t at; (at = opt.referenceFile.find("{dir}")) != std::string::npos;) opt.referenceFile.replace(at, 5, dir);
+    }
+    auto note_rc = [S](int r) { if (S && r == BQC_ERR_DEVICE) S->ended = true; }; // a HIP error ends a session (the job fails as a single run does)
     setenv("GPU_MAX_HW_QUEUES", "8", 0); // (before the runtime starts: the batch pipeline, the reader and its producer each keep a hardware queue of their own)
     // the HIP runtime starts (~0.1 s) while the inputs are opened; from then on the reader's runs are inflated on the card
     const char* gi_env = getenv("BQC_GPU_INFLATE");
@@ -900,7 +1026,9 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     // records come from the card.  Whatever that reader does not decode itself (a read group that is not in the header, a record
     // the host reader would report, ...) ends this pass before anything has been reported, and the program starts over with the
     // host reader (host_reader_only).  BQC_GPU_DECODE=0: the host reader from the start.
-    GpuBamReader gpu_rd;
+    GpuBamReader own_gpu_rd;
+    GpuBamReader& gpu_rd = S ? S->gpu_rd : own_gpu_rd;
+    if (S) gpu_rd.set_anchor_context(nullptr); // (the context of the job before may not outlive this one's set-up)
     const char* gd_env = getenv("BQC_GPU_DECODE"); // 1: whenever possible, 0: never; unset: files of 256 MB and more (its set-up costs ~50 ms)
     bool use_gpu_reader = !from_stdin && (!shard || shard_gpu) && !host_reader_only && bam_rd.header().lane_count != 0 && !(gd_env && atoi(gd_env) == 0);
     if (shard && shard_gpu && !use_gpu_reader) { // (no @RG line: the host reader, over its range, decides what that means)
@@ -954,6 +1082,26 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     // decode thread feeds batches; this thread submits them.  It starts right away: the first batches are inflated and
     // decoded while the FASTA file is read and the device is set up.
     BatchQueue Q;
+    // a session's batch objects: taken here, given back on every way out (their device buffers return to the readers' pool, where the
+    // next file's reader counts them)
+    struct SpareLoan {
+        BatchQueue& Q; Session* S; bool given = false;
+        void give()
+        {
+            if (!S || given) return;
+            given = true;
+            std::lock_guard<std::mutex> lk(Q.m);
+            for (auto& hb : Q.spare) {
+                if (hb->dev_mem && hb->dev_free) { hb->dev_free(hb->dev_mem); hb->dev_mem = nullptr; hb->dev_cap = 0; }
+                if (S->spare.size() < 8) S->spare.push_back(std::move(hb));
+            }
+            Q.spare.clear();
+        }
+        ~SpareLoan() { give(); }
+    } spare_loan{Q, S};
+    size_t n_spare_kept = 0;
+    if (S) { n_spare_kept = S->spare.size(); Q.spare = std::move(S->spare); S->spare.clear(); }
+    struct ReaderEnd { GpuBamReader& r; bool on; ~ReaderEnd() { if (on) r.end_file(); } } reader_end{gpu_rd, S && use_gpu_reader}; // (the file is over on every way out)
     std::atomic<bool> gpu_reader_opened{false};
     std::thread dec;
     auto stop_decoder = [&]() {
@@ -1033,7 +1181,36 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     int rc = 0;
     std::string create_err;
     double t_create_s = 0, t_c_warm = 0, t_c_reader = 0, t_c_create = 0;
+    // A session: the contigs on the card stay when this job names the same genome (same FASTA file, same @SQ lines); the context stays
+    // — bqc_reset — when the options that size it are the same as well; another context over the same genome takes the contigs over
+    // (bqc_move_references).  Another genome: the old context goes first, with its contigs, and everything is as in a single run.
+    RefKey ref_key;
+    CtxKey ctx_key;
+    bool refs_kept = false, ctx_kept = false;
+    if (S) {
+        ref_key = make_ref_key(opt.referenceFile, H);
+        ctx_key.n_lanes = bo.n_lanes; ctx_key.n_refs = bo.n_refs; ctx_key.max_read_len = bo.max_read_len; ctx_key.hist_cap = bo.hist_cap; ctx_key.isize = bo.isize;
+        ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch;
+        if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
+        ctx_key.main_chrom = main_chrom;
+        refs_kept = S->ctx && ref_key == S->ref_key;
+        ctx_kept = refs_kept && ctx_key == S->ctx_key;
+    }
+    const uint32_t contigs_before = refs_kept ? S->contigs_on_card : 0;
     std::thread creator([&] {
+        if (ctx_kept) {
+            const auto c0 = clk::now();
+            ctx = S->ctx; S->ctx = nullptr;
+            rc = bqc_reset(ctx);
+            if (rc) create_err = bqc_last_error(ctx);
+            t_create_s = t_c_create = secs(c0, clk::now());
+            return;
+        }
+        bqc_ctx* old = nullptr;
+        if (S) {
+            old = S->ctx; S->ctx = nullptr;
+            if (old && !refs_kept) { bqc_destroy(old); old = nullptr; S->ref_key = RefKey(); S->contigs_on_card = 0; }
+        }
         const auto c0 = clk::now();
         // Who sets up when (round 4): the warm-up thread starts the runtime (~60 ms) and then makes the program's four streams one after the
         // other (20 + 3 x 8-10 ms: hardware queues, serial whoever asks); the reader allocates its buffers as soon as the runtime is up
@@ -1045,11 +1222,16 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         const auto c2 = clk::now();
         rc = bqc_create(&bo, &ctx);
         if (rc) create_err = bqc_last_error(nullptr);
+        else if (old) { // the same genome under another context: its contigs change owner, nothing is uploaded
+            rc = bqc_move_references(old, ctx);
+            if (rc) create_err = bqc_last_error(ctx);
+        }
         else if (!shard) { // one allocation for the contigs, sized from the BAM header, while nothing runs on the card yet (an allocation beside running kernels waits for them)
             uint64_t total = 0;
             for (uint32_t r = 0; r < n_refs; ++r) total += H.ref_lens[r];
             (void)bqc_reserve_references(ctx, total, n_refs);
         }
+        if (old) { bqc_destroy(old); if (rc) { S->ref_key = RefKey(); S->contigs_on_card = 0; } }
         t_create_s = secs(c0, clk::now());
         t_c_warm = secs(c0, c1); t_c_reader = secs(c1, c2); t_c_create = secs(c2, clk::now());
     });
@@ -1062,9 +1244,11 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     MappedFasta lazy_fa;
     const bool lazy_refs = shard && !(getenv("BQC_EAGER_REFS") && getenv("BQC_EAGER_REFS")[0] == '1') && lazy_fa.open(opt.referenceFile.c_str()) == 1;
     if (lazy_refs) { for (const auto& r : lazy_fa.recs) fa.push_back(FastaRecord{r.name, {}}); }
+    else if (refs_kept) {} // (a session: the contigs are on the card, the file is neither parsed nor uploaded again)
     else if (!load_fasta(opt.referenceFile.c_str(), &H.ref_names, fa, ferr)) fprintf(stderr, "%s\n", ferr.c_str()); // return value ignored (:291)
     std::vector<int32_t> fasta_index(std::max(1u, n_refs), -1);
-    for (uint32_t r = 0; r < n_refs; ++r)
+    if (refs_kept) fasta_index = S->fasta_index;
+    else for (uint32_t r = 0; r < n_refs; ++r)
         for (size_t i = 0; i < fa.size(); ++i) if (fa[i].name == H.ref_names[r]) { fasta_index[r] = (int32_t)i; break; }
     const auto t_fasta = clk::now();
     creator.join();
@@ -1086,8 +1270,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         gsam_rd.allow_kernels();
     });
     const auto t_create = clk::now();
-    if (rc) { fprintf(stderr, "ERROR: %s\n", create_err.c_str()); stop_decoder(); return shard_abort(); }
-    if ((rc = bqc_set_fasta_index(ctx, fasta_index.data()))) { fprintf(stderr, "ERROR: %s\n", bqc_last_error(ctx)); stop_decoder(); bqc_destroy(ctx); return shard_abort(); }
+    // where a context goes on every way out: back to the session (the next job resets it, or takes its contigs, or destroys it)
+    auto give_ctx = [&]() { if (!ctx) return; if (S) { S->ctx = ctx; S->ctx_key = ctx_key; } else bqc_destroy(ctx); ctx = nullptr; };
+    if (rc) { note_rc(rc); fprintf(stderr, "ERROR: %s\n", create_err.c_str()); stop_decoder(); give_ctx(); return shard_abort(); }
+    if (!ctx_kept && (rc = bqc_set_fasta_index(ctx, fasta_index.data()))) { note_rc(rc); fprintf(stderr, "ERROR: %s\n", bqc_last_error(ctx)); stop_decoder(); give_ctx(); return shard_abort(); }
     // The references go to the card BEHIND the start of the record loop: a thread of its own uploads the contigs in the BAM header's order
     // (a human genome is 3.1 GB: 0.35-0.45 s that the loop used to wait for) and the submitting thread only waits when a batch holds a
     // read on a contig that is not there yet — the first one, as a rule.  (bqc_set_reference may be called beside bqc_submit* for contigs
@@ -1106,15 +1292,17 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     // alike — page-locking and large copies beside running inflate kernels hold up the other threads' calls into the runtime — so by
     // default the uploader is waited for before the loop starts; what is kept of it: one allocation for all contigs, made with the context.
     const bool refs_beside_loop = bg_refs && getenv("BQC_BG_REFS") && getenv("BQC_BG_REFS")[0] == '1';
+    std::atomic<bool> ref_skipped{false}; // the uploader was stopped before a contig of the FASTA file: the genome on the card is not whole
     auto upload_all = [&] {
         for (uint32_t r = 0; r < n_refs; ++r) {
             uint8_t st = 1;
+            if (fasta_index[r] >= 0 && ref_stop.load()) ref_skipped = true;
             if (fasta_index[r] >= 0 && !ref_stop.load()) {
                 auto& c = fa[fasta_index[r]].codes;
                 // (from pageable memory: page-locking the 3.1 GB first — hipHostRegister — and copying at the link's speed measured SLOWER
                 // for the whole genome, 0.63-0.82 s against 0.35-0.46 s)
                 const int src = bqc_set_reference(ctx, (int32_t)r, c.data(), c.size());
-                if (src) { std::lock_guard<std::mutex> lk(ref_m); if (ref_err.empty()) ref_err = bqc_last_error(ctx); st = 2; }
+                if (src) { note_rc(src); std::lock_guard<std::mutex> lk(ref_m); if (ref_err.empty()) ref_err = bqc_last_error(ctx); st = 2; }
                 // (the host copy is NOT given back here: returning a human genome's 3.1 GB to the kernel costs 0.35-0.4 s — measured:
                 // "references" 0.57 s with the contigs freed one by one, 0.20 s without — and the program's exit does it for nothing)
             }
@@ -1122,12 +1310,22 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
             ref_cv.notify_all();
         }
     };
-    if (bg_refs && refs_beside_loop) ref_loader = std::thread(upload_all);
+    if (refs_kept) { for (uint32_t r = 0; r < n_refs; ++r) ref_state[r] = 1; } // (a session: they are there)
+    else if (bg_refs && refs_beside_loop) ref_loader = std::thread(upload_all);
     else if (bg_refs) upload_all(); // (in this thread, before the loop: the default)
+    auto note_refs = [&]() { // a session remembers which genome its context holds, once every contig of it has arrived
+        if (!S || refs_kept || !bg_refs) return;
+        std::lock_guard<std::mutex> lk(ref_m);
+        if (!ref_err.empty() || !ref_key.valid || ref_skipped.load()) return; // (BQC_BG_REFS=1: contigs no read asked for may have been left out)
+        for (uint32_t r = 0; r < n_refs; ++r) if (ref_state[r].load() != 1) return;
+        S->ref_key = ref_key; S->fasta_index = fasta_index; S->contigs_on_card = 0;
+        for (uint32_t r = 0; r < n_refs; ++r) S->contigs_on_card += fasta_index[r] >= 0;
+    };
     auto destroy_ctx = [&]() { // (every way out: the uploader first, it uses the context)
         ref_stop = true;
         if (ref_loader.joinable()) ref_loader.join();
-        bqc_destroy(ctx);
+        note_refs();
+        give_ctx();
     };
     std::vector<raw_vector<uint8_t>> uploaded_codes; // (lazy_refs) host copies of contigs that are on the card: kept, see above
     double t_lazy_refs = 0;
@@ -1242,11 +1440,11 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
             uint64_t ticket = 0;
             if (hb->anchored) { rc = bqc_submit_anchored(ctx, &v, (bqc_anchored*)hb->anchored, &ticket); hb->anchored = nullptr; }
             else rc = bqc_submit_async(ctx, &v, &ticket);
-            if (rc) { fprintf(stderr, "%s\n", bqc_last_error(ctx)); status = 1; }
+            if (rc) { note_rc(rc); fprintf(stderr, "%s\n", bqc_last_error(ctx)); status = 1; }
             inflight.push_back(InFlight{ticket, std::move(hb)});
             recycle(false);
         } else {
-            if ((rc = bqc_submit(ctx, &v))) { fprintf(stderr, "%s\n", bqc_last_error(ctx)); status = 1; }
+            if ((rc = bqc_submit(ctx, &v))) { note_rc(rc); fprintf(stderr, "%s\n", bqc_last_error(ctx)); status = 1; }
             std::lock_guard<std::mutex> lk(Q.m); // (bqc_submit has staged the batch)
             if (Q.spare.size() < 4) Q.spare.push_back(std::move(hb));
         }
@@ -1255,8 +1453,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     recycle(true);
     ref_stop = true; // (contigs no read has asked for are not waited for)
     if (ref_loader.joinable()) ref_loader.join();
-    if (!status && (rc = bqc_sync(ctx))) { fprintf(stderr, "%s\n", bqc_last_error(ctx)); status = 1; } // what the device found in the last batches
+    if (!status && (rc = bqc_sync(ctx))) { note_rc(rc); fprintf(stderr, "%s\n", bqc_last_error(ctx)); status = 1; } // what the device found in the last batches
     dec.join();
+    if (S && use_gpu_reader) gpu_rd.end_file(); // (its threads are gone and its streams idle: what it holds can be told, and the next file may open it)
+    note_rc(Q.err_code);
     if (timing) fprintf(stderr, "[timing] records decoded %s\n", use_gpu_reader ? "on the GPU (csrc/gpu_bam.hip)" : gsam_card ? "on the GPU (csrc/gpu_sam.hip)" : "on the host");
     if (timing) { // (every buffer of the run exists at this point: what is in use now is the run's peak)
         size_t free_b = 0, total_b = 0, pinned = 0;
@@ -1284,9 +1484,14 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (Q.err_code == GpuBamReader::kUnsupported) { // nothing has been reported yet: the same file again, through the host reader
         if (timing) fprintf(stderr, "[timing] %s\n", Q.err.c_str());
         destroy_ctx();
-        g_pins.release_all();
-        return run_program(argc, argv, shard, true);
+        if (!S) g_pins.release_all();
+        spare_loan.give();
+        if (S && !S->started_over) { S->started_over = true; S->first_ctx_kept = ctx_kept; S->first_contigs = contigs_before; }
+        return run_program(argc, argv, shard, true, S); // (a session: inside the job, with what the session holds)
     }
+    if (timing && S) // what this job found in place: facts, told when everything it needed exists
+        fprintf(stderr, "[timing] job %u of %u: context %s, %u of %u contigs already on the card, reader buffers %s\n", S->job, std::max(S->job, S->n_jobs), (S->started_over ? S->first_ctx_kept : ctx_kept) ? "kept" : "created",
+                S->started_over ? S->first_contigs : contigs_before, n_refs, use_gpu_reader ? gpu_rd.buffers_report() : n_spare_kept ? "kept" : "new");
     for (uint64_t k = 0; k < n_noqual_deferred; ++k) fputs("ERROR: length of sequence and quality is not the same\n", stderr);
     if (!status && Q.err_code) {
         if (Q.err_code == BQC_ERR_IO) fprintf(stderr, "ERROR: Could not read record from BAM File %s\n", opt.bamFile.c_str()); // :308
@@ -1319,7 +1524,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const bqc_counts* counts = nullptr;
     const auto t_loop_end = clk::now();
     since_launch("record loop and its checks over");
-    if ((rc = bqc_finalize(ctx, &counts))) { fprintf(stderr, "ERROR: %s\n", bqc_last_error(ctx)); destroy_ctx(); return 1; }
+    if ((rc = bqc_finalize(ctx, &counts))) { note_rc(rc); fprintf(stderr, "ERROR: %s\n", bqc_last_error(ctx)); destroy_ctx(); return 1; }
     const auto t_final = clk::now();
     bqc_header_info hi;
     hi.sample_id = rd.header().sample_id.c_str();
@@ -1330,11 +1535,11 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1';
+    const bool fast_exit = !S && !rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
-        g_pins.release_all();
+        if (!S) g_pins.release_all();
     };
     if (!done_fd) teardown();
     if (timing) {
@@ -1363,7 +1568,107 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     return 0;
 }
 
-extern "C" int bqc_main(int argc, const char** argv) { return run_program(argc, argv, nullptr); }
+// ---------------------------------------------------------------------------------------------------
+// one process, many files
+// ---------------------------------------------------------------------------------------------------
+extern "C" int bqc_session_open(int argc, const char** argv, bqc_session** out)
+{
+    if (!out || argc < 1 || !argv) return 1;
+    *out = nullptr;
+    ProgramOptions opt;
+    std::string perr;
+    const int pr = parse_args(argc, argv, opt, perr, true);
+    if (pr == 1) fprintf(stderr, "%s\n", perr.c_str());
+    if (pr != 0) return 1; // (help and version are the program's to answer, not a session's)
+    bqc_session* S = new bqc_session();
+    S->args.assign(argv, argv + argc);
+    *out = S;
+    return 0;
+}
+
+// The job's exit status, as the single run's; 2: not run — the session has ended on a HIP error (in an earlier job: the job that met
+// the error is a failed one, 1).  The rule is enforced here and nowhere else: run_program only notes the error (note_rc).
+extern "C" int bqc_session_run(bqc_session* S, const char* input, const char* output)
+{
+    if (!S || !input || !output) return 1;
+    if (S->ended.load()) return 2;
+    if (strcmp(input, "-") == 0) { fprintf(stderr, "bamqualcheck: a stream on stdin is not a job\n"); return 1; }
+    ++S->job;
+    S->started_over = false;
+    std::vector<const char*> av;
+    for (const std::string& a : S->args) av.push_back(a.c_str());
+    av.push_back("-o"); av.push_back(output);
+    const std::string in = input[0] == '-' ? std::string("./") + input : std::string(input); // (a path, whatever it starts with)
+    av.push_back(in.c_str());
+    return run_program((int)av.size(), av.data(), nullptr, false, S);
+}
+
+extern "C" void bqc_session_close(bqc_session* S)
+{
+    if (!S) return;
+    delete S; // the context with its contigs, the reader's buffers, the batch objects
+    g_pins.release_all();
+}
+
+// --manifest LIST: a loop over the three calls above.  The front end's early-exit byte (BQC_DONE_FD) goes out behind the LAST job, and
+// the one teardown happens behind that byte.
+static int run_manifest(int argc, const char** argv)
+{
+    ProgramOptions opt;
+    std::string perr;
+    const int pr = parse_args(argc, argv, opt, perr);
+    if (pr == 2) return 0;
+    if (pr == 1) { fprintf(stderr, "%s\n", perr.c_str()); return 1; }
+    std::vector<const char*> av;
+    for (int i = 0; i < argc; ++i) { // the session's options: everything but the list
+        if (i > 0 && strcmp(argv[i], "--manifest") == 0) { ++i; continue; }
+        if (i > 0 && strncmp(argv[i], "--manifest=", 11) == 0) continue;
+        av.push_back(argv[i]);
+    }
+    bqc_session* S = nullptr;
+    if (bqc_session_open((int)av.size(), av.data(), &S) != 0) return 1;
+    S->n_jobs = (uint32_t)opt.jobs.size();
+    const bool timing = getenv("BQC_TIMING") && getenv("BQC_TIMING")[0] == '1';
+    int status = 0;
+    for (size_t k = 0; k < opt.jobs.size(); ++k) {
+        const int rc = bqc_session_run(S, opt.jobs[k].first.c_str(), opt.jobs[k].second.c_str());
+        if (rc == 0) continue;
+        status = 1;
+        fflush(stdout);
+        fprintf(stderr, "bamqualcheck: job %zu (%s): %s\n", k + 1, opt.jobs[k].first.c_str(), rc == 2 ? "not run" : "failed");
+    }
+    if (timing) { // what the session holds behind its last job
+        size_t free_b = 0, total_b = 0, pinned = 0, rd_dev = 0, rd_pinned = 0;
+        { std::lock_guard<std::mutex> lk(g_pins.m); for (auto& kv : g_pins.blocks) pinned += kv.second; }
+        S->gpu_rd.memory_held(rd_dev, rd_pinned);
+        if (!S->ended.load() && hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+            fprintf(stderr, "[timing] session after %zu jobs: device memory in use %.2f GB of %.0f GB (the reader and its batch pool %.2f GB of it); page-locked: decode buffers %.2f GB, the reader's ring and tables %.2f GB\n",
+                    opt.jobs.size(), (total_b - free_b) / 1e9, total_b / 1e9, rd_dev / 1e9, pinned / 1e9, rd_pinned / 1e9);
+    }
+    const bool fast_exit = getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1';
+    const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr;
+    fflush(stdout); fflush(stderr);
+    if (done_fd) { // nothing is printed from here on: the list is reported complete, then this process cleans up on its own
+        const int fd = atoi(done_fd);
+        const unsigned char st = (unsigned char)status;
+        (void)prctl(PR_SET_PDEATHSIG, 0);
+        if (write(fd, &st, 1) == 1) {
+            close(fd);
+            const int nul = open("/dev/null", O_WRONLY);
+            if (nul >= 0) { dup2(nul, 1); dup2(nul, 2); }
+        }
+    }
+    bqc_session_close(S);
+    if (fast_exit) _exit(status); // (without the static destructors of the HIP runtime, as the single run)
+    return status;
+}
+
+extern "C" int bqc_main(int argc, const char** argv)
+{
+    for (int i = 1; i < argc; ++i)
+        if (strcmp(argv[i], "--manifest") == 0 || strncmp(argv[i], "--manifest=", 11) == 0) return run_manifest(argc, argv);
+    return run_program(argc, argv, nullptr);
+}
 
 // The front end of `--gpus N` checks the command line ONCE, before it forks (a usage error is then printed once, and no worker
 // starts RCCL for it), and learns the input path the workers will use from the same parser they use.

@@ -486,6 +486,7 @@ extern "C" int bqc_main_multi(int argc, const char** argv, int n_gpus)
         const int pr = bqc_program_args(argc, argv, path, sizeof path);
         if (pr == 2) return 0;
         if (pr != 0) return 1;
+        if (!path[0]) { fprintf(stderr, "bamqualcheck: --gpus with --manifest is not supported: run one process per card (--device), each with a list of its own\n"); return 1; }
         bam = path;
     }
     fflush(stdout); fflush(stderr);

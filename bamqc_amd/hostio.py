@@ -198,6 +198,47 @@ def synth_stream(bam_path, fasta_path, seed, n_reads, ref_names, ref_lens, read_
         raise IOError("bqc_synth_stream failed: %d" % rc)
 
 
+class Session:
+    """Many files through one resident worker (include/bamqc_host.h: bqc_session_*): the runtime, the genome on the card, the
+    context and the reader's buffers outlive a job.  `options`: the program's, without an input, -o and --manifest.
+
+        with hostio.Session(["-r", "genome.fa", "-c", "chr1"]) as s:
+            status = s.run("a.bam", "a.bamqc")     # 0 / 1 as the program's exit status; 2: not run (the session ended on a HIP error)
+    """
+
+    def __init__(self, options, prog="bamqualcheck"):
+        self.lib = _lib.load()
+        argv = [prog] + [str(a) for a in options]
+        args = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
+        self.h = C.c_void_p()
+        if self.lib.bqc_session_open(len(argv), args, C.byref(self.h)) != 0:
+            self.h = None
+            raise ValueError("bqc_session_open: not a session's options: %r" % (list(options),))
+
+    def run(self, input, output):
+        if not self.h:
+            raise ValueError("the session is closed")
+        return int(self.lib.bqc_session_run(self.h, str(input).encode(), str(output).encode()))
+
+    def close(self):
+        if self.h:
+            self.lib.bqc_session_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def main(argv):
     """Run the bamqualcheck program in-process; returns its exit status."""
     lib = _lib.load()

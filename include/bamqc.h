@@ -201,6 +201,9 @@ int bqc_set_reference(bqc_ctx* ctx, int32_t rid, const uint8_t* dna5, uint64_t l
 /* Optional, before the first bqc_set_reference: one device allocation for contigs of total_bases bases in all, which
  * bqc_set_reference then carves from (an allocation made while kernels run waits for them). */
 int bqc_reserve_references(bqc_ctx* ctx, uint64_t total_bases, uint32_t n_contigs);
+/* The contigs of `from` become those of `to` without another upload (one process, many files: a context for another number of read
+ * groups over the same genome).  Same device and n_refs; `to` has no reference yet.  `from` is only good for bqc_destroy afterwards. */
+int bqc_move_references(bqc_ctx* from, bqc_ctx* to);
 /* (ONE uploader thread may call bqc_set_reference while another thread submits batches — the program's non-default BQC_BG_REFS=1 mode —
  * under these rules: the contig is one no submitted batch has a read on; the uploader is the only caller of bqc_set_reference /
  * bqc_reserve_references at that time; and its error is read with bqc_last_error only after the submitting thread has stopped.  The call

@@ -160,8 +160,25 @@ int bqc_main_multi(int argc, const char** argv, int n_gpus);
 
 /* The program's command line, parsed as bqc_main parses it (CommandLineParser.hpp:43-149) without running anything: 0 = valid
  * (the input path — a file name or "-" — is copied to input_path), 1 = usage error (message printed on stderr), 2 = -h /
- * --version answered on stdout.  bqc_main_multi calls it once before it forks its workers. */
+ * --version answered on stdout.  bqc_main_multi calls it once before it forks its workers.
+ * `--manifest LIST` (instead of the input and -o): the list is read and checked by the same rules — 0 with an EMPTY input_path for a
+ * valid one, 1 for whatever is wrong with it (nothing on disk is touched either way). */
 int bqc_program_args(int argc, const char** argv, char* input_path, uint64_t cap);
+
+/* One process, many files (`bamqualcheck --manifest LIST` is a loop over these): a session owns what outlives a job — the HIP
+ * runtime and its streams, the reference genome on the card (kept while the jobs name the same FASTA file and the same @SQ lines),
+ * the context (kept — bqc_reset — while the options that size it stay the same; otherwise a new one takes the contigs over), the
+ * reader's device and page-locked buffers (kept, grown where a file needs more, never shrunk).  Every job is a single run in all a
+ * user can see: same messages, same exit status, byte-identical output file.
+ * bqc_session_open: argv as the program's (argv[0] included), WITHOUT an input, -o and --manifest; 0, or 1 for a usage error
+ * (message on stderr).  Nothing touches the card yet.
+ * bqc_session_run: one job; returns its exit status (0 / 1).  After a job that failed on its INPUT the next one runs.  A HIP error
+ * (BQC_ERR_DEVICE from any call) ends the session: that job returns 1, every later call 2 without starting anything on the card.
+ * bqc_session_close: the one teardown.  One thread at a time; one session per process and device. */
+typedef struct bqc_session bqc_session;
+int bqc_session_open(int argc, const char** argv, bqc_session** out);
+int bqc_session_run(bqc_session* session, const char* input, const char* output);
+void bqc_session_close(bqc_session* session);
 
 #ifdef __cplusplus
 }

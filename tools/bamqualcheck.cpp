@@ -31,13 +31,19 @@ int main(int argc, const char** argv)
     setenv("BQC_FAST_EXIT", "1", 0); // a finished run exits without the HIP runtime's static destructors (see driver.cpp)
     // --gpus N / --gpus=N: taken out of the arguments here (the reference's options are bqc_main's)
     int n_gpus = 0;
+    bool manifest = false; // --manifest LIST: many files through one worker (driver.cpp); not with --gpus
     bool plain = false; // -h / --help / --version: answered once, by this process
     std::vector<const char*> rest;
     for (int i = 0; i < argc; ++i) {
         if (i > 0 && strcmp(argv[i], "--gpus") == 0 && i + 1 < argc) { n_gpus = atoi(argv[++i]); if (n_gpus < 1) n_gpus = -1; continue; }
         if (i > 0 && strncmp(argv[i], "--gpus=", 7) == 0) { n_gpus = atoi(argv[i] + 7); if (n_gpus < 1) n_gpus = -1; continue; }
         if (i > 0 && (strcmp(argv[i], "-h") == 0 || strcmp(argv[i], "--help") == 0 || strcmp(argv[i], "--version") == 0)) plain = true;
+        if (i > 0 && (strcmp(argv[i], "--manifest") == 0 || strncmp(argv[i], "--manifest=", 11) == 0)) manifest = true;
         rest.push_back(argv[i]);
+    }
+    if (manifest && n_gpus != 0 && !plain) { // (before anything is forked)
+        fprintf(stderr, "bamqualcheck: --gpus with --manifest is not supported: run one process per card (--device), each with a list of its own\n");
+        return 1;
     }
     if (n_gpus < 0) { fprintf(stderr, "bamqualcheck: --gpus wants a positive number\n"); return 1; }
     const char* force = getenv("BQC_GPUS_FORCE"); // (1: also --gpus 1 goes through the multi-GPU path: its RCCL set-up and reduce on one card)
