@@ -48,9 +48,36 @@ __device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* sh, ui
     *total = tot;
     return base + inc - v;
 }
+// exclusive sums of N values over the workgroup's threads in thread order (in place); tot: the sums over all threads.  `sh`: N * waves words.
+// NW: the workgroup's waves where the kernel knows them (the loops over them unroll), 0: taken from blockDim.  between(): run by every
+// thread between the two barriers — it sees what the workgroup wrote to LDS before the scan, and what it writes the workgroup sees behind it
+struct NothingBetween { __device__ __forceinline__ void operator()() const {} };
+template <int N, int NW = 0, class Between = NothingBetween>
+__device__ __forceinline__ void block_scan_excl_n(uint32_t v[N], uint32_t* sh, uint32_t tot[N], Between between = Between())
+{
+    const uint32_t w = threadIdx.x >> 6, nw = NW ? NW : blockDim.x >> 6;
+    uint32_t inc[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) inc[k] = wave_scan_incl(v[k]);
+    block_sync();
+    if (lane_id() == WAVE - 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) sh[N * w + k] = inc[k];
+    }
+    between();
+    block_sync();
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        uint32_t base = 0, t = 0;
+        for (uint32_t q = 0; q < nw; ++q) { const uint32_t x = sh[N * q + k]; if (q < w) base += x; t += x; }
+        tot[k] = t;
+        v[k] = base + inc[k] - v[k];
+    }
+}
+template <int NW = 0>
 __device__ __forceinline__ uint32_t block_scan_excl_max(uint32_t v, uint32_t* sh, uint32_t* total)
 {
-    const uint32_t inc = wave_scan_incl_max(v), w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const uint32_t inc = wave_scan_incl_max(v), w = threadIdx.x >> 6, nw = NW ? NW : blockDim.x >> 6;
     block_sync();
     if (lane_id() == WAVE - 1) sh[w] = inc;
     block_sync();
@@ -132,10 +159,7 @@ __global__ __launch_bounds__(PS_THREADS) void k_prep_sizes(PrepArgs a)
 // ---------------------------------------------------------------------------------------------------
 // per read
 // ---------------------------------------------------------------------------------------------------
-// checkFlagsAndQuality (TripletCounting.hpp:136-168): 1 eligible, 0 not, -1 fatal
-// A read's CIGAR as the pre-pass sees it: the first four words in registers — requested for all of a thread's reads at once, before any
-// of them is looked at (round 4: read where they were needed, behind the stores and atomics of the read before, they were a chain of
-// dependent round trips per thread: the kernel's whole time) —, the rest from memory.
+// A read's CIGAR as the deferred path sees it: the first four words in registers, requested together, the rest from memory.
 struct CigarView {
     uint32_t w[4];
     const uint32_t* cg;
@@ -145,52 +169,101 @@ struct CigarView {
         return cg[k];
     }
 };
-__device__ __forceinline__ int triplet_eligible(uint32_t flag, uint32_t mapq, int32_t as, const CigarView& cv, uint32_t ncig)
-{
-    if (!(flag & 0x1) || !(flag & 0x2) || (flag & 0x4) || (flag & 0x8) || (flag & 0x100)) return 0;
-    if (mapq < 60) return 0;
-    if (as == BQC_AS_ABSENT || as < 0) return -1;
-    if (as < 50) return 0;
-    uint32_t clipped = 0;
-    for (uint32_t k = 0; k < ncig; ++k) {
-        const uint32_t wd = cv.at(k), op = wd & 15u;
-        if (op == 4u || op == 5u) clipped += wd >> 4;
-    }
-    return clipped > 0 ? 0 : 1;
-}
 
-// One read's share of the pre-pass.  Everything but the payload offsets and the cross-read part of the FASTA scan.
-struct ReadIn { uint32_t L, nc, flag, lane, mapq; int32_t rid, pos, as; CovEntry ce; };
-struct ReadOut { uint32_t flag, cls, tgt1; CovEntry ce; };
-__device__ __forceinline__ ReadOut prep_one(const PrepArgs& a, const DevRefs& refs, uint32_t i, const ReadIn& in, uint32_t co, bool offsets_ok,
-                                            const CigarView& cv, bool ref_loaded /* refs.ref[rid] != nullptr (rid in range) */, int32_t target_in /* the contig's FASTA record, -1: none */)
+// One read's share of the pre-pass: everything but the payload offsets and the cross-read part of the FASTA scan.  A read whose CIGAR
+// needs no walk — at most one operation, and not set aside by a shard — is done by prep_simple from CIGAR word 0, in the unrolled
+// body of k_prep_reads; every other read by prep_walk, of which the kernel holds ONE copy, called in a loop over those reads.
+// Round 8 carried the walks, a four-word CigarView and 64-bit interval arithmetic in each of the four unrolled copies: 128 VGPRs
+// for a path that 5 % of a short-read batch's reads take.
+struct ReadIn { uint32_t L, nc, flag, lane, mapq; int32_t as; CovEntry ce; };
+struct ReadOut { uint32_t flag, cls, eo; CovEntry ce; }; // (its FASTA position + 1 is tgt1_in where flag has BQC_FLAG_TRIPLET)
+#define PR_EO_NONE 7u // eo: the lowest order of the error keys the read raises (the lowest wins in ErrRec::first_key), PR_EO_NONE: none
+
+// The columns of a thread's four reads as they arrive: a read's fields are taken out where it is looked at, not before.
+struct Quad {
+    uint32_t L[4], nc[2], flag[2], lane, mapq; // (n_cigar and flag: 16 bits a read, lane and mapq: 8)
+    int32_t rid[4], as[4];
+    uint32_t cov[8]; // CovEntry {win, off_len} a read
+    __device__ __forceinline__ uint32_t ncig(int j) const { return (nc[j >> 1] >> (16 * (j & 1))) & 0xFFFFu; }
+    __device__ __forceinline__ ReadIn read(int j) const
+    {
+        return ReadIn{L[j], ncig(j), (flag[j >> 1] >> (16 * (j & 1))) & 0xFFFFu, (lane >> (8 * j)) & 0xFFu, (mapq >> (8 * j)) & 0xFFu, as[j], CovEntry{cov[2 * j], cov[2 * j + 1]}};
+    }
+};
+
+// What both paths do before the coverage: the checks of the read's length and read group, and — primary records only
+// (bamqualcheck.cpp:318-327) — checkFlagsAndQuality (TripletCounting.hpp:136-168; `clipped()`: the CIGAR holds soft- or hard-clipped
+// bases, asked last and only of a read that is eligible otherwise), the forward-only FASTA scan's own-read part (:254-259) and the
+// mate check.  Returns the read's flag word with BQC_FLAG_TRIPLET decided; *eo: the lowest order of the error keys it raises — the
+// thread sends ONE key, its lowest, where each check used to branch around an atomic of its own.
+template <class Clipped>
+__device__ __forceinline__ uint32_t read_checks(const PrepArgs& a, const ReadIn& in, uint32_t tgt1_in /* the contig's FASTA record + 1; 0: none, or not loaded */, Clipped clipped, uint32_t* eo)
 {
-    ReadOut o;
     uint32_t flag = in.flag & (0x0FFFu | BQC_FLAG_MATE_MAIN | BQC_FLAG_NO_QUAL);
-    const uint32_t L = in.L, lane = in.lane;
-    uint32_t nc = in.nc;
-    o.tgt1 = 0;
-    if (L > a.max_read_len) err_key(a.err, i, 1);
-    else if (lane >= a.n_lanes) err_key(a.err, i, 2);
+    uint32_t o = in.L > a.max_read_len ? 1u : in.lane >= a.n_lanes ? 2u : PR_EO_NONE;
     // (BQC_FLAG_NO_QUAL — quality block starting with 0xFF, SURVEY U1 — is a fact of the record's decoding and arrives with the
     // flag column: probing qual[qo] here cost one 128-byte line per read, more than every other byte this kernel reads)
-    if (!offsets_ok) nc = 0; // (the batch fails: the block's check in k_prep_reads)
-    const bool fast = !a.no_fast && L <= BQC_FAST_MAXLEN;
+    // Written as conditions, not as nested branches: the compiler then selects, where it used to jump around every step.
+    const bool primary = !(flag & 0x900u);
+    const bool counted = primary && !(flag & 0x600u);                                  // neither duplicate nor QC fail: tripletCounting, :338-342
+    const bool mapped_pair = (flag & 0x10Fu) == 0x3u && in.mapq >= 60;                 // paired, proper, neither mate unmapped, not secondary
+    const bool as_bad = in.as == BQC_AS_ABSENT || in.as < 0;                           // (fatal for a read that got this far)
+    bool eligible = counted && mapped_pair && !as_bad && in.as >= 50;
+    if (eligible) eligible = !clipped();
+    if (counted && mapped_pair && as_bad) o = min(o, 4u);
+    if (eligible && !tgt1_in) o = min(o, 5u);                                          // Genome: forward-only FASTA scan, no record for the contig
+    if (eligible && tgt1_in) flag |= BQC_FLAG_TRIPLET;
+    if (primary && !(flag & 0xC0u)) o = min(o, 6u);
+    *eo = o;
+    return flag;
+}
+__device__ __forceinline__ uint32_t mate_class(const PrepArgs& a, uint32_t flag, uint32_t L) // mate slot of a fast read (first mate / everything else) or 2 = generic path
+{
+    return !a.no_fast && L <= BQC_FAST_MAXLEN ? ((flag & 0x40u) ? 0u : 1u) : 2u;
+}
+
+// nc <= 1, ce.win != BQC_COV_PENDING: `w0` is the CIGAR's one word (0: none).  No segment, no second interval.
+__device__ __forceinline__ ReadOut prep_simple(const PrepArgs& a, const ReadIn& in, uint32_t w0, uint32_t tgt1_in)
+{
+    const uint32_t op = w0 & 15u, nn = w0 >> 4;
+    ReadOut o;
+    o.flag = read_checks(a, in, tgt1_in, [&] { return (op == 4u || op == 5u) && nn > 0; }, &o.eo);
+    o.ce = CovEntry{in.ce.win, 0};
+    if (in.ce.win != BQC_COV_NONE) { // OverallNumbers.hpp:112-131 for one operation: [pos, pos + nn) cut at 2 * BQC_VSIZE
+        o.flag |= BQC_FLAG_COV;
+        const uint32_t pos = in.ce.off_len;
+        if ((op == 0u || op == 2u) && pos < 2u * BQC_VSIZE) { // (pos + nn < 2^32 here)
+            const uint32_t hi = min(pos + nn, 2u * BQC_VSIZE);
+            if (pos < hi) o.ce.off_len = pos | ((hi - pos) << 16);
+        }
+    }
+    o.cls = mate_class(a, o.flag, in.L) << 8;
+    return o;
+}
+
+// Any read: several operations, a set-aside read of a shard, or a read whose CIGAR is not looked at (offsets_ok false: the batch fails
+// with the block's check in k_prep_reads).  Reloads the read's columns — they have just been read by this workgroup — and its CIGAR.
+__device__ __forceinline__ ReadOut prep_walk(const PrepArgs& a, uint32_t i, uint32_t nc_in, uint32_t co, bool offsets_ok, uint32_t tgt1_in)
+{
+    const ReadIn in{a.l_seq[i], offsets_ok ? nc_in : 0u, a.flag_in[i], a.lane[i], a.mapq[i], a.as_[i], a.cov_in[i]};
+    const int32_t bam_pos = a.pos[i];
+    const uint32_t L = in.L, lane = in.lane, nc = in.nc;
+    CigarView cv;
+    cv.cg = a.cigar + co;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) cv.w[k] = k < nc ? cv.cg[k] : 0u;
+    ReadOut o;
+    uint32_t flag = read_checks(a, in, tgt1_in, [&] {
+        uint32_t clipped = 0;
+        for (uint32_t k = 0; k < nc; ++k) {
+            const uint32_t wd = cv.at(k), op = wd & 15u;
+            if (op == 4u || op == 5u) clipped += wd >> 4;
+        }
+        return clipped > 0;
+    }, &o.eo);
+    const uint32_t cl = mate_class(a, flag, L);
     uint32_t nseg = 0;
     CovEntry ce = in.ce;
-    if (!(flag & 0x900u)) { // primary record: bamqualcheck.cpp:318-327
-        const bool dup = flag & 0x400u, qcf = flag & 0x200u;
-        if (!dup && !qcf) { // tripletCounting, :338-342
-            const int e = triplet_eligible(flag, in.mapq, in.as, cv, nc);
-            if (e < 0) err_key(a.err, i, 4);
-            if (e > 0) { // Genome: forward-only FASTA scan (TripletCounting.hpp:254-259)
-                const int32_t target = target_in;
-                if (target < 0 || !ref_loaded) err_key(a.err, i, 5);
-                else { o.tgt1 = (uint32_t)target + 1u; flag |= BQC_FLAG_TRIPLET; }
-            }
-        }
-        if (!(flag & 0xC0u)) err_key(a.err, i, 6);
-    }
     // The read's covered interval(s) relative to its first live window (OverallNumbers.hpp:112-131): `c` runs over the
     // seq-oriented CIGAR (reversed for reverse reads, bamqualcheck.cpp:349) and advances on S, M and D; M and D add
     // coverage.  DEFINED: increments at window offset >= 2000 are dropped.  One interval unless a clip sits between
@@ -223,7 +296,7 @@ __device__ __forceinline__ ReadOut prep_one(const PrepArgs& a, const DevRefs& re
             if (k < a.cov_extra_cap) a.cov_extra[k] = CovExtra{ce.win, v, lane, 0};
             else atomicOr(&a.err->flags, BQC_DEVERR_INTERNAL); // (capacity = CIGAR words / 2 + 1: cannot happen)
         };
-        if (nc == 1u) { // (nearly every read: no loop)
+        if (nc == 1u) {
             const uint32_t w = cv.w[0], op = w & 15u, nn = w >> 4;
             if (op == 0u || op == 2u) emit(pos, pos + nn);
         } else {
@@ -243,11 +316,11 @@ __device__ __forceinline__ ReadOut prep_one(const PrepArgs& a, const DevRefs& re
     } else ce.off_len = 0;
     // k_short evaluates triplets with chromPos = pos + i inside the first CIGAR operation (assumed match-like,
     // TripletCounting.hpp:203); every further match-like operation becomes a segment entry with its own offset
-    if (fast && (flag & BQC_FLAG_TRIPLET) && nc > 1 && L >= 3) {
+    if (cl != 2u && (flag & BQC_FLAG_TRIPLET) && nc > 1 && L >= 3) {
         const uint32_t n0 = cv.w[0] >> 4;
         if (n0 != 0) { // (n0 == 0: every position counts as inside the first operation, no walk)
             uint64_t rp = n0;
-            int64_t cpos = (int64_t)in.pos + n0;
+            int64_t cpos = (int64_t)bam_pos + n0;
             for (uint32_t k2 = 1; k2 < nc && rp < L; ++k2) {
                 const uint32_t wk = cv.at(k2), op = wk & 15u, nn = wk >> 4;
                 if (op == 2u || op == 3u || op == 5u || op == 6u) cpos += nn;   // D N H P
@@ -266,20 +339,21 @@ __device__ __forceinline__ ReadOut prep_one(const PrepArgs& a, const DevRefs& re
     }
     o.flag = flag;
     o.ce = ce;
-    o.cls = ((fast ? ((flag & 0x40u) ? 0u : 1u) : 2u) << 8) | nseg; // mate slot of a fast read (first mate / everything else) or 2 = generic path; segments
+    o.cls = (cl << 8) | nseg;
     return o;
 }
+__device__ __forceinline__ uint32_t pick4(const uint32_t v[4], uint32_t j) { return j == 0u ? v[0] : j == 1u ? v[1] : j == 2u ? v[2] : v[3]; }
 
 // Thread t of a workgroup owns the four consecutive reads b0 + 4t .. + 3: their columns are 8- / 16-byte loads, the payload
-// offsets are a serial prefix inside the thread plus ONE workgroup scan per quantity, and so is the forward-only FASTA scan.
+// offsets are a serial prefix inside the thread plus ONE three-wide workgroup scan, and so is the forward-only FASTA scan.
 #ifndef PR_WAVES_PER_EU
-#define PR_WAVES_PER_EU 4
+#define PR_WAVES_PER_EU 5
 #endif
 __global__ __launch_bounds__(PR_THREADS) __attribute__((amdgpu_waves_per_eu(PR_WAVES_PER_EU, PR_WAVES_PER_EU))) void k_prep_reads(PrepArgs a, DevRefs refs)
 {
-    __shared__ uint32_t sh[2 * (PR_THREADS / 64)];
+    __shared__ uint32_t sh[3 * (PR_THREADS / 64)];
     __shared__ uint32_t red[8];
-    __shared__ unsigned long long gsum[3 * (PR_THREADS / 64) + 6];
+    __shared__ unsigned long long gsum[3 * (PR_THREADS / 64) + 6], gtot[3];
     const uint32_t i0 = blockIdx.x * PR_BLOCK + 4u * threadIdx.x;
     if (threadIdx.x < 8) red[threadIdx.x] = threadIdx.x == 0 ? 0xFFFFFFFFu : 0u;
     // The block's bases: the totals of the groups before this block's (thread t: groups t, t + 256, ..) and the sums inside the group up
@@ -304,117 +378,168 @@ __global__ __launch_bounds__(PR_THREADS) __attribute__((amdgpu_waves_per_eu(PR_W
         const unsigned long long* incl_p = grp_last ? a.grp_sizes + 3ull * grp : a.blk_sizes + 3ull * (blockIdx.x + 1);
         in_grp = threadIdx.x < 3 ? a.blk_sizes[3ull * blockIdx.x + threadIdx.x] : incl_p[threadIdx.x - 3];
     }
-    auto sum_groups = [&] { // over the workgroup, into LDS: read behind the barriers of the scans below
-        for (int k = 0; k < 3; ++k) grp_before[k] += grp_more[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-            for (int k = 0; k < 3; ++k) grp_before[k] += __shfl_xor(grp_before[k], o);
-        if (lane_id() == 0) for (int k = 0; k < 3; ++k) gsum[3 * (threadIdx.x >> 6) + k] = grp_before[k];
+    auto sum_groups = [&] { // over the workgroup, into LDS: read behind the barriers of the scan below.  A wave's LDS operations run in
+        // their order: its lane 0 clears the wave's three words, then the lanes that hold a group add to them
+        unsigned long long* mine = gsum + 3 * (threadIdx.x >> 6);
+        if (lane_id() == 0) for (int k = 0; k < 3; ++k) mine[k] = 0;
+        if (threadIdx.x < grp) for (int k = 0; k < 3; ++k) atomicAdd(mine + k, grp_before[k] + grp_more[k]);
         if (threadIdx.x < 6) gsum[3 * (PR_THREADS / 64) + threadIdx.x] = in_grp;
     };
-    ReadIn in[4];
+    Quad q;
     const uint32_t nlive = i0 >= a.n ? 0u : min(4u, a.n - i0);
     if ((unsigned long long)(blockIdx.x + 1) * PR_BLOCK <= a.n) { // (every block but a batch's last: the same for all its threads, so that they can sum together inside)
         const uint4 vl = *(const uint4*)(a.l_seq + i0);
         const uint2 vc = *(const uint2*)(a.n_cigar + i0), vf = *(const uint2*)(a.flag_in + i0);
         const uint32_t vlane = *(const uint32_t*)(a.lane + i0), vmq = *(const uint32_t*)(a.mapq + i0);
-        const int4 vr = *(const int4*)(a.rid + i0), vp = *(const int4*)(a.pos + i0), va = *(const int4*)(a.as_ + i0);
+        const int4 vr = *(const int4*)(a.rid + i0), va = *(const int4*)(a.as_ + i0);
         const uint4 c01 = *(const uint4*)(a.cov_in + i0), c23 = *(const uint4*)(a.cov_in + i0 + 2);
         // (the sums are taken HERE, while the columns are in flight: without this the compiler adds the two loaded halves, and waits
         // for them, in front of the column loads)
         asm volatile("" : "+v"(grp_before[0]), "+v"(grp_before[1]), "+v"(grp_before[2]));
         sum_groups();
-        const uint32_t Ls[4] = {vl.x, vl.y, vl.z, vl.w}, ncs[4] = {vc.x & 0xFFFFu, vc.x >> 16, vc.y & 0xFFFFu, vc.y >> 16};
-        const uint32_t fs[4] = {vf.x & 0xFFFFu, vf.x >> 16, vf.y & 0xFFFFu, vf.y >> 16};
-        const int32_t rs[4] = {vr.x, vr.y, vr.z, vr.w}, ps[4] = {vp.x, vp.y, vp.z, vp.w}, as[4] = {va.x, va.y, va.z, va.w};
-        const CovEntry cs[4] = {{c01.x, c01.y}, {c01.z, c01.w}, {c23.x, c23.y}, {c23.z, c23.w}};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) in[j] = ReadIn{Ls[j], ncs[j], fs[j], (vlane >> (8 * j)) & 0xFFu, (vmq >> (8 * j)) & 0xFFu, rs[j], ps[j], as[j], cs[j]};
+        q = Quad{{vl.x, vl.y, vl.z, vl.w}, {vc.x, vc.y}, {vf.x, vf.y}, vlane, vmq, {vr.x, vr.y, vr.z, vr.w}, {va.x, va.y, va.z, va.w},
+                 {c01.x, c01.y, c01.z, c01.w, c23.x, c23.y, c23.z, c23.w}};
     } else {
         sum_groups();
+        q = Quad{{0, 0, 0, 0}, {0, 0}, {0x09000900u, 0x09000900u}, 0, 0, {-1, -1, -1, -1}, {0, 0, 0, 0}, {BQC_COV_NONE, 0, BQC_COV_NONE, 0, BQC_COV_NONE, 0, BQC_COV_NONE, 0}};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            in[j] = ReadIn{0, 0, 0x900u, 0, 0, -1, 0, 0, CovEntry{BQC_COV_NONE, 0}};
-            if ((uint32_t)j < nlive) { const uint32_t i = i0 + j; in[j] = ReadIn{a.l_seq[i], a.n_cigar[i], a.flag_in[i], a.lane[i], a.mapq[i], a.rid[i], a.pos[i], a.as_[i], a.cov_in[i]}; }
-        }
+        for (int j = 0; j < 4; ++j)
+            if ((uint32_t)j < nlive) {
+                const uint32_t i = i0 + j, h = 16 * (j & 1);
+                const CovEntry ce = a.cov_in[i];
+                q.L[j] = a.l_seq[i]; q.rid[j] = a.rid[i]; q.as[j] = a.as_[i]; q.cov[2 * j] = ce.win; q.cov[2 * j + 1] = ce.off_len;
+                q.nc[j >> 1] |= (uint32_t)a.n_cigar[i] << h; q.flag[j >> 1] = (q.flag[j >> 1] & ~(0xFFFFu << h)) | ((uint32_t)a.flag_in[i] << h);
+                q.lane |= (uint32_t)a.lane[i] << (8 * j); q.mapq |= (uint32_t)a.mapq[i] << (8 * j);
+            }
     }
     // payload offsets: prefix inside the thread, then across the workgroup
-    uint32_t ls[4], lq[4], lc[4], ts = 0, tq = 0, tc = 0;
+    uint32_t ls[4], lq[4], lc[4], x[3] = {0, 0, 0}, tot[3];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { ls[j] = ts; lq[j] = tq; lc[j] = tc; ts += (in[j].L + 1) / 2; tq += in[j].L; tc += in[j].nc; }
-    uint32_t tot;
-    const uint32_t xs = block_scan_excl(ts, sh, &tot), xq = block_scan_excl(tq, sh, &tot), xc = block_scan_excl(tc, sh, &tot);
+    for (int j = 0; j < 4; ++j) { ls[j] = x[0]; lq[j] = x[1]; lc[j] = x[2]; x[0] += (q.L[j] + 1) / 2; x[1] += q.L[j]; x[2] += q.ncig(j); }
+    block_scan_excl_n<3, PR_THREADS / 64>(x, sh, tot, [&] { // (the waves' group sums, added by three threads: nine words for every thread to read, not 18)
+        if (threadIdx.x < 3) {
+            unsigned long long t = 0;
+            for (uint32_t w = 0; w < PR_THREADS / 64; ++w) t += gsum[3 * w + threadIdx.x];
+            gtot[threadIdx.x] = t;
+        }
+    });
     unsigned long long excl[3], incl[3];
-    for (int k = 0; k < 3; ++k) { // (behind the scans' barriers; the same in every lane: scalar registers)
-        unsigned long long t = 0;
-        for (uint32_t w = 0; w < PR_THREADS / 64; ++w) t += gsum[3 * w + k];
-        grp_before[k] = uniform64(t); excl[k] = uniform64(gsum[3 * (PR_THREADS / 64) + k]); incl[k] = uniform64(gsum[3 * (PR_THREADS / 64) + 3 + k]);
+    for (int k = 0; k < 3; ++k) { // (behind the scan's barriers; the same in every lane: scalar registers)
+        grp_before[k] = uniform64(gtot[k]); excl[k] = uniform64(gsum[3 * (PR_THREADS / 64) + k]); incl[k] = uniform64(gsum[3 * (PR_THREADS / 64) + 3 + k]);
     }
     unsigned long long base[3];
-    if (prep_block_bases(grp_before, excl, incl, base) && threadIdx.x == 0) err_key(a.err, blockIdx.x * PR_BLOCK, 3);
-    const unsigned long long bs = base[0] + xs, bq = base[1] + xq, bc = base[2] + xc;
-    ReadOut out[4];
-    // what the four reads need from memory besides their columns, all of it requested before the first read is looked at
-    CigarView cv[4];
-    bool ref_loaded[4];
-    int32_t target[4];
-    unsigned long long cos[4];
-    bool oks[4];
+    const bool over = prep_block_bases(grp_before, excl, incl, base); // (the same in every lane)
+    if (over && threadIdx.x == 0) err_key(a.err, blockIdx.x * PR_BLOCK, 3);
+    const uint32_t bs = (uint32_t)base[0] + x[0], bq = (uint32_t)base[1] + x[1], bc = (uint32_t)base[2] + x[2];
+    uint32_t bad = 0; // reads whose payload ends leave 32 bits: the block's end does, in some quantity (the batch fails)
+    if (over) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned long long so = base[0] + x[0] + ls[j], qo = base[1] + x[1] + lq[j], co = base[2] + x[2] + lc[j];
+            if (so + (q.L[j] + 1) / 2 > 0xFFFFFFFFull || qo + q.L[j] > 0xFFFFFFFFull || co + q.ncig(j) > 0xFFFFFFFFull) bad |= 1u << j;
+        }
+        bad &= (1u << nlive) - 1u;
+    }
+    // the offsets leave first: nothing below changes them
+    const uint32_t cos[4] = {bc + lc[0], bc + lc[1], bc + lc[2], bc + lc[3]};
+    if (nlive == 4u) {
+        *(uint4*)(a.seq_off + i0) = make_uint4(bs + ls[0], bs + ls[1], bs + ls[2], bs + ls[3]);
+        *(uint4*)(a.qual_off + i0) = make_uint4(bq + lq[0], bq + lq[1], bq + lq[2], bq + lq[3]);
+        *(uint4*)(a.cigar_off + i0) = make_uint4(cos[0], cos[1], cos[2], cos[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) // (constant indices: a thread's arrays stay in registers)
+            if ((uint32_t)j < nlive) { a.seq_off[i0 + j] = bs + ls[j]; a.qual_off[i0 + j] = bq + lq[j]; a.cigar_off[i0 + j] = cos[j]; }
+    }
+    // what the four reads need from memory besides their columns, all of it requested before the first read is looked at: CIGAR word 0
+    // and the contig's entries of the reference tables.  `walk`: the reads that go through prep_walk
+    uint32_t w0[4], tgt1[4], walk = 0, maxfast = 0, maxlong = 0;
+    const uint8_t* ref_ptr[4]; // (taken as values and looked at behind the last request: `rid_ok && refs.ref[rid] != nullptr` made the wave wait for each one in turn)
+    int32_t target[4];         // the contig's FASTA record, -1: none
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const unsigned long long so = bs + ls[j], qo = bq + lq[j], co = bc + lc[j];
-        cos[j] = co;
-        oks[j] = so + (in[j].L + 1) / 2 <= 0xFFFFFFFFull && qo + in[j].L <= 0xFFFFFFFFull && co + in[j].nc <= 0xFFFFFFFFull;
-        const bool live = (uint32_t)j < nlive && oks[j];
-        cv[j].cg = a.cigar + (uint32_t)co;
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) cv[j].w[k] = live && k < in[j].nc ? cv[j].cg[k] : 0u;
-        const int32_t rid = in[j].rid;
-        const bool rid_ok = (uint32_t)j < nlive && rid >= 0 && (uint32_t)rid < refs.n_refs;
-        ref_loaded[j] = rid_ok && refs.ref[rid] != nullptr;
-        target[j] = rid_ok ? (a.fasta_index ? a.fasta_index[rid] : rid) : -1;
+        const bool live = (uint32_t)j < nlive, ok = !((bad >> j) & 1u);
+        const uint32_t nc = q.ncig(j), L = q.L[j];
+        if (live && (!ok || nc > 1u || q.cov[2 * j] == BQC_COV_PENDING)) walk |= 1u << j;
+        w0[j] = live && ok && nc ? a.cigar[cos[j]] : 0u;
+        const int32_t rid = q.rid[j];
+        const bool rid_ok = live && rid >= 0 && (uint32_t)rid < refs.n_refs;
+        ref_ptr[j] = rid_ok ? refs.ref[rid] : nullptr;
+        target[j] = rid_ok ? rid : -1;
+        const bool fast = !a.no_fast && L <= BQC_FAST_MAXLEN; // (mate_class: the CIGAR has no say)
+        maxfast = max(maxfast, live && fast ? L : 0u); maxlong = max(maxlong, live && !fast ? L : 0u);
     }
-    uint32_t tmax = 0, tmin = 0xFFFFFFFFu, maxfast = 0, maxlong = 0, cnt[4] = {0, 0, 0, 0};
+    if (a.fasta_index) { // (a branch of its own, the same for every thread: inside the loop above each of these loads was waited for where it stood)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (target[j] >= 0) target[j] = a.fasta_index[target[j]];
+    }
+    // (nothing is derived from one of these words before all are requested: the compiler would put the test right behind each load)
+    asm volatile("" : "+v"(target[0]), "+v"(target[1]), "+v"(target[2]), "+v"(target[3]), "+v"(ref_ptr[0]), "+v"(ref_ptr[1]), "+v"(ref_ptr[2]), "+v"(ref_ptr[3]));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tgt1[j] = ref_ptr[j] != nullptr && target[j] >= 0 ? (uint32_t)target[j] + 1u : 0u;
+    // the reads that need no walk, and the thread's 8- and 16-byte stores; a read of the other kind leaves them as no read at all
+    uint32_t fc[4]; // flag | cls << 16: what the thread still needs of a read once it is stored
+    uint32_t ekey = 0xFFFFFFFFu; // the thread's lowest error key, (read - i0) << 3 | order
+    {
+        ReadOut out[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            out[j] = ReadOut{0x900u, 2u << 8, PR_EO_NONE, CovEntry{BQC_COV_NONE, 0}};
+            if ((uint32_t)j < nlive && !((walk >> j) & 1u)) out[j] = prep_simple(a, q.read(j), w0[j], tgt1[j]);
+            fc[j] = out[j].flag | (out[j].cls << 16);
+            if (out[j].eo != PR_EO_NONE) ekey = min(ekey, (uint32_t)j << 3 | out[j].eo);
+        }
+        if (nlive == 4u) {
+            *(uint2*)(a.flag_out + i0) = make_uint2((fc[0] & 0xFFFFu) | (fc[1] << 16), (fc[2] & 0xFFFFu) | (fc[3] << 16));
+            *(uint2*)(a.cls + i0) = make_uint2((fc[0] >> 16) | (fc[1] & 0xFFFF0000u), (fc[2] >> 16) | (fc[3] & 0xFFFF0000u));
+            *(uint4*)(a.cov_out + i0) = make_uint4(out[0].ce.win, out[0].ce.off_len, out[1].ce.win, out[1].ce.off_len);
+            *(uint4*)(a.cov_out + i0 + 2) = make_uint4(out[2].ce.win, out[2].ce.off_len, out[3].ce.win, out[3].ce.off_len);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if ((uint32_t)j < nlive) { a.flag_out[i0 + j] = (uint16_t)fc[j]; a.cls[i0 + j] = (uint16_t)(fc[j] >> 16); a.cov_out[i0 + j] = out[j].ce; }
+        }
+    }
+    // the other reads, one after another through the kernel's one copy of prep_walk: each stores its own entries over the thread's
+    // (a thread's stores to one address arrive in their order).  A short-read batch: one read in twenty.
+#pragma nounroll
+    for (uint32_t m = walk; m; m &= m - 1u) {
+        const uint32_t jj = (uint32_t)__ffs((int)m) - 1u, i = i0 + jj;
+        const uint32_t nc = ((jj & 2u ? q.nc[1] : q.nc[0]) >> (16u * (jj & 1u))) & 0xFFFFu;
+        const ReadOut r = prep_walk(a, i, nc, pick4(cos, jj), !((bad >> jj) & 1u), pick4(tgt1, jj));
+        a.flag_out[i] = (uint16_t)r.flag; a.cls[i] = (uint16_t)r.cls; a.cov_out[i] = r.ce;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) if (jj == j) fc[j] = r.flag | (r.cls << 16);
+        if (r.eo != PR_EO_NONE) ekey = min(ekey, jj << 3 | r.eo);
+    }
+    // the four reads in their order, whichever path each took
+    uint32_t tmax = 0, tmin = 0xFFFFFFFFu, cnt = 0, nseg = 0; // cnt: reads per class, 9 bits each (a wave holds 256 reads)
     bool local_bad[4] = {false, false, false, false};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        out[j] = ReadOut{0x900u, 2u << 8, 0, CovEntry{BQC_COV_NONE, 0}};
+        if (!(fc[j] & BQC_FLAG_TRIPLET)) tgt1[j] = 0; // (from here on: the FASTA position + 1 of an ELIGIBLE read)
         if ((uint32_t)j >= nlive) continue;
-        out[j] = prep_one(a, refs, i0 + j, in[j], (uint32_t)cos[j], oks[j], cv[j], ref_loaded[j], target[j]);
-        if (out[j].tgt1) { local_bad[j] = out[j].tgt1 < tmax; tmax = max(tmax, out[j].tgt1); tmin = min(tmin, out[j].tgt1); }
-        const uint32_t cl = out[j].cls >> 8;
-        if (cl == 2u) maxlong = max(maxlong, in[j].L); else maxfast = max(maxfast, in[j].L);
-        cnt[cl] += 1; cnt[3] += out[j].cls & 0xFFu;
-    }
-    if (nlive == 4u) {
-        *(uint4*)(a.seq_off + i0) = make_uint4((uint32_t)bs + ls[0], (uint32_t)bs + ls[1], (uint32_t)bs + ls[2], (uint32_t)bs + ls[3]);
-        *(uint4*)(a.qual_off + i0) = make_uint4((uint32_t)bq + lq[0], (uint32_t)bq + lq[1], (uint32_t)bq + lq[2], (uint32_t)bq + lq[3]);
-        *(uint4*)(a.cigar_off + i0) = make_uint4((uint32_t)bc + lc[0], (uint32_t)bc + lc[1], (uint32_t)bc + lc[2], (uint32_t)bc + lc[3]);
-        *(uint2*)(a.flag_out + i0) = make_uint2(out[0].flag | (out[1].flag << 16), out[2].flag | (out[3].flag << 16));
-        *(uint2*)(a.cls + i0) = make_uint2(out[0].cls | (out[1].cls << 16), out[2].cls | (out[3].cls << 16));
-        *(uint4*)(a.cov_out + i0) = make_uint4(out[0].ce.win, out[0].ce.off_len, out[1].ce.win, out[1].ce.off_len);
-        *(uint4*)(a.cov_out + i0 + 2) = make_uint4(out[2].ce.win, out[2].ce.off_len, out[3].ce.win, out[3].ce.off_len);
-    } else {
-        for (uint32_t j = 0; j < nlive; ++j) {
-            const uint32_t i = i0 + j;
-            a.seq_off[i] = (uint32_t)bs + ls[j]; a.qual_off[i] = (uint32_t)bq + lq[j]; a.cigar_off[i] = (uint32_t)bc + lc[j];
-            a.flag_out[i] = (uint16_t)out[j].flag; a.cls[i] = (uint16_t)out[j].cls; a.cov_out[i] = out[j].ce;
-        }
+        if (tgt1[j]) { local_bad[j] = tgt1[j] < tmax; tmax = max(tmax, tgt1[j]); tmin = min(tmin, tgt1[j]); }
+        cnt += 1u << (9u * (fc[j] >> 24)); nseg += (fc[j] >> 16) & 0xFFu;
     }
     // forward-only FASTA scan: an eligible read whose position lies before an earlier eligible read's — inside the thread
     // (local_bad), inside the workgroup (here), across workgroups (k_build_plan)
     uint32_t blk_max;
-    const uint32_t before = block_scan_excl_max(tmax, sh, &blk_max);
+    const uint32_t before = block_scan_excl_max<PR_THREADS / 64>(tmax, sh, &blk_max);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-        if (out[j].tgt1 && (local_bad[j] || out[j].tgt1 < before)) err_key(a.err, i0 + j, 5);
+        if (tgt1[j] && (local_bad[j] || tgt1[j] < before)) ekey = min(ekey, (uint32_t)j << 3 | 5u);
+    if (ekey != 0xFFFFFFFFu) err_key(a.err, i0 + (ekey >> 3), ekey & 7u);
     // block partials: FASTA positions (for the scan across blocks), longest fast / generic read; class counts of the super-window
     if (tmin != 0xFFFFFFFFu) atomicMin(&red[0], tmin);
     if (maxfast) atomicMax(&red[1], maxfast);
     if (maxlong) atomicMax(&red[2], maxlong);
     if (!a.order) { // stream order: the block's reads lie in one super-window
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const uint32_t v = wave_sum(cnt[k]); if (lane_id() == 0 && v) atomicAdd(&red[4 + k], v); }
+        const uint32_t c = wave_scan_incl(cnt), sg = wave_scan_incl(nseg); // (sums in the wave's last lane)
+        if (lane_id() == WAVE - 1) {
+            for (uint32_t k = 0; k < 3u; ++k) { const uint32_t v = (c >> (9u * k)) & 0x1FFu; if (v) atomicAdd(&red[4 + k], v); }
+            if (sg) atomicAdd(&red[7], sg);
+        }
     }
     block_sync();
     if (threadIdx.x == 0) {
@@ -606,28 +731,6 @@ __global__ __launch_bounds__(1024) void k_build_plan(PrepArgs a)
     }
 }
 
-// exclusive sums of four values over the workgroup's threads in thread order (in place); tot: the sums over all threads.  `sh`: 4 * waves words
-__device__ __forceinline__ void block_scan_excl4(uint32_t v[4], uint32_t* sh, uint32_t tot[4])
-{
-    const uint32_t w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t inc[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) inc[k] = wave_scan_incl(v[k]);
-    block_sync();
-    if (lane_id() == WAVE - 1) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sh[4 * w + k] = inc[k];
-    }
-    block_sync();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint32_t base = 0, t = 0;
-        for (uint32_t q = 0; q < nw; ++q) { const uint32_t x = sh[4 * q + k]; if (q < w) base += x; t += x; }
-        tot[k] = t;
-        v[k] = base + inc[k] - v[k];
-    }
-}
-
 // entries of one super-window: read groups (first-mate slots | other slots, missing ones null), segment entries, generic reads.
 // Thread t owns the positions [SC_PER * t, + SC_PER) of the super-window: their classes are requested together (two 16-byte loads
 // in stream order), ranked by ONE workgroup scan of four counts, and placed from registers; the read groups leave LDS coalesced.
@@ -668,7 +771,7 @@ __global__ __launch_bounds__(PR_THREADS) void k_build_scatter(PrepArgs a)
 #pragma unroll
     for (int k = 0; k < SC_PER; ++k) co[k] = (v[k] >> 8) < 3u && (v[k] & 0xFFu) ? a.cigar_off[r[k]] : 0u;
     uint32_t tot[4];
-    block_scan_excl4(c, sh, tot); // c: this thread's first ranks (its barriers also order the null entries before the placement)
+    block_scan_excl_n<4>(c, sh, tot); // c: this thread's first ranks (its barriers also order the null entries before the placement)
     uint32_t k0 = c[0], k1 = c[1], k2 = c[2], k3 = c[3];
 #pragma unroll
     for (int k = 0; k < SC_PER; ++k) {
