@@ -1,5 +1,5 @@
 """GPU: the generic per-base kernel (any read length) stays covered now that short reads take the
-fast path: BQC_NO_FAST=1 routes every read through k_reads + k_bases."""
+fast path: BQC_NO_FAST=1 routes every read through k_reads + k_long."""
 import numpy as np
 import pytest
 

@@ -16,6 +16,7 @@ import pytest
 from bamqc_amd import hostio
 from tests import synth
 from tests.cli_oracle import oracle_bamqualcheck
+from tests.long_layout import dna_ref, expected_triplets, reads_on_ref  # (shared with the k_long layout tests)
 from tests.parity import assert_parity, run_gpu, split
 
 pytestmark = pytest.mark.gpu
@@ -53,37 +54,6 @@ def qual_passes(phred, q):
     return signed(np.asarray(phred) + 33) >= signed(q + 33)
 
 
-def dna_ref(seed, n):
-    return np.random.default_rng(seed).integers(0, 4, n).astype(np.uint8)  # no N: every base of a read on it is A/C/G/T
-
-
-def reads_on_ref(ref, pos, L, flag, qual, cigar=None, nm=None):
-    """Reads copied from the reference at `pos` (BAM orientation), one lane.  qual: flat uint8 (sum(L) bytes);
-    cigar: list of [(n, op), ...] per read (default all-M)."""
-    pos = np.asarray(pos, np.int64)
-    L = np.asarray(L, np.int64)
-    n = len(pos)
-    seqs = []
-    for lo in range(0, n, 100_000):  # (in slices: the index arrays stay small)
-        p, l = pos[lo:lo + 100_000], L[lo:lo + 100_000]
-        lp = l + (l & 1)
-        k = np.arange(int(lp.sum()), dtype=np.int64) - np.repeat(np.cumsum(lp) - lp, lp)
-        idx = np.minimum(np.repeat(p, lp) + k, len(ref) - 1)
-        nib = np.where(k < np.repeat(l, lp), synth.NIB[ref[idx]], 0).astype(np.uint8)
-        seqs.append((nib[0::2] << 4) | nib[1::2])
-    if cigar is None:
-        cig = (L.astype(np.uint32) << 4)  # M
-        ncig = np.ones(n, np.uint16)
-    else:
-        cig = np.concatenate([synth.cigar_words(c) for c in cigar])
-        ncig = np.array([len(c) for c in cigar], np.uint16)
-    return dict(flag=np.asarray(flag, np.uint16), mapq=np.full(n, 60, np.uint8), lane=np.zeros(n, np.uint8),
-                rid=np.zeros(n, np.int32), pos=pos.astype(np.int32), tlen=np.full(n, 400, np.int32),
-                nm=np.zeros(n, np.int32) if nm is None else np.asarray(nm, np.int32), as_=np.minimum(L, 1 << 30).astype(np.int32),
-                l_seq=L.astype(np.uint32), n_cigar=ncig, seq=np.concatenate(seqs), qual=np.asarray(qual, np.uint8),
-                cigar=cig.astype(np.uint32))
-
-
 def uniform_batch(seed, n, L, phred, ref, reverse_every=2):
     """n primary first-mate reads of length L, all-M on the reference, every base of Phred `phred`, a part on the reverse strand."""
     rng = np.random.default_rng(seed)
@@ -91,22 +61,6 @@ def uniform_batch(seed, n, L, phred, ref, reverse_every=2):
     flag = np.full(n, 0x1 | 0x2 | 0x40 | 0x1000, np.uint16)
     flag[::reverse_every] |= 0x10
     return reads_on_ref(ref, pos, np.full(n, L), flag, np.full(n * L, phred, np.uint8))
-
-
-def expected_triplets(ref, cols, phred):
-    """TripletCounting.hpp:195-236 for eligible all-M reads on an N-free contig, copied from it: every position 1..L-2 of the
-    read (chromPos = pos + readPos lies in [1, len - 2]) counts iff (signed char)(phred + 33) >= '5', into context
-    ref[p-1] ref[p] ref[p+1], group forward / reverse x first / second, base ref[p]."""
-    t = np.zeros(64 * 16, np.uint64)
-    if not (20 <= phred <= 94):
-        return t
-    L = int(cols["l_seq"][0])
-    p = cols["pos"].astype(np.int64)[:, None] + np.arange(1, L - 1)[None, :]
-    ctx = ref[p - 1].astype(np.int64) * 16 + ref[p] * 4 + ref[p + 1]
-    fl = cols["flag"].astype(np.int64)
-    grp = np.where(fl & 0x10, 2, 0) + np.where(fl & 0x40, 0, 1)
-    np.add.at(t, (ctx * 16 + grp[:, None] * 4 + ref[p]).ravel(), 1)
-    return t
 
 
 def n_cu():
