@@ -30,6 +30,12 @@ public:
     // by the walk's own guess (three records in a row that look like records) — neighbouring shards verify it afterwards:
     // range_over() of a shard must equal range_first() of its successor.
     void set_range(uint64_t begin_block, uint64_t end_block) { range_b0_ = begin_block; range_b1_ = end_block; ranged_ = true; }
+    // A STREAM instead of a file (a pipe, a FIFO, stdin: DESIGN section 4.5c): call before open(), whose path is then not opened.  `fd`
+    // is read once, in order, by one reader thread and is the reader's from here on (closed with the file unless it is 0); `prefix`
+    // is every byte that has left it so far, from the stream's first one — the header's, and what was held while the runtime started —
+    // and is the input of the first run or runs: it arrives by move and is not read again; `ended`: the descriptor has reported its
+    // end.  A stream is never ranged, and next_batch never answers kUnsupported for one: there is no second pass over a stream.
+    void set_stream(int fd, raw_vector<uint8_t>&& prefix, bool ended) { stream_fd_ = fd; stream_prefix_ = std::move(prefix); stream_ended_ = ended; stream_set_ = true; }
     uint64_t range_first() const { return range_first_; } // uncompressed offset of the shard's first record, relative to its begin block (valid after the first batch)
     uint64_t range_over() const { return range_over_; }   // where the record after the shard's last one starts, relative to the end block (valid after the last batch)
     // The file is read and copied to the card from open() on; the first inflate kernel waits for this call: a caller that still has
@@ -46,7 +52,7 @@ public:
     void set_anchor_context(bqc_ctx* ctx) { anchor_ctx_ = ctx; }
     uint64_t batches_anchored() const { return n_anchored_; }
     uint64_t batches() const { return n_batches_; } // batches of records the card has decoded (those handed over to the host decoder included)
-    double seconds_reading() const { return t_read_; } // time spent in pread, summed over the reader threads
+    double seconds_reading() const { return t_read_; } // time spent in pread, summed over the reader threads (a stream: in read() and waiting for the pipe, one thread)
     double seconds_waiting_for_runs() const { return t_wait_run_; } // time the consumer waited for the next inflated run (file, copy or inflate behind)
     double seconds_producer_waiting_for_chunks() const { return t_wait_chunk_; } // time the producer waited for the ring's reader threads
     // set by open() once its device buffers are allocated (also when it fails before that): a caller that creates its own device
@@ -71,6 +77,9 @@ private:
     bool anchors_ok_ = true; // (decode thread)
     double t_read_ = 0, t_wait_run_ = 0, t_wait_chunk_ = 0;
     bool ranged_ = false;
+    bool stream_set_ = false, stream_ended_ = false;
+    int stream_fd_ = -1;
+    raw_vector<uint8_t> stream_prefix_;
     bool reopened_ = false;
     size_t held_before_ = 0; // bytes held when open() took the buffers over
     uint64_t range_b0_ = 0, range_b1_ = UINT64_MAX, range_first_ = 0, range_over_ = 0;

@@ -1,6 +1,6 @@
 // gpu_bam.hip — BAM input decoded on the GPU (row N2 of the scope table, step 2: see gpu_bam.h).
 //
-//   file --pread, three threads--> ring of page-locked chunks --H2D--> k_inflate + k_gi_crc (gpu_inflate.hip) --> the uncompressed stream, in device memory
+//   file --pread, three threads (a stream: what was read before the reader existed, then read() by one thread)--> ring of page-locked chunks --H2D--> k_inflate + k_gi_crc (gpu_inflate.hip) --> the uncompressed stream, in device memory
 //        --> k_gb_walk: where the records are        --> k_gb_decode: the fixed columns + where each record's payload goes
 //        --> k_gb_copy: bases / qualities / CIGARs into packed columns (device)   --> D2H of the fixed columns only (26 B per read)
 //
@@ -13,7 +13,8 @@
 // (a read group that is not in the header, a second NM tag, no RG tag, ...) is decoded by the host reader's own code
 // (bam_decode_records) from the bytes on the card; a walk that cannot be verified, a corrupt record or a file that ends inside a
 // record make next_batch return kUnsupported: the caller starts over with the host reader, which is the one to decide what the
-// user is told.
+// user is told.  A STREAM (set_stream: a pipe, a FIFO, BAM on stdin) cannot be started over: there the host reader's own walk
+// (bam_walk_one) runs over the window's bytes from the first record the card cannot vouch for (next_batch: host_walk).
 //
 // The file — or one worker's byte range of it (set_range: the multi-GPU program) — is taken in few, large RUNS of BGZF blocks (large
 // inflate launches are the cheapest per block: 10 ms for 9 K blocks, 29 ms for 45 K, gpu_inflate.hip): reader threads fill a ring of page-locked chunks, a
@@ -30,6 +31,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <fcntl.h>
+#include <poll.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -503,7 +505,8 @@ struct GpuBamReader::Impl {
         if (ps) (void)hipStreamSynchronize(ps);
         if (ring_alloc.joinable()) ring_alloc.join();
         if (s) (void)hipStreamSynchronize(s);
-        if (fd >= 0) { close(fd); fd = -1; }
+        if (fd > 0 || (fd == 0 && !seq)) close(fd);
+        fd = -1;
     }
     template <typename B> static void take(B& mine, B& theirs) { std::swap(mine.p, theirs.p); std::swap(mine.cap, theirs.cap); }
     // The reader is opened again (one process, many files): every BUFFER of the reader before — streams, events, status words, the
@@ -599,6 +602,20 @@ struct GpuBamReader::Impl {
     bool release_chunk(uint64_t i, hipStream_t st);
     size_t kMaxRunOut = (size_t)3200 << 20; // uncompressed bytes of a run (BQC_GB_MAX_RUN_OUT_MB: tests)
     raw_vector<uint8_t> first_raw; // the first run: read while the device is still starting
+    // A STREAM (GpuBamReader::set_stream): `fd` is read once, in order — read(), by ONE reader thread, into the ring's chunks from the
+    // stream's position prefix.size() on — and every offset above (ring_base, parsed_off, read_limit) is a position in the stream.
+    // The prefix, what had left the descriptor before this reader existed, is the input of the first run or runs (a run ends where
+    // run_bytes, its output buffer or the first run's cap say, the rest of the prefix is the next run's); the ring takes over when the
+    // prefix holds no whole block any more, and the head of a block it ends with (at most 64 KiB, whatever the prefix's size) goes
+    // into the headroom in front of the ring's first chunk.
+    bool seq = false;
+    uint64_t n_calls = 0;          // (consumer) calls of next_batch
+    raw_vector<uint8_t> prefix;
+    size_t prefix_at = 0;          // (producer) the first byte of the prefix no run has taken
+    bool prefix_done = true;       // (producer) the ring is the source from here on
+    bool prefix_ended = false;     // the stream ended inside the prefix: no ring
+    size_t prefix_tail = SIZE_MAX; // (producer) bytes of the prefix behind its last whole block, still to go in front of the ring's first chunk (SIZE_MAX: none)
+    uint64_t prefix_last_run = 0;  // (producer) the last run that was copied from the prefix: the bytes go when its buffer is free again
     bool dev_ready = false;        // (under m) streams and buffers exist: the producer may touch the device
     bool kernels_ok = false;       // (under m) GpuBamReader::allow_kernels(): the first inflate kernel may be launched
     void produce();
@@ -656,7 +673,19 @@ bool GpuBamReader::open(const char* path, int device, const BamHeader& hdr, uint
     if (const char* e = getenv("BQC_GB_RUN_MB")) I.run_bytes = (size_t)std::max(1, atoi(e)) << 20;
     if (const char* e = getenv("BQC_GB_READERS")) { I.kReaders = std::min(8, std::max(1, atoi(e))); I.kSlots = 2 * I.kReaders; }
     if (const char* e = getenv("BQC_GB_MAX_RUN_OUT_MB")) I.kMaxRunOut = (size_t)std::max(1, atoi(e)) << 20;
-    I.fd = ::open(path, O_RDONLY);
+    if (const char* e = getenv("BQC_GB_CHUNK_KB")) I.chunk_bytes = (size_t)std::max(256, atoi(e)) << 10; // (tests: a small stream wraps the ring; the headroom is 128 KB)
+    if (stream_set_) { // the descriptor and what has been read of it are this reader's now
+        stream_set_ = false;
+        I.seq = true;
+        I.fd = stream_fd_; stream_fd_ = -1;
+        I.prefix.swap(stream_prefix_); raw_vector<uint8_t>().swap(stream_prefix_);
+        I.prefix_ended = stream_ended_;
+        I.prefix_done = false;
+        I.kReaders = 1; // (one thread reads a descriptor in order; the chunks stay six)
+        if (ranged_) { err = "GPU reader: a stream cannot be read in parts"; return false; }
+        if (I.prefix_ended) I.run_bytes = std::min<size_t>(I.run_bytes, I.prefix.size() + (1u << 20)); // (the one case in which a stream's size is known)
+        I.ring_open = !I.prefix_ended; // (ring_base 0: chunk i is what the i-th read of chunk_bytes gives)
+    } else I.fd = ::open(path, O_RDONLY);
     if (I.fd < 0) { err = std::string("could not open ") + path; return false; }
     if (ranged_) {
         I.begin_off = range_b0_; I.mark_off = range_b1_;
@@ -668,7 +697,7 @@ bool GpuBamReader::open(const char* path, int device, const BamHeader& hdr, uint
     I.n_ref = (int32_t)hdr.ref_names.size();
     { // (the sizes the producer works with are final before it starts)
         struct stat st;
-        if (fstat(I.fd, &st) == 0 && st.st_size > 0) {
+        if (!I.seq && fstat(I.fd, &st) == 0 && st.st_size > 0) { // (a stream has no size: its run buffers are sized by run_bytes alone)
             const uint64_t upto = std::min<uint64_t>((uint64_t)st.st_size, I.mark_off == UINT64_MAX ? UINT64_MAX : I.mark_off + Impl::kBeyond + (1u << 17));
             I.run_bytes = std::min<size_t>(I.run_bytes, (size_t)(upto > I.begin_off ? upto - I.begin_off : 0) + (1u << 20));
         }
@@ -851,8 +880,17 @@ void GpuBamReader::Impl::reader_loop()
         const uint64_t at = ring_base + i * chunk_bytes;
         size_t got = 0;
         const double t0 = now_s();
-        while (got < chunk_bytes) {
-            const ssize_t k = pread(fd, S.p + kHeadroom + got, chunk_bytes - got, (off_t)(at + got));
+        while (got < chunk_bytes) { // (a chunk is filled completely unless the input ends in it: a pipe gives 64 KB or less at a time)
+            ssize_t k;
+            if (seq) {
+                struct pollfd pf{fd, POLLIN, 0};
+                if (poll(&pf, 1, 100) <= 0) { // nothing yet (or a signal): is the reader still wanted?
+                    std::lock_guard<std::mutex> lk(rm);
+                    if (rstop) return;
+                    continue;
+                }
+                k = read(fd, S.p + kHeadroom + got, chunk_bytes - got);
+            } else k = pread(fd, S.p + kHeadroom + got, chunk_bytes - got, (off_t)(at + got));
             if (k < 0) { if (errno == EINTR) continue; break; } // (a read error shows as a short chunk: "truncated BGZF file")
             if (k == 0) break;
             got += (size_t)k;
@@ -863,6 +901,7 @@ void GpuBamReader::Impl::reader_loop()
             S.len = got; S.index = i; S.filled = true;
         }
         rcv.notify_all();
+        if (seq && got < chunk_bytes) return; // (the stream has ended: nothing is behind it)
     }
 }
 
@@ -904,9 +943,49 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
     // A run ends where its output buffer does (sized in open() for 3.6 x the compressed bytes: a file that inflates further gets
     // more, smaller runs — never a buffer released and allocated again behind a running kernel).
     const size_t out_limit = std::min(kMaxRunOut, out_cap - head - 64);
-    if (produced == 0) {
+    static const size_t first_cap = getenv("BQC_GB_FIRST_MB") ? (size_t)std::max(64, atoi(getenv("BQC_GB_FIRST_MB"))) << 20 : (size_t)320 << 20; // (10 M-read file, 896 MB: 0.29 s with 640, 0.26 with 320, 0.27 with 192, 0.28 with 128 — tools/first_run_mb.py)
+    // the device is up and the run's buffers are there (no-ops for the two buffers open() has allocated; the third one is allocated here, whole:
+    // the chunks are copied in as they are read)
+    auto prepare = [&]() {
+        if (!wait_ready()) return false;
+        if (!R.d_comp.need(run_bytes + chunk_bytes + (1u << 17) + 64, true) || !R.d_out.need(out_cap, true) || !R.d_blocks.need(run_bytes / 2048) || !R.d_crc.need(run_bytes / 2048) ||
+            !R.d_tok.need(bqc_gpu_inflate_token_words(out_cap, run_bytes / 2048), true) || !R.d_ntok.need(run_bytes / 2048)) return false;
+        he = hipMemsetAsync(R.d_status, 0, 4, R.s);
+        return true;
+    };
+    hipStream_t copy_s = R.s; // where the run's bytes are copied (the ring's chunks: the copy stream)
+    bool ring = false;        // the run takes chunks of the ring
+    if (seq && prefix_last_run != UINT64_MAX && prefix_done && produced >= prefix_last_run + kRuns) { // (R is the buffer of the last run copied from the prefix, free again: that copy has run)
+        raw_vector<uint8_t>().swap(prefix);
+        prefix_last_run = UINT64_MAX;
+    }
+    if (seq && !prefix_done) {
+        // A stream's prefix, in memory since before this reader existed: this run takes its next whole blocks — all of them, or as many as
+        // run_bytes (the first run: its cap), out_limit and the output buffer allow; the rest is the next run's, and nothing is read twice.
+        const size_t left = prefix.size() - prefix_at;
+        const size_t have = std::min(left, produced == 0 ? std::min<size_t>(run_bytes, first_cap) : run_bytes);
+        const uint8_t* const src = prefix.data() + prefix_at;
+        const size_t p = parse_blocks(R, src, have, 0, nb, utotal, stop_at, out_limit, stopped);
+        if (p == SIZE_MAX) { R.rc = -1; return; }
+        // every whole block of the prefix has been taken: what is left (rem) is the head of a block, or nothing
+        const bool all = have == left && (p == have || utotal + 65536 <= out_limit);
+        const size_t rem = all ? left - p : 0;
+        if (rem > kHeadroom) { R.err = "corrupt BGZF block (larger than 64 KiB)"; R.rc = -1; return; }
+        if (all && prefix_ended) { // the stream ended before this reader existed
+            if (rem) { R.err = "truncated BGZF file"; R.rc = -1; return; }
+            file_eof = true;
+        }
+        if (!prepare()) { R.rc = -2; return; }
+        if (he == hipSuccess && p) he = hipMemcpyAsync(R.d_comp.p, src, p, hipMemcpyHostToDevice, R.s);
+        d_off = p; parsed_off += p; prefix_at += p;
+        prefix_last_run = produced;
+        if (all) { // the ring takes over: in this run when the prefix gave it nothing, otherwise with the next (this one is not kept waiting for the pipe)
+            prefix_done = true;
+            prefix_tail = file_eof ? SIZE_MAX : rem;
+            ring = !file_eof && p == 0;
+        }
+    } else if (produced == 0) {
         // the first run: at least 64 MB (the first batch is there when the device is), and whatever more can be read until the device is up
-        static const size_t first_cap = getenv("BQC_GB_FIRST_MB") ? (size_t)std::max(64, atoi(getenv("BQC_GB_FIRST_MB"))) << 20 : (size_t)320 << 20; // (10 M-read file, 896 MB: 0.29 s with 640, 0.26 with 320, 0.27 with 192, 0.28 with 128 — tools/first_run_mb.py)
         const size_t piece = 32u << 20;
         size_t cap = std::min<size_t>(run_bytes, first_cap);
         if (stop_at != UINT64_MAX) cap = (size_t)std::min<uint64_t>(cap, stop_at + (1u << 17) - begin_off);
@@ -965,14 +1044,20 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
         if (he == hipSuccess && p) he = hipMemcpyAsync(R.d_comp.p, first_raw.data(), p, hipMemcpyHostToDevice, R.s);
         d_off = p;
     } else {
-        if (!wait_ready()) { R.rc = -2; return; }
-        // (no-ops for the two buffers open() has allocated; the third one is allocated here, whole: the chunks are copied in as they are read)
-        if (!R.d_comp.need(run_bytes + chunk_bytes + (1u << 17) + 64, true) || !R.d_out.need(out_cap, true) || !R.d_blocks.need(run_bytes / 2048) || !R.d_crc.need(run_bytes / 2048) ||
-            !R.d_tok.need(bqc_gpu_inflate_token_words(out_cap, run_bytes / 2048), true) || !R.d_ntok.need(run_bytes / 2048)) { R.rc = -2; return; }
-        he = hipMemsetAsync(R.d_status, 0, 4, R.s);
+        if (!prepare()) { R.rc = -2; return; }
+        ring = true;
+    }
+    if (ring) {
         static const bool own_copy_stream = !(getenv("BQC_GB_COPY_STREAM") && getenv("BQC_GB_COPY_STREAM")[0] == '0');
         if (own_copy_stream && !cs && hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); cs = nullptr; }
-        hipStream_t const copy_s = own_copy_stream && cs ? cs : R.s;
+        copy_s = own_copy_stream && cs ? cs : R.s;
+        if (prefix_tail != SIZE_MAX) { // a stream: the head of the block its prefix ends with, in front of the ring's first chunk
+            Slot* N = wait_chunk(0);
+            if (!N) { R.rc = -2; return; }
+            if (prefix_tail) memcpy(N->p + kHeadroom - prefix_tail, prefix.data() + prefix_at, prefix_tail);
+            ring_at = kHeadroom - prefix_tail;
+            prefix_tail = SIZE_MAX;
+        }
         if (stop_at != UINT64_MAX) { // the readers may go as far as this run can want
             { std::lock_guard<std::mutex> lk(rm); read_limit = std::max(read_limit, stop_at + (1u << 17)); }
             rcv.notify_all();
@@ -1003,7 +1088,7 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
             ring_at = kHeadroom - rem;
         }
     }
-    if (he == hipSuccess && cs && produced != 0) { // (the run's chunks went through the copy stream: its kernels wait for the last of them)
+    if (he == hipSuccess && copy_s != R.s) { // (the run's chunks went through the copy stream: its kernels wait for the last of them)
         he = hipEventRecord(R.copied, cs);
         if (he == hipSuccess) he = hipStreamWaitEvent(R.s, R.copied, 0);
     }
@@ -1081,15 +1166,65 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         I.s_ready = true;
         if (!I.s || hipStreamSynchronize(I.ps) != hipSuccess) { err = "GPU reader: no stream"; err_code = BQC_ERR_DEVICE; return -1; } // (the status word's memset is on the producer's)
     }
+    const double t0 = now_s();
+    ++I.n_calls;
     auto fail_dev = [&](const char* what) { err = std::string("GPU reader: ") + what; err_code = BQC_ERR_DEVICE; return -1; };
-    auto unsupported = [&](const char* why) { err = std::string("GPU reader hands over to the host reader: ") + why; err_code = kUnsupported; return -1; };
+    // (a stream cannot be read a second time: what would end a file's pass is decided here — host_walk below — and what is left, a record
+    // larger than the reader's spare room among it, is an error of the stream)
+    auto unsupported = [&](const char* why) {
+        if (I.seq) { err = std::string("GPU reader: ") + why; err_code = BQC_ERR_IO; return -1; }
+        err = std::string("GPU reader hands over to the host reader: ") + why; err_code = kUnsupported; return -1;
+    };
+    // A STREAM, where the card cannot vouch for the records at the window's start (a walk that cannot be verified, a record the host
+    // reader will report, a stream that ends inside a record): the window's walked bytes come back — one copy, as for a batch handed
+    // over — and the host reader's own walk (bam_walk_one, host/bam_io.cpp) runs over them, then its decoder.  The records the walk
+    // accepts are a host batch; its error is the answer, in the host reader's words; where it accepts every record and ends at one
+    // that is not all there while the stream goes on, the card continues from that position (known: no guess is needed).
+    // 1 / 0 / -1 as next_batch; 2: not one whole record in these bytes and more can come (the caller widens the window or takes the next run).
+    auto host_walk = [&](const uint8_t* base, uint64_t avail) -> int {
+        try { I.handover_raw.resize((size_t)avail); } catch (const std::bad_alloc&) { err = "GPU reader: no host memory for the records of a stream"; err_code = BQC_ERR_IO; return -1; }
+        if (avail && hipMemcpy(I.handover_raw.data(), base, (size_t)avail, hipMemcpyDeviceToHost) != hipSuccess) return fail_dev("copy failed");
+        const uint8_t* raw = I.handover_raw.data();
+        const bool more = avail < I.end - I.cur || !I.stream_done; // bytes behind these exist, or may
+        std::vector<BamRec>& recs = I.handover_recs;
+        recs.clear();
+        size_t rel = 0, hso = 0, hqo = 0, hco = 0, hbases = 0;
+        bool io_error = false, need_more = false;
+        std::string werr;
+        while (recs.size() < max_reads && hbases < max_bases) { // (BamReader::next_batch: a record is walked when all of it is there, or its block_size is below 32)
+            const size_t have = (size_t)avail - rel;
+            const uint32_t bs0 = have >= 4 ? BrBytes{raw}.u32(rel) : 32u;
+            if (have < 4 || (bs0 >= 32 && have < 4 + (uint64_t)bs0)) {
+                if (more) need_more = true;
+                else if (have) { werr = bam_walk_message(BR_INCOMPLETE); io_error = true; }
+                break;
+            }
+            const int c = bam_walk_one(raw, (size_t)avail, rel, nrec_ + recs.size(), true, recs, hso, hqo, hco, hbases);
+            if (c != BR_OK) { werr = bam_walk_message(c); io_error = true; break; }
+        }
+        if (recs.empty() && need_more) return 2;
+        o.d_seq = o.d_qual = nullptr; o.d_cigar = nullptr; // (a host batch; its device buffer stays for the next one)
+        std::string derr;
+        int dcode = 0;
+        const bool fine = bam_decode_records(raw, recs, hdr_, main_, bqc_host_threads(), o, derr, dcode);
+        ++n_handed_over_;
+        anchors_ok_ = false; // (the host keeps the window state from this batch on, as after any batch handed over)
+        if (hdr_.lane_names.size() != I.n_lane_ids && !I.upload_lanes(hdr_)) return fail_dev("out of device memory");
+        I.cur += rel;
+        nrec_ += recs.size();
+        if (!recs.empty()) { I.avg_rec_bytes = (double)rel / (double)recs.size(); I.avg_rec_bases = (double)hbases / (double)recs.size(); }
+        if (I.timing) fprintf(stderr, "[gpu reader] %zu records of a stream walked and decoded by the host reader's code (%.1f ms)\n", recs.size(), (now_s() - t0) * 1e3);
+        // the first error in record order wins; an I/O error of the walk comes after every indexed record (BamReader::next_batch)
+        if (!fine) { err = derr; err_code = dcode; return -1; }
+        if (io_error) { err = werr; err_code = BQC_ERR_IO; return -1; }
+        return recs.empty() ? 0 : 1;
+    };
     if (!I.main_set) {
         I.n_main = (uint32_t)main_.size();
         if (!I.d_main.need(main_.size() + 1)) return fail_dev("out of device memory");
         if (!main_.empty() && hipMemcpy(I.d_main.p, main_.data(), main_.size(), hipMemcpyHostToDevice) != hipSuccess) return fail_dev("copy failed");
         I.main_set = true;
     }
-    const double t0 = now_s();
     double t_adv = 0, t_walk = 0, t_dec = 0;
     if (I.range_done) return 0;
     auto end_of_range = [&](uint64_t next_record_abs) { // the shard is over: where the successor's first record starts, relative to the end block
@@ -1143,6 +1278,12 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         uint64_t pos = 0, n = 0, bases = 0, so = 0, qo = 0, co = 0;
         uint32_t last_taken = 0;
         bool over = false; // the chain has reached the shard's end
+        bool trouble = false; // (a stream) the chain has reached a record the card cannot vouch for: the segments in front of it are this batch
+        // tests: BQC_TEST_STREAM_TROUBLE=k — every k-th call on a stream distrusts its window's first record, so that clean streams go through
+        // host_walk: records accepted up to one that is not all there (the card continues), and windows without one whole record (widened, advanced)
+        static const uint64_t test_trouble = getenv("BQC_TEST_STREAM_TROUBLE") ? (uint64_t)std::max(1, atoi(getenv("BQC_TEST_STREAM_TROUBLE"))) : 0;
+        const bool forced = I.seq && test_trouble && I.n_calls % test_trouble == 0;
+        if (forced) trouble = true;
         if (I.need_locate) { // a shard in the middle of the file: its first record is the first guess of the walk (verified by the predecessor shard afterwards)
             uint32_t s0 = 0;
             while (s0 < nseg && (I.h_seg.p[s0].flags & GB_NO_START)) ++s0;
@@ -1165,7 +1306,7 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
             I.need_locate = false;
             if (pos) { I.cur += pos; continue; } // (the window now starts at the record: walked again from there, as every other batch)
         }
-        for (uint32_t s = 0; s < nseg; ++s) {
+        for (uint32_t s = 0; s < nseg && !forced; ++s) {
             GbBase& B = I.h_base.p[s];
             B = GbBase{so, qo, co, (uint32_t)n, 0};
             const uint64_t seg_end = std::min<uint64_t>(avail, (uint64_t)(s + 1) * GB_SEG);
@@ -1177,9 +1318,9 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
                 if (walk_by_lanes) hipLaunchKernelGGL(k_gb_walk, dim3(1), dim3(64), 0, I.s, base, avail, s, 1u, pos, limit, I.n_ref, I.d_seg.p, I.d_rec.p);
                 else hipLaunchKernelGGL(k_gb_walk_wave, dim3(1), dim3(64), 0, I.s, base, avail, s, 1u, pos, limit, I.n_ref, I.d_seg.p, I.d_rec.p);
                 if (hipMemcpyAsync(&S, I.d_seg.p + s, sizeof(GbSeg), hipMemcpyDeviceToHost, I.s) != hipSuccess || !I.sync()) return fail_dev("walk failed");
-                if (S.first != pos) return unsupported("the record walk could not be verified");
+                if (S.first != pos) { if (I.seq) { trouble = true; break; } return unsupported("the record walk could not be verified"); }
             }
-            if (S.flags & GB_CORRUPT) return unsupported("a record the host reader will report");
+            if (S.flags & GB_CORRUPT) { if (I.seq) { trouble = true; break; } return unsupported("a record the host reader will report"); }
             if (n && (n + S.count > max_reads || bases >= max_bases)) break;
             B.take = 1;
             last_taken = s + 1;
@@ -1189,6 +1330,11 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         }
         if (pos >= limit) over = true;
         if (n == 0 && over) { I.cur += pos; end_of_range(I.abs_of(I.cur)); return 0; }
+        if (n == 0 && I.seq && (trouble || (I.stream_done && avail == I.end - I.cur))) { // a stream: decided here, by the host reader's walk
+            const int hw = host_walk(base, avail);
+            if (hw != 2) { I.grow_window = 0; return hw; }
+            if (avail == I.end - I.cur) trouble = false; // (the window is all there is for now: the next run's bytes behind it, below)
+        }
         if (n == 0 && avail < I.end - I.cur) { I.grow_window += 2 * avail + (64u << 20); continue; } // (a record longer than the walked part of the window)
         I.grow_window = 0;
         if (n == 0) { // not one complete record in the window: the next run's bytes behind it
@@ -1224,7 +1370,7 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
             // walk, bam_decode_records (host/bam_io.cpp) fills the batch's host columns and decides what is an error — and the run goes
             // on from the card with the next batch.
             if (hipMemsetAsync(I.d_status, 0, 4, I.s) != hipSuccess) return fail_dev("memset failed");
-            try { I.handover_raw.resize((size_t)pos); } catch (const std::bad_alloc&) { return unsupported("no host memory for a batch handed over"); }
+            try { I.handover_raw.resize((size_t)pos); } catch (const std::bad_alloc&) { return unsupported("no host memory for a batch handed over"); } // (a stream: an I/O error)
             if (hipMemcpy(I.handover_raw.data(), base, (size_t)pos, hipMemcpyDeviceToHost) != hipSuccess) return fail_dev("copy failed");
             std::vector<BamRec>& recs = I.handover_recs;
             recs.clear();
@@ -1236,7 +1382,12 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
                 hso += (h.l_seq + 1u) / 2u; hqo += h.l_seq; hco += h.n_cig;
                 q += 4ull + h.bs;
             }
-            if (recs.size() != N || hso != so || hqo != qo || hco != co) return unsupported("the record walk could not be verified");
+            if (recs.size() != N || hso != so || hqo != qo || hco != co) {
+                if (!I.seq) return unsupported("the record walk could not be verified");
+                const int hw = host_walk(base, avail); // (a stream: the host reader's walk decides, from the batch's first record)
+                if (hw != 2) return hw;
+                continue;
+            }
             o.d_seq = o.d_qual = nullptr; o.d_cigar = nullptr; // (a host batch; its device buffer stays for the next one)
             const bool fine = bam_decode_records(I.handover_raw.data(), recs, hdr_, main_, bqc_host_threads(), o, err, err_code);
             ++n_handed_over_;

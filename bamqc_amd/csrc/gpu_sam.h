@@ -18,6 +18,8 @@ public:
     // The reader owns the descriptor from its first byte (closed with the reader unless it is 0).  Reads, in the calling thread, until
     // the header is complete and `hold_bytes` bytes or the end of the stream have been seen, and parses the header (no device needed).
     bool start(int fd, size_t hold_bytes, std::string& err);
+    // (before start()) the descriptor's first bytes, read by a caller that had to look at them: "-" may carry BGZF, which is BAM
+    void preload(const void* p, size_t n) { pre_.assign((const char*)p, (const char*)p + n); }
     // after start(): the whole stream is in memory.  A caller may then leave open() out: next_batch parses on the host.
     bool stream_ended() const { return pre_eof_; }
     // the device side: buffers for batches of batch_reads / batch_bases, the reader thread over the rest of the stream

@@ -96,6 +96,18 @@ bool BamReader::open(const char* path, std::string& err, bool header_first)
 {
     if (!bg_.open(path, err)) return false;
     if (header_first) bg_.first_run_bytes(1u << 20);
+    return read_header(err);
+}
+
+bool BamReader::open_stream(std::shared_ptr<BgzfStream> src, std::string& err)
+{
+    if (!bg_.open_stream(std::move(src))) { err = "no input stream"; return false; }
+    bg_.first_run_bytes(1u << 20);
+    return read_header(err);
+}
+
+bool BamReader::read_header(std::string& err)
+{
     std::string e;
     if (!fill(12, e) || memcmp(buf_.data(), "BAM\1", 4) != 0) { err = e.empty() ? "not a BAM file" : e; return false; }
     const uint32_t l_text = rd32(buf_.data() + 4);
@@ -332,19 +344,13 @@ int BamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, std:
             if (bs0 < 32 || !fill(rel + 4 + (size_t)bs0, e)) { err = e.empty() ? "truncated BAM record" : e; io_error = true; break; }
         }
         // (all of the record is there now, or its block_size is below 32)
-        const BrBytes src{buf_.data() + cur_};
-        BrHead h;
-        const BrCheck c = br_step(src, buf_.size() - cur_, rel, h);
-        if (c != BR_OK) { err = c == BR_CORRUPT ? "corrupt BAM record" : "truncated BAM record"; io_error = true; break; }
-        const int32_t rid = (int32_t)src.u32(rel + 4);
         bool keep = true;
-        if (filter_) keep = rid < 0 ? keep_unplaced_ : ((size_t)rid < keep_.size() && keep_[rid]);
-        if (keep) {
-            recs.push_back(BamRec{rel, h.bs, h.l_seq, h.n_cig, so, qo, co, nrec_});
-            so += (h.l_seq + 1) / 2; qo += h.l_seq; co += h.n_cig;
-            bases += h.l_seq;
+        if (filter_ && buf_.size() - cur_ >= rel + 8) {
+            const int32_t rid = (int32_t)BrBytes{buf_.data() + cur_}.u32(rel + 4);
+            keep = rid < 0 ? keep_unplaced_ : ((size_t)rid < keep_.size() && keep_[rid]);
         }
-        rel += 4 + (size_t)h.bs;
+        const int c = bam_walk_one(buf_.data() + cur_, buf_.size() - cur_, rel, nrec_, keep, recs, so, qo, co, bases);
+        if (c != BR_OK) { err = bam_walk_message(c); io_error = true; break; }
         ++nrec_;
     }
     if (nrec_ > nrec_at_start) {
@@ -368,6 +374,22 @@ int BamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, std:
     if (io_error) { err_code = BQC_ERR_IO; return -1; }
     return n ? 1 : 0;
 }
+
+int bam_walk_one(const uint8_t* base, size_t avail, size_t& rel, uint64_t nrec, bool keep, std::vector<BamRec>& recs, size_t& so, size_t& qo, size_t& co, size_t& bases)
+{
+    BrHead h;
+    const BrCheck c = br_step(BrBytes{base}, avail, rel, h);
+    if (c != BR_OK) return c;
+    if (keep) {
+        recs.push_back(BamRec{rel, h.bs, h.l_seq, h.n_cig, so, qo, co, nrec});
+        so += (h.l_seq + 1) / 2; qo += h.l_seq; co += h.n_cig;
+        bases += h.l_seq;
+    }
+    rel += 4 + (size_t)h.bs;
+    return BR_OK;
+}
+// what the user is told of a record the walk stops at: stated here, for every reader
+const char* bam_walk_message(int c) { return c == BR_CORRUPT ? "corrupt BAM record" : "truncated BAM record"; }
 
 // The records `recs` of the byte range at `base` into the batch's columns, by all host threads: tag scan (RG -> lane through the
 // header's table, every integer NM, first AS) and copies of the payload to where the walk has placed it.  Unknown RG ids

@@ -75,12 +75,22 @@ struct BamRec { size_t off; uint32_t bs, l_seq, n_cig; size_t so, qo, co; uint64
 // a batch it hands over: csrc/gpu_bam.hip): see bam_io.cpp.
 bool bam_decode_records(const uint8_t* base, const std::vector<BamRec>& recs, BamHeader& hdr, const std::vector<uint8_t>& main_chrom, unsigned threads, HostBatch& o,
                         std::string& err, int& err_code);
+// One step of the serial walk over the block_size chain (BamReader::next_batch, and the reader on the card where it cannot vouch for a
+// stream's records: csrc/gpu_bam.hip): the record at base[rel] of `avail` bytes.  0 (BR_OK, host/bam_record.h): it is appended to `recs`
+// when `keep` (placed behind the payload of those before it: so / qo / co; bases counts its l_seq) and rel moves behind it; anything
+// else: nothing has changed, and bam_walk_message says what the user is told.
+int bam_walk_one(const uint8_t* base, size_t avail, size_t& rel, uint64_t nrec, bool keep, std::vector<BamRec>& recs, size_t& so, size_t& qo, size_t& co, size_t& bases);
+const char* bam_walk_message(int br_check);
 
 class BamReader : public RecordReader {
 public:
     // header_first: the first run of BGZF blocks is a small one (the caller may only want the header: the program when the records
     // are to be decoded on the GPU)
     bool open(const char* path, std::string& err, bool header_first = false);
+    // A stream (host/bgzf.h: BgzfStream) instead of a file: {the bytes the stream object holds, then its descriptor}.  The header is
+    // read through a small first run, as with header_first; what the stream object keeps meanwhile is its owner's business (the program
+    // keeps everything until it knows whether the card takes the stream: DESIGN section 4.5c).
+    bool open_stream(std::shared_ptr<BgzfStream> src, std::string& err);
     // One shard of the record stream (multi-GPU): the header is read from the file's start as always; records are then taken
     // from the first record that STARTS in a BGZF block at or behind bgzf_find_block(begin_hint) — located by the same test
     // the parallel record walk uses for its guesses — up to the last record that starts before the block at
@@ -108,6 +118,7 @@ public:
 
 private:
     bool fill(size_t need, std::string& err); // ensure `need` bytes are available at cur_
+    bool read_header(std::string& err);
     BgzfReader bg_;
     BamHeader hdr_;
     raw_vector<uint8_t> buf_, chunk_;

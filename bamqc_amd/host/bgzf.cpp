@@ -5,10 +5,12 @@
 #include "parallel.h"
 #include "../csrc/gpu_inflate.h"
 
+#include <unistd.h>
 #include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cstring>
 #include <thread>
@@ -37,6 +39,73 @@ static std::atomic<int> g_gpu_device{-1};
 static std::atomic<uint64_t> g_gpu_blocks{0};
 void bgzf_gpu_inflate_device(int device) { g_gpu_device = device; }
 uint64_t bgzf_gpu_inflated_blocks() { return g_gpu_blocks.load(); }
+
+BgzfStream::~BgzfStream() { if (fd > 0) close(fd); }
+
+size_t BgzfStream::raw_read(uint8_t* dst, size_t want)
+{
+    if (f) return fread(dst, 1, want, f);
+    ssize_t r;
+    do r = ::read(fd, dst, want); while (r < 0 && errno == EINTR);
+    return r > 0 ? (size_t)r : 0;
+}
+
+void BgzfStream::preload(const uint8_t* p, size_t n)
+{
+    std::lock_guard<std::mutex> lk(m);
+    held.insert(held.end(), p, p + n);
+    total += n;
+}
+
+size_t BgzfStream::read_at(uint64_t pos, uint8_t* dst, size_t want)
+{
+    std::lock_guard<std::mutex> lk(m);
+    size_t got = 0;
+    while (got < want) {
+        const uint64_t at = pos + got;
+        if (at < held.size()) {
+            const size_t n = (size_t)std::min<uint64_t>(want - got, held.size() - at);
+            memcpy(dst + got, held.data() + at, n);
+            got += n;
+            continue;
+        }
+        if (!keep && held.capacity()) raw_vector<uint8_t>().swap(held); // (its reader has passed it)
+        if (ended || at != total) break; // (at != total: not the next byte of the stream — nobody asks for that)
+        const size_t r = raw_read(dst + got, want - got);
+        if (r == 0) { ended = true; break; }
+        if (keep) { const size_t h = held.size(); held.resize(h + r); memcpy(held.data() + h, dst + got, r); }
+        total += r;
+        got += r;
+    }
+    return got;
+}
+
+void BgzfStream::hold(size_t upto)
+{
+    std::lock_guard<std::mutex> lk(m);
+    if (!keep) return;
+    if (held.capacity() < upto) held.reserve(upto + (1u << 20)); // (address space: once, not by doubling)
+    while (!ended && total < upto) {
+        const size_t h = held.size(), want = std::min<size_t>(1u << 20, upto - (size_t)total);
+        held.resize(h + want);
+        const size_t r = raw_read(held.data() + h, want);
+        held.resize(h + r);
+        total += r;
+        if (r == 0) ended = true;
+    }
+}
+
+bool BgzfStream::has_ended()
+{
+    std::lock_guard<std::mutex> lk(m);
+    return ended;
+}
+
+void BgzfStream::release()
+{
+    std::lock_guard<std::mutex> lk(m);
+    keep = false;
+}
 
 BgzfReader::~BgzfReader() { stop(); }
 
@@ -156,6 +225,14 @@ bool BgzfReader::open(const char* path, std::string& err, unsigned threads)
     return true;
 }
 
+bool BgzfReader::open_stream(std::shared_ptr<BgzfStream> src, unsigned threads)
+{
+    src_ = std::move(src);
+    src_pos_ = 0;
+    threads_ = threads ? threads : default_threads();
+    return src_ != nullptr;
+}
+
 bool BgzfReader::open_at(const char* path, uint64_t begin, uint64_t mark, std::string& err, unsigned threads)
 {
     if (!open(path, err, threads)) return false;
@@ -239,7 +316,8 @@ bool BgzfReader::plan_run(raw_vector<uint8_t>& raw, Run& run, std::string& err, 
     }
     if (have) memcpy(raw.data(), tail_.data(), have);
     const auto tt0 = std::chrono::steady_clock::now();
-    size_t got = fread(raw.data() + have, 1, want, f_);
+    size_t got = src_ ? src_->read_at(src_pos_, raw.data() + have, want) : fread(raw.data() + have, 1, want, f_);
+    src_pos_ += got;
     run.read_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tt0).count();
     run.read_bytes = got;
     cbytes_ += got;

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -15,9 +16,38 @@
 
 #include "raw_vector.h"
 
+// A descriptor that is read ONCE, in order (a pipe, a FIFO, stdin), and what has been read of it so far.  While `keep` is set every
+// byte that leaves the descriptor is also kept in `held`, so that whoever decides later how the stream is to be read (the program:
+// on the card or on the host) still has it from its first byte; a reader asks for the bytes at a position of the
+// stream — from `held` where they are there, from the descriptor behind them.  Nothing seeks.
+struct BgzfStream {
+    int fd = -1;                // the descriptor (closed with the object unless it is stdin's, or release_fd() has given it away)
+    FILE* f = nullptr;          // ... or a stdio stream that wraps it (stdin after a look at its first bytes): never closed here
+    raw_vector<uint8_t> held;   // the stream's bytes [0, held.size()), while keep
+    uint64_t total = 0;         // bytes that have left the descriptor
+    bool ended = false;         // the descriptor has reported its end (or an error: the stream is then cut short, which its readers report)
+    bool keep = true;
+    std::mutex m;               // one reader at a time
+    explicit BgzfStream(int fd_) : fd(fd_) {}
+    explicit BgzfStream(FILE* f_) : f(f_) {}
+    BgzfStream(const BgzfStream&) = delete;
+    BgzfStream& operator=(const BgzfStream&) = delete;
+    ~BgzfStream();
+    void preload(const uint8_t* p, size_t n); // bytes somebody has read from the descriptor before this object existed (its first ones)
+    size_t read_at(uint64_t pos, uint8_t* dst, size_t want); // up to `want` bytes from stream position `pos`; fewer: the stream ends there
+    void hold(size_t upto);     // reads on (into `held`) until the stream has given `upto` bytes or has ended
+    void release();             // nothing is kept from here on; what is held goes when its reader has passed it
+    bool has_ended();           // `ended`, for a caller beside whom a reader may still be inside read_at
+    int release_fd() { const int d = fd; fd = -1; return d; } // the descriptor changes hands (with `held`: the reader on the card)
+private:
+    size_t raw_read(uint8_t* dst, size_t want);
+};
+
 class BgzfReader {
 public:
     ~BgzfReader();
+    // a stream instead of a file: {what the stream object holds, then its descriptor}, from the stream's first byte
+    bool open_stream(std::shared_ptr<BgzfStream> src, unsigned threads = 0);
     void stop(); // ends the read-ahead and closes the file (what the destructor does); the reader yields nothing more
     bool open(const char* path, std::string& err, unsigned threads = 0);
     // Start at `begin` (the file offset of a BGZF block, see bgzf_find_block) instead of the file's start.  `mark` (a later block
@@ -59,6 +89,8 @@ private:
     std::vector<raw_vector<uint8_t>> spare_; // buffers handed back by next_chunk
     bool ra_started_ = false, ra_done_ = false, stop_ = false;
     FILE* f_ = nullptr;
+    std::shared_ptr<BgzfStream> src_; // (instead of f_)
+    uint64_t src_pos_ = 0;
     unsigned threads_ = 1;
     uint64_t cbytes_ = 0;
     bool eof_ = false;

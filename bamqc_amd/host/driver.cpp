@@ -291,16 +291,86 @@ struct bqc_bam {
     }
 };
 
-static bool is_sam_path(const char* path) // SAM text: stdin or a file
+static bool is_sam_path(const char* path) // SAM text: stdin (unless it carries BGZF: see below) or a file
 {
     const size_t n = strlen(path);
     return strcmp(path, "-") == 0 || (n > 4 && strcmp(path + n - 4, ".sam") == 0);
+}
+
+// ---- BAM as a STREAM -----------------------------------------------------------------------------------------
+// An input that is not a regular file (a FIFO, /dev/stdin, /dev/fd/N, a process substitution) can be read once, in order: a stream.
+// "-" is a stream of SAM text unless its first two bytes are 1f 8b, a gzip member's — BGZF, hence BAM: no SAM text starts with 0x1f.
+// A BAM stream of at least this many compressed bytes goes to the card (BQC_GPU_DECODE unset); a shorter one has ended while the
+// calling thread held it, and the host reader takes it from memory.  Measured (profiles/bam_stream_ab.json): whole-program
+// time, the parent's host reader against the card, at 16 / 64 / 256 MB — the card is slower at 16, ties at 64 (0.231 against 0.226 s) and is not
+// slower from 256 MB on (0.21 against 0.27 s): the threshold of files.
+static const size_t kBamStreamCardFrom = 256u << 20;
+// (a path that ends in ".sam" is SAM text whatever it is — a FIFO too, read once by the readers of SAM text as ever — and never a BAM stream)
+static bool is_stream_path(const char* path)
+{
+    struct stat st;
+    return !is_sam_path(path) && stat(path, &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode);
+}
+static bool is_bgzf_magic(const uint8_t* p, size_t n) { return n >= 2 && p[0] == 0x1f && p[1] == 0x8b; }
+// the first bytes of a descriptor nobody has read from yet: at least two, unless it ends before (into `first`)
+static void sniff_fd(int fd, std::vector<uint8_t>& first)
+{
+    first.resize(1u << 16);
+    size_t n = 0;
+    while (n < 2) {
+        const ssize_t r = read(fd, first.data() + n, first.size() - n);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) break;
+        n += (size_t)r;
+    }
+    first.resize(n);
+}
+// The same look at a stdio stream.  true: BGZF — the two bytes have been taken and are in `taken` (for BgzfStream::preload).  false: text,
+// and the stream is as it was: one byte goes back with the one ungetc ISO C guarantees; only text that starts with 0x1f but is no gzip
+// member — no SAM, a line the parser refuses either way — needs a second one, which glibc grants for bytes just read from the buffer.
+static bool sniff_stdio_bgzf(FILE* f, std::vector<uint8_t>& taken)
+{
+    const int c0 = getc(f);
+    if (c0 == EOF) return false;
+    if (c0 != 0x1f) { ungetc(c0, f); return false; }
+    const int c1 = getc(f);
+    if (c1 == 0x8b) { taken = {0x1f, 0x8b}; return true; }
+    if (c1 != EOF) ungetc(c1, f);
+    ungetc(c0, f);
+    return false;
+}
+// (tests) BQC_STREAM_HOLD=N: the stream object holds N bytes before its first reader exists — the header is then parsed, and the stream
+// read, over {a prefix cut at N, then the descriptor}, wherever N lies: inside the header, inside a block, behind the stream's end
+static void stream_test_hold(BgzfStream& src) { if (const char* e = getenv("BQC_STREAM_HOLD")) src.hold((size_t)strtoull(e, nullptr, 10)); }
+// Whether the card takes a BAM stream whose header `rd` has just read through `src` (which has kept every byte so far): the calling
+// thread holds the stream until kBamStreamCardFrom bytes or its end — BQC_GPU_DECODE=1: the card, with nothing held beyond the header;
+// =0: never; no @RG line: never (the host reader decides what that means).  false: the host reader goes on, over {what is held, then
+// the descriptor}, and nothing more is kept.
+static bool bam_stream_to_card(BamReader& rd, BgzfStream& src, bool allowed)
+{
+    const char* gd = getenv("BQC_GPU_DECODE");
+    bool card = allowed && !(gd && atoi(gd) == 0) && rd.header().lane_count != 0;
+    if (card && !gd) { src.hold(kBamStreamCardFrom); card = !src.has_ended(); }
+    if (!card) src.release();
+    return card;
 }
 extern "C" int bqc_bam_open(const char* path, bqc_bam** out)
 {
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
-    if (is_sam_path(path)) {
+    std::vector<uint8_t> taken;
+    if (strcmp(path, "-") == 0 ? sniff_stdio_bgzf(stdin, taken) : is_stream_path(path)) { // a BAM stream: the host reader over the descriptor
+        std::shared_ptr<BgzfStream> src;
+        if (strcmp(path, "-") == 0) { src = std::make_shared<BgzfStream>(stdin); src->preload(taken.data(), taken.size()); }
+        else {
+            const int fd = open(path, O_RDONLY);
+            if (fd < 0) { b->err = std::string("could not open ") + path; *out = b; return BQC_ERR_IO; }
+            src = std::make_shared<BgzfStream>(fd);
+        }
+        stream_test_hold(*src);
+        src->release(); // (nothing more is kept: nobody else will want it)
+        if (!b->bam.open_stream(src, b->err)) { *out = b; return BQC_ERR_IO; }
+    } else if (is_sam_path(path)) {
         b->is_sam = true;
         b->sam_file = strcmp(path, "-") == 0 ? stdin : fopen(path, "r");
         if (!b->sam_file) { b->err = std::string("could not open ") + path; *out = b; return BQC_ERR_IO; }
@@ -315,10 +385,31 @@ extern "C" int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out)
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
     *out = b;
+    const bool dash = strcmp(path, "-") == 0;
+    std::vector<uint8_t> first; // "-": its first bytes say what it carries
+    if (dash) sniff_fd(0, first);
+    if (dash ? is_bgzf_magic(first.data(), first.size()) : is_stream_path(path)) { // a BAM stream
+        const int fd = dash ? 0 : open(path, O_RDONLY);
+        if (fd < 0) { b->err = std::string("could not open ") + path; return BQC_ERR_IO; }
+        auto src = std::make_shared<BgzfStream>(fd);
+        src->preload(first.data(), first.size());
+        stream_test_hold(*src);
+        if (!b->bam.open_stream(src, b->err)) return BQC_ERR_IO; // the header, on the host, from the bytes the stream object keeps
+        if (!bam_stream_to_card(b->bam, *src, true)) { b->refresh_lanes(); return 0; } // (the host reader goes on)
+        b->gpu.reset(new GpuBamReader());
+        const uint64_t first_record = b->bam.stream_pos();
+        b->bam.close();
+        b->gpu->set_stream(src->release_fd(), std::move(src->held), src->has_ended()); // (the host reader is closed: nobody is inside the stream object)
+        if (!b->gpu->open(path, device, b->bam.header(), first_record, 1u << 20, 256u << 20, b->err)) { b->gpu.reset(); return BQC_ERR_DEVICE; }
+        b->gpu->allow_kernels();
+        b->refresh_lanes();
+        return 0;
+    }
     if (is_sam_path(path)) { // SAM text: the reader takes the descriptor from its first byte
-        const int fd = strcmp(path, "-") == 0 ? 0 : open(path, O_RDONLY);
+        const int fd = dash ? 0 : open(path, O_RDONLY);
         if (fd < 0) { b->err = std::string("could not open ") + path; return BQC_ERR_IO; }
         b->gsam.reset(new GpuSamReader());
+        if (dash) b->gsam->preload(first.data(), first.size());
         if (!b->gsam->start(fd, 0, b->err)) { b->gsam.reset(); return BQC_ERR_IO; }
         if (!b->gsam->open(device, 1u << 20, 256u << 20, b->err)) { b->gsam.reset(); return BQC_ERR_DEVICE; }
         b->gsam->allow_kernels();
@@ -373,6 +464,7 @@ extern "C" uint64_t bqc_bam_range_begin_block(const bqc_bam* b) { return b->gpu 
 extern "C" uint64_t bqc_bam_range_end_block(const bqc_bam* b) { return b->gpu ? b->g_b1 : b->bam.range_end_block(); }
 extern "C" uint64_t bqc_bam_range_first(const bqc_bam* b) { return b->gpu ? b->gpu->range_first() : b->bam.range_first(); }
 extern "C" uint64_t bqc_bam_range_over(const bqc_bam* b) { return b->gpu ? b->gpu->range_over() : b->bam.range_over(); }
+extern "C" int bqc_bam_on_card(const bqc_bam* b) { return b && (b->gpu || (b->gsam && b->gsam->on_card())) ? 1 : 0; }
 extern "C" uint64_t bqc_bam_batches_handed_over(const bqc_bam* b) { return b && b->gpu ? b->gpu->batches_handed_over() : b && b->gsam ? b->gsam->batches_handed_over() : 0; }
 extern "C" uint64_t bqc_file_size(const char* path) { return path ? bgzf_file_size(path) : 0; }
 extern "C" void bqc_gpu_inflate_device(int device) { bgzf_gpu_inflate_device(device); }
@@ -695,6 +787,7 @@ bool input_extension_ok(const std::string& path, std::string& err)
 {
     size_t dot = path.rfind('.');
     std::string ext = dot == std::string::npos ? "" : path.substr(dot + 1);
+    if (ext != "bam" && ext != "sam" && is_stream_path(path.c_str())) return true; // (a pipe has no name to speak of: /dev/stdin, /dev/fd/N, a process substitution)
     if (ext != "bam" && ext != "sam") { err = "bamqualcheck: the given path '" + path + "' does not have one of the valid file extensions [*.-, *.bam, *.sam]"; return false; }
     return true;
 }
@@ -988,17 +1081,39 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     // first byte.  BQC_GPU_DECODE unset: a stream that ends within its first kSamCardFrom bytes (read here, while the runtime starts) is
     // parsed on the host from memory, and no device reader is set up.
     const char* const gd_stdin = getenv("BQC_GPU_DECODE");
-    const bool use_gsam = from_stdin && !(gd_stdin && atoi(gd_stdin) == 0);
     // a failure before the hook is reached must still reach it: the other processes wait for this one
     auto shard_abort = [&]() { if (shard) { bqc_shard_info si{}; si.status = 1; bqc_shard_result sr{}; (void)shard->hook(shard->user, &si, &sr); } return 1; };
     if (shard && from_stdin) { fprintf(stderr, "ERROR: a stream on stdin cannot be split between processes\n"); return shard_abort(); }
+    // A BAM stream: an input that is not a regular file, or "-" whose first two bytes are a gzip member's (looked
+    // at inside the bytes the readers take anyway: the reader of SAM text gets them back).  Its header is parsed by the host reader from
+    // bytes that are kept; the card takes the stream, prefix first, or the host reader goes on from where it is.  Nothing is read twice.
+    std::shared_ptr<BgzfStream> bam_stream;
+    std::vector<uint8_t> stdin_first;
+    if (from_stdin && gd_stdin && atoi(gd_stdin) == 0) { // (the host's SAM parser reads stdin through stdio)
+        if (sniff_stdio_bgzf(stdin, stdin_first)) { bam_stream = std::make_shared<BgzfStream>(stdin); bam_stream->preload(stdin_first.data(), stdin_first.size()); }
+    }
+    else if (from_stdin) {
+        sniff_fd(0, stdin_first);
+        if (is_bgzf_magic(stdin_first.data(), stdin_first.size())) { bam_stream = std::make_shared<BgzfStream>(0); bam_stream->preload(stdin_first.data(), stdin_first.size()); }
+    } else if (!shard && is_stream_path(opt.bamFile.c_str())) {
+        const int fd = open(opt.bamFile.c_str(), O_RDONLY);
+        if (fd >= 0) bam_stream = std::make_shared<BgzfStream>(fd);
+    }
+    if (bam_stream) stream_test_hold(*bam_stream);
+    const bool sam_stdin = from_stdin && !bam_stream;
+    const bool use_gsam = sam_stdin && !(gd_stdin && atoi(gd_stdin) == 0);
+    bool stream_card = false; // the card takes the BAM stream
     bool opened;
     // a shard of the file: its block boundaries are found here (BamReader::open_range finds the same ones: bgzf_find_block is a
     // function of the hint), so that either reader can take the range
     uint64_t shard_b0 = 0, shard_b1 = UINT64_MAX;
     bool shard_gpu = false;
-    if (use_gsam) opened = gsam_rd.start(0, gd_stdin ? 0 : kSamCardFrom, err);
-    else if (from_stdin) opened = sam_rd.open(stdin, err);
+    if (use_gsam) { gsam_rd.preload(stdin_first.data(), stdin_first.size()); opened = gsam_rd.start(0, gd_stdin ? 0 : kSamCardFrom, err); }
+    else if (sam_stdin) opened = sam_rd.open(stdin, err);
+    else if (bam_stream) {
+        opened = bam_rd.open_stream(bam_stream, err); // the header (a stream that is no BAM, or ends inside it, fails here in the host reader's words)
+        if (opened) stream_card = bam_stream_to_card(bam_rd, *bam_stream, !host_reader_only); // (the calling thread holds the stream meanwhile: the runtime starts beside it)
+    }
     else if (shard) { // this process's part of the compressed file
         const uint64_t size = bqc_file_size(opt.bamFile.c_str());
         const uint64_t lo = size / shard->count * shard->index, hi = shard->index + 1 == shard->count ? UINT64_MAX : size / shard->count * (shard->index + 1);
@@ -1030,7 +1145,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     GpuBamReader& gpu_rd = S ? S->gpu_rd : own_gpu_rd;
     if (S) gpu_rd.set_anchor_context(nullptr); // (the context of the job before may not outlive this one's set-up)
     const char* gd_env = getenv("BQC_GPU_DECODE"); // 1: whenever possible, 0: never; unset: files of 256 MB and more (its set-up costs ~50 ms)
-    bool use_gpu_reader = !from_stdin && (!shard || shard_gpu) && !host_reader_only && bam_rd.header().lane_count != 0 && !(gd_env && atoi(gd_env) == 0);
+    bool use_gpu_reader = !sam_stdin && (!shard || shard_gpu) && !host_reader_only && bam_rd.header().lane_count != 0 && !(gd_env && atoi(gd_env) == 0);
     if (shard && shard_gpu && !use_gpu_reader) { // (no @RG line: the host reader, over its range, decides what that means)
         bam_rd.~BamReader();
         new (&bam_rd) BamReader();
@@ -1039,7 +1154,8 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         if (!bam_rd.open_range(opt.bamFile.c_str(), lo, hi, err)) { fprintf(stderr, "ERROR: Could not open %s for reading.\n", opt.bamFile.c_str()); return shard_abort(); }
         shard_gpu = false;
     }
-    if (use_gpu_reader && !shard) { // a regular file: the reader opens it a second time
+    if (bam_stream) use_gpu_reader = stream_card;
+    else if (use_gpu_reader && !shard) { // a regular file: the reader opens it a second time
         struct stat st;
         use_gpu_reader = stat(opt.bamFile.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (gd_env || (uint64_t)st.st_size >= (256ull << 20));
     }
@@ -1052,7 +1168,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         bqc_raw_vector_pin_hook = pin_hook;
     }
     const bool gsam_card = use_gsam && gsam_rd.header().lane_count != 0 && (gd_stdin || !gsam_rd.stream_ended());
-    RecordReader& rd = use_gsam ? static_cast<RecordReader&>(gsam_rd) : from_stdin ? static_cast<RecordReader&>(sam_rd) : use_gpu_reader ? static_cast<RecordReader&>(gpu_rd) : static_cast<RecordReader&>(bam_rd);
+    RecordReader& rd = use_gsam ? static_cast<RecordReader&>(gsam_rd) : sam_stdin ? static_cast<RecordReader&>(sam_rd) : use_gpu_reader ? static_cast<RecordReader&>(gpu_rd) : static_cast<RecordReader&>(bam_rd);
     if (use_gpu_reader) gpu_rd.header() = bam_rd.header(); // (complete once opened, in the decode thread: the device is not up yet)
     if (!shard || shard->index == 0) {
         FILE* of = fopen(opt.outputFile.c_str(), "wb"); // opened (truncated) before the scan, :278-283
@@ -1113,11 +1229,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (H.lane_count != 0) dec = std::thread([&]() {
         if (use_gpu_reader) {
             std::string e;
+            if (bam_stream) gpu_rd.set_stream(bam_stream->release_fd(), std::move(bam_stream->held), bam_stream->has_ended()); // (by move: the prefix is the first runs' input)
             const bool ok = gpu_rd.open(opt.bamFile.c_str(), opt.device, gpu_rd.header(), first_record_u, opt.batch_reads, 256ull << 20, e);
             gpu_reader_opened = true; // (the context is created after this: see there)
             if (!ok) {
                 std::lock_guard<std::mutex> lk(Q.m);
-                Q.err = e; Q.err_code = GpuBamReader::kUnsupported; Q.done = true; Q.cv.notify_all();
+                Q.err = e; Q.err_code = bam_stream ? BQC_ERR_DEVICE : GpuBamReader::kUnsupported; Q.done = true; Q.cv.notify_all(); // (a stream cannot be started over)
                 return;
             }
             gpu_rd.set_main_chrom(main_chrom);
@@ -1468,7 +1585,8 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (timing && lazy_refs) fprintf(stderr, "[timing] %u of %u contigs loaded, when their first reads arrived: %.3f s\n", n_lazy_refs, n_refs, t_lazy_refs);
     if (timing && use_gpu_reader) fprintf(stderr, "[timing] %llu batches anchored on the card (fixed columns never on the host) of %llu batches\n", (unsigned long long)gpu_rd.batches_anchored(), (unsigned long long)gpu_rd.batches());
     if (timing && use_gpu_reader)
-        fprintf(stderr, "[timing] reader on the card: pread %.2f s summed over its reader threads, the producer waited %.2f s for them, the decode thread waited %.2f s for inflated runs\n",
+        fprintf(stderr, bam_stream ? "[timing] reader on the card: a stream, read() and waiting for it %.2f s in its one reader thread, the producer waited %.2f s for chunks, the decode thread waited %.2f s for inflated runs\n"
+                                   : "[timing] reader on the card: pread %.2f s summed over its reader threads, the producer waited %.2f s for them, the decode thread waited %.2f s for inflated runs\n",
                 gpu_rd.seconds_reading(), gpu_rd.seconds_producer_waiting_for_chunks(), gpu_rd.seconds_waiting_for_runs());
     if (timing && use_gsam) {
         fprintf(stderr, "[sam reader] %llu batches on the card, %llu handed over, %llu anchored\n", (unsigned long long)gsam_rd.batches(), (unsigned long long)gsam_rd.batches_handed_over(),
@@ -1480,6 +1598,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (timing)
         fprintf(stderr, "[timing] %llu records: decode thread busy %.2f s, submit thread (host pass + enqueue; page-locking %.2f s) %.2f s, waiting for the decoder %.2f s, loop %.2f s\n",
                 (unsigned long long)n_total, t_decode, g_pins.t_register, t_submit, t_wait, secs(t_setup, clk::now()));
+    if (Q.err_code == GpuBamReader::kUnsupported && bam_stream) { // (cannot happen: the reader decides a stream's records itself — and there is no second pass over a stream)
+        fprintf(stderr, "ERROR: internal error: the reader on the card gave up a stream (%s)\n", Q.err.c_str());
+        Q.err_code = 0; status = 1;
+    }
     if (Q.err_code == GpuBamReader::kUnsupported && status) Q.err_code = 0; // (an error of the records before it has been reported: that is the run's result)
     if (Q.err_code == GpuBamReader::kUnsupported) { // nothing has been reported yet: the same file again, through the host reader
         if (timing) fprintf(stderr, "[timing] %s\n", Q.err.c_str());

@@ -33,7 +33,8 @@ class BamFile:
     def __init__(self, path, begin_hint=None, end_hint=None, gpu=None):
         """The whole file, or (begin_hint / end_hint: compressed byte offsets) one shard of its record stream.
         gpu: a device index — the file is inflated and decoded on that GPU (batches are fetched back); SAM text (a path ending
-        in .sam, or "-") is decoded there too."""
+        in .sam, or "-") is decoded there too.  A path that is no regular file (a FIFO, /dev/stdin) and "-" that starts with a gzip
+        member's two bytes are BAM streams: read once, in order, by either reader (include/bamqc_host.h: bqc_bam_open, bqc_bam_open_gpu)."""
         self.lib = _lib.load()
         self.h = C.c_void_p()
         if gpu is not None and (begin_hint is not None or end_hint is not None):
@@ -66,6 +67,11 @@ class BamFile:
     def batches_handed_over(self):
         """GPU reader: batches that held a record the card does not decode and went through the host decoder."""
         return int(self.lib.bqc_bam_batches_handed_over(self.h))
+
+    @property
+    def on_card(self):
+        """True when a reader on the card decodes this input (False: a host reader, also where gpu= left a short stream to it)."""
+        return bool(self.lib.bqc_bam_on_card(self.h))
 
     def lanes(self):
         """[(name, index)] in output order (lexicographic by @RG ID)."""

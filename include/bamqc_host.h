@@ -57,6 +57,13 @@ int bqc_sam_write(const char* path, const bqc_batch* b, uint32_t n_refs, const c
 
 /* ---- BAM / FASTA input (replaces SeqAn BamStream / SequenceStream) --------- */
 typedef struct bqc_bam bqc_bam;
+/* What a path is, for this function and bqc_bam_open_gpu alike: a path that ends in ".sam" is SAM text, whatever kind of file it is (a
+ * FIFO too: read once, as ever); "-" (stdin) is SAM text unless its first two bytes are 1f 8b; every other path is BAM — a file when it is a
+ * regular file, otherwise a BAM STREAM, read once and in order.
+ * Here: a BAM file; SAM text; a BAM stream, read by the same host reader:
+ * a path that is not a regular file and does not end in ".sam" (a FIFO, /dev/stdin, /dev/fd/N), and "-" when its first two bytes are 1f 8b (a gzip member's: BGZF,
+ * hence BAM — no SAM text starts with 0x1f).  A stream that is no BAM, or ends inside its header, fails as a file does ("not a BAM
+ * file", "truncated BAM header", or the BGZF layer's words). */
 int bqc_bam_open(const char* path, bqc_bam** out);  /* on failure *out still holds the message */
 /* One shard of the record stream (multi-GPU): the records that START in the BGZF blocks between the first block boundary at
  * or behind the compressed offset begin_hint and the first one at or behind end_hint (0 / UINT64_MAX: the file's ends).  A
@@ -71,9 +78,18 @@ int bqc_bam_open_range(const char* path, uint64_t begin_hint, uint64_t end_hint,
  * A path that ends in ".sam", and "-" (stdin), is SAM text and is decoded on the card as well (the reader takes the descriptor from
  * its first byte).  A stream cannot be started over, so -1000 never comes back for it: a batch with a line the card has no rule for
  * (bqc_bam_batches_handed_over counts them too) is parsed by the host's line parser, whose errors and messages are the ones reported;
- * the records in front of a failing line are delivered before its error. */
+ * the records in front of a failing line are delivered before its error.
+ * A BAM STREAM (a path that is not a regular file and does not end in ".sam"; "-" with the two bytes 1f 8b in front, looked at inside the bytes the reader takes
+ * anyway) is read once, in order, and decoded on the card too: its header is parsed on the host from the stream's first bytes, which are
+ * kept and become the card reader's first input.  BQC_GPU_DECODE=1 forces the card, =0 forbids it; unset, the calling thread holds the
+ * stream's first 256 MB: a stream that ends inside them, and one without an @RG line, is read by the host reader from {those bytes, then
+ * the descriptor}, and no device reader is set up.  -1000 never comes back for a stream either: where the card cannot vouch for the records
+ * (a walk that cannot be verified, a corrupt record, a stream that ends inside a record) the records in front are delivered as a batch, and
+ * the next call runs the host reader's own walk and decoder over the bytes from there (counted by bqc_bam_batches_handed_over): its records
+ * are a batch, its error ("corrupt BAM record", "truncated BAM record", BQC_ERR_IO) is the answer, and where it only needs more bytes the card goes on. */
 int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out);
 uint64_t bqc_bam_batches_handed_over(const bqc_bam* b);
+int bqc_bam_on_card(const bqc_bam* b); /* 1: a reader on the card decodes this input; 0: a host reader (bqc_bam_open; a stream bqc_bam_open_gpu left to it) */
 /* A shard (as bqc_bam_open_range) read, inflated and decoded on GPU `device`: only the shard's bytes of the file are touched.
  * SAM text has no shards: BQC_ERR_ARG. */
 int bqc_bam_open_gpu_range(const char* path, int device, uint64_t begin_hint, uint64_t end_hint, bqc_bam** out);
