@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "../host/bam_io.h"
 
 class GpuBamReader : public RecordReader {
@@ -66,6 +68,20 @@ public:
     void end_file();
     void memory_held(size_t& device_bytes, size_t& pinned_bytes); // what the reader (and the batches' payload pool) holds now
     const char* buffers_report(); // "new": first open(); "kept": opened again and nothing had to grow since; "grown"
+    // The PRODUCER alone, for BGZF that carries something other than BAM records (SAM text: gpu_sam.hip): the file or
+    // stream (set_stream) is read, copied, inflated and CRC-checked run by run exactly as for next_batch — the same threads, ring,
+    // buffers and kernel launches — and the caller consumes the inflated bytes itself, on the card.  open_runs instead of open(): no walk,
+    // column or batch buffers; the first `skip_u` inflated bytes are dropped (a header the host has parsed); `spare` bytes in front of
+    // and behind every window may be read (not written) by the caller's kernels.
+    bool open_runs(const char* path, int device, uint64_t skip_u, size_t spare, std::string& err);
+    hipStream_t consumer_stream(); // the stream next_run queues on (the reader's; nullptr: none could be made): the caller's kernels go there too
+    // The caller is done with the first `used` bytes of the window it has (none before the first call); the next run joins what is left:
+    // 1: the window is [window, window + n) — what was left, then the run's bytes (n may be 0: an empty run) — and `last` says that no
+    // run follows; 0: no more runs (the window it had is all there is); -1: err / err_code — the BGZF layer's words for a damaged or cut
+    // stream (BQC_ERR_IO, as the host reader's), a device error, or more left over than the room in front of a run (max_left()).
+    // Window offsets fit 32 bits: n < 4 GB, checked where the runs are sized.
+    int next_run(size_t used, const uint8_t*& window, size_t& n, bool& last, std::string& err, int& err_code);
+    size_t max_left() const;
 
 private:
     struct Impl;
@@ -81,6 +97,8 @@ private:
     int stream_fd_ = -1;
     raw_vector<uint8_t> stream_prefix_;
     bool reopened_ = false;
+    bool runs_only_ = false; // open_runs
+    size_t runs_spare_ = 64;
     size_t held_before_ = 0; // bytes held when open() took the buffers over
     uint64_t range_b0_ = 0, range_b1_ = UINT64_MAX, range_first_ = 0, range_over_ = 0;
 };

@@ -459,6 +459,7 @@ struct GpuBamReader::Impl {
     size_t run_bytes = 832u << 20; // (large inflate launches are the cheapest per block: few, large runs; the first one is 64 MB)
     size_t head = 16u << 20;    // room in front of a run's output for the unfinished record before it
     size_t out_cap = 0;         // bytes of a run's output buffer (head included): set in open() before the producer starts
+    size_t spare = 64;          // bytes kept free behind a run's output (open_runs: what the caller's kernels may over-read)
     static const int kRuns = 3; // one being walked, one being inflated, one being read
     GbRun runs[kRuns];
     // producer thread: file -> runs
@@ -701,7 +702,10 @@ bool GpuBamReader::open(const char* path, int device, const BamHeader& hdr, uint
             const uint64_t upto = std::min<uint64_t>((uint64_t)st.st_size, I.mark_off == UINT64_MAX ? UINT64_MAX : I.mark_off + Impl::kBeyond + (1u << 17));
             I.run_bytes = std::min<size_t>(I.run_bytes, (size_t)(upto > I.begin_off ? upto - I.begin_off : 0) + (1u << 20));
         }
-        I.out_cap = I.head + I.run_bytes / 5 * 18 + 64;
+        I.spare = runs_only_ ? std::max<size_t>(64, runs_spare_) : 64;
+        I.out_cap = I.head + I.run_bytes / 5 * 18 + I.spare;
+        // (open_runs) the consumer's offsets into a window — what is left of a run in front of the next one's bytes — are 32-bit
+        if (runs_only_) I.kMaxRunOut = std::min<size_t>(I.kMaxRunOut, ((size_t)4 << 30) - I.head - I.spare - ((size_t)1 << 20));
     }
     I.producer = std::thread([&I] { I.produce(); }); // reads the first run of the file while the device is set up below
     // the ring's chunks: allocated and touched here, by a thread of their own, while the runtime starts; page-locked below (measured,
@@ -744,13 +748,14 @@ bool GpuBamReader::open(const char* path, int device, const BamHeader& hdr, uint
                  R.d_tok.need(bqc_gpu_inflate_token_words(out_cap, nb_cap), true) && R.d_ntok.need(nb_cap);
         }
         const double t_b = now_s();
-        ok = ok && I.d_seg.need(seg_cap) && I.h_seg.need(seg_cap) && I.d_rec.need(seg_cap * GB_MAXR, true) && I.d_base.need(seg_cap) && I.h_base.need(seg_cap);
+        // (open_runs: the consumer is somebody else — no walk, column or batch buffers)
+        ok = ok && (runs_only_ || (I.d_seg.need(seg_cap) && I.h_seg.need(seg_cap) && I.d_rec.need(seg_cap * GB_MAXR, true) && I.d_base.need(seg_cap) && I.h_base.need(seg_cap)));
         const size_t reads = std::min<size_t>(std::max<size_t>(batch_reads, 1), 1u << 22);
-        ok = ok && I.d_cols.need(((reads + 63 + GB_MAXR) & ~(size_t)63) * (7 * 4 + 3 * 8 + 2 * 2 + 2) + 256);
+        ok = ok && (runs_only_ || I.d_cols.need(((reads + 63 + GB_MAXR) & ~(size_t)63) * (7 * 4 + 3 * 8 + 2 * 2 + 2) + 256));
         if (!ok) { err = "GPU reader: out of device memory"; return false; }
         const size_t typical = std::min<size_t>(reads * 400, batch_bases / 2 * 3 + reads * 40 + (64u << 20)) + (1u << 20);
         const double t_c = now_s();
-        gb_pool_fill(typical, 10); // (a batch's buffer comes back when its kernels are through: three in the pipeline, three queued, the decoder's, spares)
+        if (!runs_only_) gb_pool_fill(typical, 10); // (a batch's buffer comes back when its kernels are through: three in the pipeline, three queued, the decoder's, spares)
         buffers_allocated = true; // (the caller creates its context from here on: side by side with these allocations the two were measured to hold each other up)
         if (I.timing) fprintf(stderr, "[gpu reader] open: run buffers %.1f, walk buffers %.1f, batch pool %.1f ms\n", (t_b - t_a) * 1e3, (t_c - t_b) * 1e3, (now_s() - t_c) * 1e3);
     }
@@ -942,7 +947,7 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
     bool stopped = false;
     // A run ends where its output buffer does (sized in open() for 3.6 x the compressed bytes: a file that inflates further gets
     // more, smaller runs — never a buffer released and allocated again behind a running kernel).
-    const size_t out_limit = std::min(kMaxRunOut, out_cap - head - 64);
+    const size_t out_limit = std::min(kMaxRunOut, out_cap - head - spare);
     static const size_t first_cap = getenv("BQC_GB_FIRST_MB") ? (size_t)std::max(64, atoi(getenv("BQC_GB_FIRST_MB"))) << 20 : (size_t)320 << 20; // (10 M-read file, 896 MB: 0.29 s with 640, 0.26 with 320, 0.27 with 192, 0.28 with 128 — tools/first_run_mb.py)
     // the device is up and the run's buffers are there (no-ops for the two buffers open() has allocated; the third one is allocated here, whole:
     // the chunks are copied in as they are read)
@@ -1039,7 +1044,7 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
         }
         rcv.notify_all();
         if (!wait_ready()) { R.rc = -2; return; }
-        if (!R.d_comp.need(p + 64) || !R.d_out.need(head + utotal + 64)) { R.rc = -2; return; }
+        if (!R.d_comp.need(p + 64) || !R.d_out.need(head + utotal + spare)) { R.rc = -2; return; }
         he = hipMemsetAsync(R.d_status, 0, 4, R.s);
         if (he == hipSuccess && p) he = hipMemcpyAsync(R.d_comp.p, first_raw.data(), p, hipMemcpyHostToDevice, R.s);
         d_off = p;
@@ -1068,7 +1073,7 @@ void GpuBamReader::Impl::fill_run(GbRun& R)
             const size_t have = kHeadroom + S->len - ring_at;
             const size_t p = parse_blocks(R, S->p + ring_at, have, d_off, nb, utotal, stop_at, out_limit, stopped);
             if (p == SIZE_MAX) { R.rc = -1; return; }
-            if (!R.d_comp.need(d_off + p + 64) || !R.d_out.need(head + utotal + 64)) { R.rc = -2; return; } // (sized at open: grows only for unusual files)
+            if (!R.d_comp.need(d_off + p + 64) || !R.d_out.need(head + utotal + spare)) { R.rc = -2; return; } // (sized at open: grows only for unusual files)
             if (p) he = hipMemcpyAsync(R.d_comp.p + d_off, S->p + ring_at, p, hipMemcpyHostToDevice, copy_s);
             if (he != hipSuccess) break;
             d_off += p; parsed_off += p; ring_at += p;
@@ -1412,4 +1417,51 @@ int GpuBamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
                     pos / 1e6, (now_s() - t0) * 1e3, t_adv * 1e3, t_walk * 1e3, walk_by_lanes ? "lane" : "wave", t_dec * 1e3, I.t_read, I.t_wait_run, (unsigned long long)I.n_rewalk, now_s());
         return 1;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the producer alone (gpu_bam.h: open_runs / next_run): the consumer is the reader of SAM text (gpu_sam.hip)
+// ---------------------------------------------------------------------------------------------------
+bool GpuBamReader::open_runs(const char* path, int device, uint64_t skip_u, size_t spare, std::string& err)
+{
+    runs_only_ = true;
+    runs_spare_ = spare;
+    return open(path, device, BamHeader(), skip_u, 1, 1, err);
+}
+
+size_t GpuBamReader::max_left() const { return p_ && p_->head > p_->spare ? p_->head - p_->spare : 0; }
+
+hipStream_t GpuBamReader::consumer_stream()
+{
+    if (!p_) return nullptr;
+    Impl& I = *p_;
+    if (!I.s_ready) { // (as next_batch: the consumer's stream, and the status word's memset on the producer's)
+        if (hipSetDevice(I.device) != hipSuccess) return nullptr;
+        if (!I.s) I.s = bqc_pool_stream(I.device, 2);
+        if (!I.s || hipStreamSynchronize(I.ps) != hipSuccess) return nullptr;
+        I.s_ready = true;
+    }
+    return I.s;
+}
+
+int GpuBamReader::next_run(size_t used, const uint8_t*& window, size_t& n, bool& last, std::string& err, int& err_code)
+{
+    err_code = 0;
+    Impl& I = *p_;
+    auto times = [&] { t_read_ = I.t_read; t_wait_run_ = I.t_wait_run; t_wait_chunk_ = I.t_wait_chunk; }; // (on every way out)
+    auto fail = [&](const std::string& what, int code) { times(); err = what; err_code = code; return -1; };
+    if (!runs_only_ || !consumer_stream()) return fail("GPU reader: no stream", BQC_ERR_DEVICE);
+    if (used > I.end - I.cur) return fail("GPU reader: more bytes used than the window holds", BQC_ERR_ARG);
+    I.cur += used;
+    // (what is left goes in front of the next run's bytes, with the caller's spare bytes still in front of it)
+    if (!I.stream_done && I.end - I.cur > max_left()) return fail("a line longer than the room in front of a run of inflated text (" + std::to_string(max_left() >> 20) + " MB)", BQC_ERR_IO);
+    const int rc = I.advance(err);
+    times();
+    if (rc == -1) { err_code = BQC_ERR_IO; return -1; }
+    if (rc < 0) return fail("GPU reader: a failed copy or out of memory", BQC_ERR_DEVICE);
+    window = I.win ? I.win + I.cur : nullptr;
+    n = I.end - I.cur;
+    last = I.stream_done;
+    if (rc == 0 && I.skip_u) return fail("truncated BGZF file", BQC_ERR_IO); // (cannot happen: the host has parsed the header these bytes are from the same stream)
+    return rc;
 }

@@ -9,7 +9,10 @@
 #include <string>
 #include <vector>
 
+#include <memory>
+
 #include "../host/bam_io.h"
+#include "gpu_bam.h"
 
 class GpuSamReader : public RecordReader {
 public:
@@ -20,6 +23,18 @@ public:
     bool start(int fd, size_t hold_bytes, std::string& err);
     // (before start()) the descriptor's first bytes, read by a caller that had to look at them: "-" may carry BGZF, which is BAM
     void preload(const void* p, size_t n) { pre_.assign((const char*)p, (const char*)p + n); }
+    // A second source (instead of start()): SAM text inside BGZF — x.sam.gz, or a stream that carries it.  The text arrives
+    // ON the card, as the output of the BGZF producer of gpu_bam.hip (GpuBamReader::open_runs / next_run: its ring, runs, inflate
+    // launches and CRC check, unchanged), and the window of next_batch is pointed at the inflated bytes: nothing is copied but the
+    // unfinished last line of a run, which goes in front of the next run's bytes.  hdr / ref_index / first_record_u: the header as the
+    // host reader parsed it (SamReader::open_bgzf*) and where the first record line starts in the text.  A stream: producer().set_stream(...)
+    // before open(); a file: `path` is opened by the producer.  BGZF damage is the stream's I/O error, in the host reader's words.
+    void start_bgzf(const BamHeader& hdr, const std::map<std::string, int32_t>& ref_index, uint64_t first_record_u, const char* path);
+    GpuBamReader& producer() { return *bg_; }
+    bool from_bgzf() const { return bg_ != nullptr; }
+    double seconds_producer_reading() const;            // the producer's reader threads in pread / read()
+    double seconds_producer_waiting_for_chunks() const; // the producer waiting for them
+    double seconds_waiting_for_runs() const;            // next_batch waiting for an inflated run
     // after start(): the whole stream is in memory.  A caller may then leave open() out: next_batch parses on the host.
     bool stream_ended() const { return pre_eof_; }
     // the device side: buffers for batches of batch_reads / batch_bases, the reader thread over the rest of the stream
@@ -42,6 +57,9 @@ public:
 
 private:
     struct Impl;
+    std::unique_ptr<GpuBamReader> bg_; // (start_bgzf) the producer of inflated text; outlives p_, whose stream is its
+    std::string bg_path_;
+    uint64_t bg_skip_ = 0;
     Impl* p_ = nullptr;
     int fd_ = -1;
     BamHeader hdr_;

@@ -9,6 +9,11 @@
 // decodes the forms listed in DESIGN section 4.5b; a line of any other form sets the batch's exception word, and THAT batch is parsed
 // by the host's line parser (host/bam_io.h: SamLineParser) from the window's bytes — it alone words the errors — and the run goes on
 // from the card with the next batch.  A stream cannot be started over, so there is no hand-over of the whole input.
+//
+// A second source: SAM text inside BGZF.  The text then arrives ON the card — the runs of the BGZF producer of gpu_bam.hip
+// (GpuBamReader::open_runs / next_run) — and the window is pointed at a run's inflated bytes instead of a buffer of its own; a run's
+// unfinished last line goes in front of the next run's bytes (the producer's copy, as for a BAM record).  Everything from k_gs_lines
+// on is the one code path of both sources.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -470,6 +475,11 @@ struct GpuSamReader::Impl {
     int wi = 0;
     size_t cur = GS_SLACK, end = GS_SLACK;
     bool all_in = false; // the stream's last byte is in the window
+    // the second source: the window is [cur, end) of bg_win, a run of inflated text in the producer's buffer (its spare bytes around it)
+    GpuBamReader* bg = nullptr;
+    const uint8_t* bg_win = nullptr;
+    bool need_run = false; // the window holds no whole line: the next run's bytes behind it
+    bool own_stream = true; // (false: the producer's consumer stream)
     uint32_t *d_status = nullptr, *h_status = nullptr;
     DevBuf<GsSeg> d_seg; PinBuf<GsSeg> h_seg;
     DevBuf<GsLine> d_line; DevBuf<GsPre> d_pre; DevBuf<GsPay> d_pay;
@@ -490,14 +500,14 @@ struct GpuSamReader::Impl {
         cv.notify_all();
         if (reader.joinable()) reader.join(); // (it looks at `stop` between two waits for input)
         (void)hipSetDevice(device);
-        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+        if (s) { (void)hipStreamSynchronize(s); if (own_stream) (void)hipStreamDestroy(s); }
         if (ev) (void)hipEventDestroy(ev);
         for (Slot& C : slots) if (C.p) (void)hipHostFree(C.p);
         if (d_status) (void)hipFree(d_status);
         if (h_status) (void)hipHostFree(h_status);
     }
     bool sync() { return hipEventRecord(ev, s) == hipSuccess && hipEventSynchronize(ev) == hipSuccess; }
-    uint8_t* win() { return d_win[wi].p; }
+    uint8_t* win() { return bg ? const_cast<uint8_t*>(bg_win) : d_win[wi].p; }
     void read_loop()
     {
         for (;;) {
@@ -588,9 +598,23 @@ GpuSamReader::~GpuSamReader()
     delete p_;
     if (fd_ > 0) close(fd_);
 }
+double GpuSamReader::seconds_producer_reading() const { return bg_ ? bg_->seconds_reading() : 0; }
+double GpuSamReader::seconds_producer_waiting_for_chunks() const { return bg_ ? bg_->seconds_producer_waiting_for_chunks() : 0; }
+double GpuSamReader::seconds_waiting_for_runs() const { return bg_ ? bg_->seconds_waiting_for_runs() : 0; }
+
+void GpuSamReader::start_bgzf(const BamHeader& hdr, const std::map<std::string, int32_t>& ref_index, uint64_t first_record_u, const char* path)
+{
+    hdr_ = hdr;
+    ref_index_ = ref_index;
+    bg_skip_ = first_record_u;
+    bg_path_ = path ? path : "";
+    bg_.reset(new GpuBamReader());
+}
+
 void GpuSamReader::allow_kernels()
 {
     if (!p_) return;
+    if (bg_) bg_->allow_kernels();
     { std::lock_guard<std::mutex> lk(p_->m); p_->kernels_ok = true; }
     p_->cv.notify_all();
 }
@@ -643,12 +667,17 @@ bool GpuSamReader::open(int device, size_t batch_reads, size_t batch_bases, std:
     const size_t reads = std::min<size_t>(std::max<size_t>(batch_reads, 1), 1u << 22);
     const size_t typical_text = std::min<size_t>(reads * 440, batch_bases * 3) + (8u << 20);
     const size_t seg_cap = typical_text / GS_SEG + 2;
-    bool ok = I.d_win[0].need(2 * GS_SLACK + typical_text + 2 * I.chunk_bytes) && I.d_seg.need(seg_cap) && I.h_seg.need(seg_cap) && I.d_line.need(seg_cap * GS_MAXR, true) &&
+    // (the second source: the producer reads its first run while the buffers below are made; no window and no ring of this reader's own)
+    if (bg_ && !bg_->open_runs(bg_path_.c_str(), device, bg_skip_, GS_SLACK, err)) return false;
+    I.bg = bg_.get();
+    if (I.bg) I.cur = I.end = 0;
+    bool ok = (I.bg || I.d_win[0].need(2 * GS_SLACK + typical_text + 2 * I.chunk_bytes)) && I.d_seg.need(seg_cap) && I.h_seg.need(seg_cap) && I.d_line.need(seg_cap * GS_MAXR, true) &&
               I.d_pre.need(seg_cap * GS_MAXR, true) && I.d_base.need(seg_cap) && I.h_base.need(seg_cap) && I.d_pay.need(reads + GS_MAXR + 64) && I.d_lut.need(256);
-    for (int k = 0; ok && k < Impl::kSlots; ++k) ok = hipHostMalloc((void**)&I.slots[k].p, I.chunk_bytes, hipHostMallocDefault) == hipSuccess;
+    for (int k = 0; ok && !I.bg && k < Impl::kSlots; ++k) ok = hipHostMalloc((void**)&I.slots[k].p, I.chunk_bytes, hipHostMallocDefault) == hipSuccess;
     if (!ok) return fail("out of memory");
     gb_pool_fill(std::min<size_t>(reads * 400, batch_bases / 2 * 3 + reads * 40 + (64u << 20)) + (1u << 20), 10);
-    I.s = bqc_pool_stream(device, 2);
+    if (I.bg) { I.s = I.bg->consumer_stream(); I.own_stream = false; } // (one stream: the producer's hand-over of a run and this reader's kernels are in order)
+    else I.s = bqc_pool_stream(device, 2);
     if (!I.s) return fail("no stream");
     if (hipEventCreateWithFlags(&I.ev, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess || hipMalloc((void**)&I.d_status, 64) != hipSuccess ||
         hipHostMalloc((void**)&I.h_status, 64, hipHostMallocDefault) != hipSuccess || hipMemset(I.d_status, 0, 64) != hipSuccess)
@@ -656,8 +685,8 @@ bool GpuSamReader::open(int device, size_t batch_reads, size_t batch_bases, std:
     uint8_t lut[256];
     for (int c = 0; c < 256; ++c) lut[c] = (uint8_t)sam_base_code((unsigned char)c); // (the host's expression: host/bam_io.h)
     if (hipMemcpy(I.d_lut.p, lut, 256, hipMemcpyHostToDevice) != hipSuccess || !I.upload_lanes(hdr_) || !I.upload_names(ref_index_)) return fail("out of device memory");
-    I.eof = pre_eof_;
-    if (!pre_eof_) I.reader = std::thread([&I] { I.read_loop(); });
+    I.eof = pre_eof_ || I.bg != nullptr;
+    if (!pre_eof_ && !I.bg) I.reader = std::thread([&I] { I.read_loop(); });
     return true;
 }
 
@@ -723,7 +752,19 @@ int GpuSamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
             want = (uint64_t)(w * 1.1) + (1u << 20) + I.grow;
             want = std::min<uint64_t>(want, 0x7FFF0000u);
         }
-        while (I.end - I.cur < want && !I.all_in) {
+        if (I.bg && (I.end == I.cur || I.need_run) && !I.all_in) { // the text arrives on the card: the next run joins what is left of the window
+            const double tw = gs_now();
+            const uint8_t* w = nullptr;
+            size_t n_ = 0;
+            bool last = false;
+            const int rc = I.bg->next_run(I.cur, w, n_, last, err, err_code);
+            t_wait_in_ += gs_now() - tw;
+            if (rc < 0) { pending_err_ = err; pending_code_ = err_code; return -1; } // the BGZF layer's words, as the host reader's (BQC_ERR_IO), or the device's — and every later call's answer: what is left in the window is no line
+            I.need_run = false;
+            if (rc > 0) { I.bg_win = w; I.cur = 0; I.end = n_; }
+            if (rc == 0 || last) I.all_in = true;
+        }
+        while (!I.bg && I.end - I.cur < want && !I.all_in) {
             const uint8_t* src;
             size_t len;
             bool from_ring = false;
@@ -752,7 +793,7 @@ int GpuSamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         }
         { std::lock_guard<std::mutex> lk(I.m); t_read_ = I.t_read; if (I.io_error) { err = "could not read the input stream"; err_code = BQC_ERR_IO; return -1; } }
         const size_t have = I.end - I.cur;
-        if (!have) return 0;
+        if (!have) { if (!I.all_in) continue; return 0; } // (an empty run: the next one)
         const uint32_t avail = (uint32_t)std::min<uint64_t>(have, want);
         const bool tail_ok = I.all_in && avail == have;
         const uint8_t* base = I.win() + I.cur;
@@ -780,6 +821,7 @@ int GpuSamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, s
         if (n == 0) {
             if (pos) { I.cur += pos; continue; } // (lines that are no records)
             if (tail_ok) return 0;               // (cannot happen: the stream's last line is complete as it is)
+            if (I.bg && avail == have) { I.need_run = true; continue; } // a line that goes on in the next run
             I.grow += 2ull * avail + (4u << 20); // a line longer than the window looked at
             if (I.grow > 0x7FFF0000u) { err = "corrupt SAM record (a line of more than 2 GB)"; err_code = BQC_ERR_IO; return -1; }
             continue;

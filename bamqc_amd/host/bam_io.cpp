@@ -462,10 +462,38 @@ bool bam_decode_records(const uint8_t* base, const std::vector<BamRec>& recs, Ba
 // ---------------------------------------------------------------------------------------------------
 // SAM text
 // ---------------------------------------------------------------------------------------------------
+// the next line of the inflated text, as getline() below gives it for the same bytes read through stdio: split at '\n', one '\r' in front
+// of it dropped, the last line as it is; false: no more lines (io_err_: the BGZF layer's error — the line it cut is not a line)
+bool SamReader::getline_bgzf(std::string& line)
+{
+    for (;;) {
+        if (at_ == chunk_.size()) {
+            std::string e;
+            at_ = 0;
+            if (!bg_->next_chunk(chunk_, e)) {
+                chunk_.clear();
+                eof_ = true;
+                if (!e.empty()) { io_err_ = e; line.clear(); return false; }
+                return !line.empty();
+            }
+            continue;
+        }
+        const char* p = (const char*)chunk_.data() + at_;
+        const size_t left = chunk_.size() - at_;
+        const char* nl = (const char*)memchr(p, '\n', left);
+        const size_t n = nl ? (size_t)(nl - p) : left;
+        line.append(p, n);
+        at_ += n + (nl ? 1 : 0);
+        text_pos_ += n + (nl ? 1 : 0);
+        if (nl) { if (!line.empty() && line.back() == '\r') line.pop_back(); return true; }
+    }
+}
+
 bool SamReader::getline(std::string& line)
 {
     line.clear();
     if (eof_) return false;
+    if (bg_) return getline_bgzf(line);
     char buf[1 << 16];
     for (;;) {
         if (!fgets(buf, sizeof buf, f_)) { eof_ = true; return !line.empty(); }
@@ -506,12 +534,36 @@ bool SamReader::open(FILE* f, std::string& err)
 {
     f_ = f;
     if (!f_) { err = "no input stream"; return false; }
+    return read_header(err);
+}
+
+bool SamReader::open_bgzf(const char* path, std::string& err)
+{
+    bg_.reset(new BgzfReader());
+    if (!bg_->open(path, err)) return false;
+    bg_->first_run_bytes(1u << 20);
+    return read_header(err);
+}
+
+bool SamReader::open_bgzf_stream(std::shared_ptr<BgzfStream> src, std::string& err)
+{
+    bg_.reset(new BgzfReader());
+    if (!bg_->open_stream(std::move(src))) { err = "no input stream"; return false; }
+    bg_->first_run_bytes(1u << 20);
+    return read_header(err);
+}
+
+bool SamReader::read_header(std::string& err)
+{
     std::string line;
-    while (getline(line)) {
+    for (;;) {
+        first_record_u_ = text_pos_; // (BGZF: where the line about to be read starts)
+        if (!getline(line)) break;
         if (line.empty()) continue;
         if (line[0] != '@') { pending_ = line; have_pending_ = true; break; }
         sam_header_line(line, hdr_, ref_index_);
     }
+    if (!io_err_.empty()) { err = io_err_; return false; }
     parse_read_groups(hdr_);
     return true;
 }
@@ -530,6 +582,7 @@ int SamReader::next_batch(HostBatch& o, size_t max_reads, size_t max_bases, std:
         if (r < 0) return -1;
         if (r) bases += o.l_seq.back();
     }
+    if (!io_err_.empty()) { err = io_err_; err_code = BQC_ERR_IO; return -1; } // (the records of this batch in front of the damage go with it, as a BAM file's)
     return o.n() ? 1 : 0;
 }
 

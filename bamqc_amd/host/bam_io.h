@@ -169,13 +169,31 @@ struct SamLineParser {
 class SamReader : public RecordReader {
 public:
     bool open(FILE* f, std::string& err); // reads the header (@ lines)
+    // The same text inside BGZF (x.sam.gz): the lines come from the inflated bytes of a BgzfReader, over a file (a FIFO
+    // too: read once, in order) or over a stream object — {what it holds, then its descriptor}, as BamReader::open_stream.  A line may
+    // straddle any number of blocks.  BGZF damage is the BGZF layer's error, in its words (BQC_ERR_IO), as for a BAM file.
+    // The first run of blocks is a small one for a file as for a stream (1 MB, and nothing is read ahead behind it until records are asked
+    // for): the header is there early — the caller may want no more, when the records go to the card — and damage behind it is an error of the
+    // read, behind the records in front of it, not of the open, for both.
+    bool open_bgzf(const char* path, std::string& err);
+    bool open_bgzf_stream(std::shared_ptr<BgzfStream> src, std::string& err);
+    uint64_t first_record_pos() const { return first_record_u_; } // where the first record line starts in the text (after open_bgzf*)
+    const std::map<std::string, int32_t>& ref_index() const { return ref_index_; } // reference name -> id, as the header gave it
+    void close() { if (bg_) bg_->stop(); raw_vector<uint8_t>().swap(chunk_); at_ = 0; eof_ = true; have_pending_ = false; } // the header stays; no more records
     BamHeader& header() override { return hdr_; }
     void set_main_chrom(const std::vector<uint8_t>& mc) override { main_ = mc; }
     int next_batch(HostBatch& out, size_t max_reads, size_t max_bases, std::string& err, int& err_code) override;
 
 private:
     bool getline(std::string& line);
+    bool getline_bgzf(std::string& line);
+    bool read_header(std::string& err);
     FILE* f_ = nullptr;
+    std::unique_ptr<BgzfReader> bg_; // (instead of f_)
+    raw_vector<uint8_t> chunk_;      // the inflated run the lines are taken from, and the first byte of it no line has taken
+    size_t at_ = 0;
+    std::string io_err_;             // the BGZF layer's error: the answer from where it was met on
+    uint64_t text_pos_ = 0, first_record_u_ = 0;
     BamHeader hdr_;
     std::map<std::string, int32_t> ref_index_;
     std::vector<uint8_t> main_;

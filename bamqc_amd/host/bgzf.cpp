@@ -107,6 +107,37 @@ void BgzfStream::release()
     keep = false;
 }
 
+BgzfCarries bgzf_stream_carries(BgzfStream& src)
+{
+    std::vector<uint8_t> m(kMaxBlock + 16), out(kMaxBlock);
+    for (uint64_t pos = 0;;) { // member by member, until one has a payload (block headers: plan_run below — what that refuses is "neither" here)
+        if (src.read_at(pos, m.data(), 18) != 18) return BGZF_NEITHER;
+        if (m[0] != 31 || m[1] != 139 || m[2] != 8 || !(m[3] & 4)) return BGZF_NEITHER;
+        const size_t xlen = m[10] | (m[11] << 8);
+        if (12 + xlen + 8 > kMaxBlock) return BGZF_NEITHER;
+        if (12 + xlen > 18 && src.read_at(pos + 18, m.data() + 18, 12 + xlen - 18) != 12 + xlen - 18) return BGZF_NEITHER;
+        size_t bsize = 0;
+        for (size_t x = 12; x + 4 <= 12 + xlen;) {
+            const size_t slen = m[x + 2] | (m[x + 3] << 8);
+            if (x + 4 + slen > 12 + xlen) return BGZF_NEITHER;
+            if (m[x] == 'B' && m[x + 1] == 'C' && slen == 2) bsize = (size_t)(m[x + 4] | (m[x + 5] << 8)) + 1;
+            x += 4 + slen;
+        }
+        if (bsize < 12 + xlen + 8) return BGZF_NEITHER;
+        const size_t have = std::max<size_t>(18, 12 + xlen);
+        if (bsize > have && src.read_at(pos + have, m.data() + have, bsize - have) != bsize - have) return BGZF_NEITHER;
+        const uint8_t* t = m.data() + bsize - 8;
+        const size_t isize = t[4] | (t[5] << 8) | (t[6] << 16) | ((size_t)t[7] << 24);
+        if (isize > kMaxBlock) return BGZF_NEITHER;
+        if (!isize) { pos += bsize; continue; }
+        Inflater inf;
+        if (!inf.run(m.data() + 12 + xlen, bsize - 12 - xlen - 8, out.data(), isize)) return BGZF_NEITHER;
+        if (out[0] == '@') return BGZF_SAM_TEXT;
+        // (a member that holds less than the magic leaves the rest to the reader of BAM streams: it looks at twelve bytes)
+        return isize < 4 || memcmp(out.data(), "BAM\1", 4) == 0 ? BGZF_BAM : BGZF_NEITHER;
+    }
+}
+
 BgzfReader::~BgzfReader() { stop(); }
 
 void BgzfReader::stop()

@@ -43,6 +43,13 @@ private:
     size_t raw_read(uint8_t* dst, size_t want);
 };
 
+// What a BGZF stream carries, by its first inflated bytes — empty members in front skipped: "BAM\1" a BAM stream,
+// a first byte of '@' SAM text; anything else, no byte at all, or a first member that is not sound: neither (the reader of BAM streams
+// then says what is wrong, in its words).  The look happens inside the bytes the stream object keeps (`keep` must still be set):
+// the readers that follow take them from there, the descriptor is read once and nothing seeks.
+enum BgzfCarries { BGZF_NEITHER = 0, BGZF_BAM = 1, BGZF_SAM_TEXT = 2 };
+BgzfCarries bgzf_stream_carries(BgzfStream& src);
+
 class BgzfReader {
 public:
     ~BgzfReader();

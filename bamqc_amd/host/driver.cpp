@@ -291,11 +291,27 @@ struct bqc_bam {
     }
 };
 
-static bool is_sam_path(const char* path) // SAM text: stdin (unless it carries BGZF: see below) or a file
+// What an input is, by its name — stated here once, for the option parser, bqc_bam_open* and run_program:
+//   IN_STDIN     "-": SAM text, unless its first two bytes are a gzip member's (is_bgzf_magic) — then a BGZF stream
+//   IN_SAM       a path that ends in ".sam", whatever it is (a FIFO too): plain SAM text
+//   IN_SAM_BGZF  a path that ends in ".sam.gz", whatever it is: SAM text inside BGZF (bgzip, samtools view -O sam,level=N); plain gzip is not read
+//   IN_STREAM    any other path that is no regular file (a FIFO, /dev/stdin, /dev/fd/N): a BGZF stream
+//   IN_BAM       any other path that ends in ".bam": a BAM file, no look at its content
+//   IN_OTHER     anything else: the program's parser refuses the name; the library opens it as a BAM file
+// A BGZF stream is BAM or SAM text by its first inflated bytes (host/bgzf.h: bgzf_stream_carries).
+enum InputKind { IN_STDIN, IN_SAM, IN_SAM_BGZF, IN_STREAM, IN_BAM, IN_OTHER };
+static InputKind input_kind(const char* path)
 {
     const size_t n = strlen(path);
-    return strcmp(path, "-") == 0 || (n > 4 && strcmp(path + n - 4, ".sam") == 0);
+    auto ends = [&](const char* sfx) { const size_t k = strlen(sfx); return n >= k && strcmp(path + n - k, sfx) == 0; };
+    if (strcmp(path, "-") == 0) return IN_STDIN;
+    if (ends(".sam.gz")) return IN_SAM_BGZF;
+    if (ends(".sam")) return IN_SAM;
+    struct stat st;
+    if (stat(path, &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode)) return IN_STREAM;
+    return ends(".bam") ? IN_BAM : IN_OTHER;
 }
+bool bqc_input_is_sam_text(const char* path) { const InputKind k = input_kind(path); return k == IN_SAM || k == IN_SAM_BGZF; } // (host_tools.h: the front end of --gpus N)
 
 // ---- BAM as a STREAM -----------------------------------------------------------------------------------------
 // An input that is not a regular file (a FIFO, /dev/stdin, /dev/fd/N, a process substitution) can be read once, in order: a stream.
@@ -305,11 +321,14 @@ static bool is_sam_path(const char* path) // SAM text: stdin (unless it carries 
 // time, the parent's host reader against the card, at 16 / 64 / 256 MB — the card is slower at 16, ties at 64 (0.231 against 0.226 s) and is not
 // slower from 256 MB on (0.21 against 0.27 s): the threshold of files.
 static const size_t kBamStreamCardFrom = 256u << 20;
-// (a path that ends in ".sam" is SAM text whatever it is — a FIFO too, read once by the readers of SAM text as ever — and never a BAM stream)
-static bool is_stream_path(const char* path)
+// (a path that ends in ".sam" is SAM text whatever it is — a FIFO too, read once by the readers of SAM text as ever — and never a BAM stream;
+// one that ends in ".sam.gz" is SAM text inside BGZF, whatever it is)
+static bool is_regular_file(const char* path, uint64_t* size = nullptr)
 {
     struct stat st;
-    return !is_sam_path(path) && stat(path, &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode);
+    if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false;
+    if (size) *size = (uint64_t)st.st_size;
+    return true;
 }
 static bool is_bgzf_magic(const uint8_t* p, size_t n) { return n >= 2 && p[0] == 0x1f && p[1] == 0x8b; }
 // the first bytes of a descriptor nobody has read from yet: at least two, unless it ends before (into `first`)
@@ -346,31 +365,48 @@ static void stream_test_hold(BgzfStream& src) { if (const char* e = getenv("BQC_
 // thread holds the stream until kBamStreamCardFrom bytes or its end — BQC_GPU_DECODE=1: the card, with nothing held beyond the header;
 // =0: never; no @RG line: never (the host reader decides what that means).  false: the host reader goes on, over {what is held, then
 // the descriptor}, and nothing more is kept.
-static bool bam_stream_to_card(BamReader& rd, BgzfStream& src, bool allowed)
+static bool stream_to_card(const BamHeader& hdr, BgzfStream& src, bool allowed, size_t card_from)
 {
     const char* gd = getenv("BQC_GPU_DECODE");
-    bool card = allowed && !(gd && atoi(gd) == 0) && rd.header().lane_count != 0;
-    if (card && !gd) { src.hold(kBamStreamCardFrom); card = !src.has_ended(); }
+    bool card = allowed && !(gd && atoi(gd) == 0) && hdr.lane_count != 0;
+    if (card && !gd) { src.hold(card_from); card = !src.has_ended(); }
     if (!card) src.release();
     return card;
 }
+static bool bam_stream_to_card(BamReader& rd, BgzfStream& src, bool allowed) { return stream_to_card(rd.header(), src, allowed, kBamStreamCardFrom); }
+// SAM text inside BGZF goes to the card by the rules of a BAM stream; a stream, or a file, of at least this many compressed
+// bytes does when BQC_GPU_DECODE is unset.  Measured (profiles/sam_bgzf_ab.json): whole-program time, this build's host reader
+// (BQC_GPU_DECODE=0) against the card forced (=1), FIFOs of 22.5 / 85.2 / 276.0 MB fed by cat, best of three — 0.274 against 0.194 s, 0.974 against
+// 0.177 s, 3.33 against 0.221 s: the card is not slower at the smallest size measured, which is the constant.  At that size the verdict rests on ONE
+// of the card's three runs (the other two, 0.363 and 0.376 s, were slower than every host run: start-up scatter); from 85 MB on every card run is
+// below every host run.  Both sides are this change's code: a switch-over point, no statement about speed.  Nothing smaller was measured, and files
+// were not (a file's st_size is held against the same constant).
+static const size_t kSamBgzfCardFrom = 22460726;
 extern "C" int bqc_bam_open(const char* path, bqc_bam** out)
 {
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
     std::vector<uint8_t> taken;
-    if (strcmp(path, "-") == 0 ? sniff_stdio_bgzf(stdin, taken) : is_stream_path(path)) { // a BAM stream: the host reader over the descriptor
+    const InputKind kind = input_kind(path);
+    if (kind == IN_STDIN ? sniff_stdio_bgzf(stdin, taken) : kind == IN_STREAM) { // a BGZF stream: a host reader over the descriptor
         std::shared_ptr<BgzfStream> src;
-        if (strcmp(path, "-") == 0) { src = std::make_shared<BgzfStream>(stdin); src->preload(taken.data(), taken.size()); }
+        if (kind == IN_STDIN) { src = std::make_shared<BgzfStream>(stdin); src->preload(taken.data(), taken.size()); }
         else {
             const int fd = open(path, O_RDONLY);
             if (fd < 0) { b->err = std::string("could not open ") + path; *out = b; return BQC_ERR_IO; }
             src = std::make_shared<BgzfStream>(fd);
         }
         stream_test_hold(*src);
+        const bool text = bgzf_stream_carries(*src) == BGZF_SAM_TEXT;
         src->release(); // (nothing more is kept: nobody else will want it)
-        if (!b->bam.open_stream(src, b->err)) { *out = b; return BQC_ERR_IO; }
-    } else if (is_sam_path(path)) {
+        if (text) {
+            b->is_sam = true;
+            if (!b->sam.open_bgzf_stream(src, b->err)) { *out = b; return BQC_ERR_IO; }
+        } else if (!b->bam.open_stream(src, b->err)) { *out = b; return BQC_ERR_IO; }
+    } else if (kind == IN_SAM_BGZF) { // (a FIFO of that name too: the file is read once, in order)
+        b->is_sam = true;
+        if (!b->sam.open_bgzf(path, b->err)) { *out = b; return BQC_ERR_IO; }
+    } else if (kind == IN_STDIN || kind == IN_SAM) {
         b->is_sam = true;
         b->sam_file = strcmp(path, "-") == 0 ? stdin : fopen(path, "r");
         if (!b->sam_file) { b->err = std::string("could not open ") + path; *out = b; return BQC_ERR_IO; }
@@ -385,15 +421,32 @@ extern "C" int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out)
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
     *out = b;
-    const bool dash = strcmp(path, "-") == 0;
+    const InputKind kind = input_kind(path);
+    const bool dash = kind == IN_STDIN;
     std::vector<uint8_t> first; // "-": its first bytes say what it carries
     if (dash) sniff_fd(0, first);
-    if (dash ? is_bgzf_magic(first.data(), first.size()) : is_stream_path(path)) { // a BAM stream
+    // SAM text inside BGZF: the header on the host, the text inflated and decoded on the card — a file always (as a BAM
+    // file), a stream by the rules of a BAM stream (the host reader goes on where the card does not take it)
+    auto sam_bgzf = [&](std::shared_ptr<BgzfStream> src) -> int {
+        b->is_sam = true;
+        if (src ? !b->sam.open_bgzf_stream(src, b->err) : !b->sam.open_bgzf(path, b->err)) return BQC_ERR_IO;
+        if (src && !stream_to_card(b->sam.header(), *src, true, kSamBgzfCardFrom)) { b->refresh_lanes(); return 0; }
+        b->gsam.reset(new GpuSamReader());
+        b->gsam->start_bgzf(b->sam.header(), b->sam.ref_index(), b->sam.first_record_pos(), path);
+        b->sam.close(); // (nobody is inside the stream object any more)
+        if (src) b->gsam->producer().set_stream(src->release_fd(), std::move(src->held), src->has_ended());
+        if (!b->gsam->open(device, 1u << 20, 256u << 20, b->err)) { b->gsam.reset(); return BQC_ERR_DEVICE; }
+        b->gsam->allow_kernels();
+        b->refresh_lanes();
+        return 0;
+    };
+    if (dash ? is_bgzf_magic(first.data(), first.size()) : kind == IN_STREAM || (kind == IN_SAM_BGZF && !is_regular_file(path))) { // a BGZF stream (DESIGN sections 4.5c, 4.5d)
         const int fd = dash ? 0 : open(path, O_RDONLY);
         if (fd < 0) { b->err = std::string("could not open ") + path; return BQC_ERR_IO; }
         auto src = std::make_shared<BgzfStream>(fd);
         src->preload(first.data(), first.size());
         stream_test_hold(*src);
+        if (kind == IN_SAM_BGZF || bgzf_stream_carries(*src) == BGZF_SAM_TEXT) return sam_bgzf(src);
         if (!b->bam.open_stream(src, b->err)) return BQC_ERR_IO; // the header, on the host, from the bytes the stream object keeps
         if (!bam_stream_to_card(b->bam, *src, true)) { b->refresh_lanes(); return 0; } // (the host reader goes on)
         b->gpu.reset(new GpuBamReader());
@@ -405,7 +458,8 @@ extern "C" int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out)
         b->refresh_lanes();
         return 0;
     }
-    if (is_sam_path(path)) { // SAM text: the reader takes the descriptor from its first byte
+    if (kind == IN_SAM_BGZF) return sam_bgzf(nullptr); // (a regular file: the producer opens it)
+    if (kind == IN_STDIN || kind == IN_SAM) { // SAM text: the reader takes the descriptor from its first byte
         const int fd = dash ? 0 : open(path, O_RDONLY);
         if (fd < 0) { b->err = std::string("could not open ") + path; return BQC_ERR_IO; }
         b->gsam.reset(new GpuSamReader());
@@ -430,6 +484,7 @@ extern "C" int bqc_bam_open_range(const char* path, uint64_t begin_hint, uint64_
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
     *out = b;
+    if (bqc_input_is_sam_text(path)) { b->err = "SAM text cannot be read in shards"; return BQC_ERR_ARG; }
     if (!b->bam.open_range(path, begin_hint, end_hint, b->err)) return BQC_ERR_IO;
     b->refresh_lanes();
     return 0;
@@ -448,7 +503,7 @@ extern "C" int bqc_bam_open_gpu_range(const char* path, int device, uint64_t beg
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
     *out = b;
-    if (is_sam_path(path)) { b->err = "SAM text cannot be read in shards"; return BQC_ERR_ARG; }
+    if (const InputKind k = input_kind(path); k == IN_STDIN || k == IN_SAM || k == IN_SAM_BGZF) { b->err = "SAM text cannot be read in shards"; return BQC_ERR_ARG; }
     if (!shard_blocks(path, begin_hint, end_hint, b->g_b0, b->g_b1, b->err)) { if (b->err.empty()) b->err = "empty shard"; return BQC_ERR_ARG; }
     if (!b->bam.open(path, b->err, true)) return BQC_ERR_IO; // the header, on the host
     b->gpu.reset(new GpuBamReader());
@@ -785,10 +840,9 @@ void usage(FILE* f)
 // the positional rule (valid values: "- bam sam" by file extension, CommandLineParser.hpp:59-60), for a path that is not "-"
 bool input_extension_ok(const std::string& path, std::string& err)
 {
-    size_t dot = path.rfind('.');
-    std::string ext = dot == std::string::npos ? "" : path.substr(dot + 1);
-    if (ext != "bam" && ext != "sam" && is_stream_path(path.c_str())) return true; // (a pipe has no name to speak of: /dev/stdin, /dev/fd/N, a process substitution)
-    if (ext != "bam" && ext != "sam") { err = "bamqualcheck: the given path '" + path + "' does not have one of the valid file extensions [*.-, *.bam, *.sam]"; return false; }
+    // (input_kind: ".sam.gz" is two extensions, and a pipe has no name to speak of — /dev/stdin, /dev/fd/N, a process substitution)
+    const InputKind k = input_kind(path.c_str());
+    if (k == IN_OTHER || k == IN_STDIN) { err = "bamqualcheck: the given path '" + path + "' does not have one of the valid file extensions [*.-, *.bam, *.sam, *.sam.gz]"; return false; }
     return true;
 }
 
@@ -1071,12 +1125,16 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     });
     struct InflateOff { ~InflateOff() { bgzf_gpu_inflate_device(-1); bqc_raw_vector_pin_hook = nullptr; } } inflate_off; // (destroyed after the joiner below has joined the thread that sets it)
     struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } warm_joiner{warm};
-    // "-": SAM text from stdin; everything else is opened as BAM (bamqualcheck.cpp:252-262: a .sam path fails to open there too)
+    // What the input is: input_kind.  "-": SAM text from stdin, or a BGZF stream; x.sam and x.sam.gz: SAM text, plain and
+    // inside BGZF (the reference opens every path as BAM, bamqualcheck.cpp:252-262: a .sam path fails to open there); anything else: BAM.
     BamReader bam_rd;
     SamReader sam_rd;
+    FILE* sam_fp = nullptr; // (a .sam file the host reader reads)
+    struct FpClose { FILE*& f; ~FpClose() { if (f && f != stdin) fclose(f); } } sam_fp_close{sam_fp};
     GpuSamReader gsam_rd;
     std::string err;
-    const bool from_stdin = opt.bamFile == "-";
+    const InputKind kind = input_kind(opt.bamFile.c_str());
+    const bool from_stdin = kind == IN_STDIN;
     // SAM text on stdin is decoded on the card (csrc/gpu_sam.hip) unless BQC_GPU_DECODE=0: the reader takes the descriptor from its
     // first byte.  BQC_GPU_DECODE unset: a stream that ends within its first kSamCardFrom bytes (read here, while the runtime starts) is
     // parsed on the host from memory, and no device reader is set up.
@@ -1084,6 +1142,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     // a failure before the hook is reached must still reach it: the other processes wait for this one
     auto shard_abort = [&]() { if (shard) { bqc_shard_info si{}; si.status = 1; bqc_shard_result sr{}; (void)shard->hook(shard->user, &si, &sr); } return 1; };
     if (shard && from_stdin) { fprintf(stderr, "ERROR: a stream on stdin cannot be split between processes\n"); return shard_abort(); }
+    if (shard && (kind == IN_SAM || kind == IN_SAM_BGZF)) { fprintf(stderr, "ERROR: SAM text cannot be read in shards\n"); return shard_abort(); } // (the front end of --gpus N says so before it forks)
     // A BAM stream: an input that is not a regular file, or "-" whose first two bytes are a gzip member's (looked
     // at inside the bytes the readers take anyway: the reader of SAM text gets them back).  Its header is parsed by the host reader from
     // bytes that are kept; the card takes the stream, prefix first, or the host reader goes on from where it is.  Nothing is read twice.
@@ -1095,21 +1154,46 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     else if (from_stdin) {
         sniff_fd(0, stdin_first);
         if (is_bgzf_magic(stdin_first.data(), stdin_first.size())) { bam_stream = std::make_shared<BgzfStream>(0); bam_stream->preload(stdin_first.data(), stdin_first.size()); }
-    } else if (!shard && is_stream_path(opt.bamFile.c_str())) {
+    } else if (!shard && (kind == IN_STREAM || (kind == IN_SAM_BGZF && !is_regular_file(opt.bamFile.c_str())))) { // (a FIFO named x.sam.gz is read once too)
         const int fd = open(opt.bamFile.c_str(), O_RDONLY);
         if (fd >= 0) bam_stream = std::make_shared<BgzfStream>(fd);
     }
     if (bam_stream) stream_test_hold(*bam_stream);
-    const bool sam_stdin = from_stdin && !bam_stream;
-    const bool use_gsam = sam_stdin && !(gd_stdin && atoi(gd_stdin) == 0);
+    // SAM text inside BGZF: by its name, or a BGZF stream by its first inflated bytes — looked at inside what the stream object keeps
+    const bool sam_bgzf = kind == IN_SAM_BGZF || (bam_stream && bgzf_stream_carries(*bam_stream) == BGZF_SAM_TEXT);
+    const bool sam_stdin = (from_stdin && !bam_stream) || kind == IN_SAM; // plain SAM text: stdin, or a path that ends in ".sam"
+    // (plain SAM text goes to the card as a stream does; a regular file by its size against kSamCardFrom — a constant measured for streams,
+    // not for files — instead of holding bytes)
+    uint64_t sam_size = 0;
+    const bool sam_regular = kind == IN_SAM && is_regular_file(opt.bamFile.c_str(), &sam_size);
+    bool use_gsam = sam_stdin && !(gd_stdin && atoi(gd_stdin) == 0) && (!sam_regular || gd_stdin || sam_size >= kSamCardFrom);
     bool stream_card = false; // the card takes the BAM stream
+    bool sam_bgzf_card = false; // ... or the SAM text inside BGZF, stream or file
     bool opened;
     // a shard of the file: its block boundaries are found here (BamReader::open_range finds the same ones: bgzf_find_block is a
     // function of the hint), so that either reader can take the range
     uint64_t shard_b0 = 0, shard_b1 = UINT64_MAX;
     bool shard_gpu = false;
-    if (use_gsam) { gsam_rd.preload(stdin_first.data(), stdin_first.size()); opened = gsam_rd.start(0, gd_stdin ? 0 : kSamCardFrom, err); }
-    else if (sam_stdin) opened = sam_rd.open(stdin, err);
+    if (use_gsam) {
+        const int fd = from_stdin ? 0 : open(opt.bamFile.c_str(), O_RDONLY);
+        if (from_stdin) gsam_rd.preload(stdin_first.data(), stdin_first.size());
+        opened = fd >= 0 && gsam_rd.start(fd, gd_stdin || sam_regular ? 0 : kSamCardFrom, err);
+    }
+    else if (sam_stdin) { sam_fp = from_stdin ? stdin : fopen(opt.bamFile.c_str(), "r"); opened = sam_fp && sam_rd.open(sam_fp, err); }
+    else if (sam_bgzf) {
+        // The header on the host, from bytes that are kept (a stream) or through the reader's small first run (a file); then
+        // the card or the host reader by the rules of a BAM stream: BQC_GPU_DECODE=1 the card, =0 the host, no @RG line the host, unset: the size
+        uint64_t size = 0;
+        const bool card_allowed = !host_reader_only && !(gd_stdin && atoi(gd_stdin) == 0);
+        const bool file_card = !bam_stream && card_allowed && is_regular_file(opt.bamFile.c_str(), &size) && (gd_stdin || size >= kSamBgzfCardFrom);
+        opened = bam_stream ? sam_rd.open_bgzf_stream(bam_stream, err) : sam_rd.open_bgzf(opt.bamFile.c_str(), err);
+        if (opened) sam_bgzf_card = bam_stream ? stream_to_card(sam_rd.header(), *bam_stream, card_allowed, kSamBgzfCardFrom) : file_card && sam_rd.header().lane_count != 0;
+        if (sam_bgzf_card) {
+            gsam_rd.start_bgzf(sam_rd.header(), sam_rd.ref_index(), sam_rd.first_record_pos(), opt.bamFile.c_str());
+            sam_rd.close(); // (its read-ahead has inflated the first run for the header; nobody is inside the stream object any more)
+            use_gsam = true;
+        }
+    }
     else if (bam_stream) {
         opened = bam_rd.open_stream(bam_stream, err); // the header (a stream that is no BAM, or ends inside it, fails here in the host reader's words)
         if (opened) stream_card = bam_stream_to_card(bam_rd, *bam_stream, !host_reader_only); // (the calling thread holds the stream meanwhile: the runtime starts beside it)
@@ -1145,7 +1229,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     GpuBamReader& gpu_rd = S ? S->gpu_rd : own_gpu_rd;
     if (S) gpu_rd.set_anchor_context(nullptr); // (the context of the job before may not outlive this one's set-up)
     const char* gd_env = getenv("BQC_GPU_DECODE"); // 1: whenever possible, 0: never; unset: files of 256 MB and more (its set-up costs ~50 ms)
-    bool use_gpu_reader = !sam_stdin && (!shard || shard_gpu) && !host_reader_only && bam_rd.header().lane_count != 0 && !(gd_env && atoi(gd_env) == 0);
+    bool use_gpu_reader = !sam_stdin && !sam_bgzf && (!shard || shard_gpu) && !host_reader_only && bam_rd.header().lane_count != 0 && !(gd_env && atoi(gd_env) == 0);
     if (shard && shard_gpu && !use_gpu_reader) { // (no @RG line: the host reader, over its range, decides what that means)
         bam_rd.~BamReader();
         new (&bam_rd) BamReader();
@@ -1154,7 +1238,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         if (!bam_rd.open_range(opt.bamFile.c_str(), lo, hi, err)) { fprintf(stderr, "ERROR: Could not open %s for reading.\n", opt.bamFile.c_str()); return shard_abort(); }
         shard_gpu = false;
     }
-    if (bam_stream) use_gpu_reader = stream_card;
+    if (bam_stream) use_gpu_reader = stream_card; // (false for SAM text inside BGZF: that is the reader of SAM text's)
     else if (use_gpu_reader && !shard) { // a regular file: the reader opens it a second time
         struct stat st;
         use_gpu_reader = stat(opt.bamFile.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (gd_env || (uint64_t)st.st_size >= (256ull << 20));
@@ -1167,8 +1251,8 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         bqc_raw_vector_free_hook = pin_free_hook;
         bqc_raw_vector_pin_hook = pin_hook;
     }
-    const bool gsam_card = use_gsam && gsam_rd.header().lane_count != 0 && (gd_stdin || !gsam_rd.stream_ended());
-    RecordReader& rd = use_gsam ? static_cast<RecordReader&>(gsam_rd) : sam_stdin ? static_cast<RecordReader&>(sam_rd) : use_gpu_reader ? static_cast<RecordReader&>(gpu_rd) : static_cast<RecordReader&>(bam_rd);
+    const bool gsam_card = sam_bgzf_card || (use_gsam && gsam_rd.header().lane_count != 0 && (gd_stdin || !gsam_rd.stream_ended()));
+    RecordReader& rd = use_gsam ? static_cast<RecordReader&>(gsam_rd) : sam_stdin || sam_bgzf ? static_cast<RecordReader&>(sam_rd) : use_gpu_reader ? static_cast<RecordReader&>(gpu_rd) : static_cast<RecordReader&>(bam_rd);
     if (use_gpu_reader) gpu_rd.header() = bam_rd.header(); // (complete once opened, in the decode thread: the device is not up yet)
     if (!shard || shard->index == 0) {
         FILE* of = fopen(opt.outputFile.c_str(), "wb"); // opened (truncated) before the scan, :278-283
@@ -1241,6 +1325,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         }
         if (gsam_card) {
             std::string e;
+            if (sam_bgzf_card && bam_stream) gsam_rd.producer().set_stream(bam_stream->release_fd(), std::move(bam_stream->held), bam_stream->has_ended()); // (as a BAM stream's: the prefix is the first runs' input)
             const bool ok = gsam_rd.open(opt.device, opt.batch_reads, 256ull << 20, e);
             gpu_reader_opened = true;
             if (!ok) {
@@ -1574,7 +1659,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     dec.join();
     if (S && use_gpu_reader) gpu_rd.end_file(); // (its threads are gone and its streams idle: what it holds can be told, and the next file may open it)
     note_rc(Q.err_code);
-    if (timing) fprintf(stderr, "[timing] records decoded %s\n", use_gpu_reader ? "on the GPU (csrc/gpu_bam.hip)" : gsam_card ? "on the GPU (csrc/gpu_sam.hip)" : "on the host");
+    if (timing) fprintf(stderr, "[timing] records decoded %s\n", use_gpu_reader ? "on the GPU (csrc/gpu_bam.hip)" : gsam_card ? (sam_bgzf_card ? "on the GPU (csrc/gpu_inflate.hip + csrc/gpu_sam.hip)" : "on the GPU (csrc/gpu_sam.hip)") : "on the host");
     if (timing) { // (every buffer of the run exists at this point: what is in use now is the run's peak)
         size_t free_b = 0, total_b = 0, pinned = 0;
         { std::lock_guard<std::mutex> lk(g_pins.m); for (auto& kv : g_pins.blocks) pinned += kv.second; }
@@ -1588,6 +1673,9 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         fprintf(stderr, bam_stream ? "[timing] reader on the card: a stream, read() and waiting for it %.2f s in its one reader thread, the producer waited %.2f s for chunks, the decode thread waited %.2f s for inflated runs\n"
                                    : "[timing] reader on the card: pread %.2f s summed over its reader threads, the producer waited %.2f s for them, the decode thread waited %.2f s for inflated runs\n",
                 gpu_rd.seconds_reading(), gpu_rd.seconds_producer_waiting_for_chunks(), gpu_rd.seconds_waiting_for_runs());
+    if (timing && sam_bgzf_card)
+        fprintf(stderr, "[sam reader] text inflated on the card: %s %.2f s in the producer's reader thread%s, the producer waited %.2f s for chunks, the decode thread waited %.2f s for inflated runs\n",
+                bam_stream ? "a stream, read() and waiting for it" : "pread", gsam_rd.seconds_producer_reading(), bam_stream ? "" : "s (summed)", gsam_rd.seconds_producer_waiting_for_chunks(), gsam_rd.seconds_waiting_for_runs());
     if (timing && use_gsam) {
         fprintf(stderr, "[sam reader] %llu batches on the card, %llu handed over, %llu anchored\n", (unsigned long long)gsam_rd.batches(), (unsigned long long)gsam_rd.batches_handed_over(),
                 (unsigned long long)gsam_rd.batches_anchored());

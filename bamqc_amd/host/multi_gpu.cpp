@@ -37,6 +37,7 @@
 #include <rccl/rccl.h> // types only: the functions are looked up in librccl at run time
 
 #include "../../include/bamqc_host.h"
+#include "host_tools.h"
 
 namespace {
 // ---- framed messages over a socket pair --------------------------------------------------------------------------------
@@ -488,6 +489,8 @@ extern "C" int bqc_main_multi(int argc, const char** argv, int n_gpus)
         if (pr != 0) return 1;
         if (!path[0]) { fprintf(stderr, "bamqualcheck: --gpus with --manifest is not supported: run one process per card (--device), each with a list of its own\n"); return 1; }
         bam = path;
+        // (said once, here, before any worker exists: every worker's run_program would say it too)
+        if (bqc_input_is_sam_text(path)) { fprintf(stderr, "ERROR: SAM text cannot be read in shards: %s is read by one process (no --gpus)\n", path); return 1; }
     }
     fflush(stdout); fflush(stderr);
     std::vector<int> fds;

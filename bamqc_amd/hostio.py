@@ -33,8 +33,11 @@ class BamFile:
     def __init__(self, path, begin_hint=None, end_hint=None, gpu=None):
         """The whole file, or (begin_hint / end_hint: compressed byte offsets) one shard of its record stream.
         gpu: a device index — the file is inflated and decoded on that GPU (batches are fetched back); SAM text (a path ending
-        in .sam, or "-") is decoded there too.  A path that is no regular file (a FIFO, /dev/stdin) and "-" that starts with a gzip
-        member's two bytes are BAM streams: read once, in order, by either reader (include/bamqc_host.h: bqc_bam_open, bqc_bam_open_gpu)."""
+        in .sam, or "-") is decoded there too.  A path that ends in .sam.gz is SAM text inside BGZF (bgzip; not plain gzip): read by the
+        host's line reader over the inflated bytes, or — gpu= — inflated and decoded on the card.  A path that is no regular file (a FIFO,
+        /dev/stdin) and "-" that starts with a gzip member's two bytes are BGZF streams, read once, in order, by either reader: BAM streams
+        when they inflate to "BAM\1", SAM text inside BGZF when their first inflated byte is '@' (include/bamqc_host.h: bqc_bam_open,
+        bqc_bam_open_gpu).  Shards (begin_hint / end_hint) are for BAM files only."""
         self.lib = _lib.load()
         self.h = C.c_void_p()
         if gpu is not None and (begin_hint is not None or end_hint is not None):

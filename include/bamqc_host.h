@@ -57,13 +57,19 @@ int bqc_sam_write(const char* path, const bqc_batch* b, uint32_t n_refs, const c
 
 /* ---- BAM / FASTA input (replaces SeqAn BamStream / SequenceStream) --------- */
 typedef struct bqc_bam bqc_bam;
-/* What a path is, for this function and bqc_bam_open_gpu alike: a path that ends in ".sam" is SAM text, whatever kind of file it is (a
- * FIFO too: read once, as ever); "-" (stdin) is SAM text unless its first two bytes are 1f 8b; every other path is BAM — a file when it is a
- * regular file, otherwise a BAM STREAM, read once and in order.
- * Here: a BAM file; SAM text; a BAM stream, read by the same host reader:
- * a path that is not a regular file and does not end in ".sam" (a FIFO, /dev/stdin, /dev/fd/N), and "-" when its first two bytes are 1f 8b (a gzip member's: BGZF,
- * hence BAM — no SAM text starts with 0x1f).  A stream that is no BAM, or ends inside its header, fails as a file does ("not a BAM
- * file", "truncated BAM header", or the BGZF layer's words). */
+/* What a path is, for this function, bqc_bam_open_gpu and the program alike (one function of the driver states it):
+ *   - a path that ends in ".sam" is plain SAM text, whatever kind of file it is (a FIFO too: read once, as ever);
+ *   - a path that ends in ".sam.gz" is SAM text inside BGZF (bgzip, samtools view -O sam,level=N), whatever kind of file it is; plain
+ *     gzip — one serial DEFLATE stream without BGZF's BC subfield — is not read: it fails to open in the BGZF layer's words;
+ *   - "-" (stdin) is plain SAM text unless its first two bytes are 1f 8b (a gzip member's: no SAM text starts with 0x1f);
+ *   - "-" with those two bytes, and any other path that is not a regular file (a FIFO, /dev/stdin, /dev/fd/N), is a BGZF STREAM, read once
+ *     and in order, and is what its first inflated bytes say (empty members in front skipped): "BAM\1" a BAM stream, a first byte of '@'
+ *     SAM text inside BGZF, anything else or nothing "not a BAM file" — looked at inside the bytes the readers take anyway;
+ *   - every other path is a BAM file, with no look at its content.
+ * Here everything is read by the host readers.  SAM text inside BGZF gives the columns, lane names, messages and record numbers of the
+ * same text read plain (a line may straddle any number of blocks); BGZF damage is the BGZF layer's I/O error, as for a BAM file.  A
+ * stream that is no BAM, or ends inside its header, fails as a file does ("not a BAM file", "truncated BAM header", or the BGZF
+ * layer's words). */
 int bqc_bam_open(const char* path, bqc_bam** out);  /* on failure *out still holds the message */
 /* One shard of the record stream (multi-GPU): the records that START in the BGZF blocks between the first block boundary at
  * or behind the compressed offset begin_hint and the first one at or behind end_hint (0 / UINT64_MAX: the file's ends).  A
@@ -79,7 +85,12 @@ int bqc_bam_open_range(const char* path, uint64_t begin_hint, uint64_t end_hint,
  * its first byte).  A stream cannot be started over, so -1000 never comes back for it: a batch with a line the card has no rule for
  * (bqc_bam_batches_handed_over counts them too) is parsed by the host's line parser, whose errors and messages are the ones reported;
  * the records in front of a failing line are delivered before its error.
- * A BAM STREAM (a path that is not a regular file and does not end in ".sam"; "-" with the two bytes 1f 8b in front, looked at inside the bytes the reader takes
+ * SAM text inside BGZF (x.sam.gz, a FIFO of that name, a BGZF stream whose first inflated byte is '@') is inflated AND decoded on the card:
+ * the header is parsed on the host, the BGZF producer of the reader of BAM files inflates the text run by run (CRC checked on the card),
+ * and the reader of SAM text decodes it where it lies.  A file always goes to the card; a stream by the rules of a BAM stream below (with
+ * 22.5 MB held instead of 256).  -1000 never comes back; BGZF damage is BQC_ERR_IO in the host reader's words, behind the records of the runs
+ * in front of it; a line of 16 MB or more that crosses a run boundary is an I/O error of this reader (the room in front of a run).
+ * A BAM STREAM (a path that is not a regular file and ends in neither ".sam" nor ".sam.gz"; "-" with the two bytes 1f 8b in front, looked at inside the bytes the reader takes
  * anyway) is read once, in order, and decoded on the card too: its header is parsed on the host from the stream's first bytes, which are
  * kept and become the card reader's first input.  BQC_GPU_DECODE=1 forces the card, =0 forbids it; unset, the calling thread holds the
  * stream's first 256 MB: a stream that ends inside them, and one without an @RG line, is read by the host reader from {those bytes, then
@@ -91,7 +102,7 @@ int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out);
 uint64_t bqc_bam_batches_handed_over(const bqc_bam* b);
 int bqc_bam_on_card(const bqc_bam* b); /* 1: a reader on the card decodes this input; 0: a host reader (bqc_bam_open; a stream bqc_bam_open_gpu left to it) */
 /* A shard (as bqc_bam_open_range) read, inflated and decoded on GPU `device`: only the shard's bytes of the file are touched.
- * SAM text has no shards: BQC_ERR_ARG. */
+ * SAM text, plain or inside BGZF (x.sam, x.sam.gz), has no shards: BQC_ERR_ARG, "SAM text cannot be read in shards" (bqc_bam_open_range too). */
 int bqc_bam_open_gpu_range(const char* path, int device, uint64_t begin_hint, uint64_t end_hint, bqc_bam** out);
 uint64_t bqc_bam_range_begin_block(const bqc_bam* b);
 uint64_t bqc_bam_range_end_block(const bqc_bam* b);   /* UINT64_MAX: end of the file */
