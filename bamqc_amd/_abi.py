@@ -106,6 +106,17 @@ class HeaderInfo(C.Structure):
                 ("lane_names", C.POINTER(C.c_char_p)), ("lane_index", u32p)]
 
 
+class RouteFacts(C.Structure):  # host/input_route.h: bqc_route_facts (the enums' values: there)
+    _fields_ = [("caller", C.c_int32), ("kind", C.c_int32), ("regular", C.c_int32), ("size", C.c_uint64), ("dash_bgzf", C.c_int32),
+                ("carries", C.c_int32), ("gpu_decode", C.c_int32), ("host_reader_only", C.c_int32), ("shard", C.c_int32),
+                ("shard_found", C.c_int32), ("shard_bytes", C.c_uint64), ("has_rg", C.c_int32), ("ended", C.c_int32)]
+
+
+class Route(C.Structure):  # bqc_route
+    _fields_ = [("refuse", C.c_int32), ("sniff", C.c_int32), ("stream", C.c_int32), ("find_blocks", C.c_int32), ("header_by", C.c_int32),
+                ("header_first", C.c_int32), ("hold", C.c_uint64), ("reader", C.c_int32), ("source", C.c_int32)]
+
+
 _BATCH_COLS = [("flag", np.uint16, u16p), ("mapq", np.uint8, u8p), ("lane", np.uint8, u8p),
                ("rid", np.int32, i32p), ("pos", np.int32, i32p), ("tlen", np.int32, i32p),
                ("nm", np.int32, i32p), ("as_", np.int32, i32p), ("l_seq", np.uint32, u32p),

@@ -102,6 +102,7 @@ _SIGNATURES = {
     "bqc_calib_read4": (C.c_int, [C.c_uint64, C.c_int]),
     "bqc_inflate_raw": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]),
     "bqc_crc32": (C.c_uint32, [C.c_char_p, C.c_uint64]),
+    "bqc_input_route": (None, [C.POINTER(_abi.RouteFacts), C.POINTER(_abi.Route)]),  # host/input_route.h (tests)
 }
 
 _LIB = None

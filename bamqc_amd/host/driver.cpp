@@ -32,6 +32,7 @@
 #include "crc32_fast.h"
 #include "inflate_fast.h"
 #include "host_tools.h"
+#include "input_route.h"
 #include "../csrc/gpu_bam.h"
 #include "../csrc/gpu_sam.h"
 #include <hip/hip_runtime_api.h>
@@ -268,68 +269,6 @@ static bool load_fasta(const char* path, const std::vector<std::string>* want, s
 // ---------------------------------------------------------------------------------------------------
 // C wrappers around the reader (python drivers, tests)
 // ---------------------------------------------------------------------------------------------------
-struct bqc_bam {
-    BamReader bam;
-    SamReader sam;
-    bool is_sam = false;
-    FILE* sam_file = nullptr;
-    std::unique_ptr<GpuBamReader> gpu; // bqc_bam_open_gpu: records decoded on the card
-    std::unique_ptr<GpuSamReader> gsam; // bqc_bam_open_gpu of SAM text: the same
-    uint64_t g_b0 = 0, g_b1 = UINT64_MAX; // bqc_bam_open_gpu_range: the shard's block boundaries
-    RecordReader& rd() { return gpu ? static_cast<RecordReader&>(*gpu) : gsam ? static_cast<RecordReader&>(*gsam) : is_sam ? static_cast<RecordReader&>(sam) : static_cast<RecordReader&>(bam); }
-    const BamHeader& hdr() const { return const_cast<bqc_bam*>(this)->rd().header(); }
-    ~bqc_bam() { if (sam_file && sam_file != stdin) fclose(sam_file); }
-    HostBatch hb;
-    bqc_batch view;
-    std::string err;
-    std::vector<std::string> lane_sorted;
-    std::vector<uint32_t> lane_idx;
-    void refresh_lanes()
-    {
-        lane_sorted.clear(); lane_idx.clear();
-        for (auto& kv : rd().header().lane_names) { lane_sorted.push_back(kv.first); lane_idx.push_back(kv.second); }
-    }
-};
-
-// What an input is, by its name — stated here once, for the option parser, bqc_bam_open* and run_program:
-//   IN_STDIN     "-": SAM text, unless its first two bytes are a gzip member's (is_bgzf_magic) — then a BGZF stream
-//   IN_SAM       a path that ends in ".sam", whatever it is (a FIFO too): plain SAM text
-//   IN_SAM_BGZF  a path that ends in ".sam.gz", whatever it is: SAM text inside BGZF (bgzip, samtools view -O sam,level=N); plain gzip is not read
-//   IN_STREAM    any other path that is no regular file (a FIFO, /dev/stdin, /dev/fd/N): a BGZF stream
-//   IN_BAM       any other path that ends in ".bam": a BAM file, no look at its content
-//   IN_OTHER     anything else: the program's parser refuses the name; the library opens it as a BAM file
-// A BGZF stream is BAM or SAM text by its first inflated bytes (host/bgzf.h: bgzf_stream_carries).
-enum InputKind { IN_STDIN, IN_SAM, IN_SAM_BGZF, IN_STREAM, IN_BAM, IN_OTHER };
-static InputKind input_kind(const char* path)
-{
-    const size_t n = strlen(path);
-    auto ends = [&](const char* sfx) { const size_t k = strlen(sfx); return n >= k && strcmp(path + n - k, sfx) == 0; };
-    if (strcmp(path, "-") == 0) return IN_STDIN;
-    if (ends(".sam.gz")) return IN_SAM_BGZF;
-    if (ends(".sam")) return IN_SAM;
-    struct stat st;
-    if (stat(path, &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode)) return IN_STREAM;
-    return ends(".bam") ? IN_BAM : IN_OTHER;
-}
-bool bqc_input_is_sam_text(const char* path) { const InputKind k = input_kind(path); return k == IN_SAM || k == IN_SAM_BGZF; } // (host_tools.h: the front end of --gpus N)
-
-// ---- BAM as a STREAM -----------------------------------------------------------------------------------------
-// An input that is not a regular file (a FIFO, /dev/stdin, /dev/fd/N, a process substitution) can be read once, in order: a stream.
-// "-" is a stream of SAM text unless its first two bytes are 1f 8b, a gzip member's — BGZF, hence BAM: no SAM text starts with 0x1f.
-// A BAM stream of at least this many compressed bytes goes to the card (BQC_GPU_DECODE unset); a shorter one has ended while the
-// calling thread held it, and the host reader takes it from memory.  Measured (profiles/bam_stream_ab.json): whole-program
-// time, the parent's host reader against the card, at 16 / 64 / 256 MB — the card is slower at 16, ties at 64 (0.231 against 0.226 s) and is not
-// slower from 256 MB on (0.21 against 0.27 s): the threshold of files.
-static const size_t kBamStreamCardFrom = 256u << 20;
-// (a path that ends in ".sam" is SAM text whatever it is — a FIFO too, read once by the readers of SAM text as ever — and never a BAM stream;
-// one that ends in ".sam.gz" is SAM text inside BGZF, whatever it is)
-static bool is_regular_file(const char* path, uint64_t* size = nullptr)
-{
-    struct stat st;
-    if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false;
-    if (size) *size = (uint64_t)st.st_size;
-    return true;
-}
 static bool is_bgzf_magic(const uint8_t* p, size_t n) { return n >= 2 && p[0] == 0x1f && p[1] == 0x8b; }
 // the first bytes of a descriptor nobody has read from yet: at least two, unless it ends before (into `first`)
 static void sniff_fd(int fd, std::vector<uint8_t>& first)
@@ -361,166 +300,201 @@ static bool sniff_stdio_bgzf(FILE* f, std::vector<uint8_t>& taken)
 // (tests) BQC_STREAM_HOLD=N: the stream object holds N bytes before its first reader exists — the header is then parsed, and the stream
 // read, over {a prefix cut at N, then the descriptor}, wherever N lies: inside the header, inside a block, behind the stream's end
 static void stream_test_hold(BgzfStream& src) { if (const char* e = getenv("BQC_STREAM_HOLD")) src.hold((size_t)strtoull(e, nullptr, 10)); }
-// Whether the card takes a BAM stream whose header `rd` has just read through `src` (which has kept every byte so far): the calling
-// thread holds the stream until kBamStreamCardFrom bytes or its end — BQC_GPU_DECODE=1: the card, with nothing held beyond the header;
-// =0: never; no @RG line: never (the host reader decides what that means).  false: the host reader goes on, over {what is held, then
-// the descriptor}, and nothing more is kept.
-static bool stream_to_card(const BamHeader& hdr, BgzfStream& src, bool allowed, size_t card_from)
-{
-    const char* gd = getenv("BQC_GPU_DECODE");
-    bool card = allowed && !(gd && atoi(gd) == 0) && hdr.lane_count != 0;
-    if (card && !gd) { src.hold(card_from); card = !src.has_ended(); }
-    if (!card) src.release();
-    return card;
-}
-static bool bam_stream_to_card(BamReader& rd, BgzfStream& src, bool allowed) { return stream_to_card(rd.header(), src, allowed, kBamStreamCardFrom); }
-// SAM text inside BGZF goes to the card by the rules of a BAM stream; a stream, or a file, of at least this many compressed
-// bytes does when BQC_GPU_DECODE is unset.  Measured (profiles/sam_bgzf_ab.json): whole-program time, this build's host reader
-// (BQC_GPU_DECODE=0) against the card forced (=1), FIFOs of 22.5 / 85.2 / 276.0 MB fed by cat, best of three — 0.274 against 0.194 s, 0.974 against
-// 0.177 s, 3.33 against 0.221 s: the card is not slower at the smallest size measured, which is the constant.  At that size the verdict rests on ONE
-// of the card's three runs (the other two, 0.363 and 0.376 s, were slower than every host run: start-up scatter); from 85 MB on every card run is
-// below every host run.  Both sides are this change's code: a switch-over point, no statement about speed.  Nothing smaller was measured, and files
-// were not (a file's st_size is held against the same constant).
-static const size_t kSamBgzfCardFrom = 22460726;
-extern "C" int bqc_bam_open(const char* path, bqc_bam** out)
-{
-    if (!path || !out) return BQC_ERR_ARG;
-    auto* b = new bqc_bam();
-    std::vector<uint8_t> taken;
-    const InputKind kind = input_kind(path);
-    if (kind == IN_STDIN ? sniff_stdio_bgzf(stdin, taken) : kind == IN_STREAM) { // a BGZF stream: a host reader over the descriptor
-        std::shared_ptr<BgzfStream> src;
-        if (kind == IN_STDIN) { src = std::make_shared<BgzfStream>(stdin); src->preload(taken.data(), taken.size()); }
-        else {
-            const int fd = open(path, O_RDONLY);
-            if (fd < 0) { b->err = std::string("could not open ") + path; *out = b; return BQC_ERR_IO; }
-            src = std::make_shared<BgzfStream>(fd);
-        }
-        stream_test_hold(*src);
-        const bool text = bgzf_stream_carries(*src) == BGZF_SAM_TEXT;
-        src->release(); // (nothing more is kept: nobody else will want it)
-        if (text) {
-            b->is_sam = true;
-            if (!b->sam.open_bgzf_stream(src, b->err)) { *out = b; return BQC_ERR_IO; }
-        } else if (!b->bam.open_stream(src, b->err)) { *out = b; return BQC_ERR_IO; }
-    } else if (kind == IN_SAM_BGZF) { // (a FIFO of that name too: the file is read once, in order)
-        b->is_sam = true;
-        if (!b->sam.open_bgzf(path, b->err)) { *out = b; return BQC_ERR_IO; }
-    } else if (kind == IN_STDIN || kind == IN_SAM) {
-        b->is_sam = true;
-        b->sam_file = strcmp(path, "-") == 0 ? stdin : fopen(path, "r");
-        if (!b->sam_file) { b->err = std::string("could not open ") + path; *out = b; return BQC_ERR_IO; }
-        if (!b->sam.open(b->sam_file, b->err)) { *out = b; return BQC_ERR_IO; }
-    } else if (!b->bam.open(path, b->err)) { *out = b; return BQC_ERR_IO; }
-    b->refresh_lanes();
-    *out = b;
-    return 0;
-}
-extern "C" int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out)
-{
-    if (!path || !out) return BQC_ERR_ARG;
-    auto* b = new bqc_bam();
-    *out = b;
-    const InputKind kind = input_kind(path);
-    const bool dash = kind == IN_STDIN;
-    std::vector<uint8_t> first; // "-": its first bytes say what it carries
-    if (dash) sniff_fd(0, first);
-    // SAM text inside BGZF: the header on the host, the text inflated and decoded on the card — a file always (as a BAM
-    // file), a stream by the rules of a BAM stream (the host reader goes on where the card does not take it)
-    auto sam_bgzf = [&](std::shared_ptr<BgzfStream> src) -> int {
-        b->is_sam = true;
-        if (src ? !b->sam.open_bgzf_stream(src, b->err) : !b->sam.open_bgzf(path, b->err)) return BQC_ERR_IO;
-        if (src && !stream_to_card(b->sam.header(), *src, true, kSamBgzfCardFrom)) { b->refresh_lanes(); return 0; }
-        b->gsam.reset(new GpuSamReader());
-        b->gsam->start_bgzf(b->sam.header(), b->sam.ref_index(), b->sam.first_record_pos(), path);
-        b->sam.close(); // (nobody is inside the stream object any more)
-        if (src) b->gsam->producer().set_stream(src->release_fd(), std::move(src->held), src->has_ended());
-        if (!b->gsam->open(device, 1u << 20, 256u << 20, b->err)) { b->gsam.reset(); return BQC_ERR_DEVICE; }
-        b->gsam->allow_kernels();
-        b->refresh_lanes();
-        return 0;
-    };
-    if (dash ? is_bgzf_magic(first.data(), first.size()) : kind == IN_STREAM || (kind == IN_SAM_BGZF && !is_regular_file(path))) { // a BGZF stream (DESIGN sections 4.5c, 4.5d)
-        const int fd = dash ? 0 : open(path, O_RDONLY);
-        if (fd < 0) { b->err = std::string("could not open ") + path; return BQC_ERR_IO; }
-        auto src = std::make_shared<BgzfStream>(fd);
-        src->preload(first.data(), first.size());
-        stream_test_hold(*src);
-        if (kind == IN_SAM_BGZF || bgzf_stream_carries(*src) == BGZF_SAM_TEXT) return sam_bgzf(src);
-        if (!b->bam.open_stream(src, b->err)) return BQC_ERR_IO; // the header, on the host, from the bytes the stream object keeps
-        if (!bam_stream_to_card(b->bam, *src, true)) { b->refresh_lanes(); return 0; } // (the host reader goes on)
-        b->gpu.reset(new GpuBamReader());
-        const uint64_t first_record = b->bam.stream_pos();
-        b->bam.close();
-        b->gpu->set_stream(src->release_fd(), std::move(src->held), src->has_ended()); // (the host reader is closed: nobody is inside the stream object)
-        if (!b->gpu->open(path, device, b->bam.header(), first_record, 1u << 20, 256u << 20, b->err)) { b->gpu.reset(); return BQC_ERR_DEVICE; }
-        b->gpu->allow_kernels();
-        b->refresh_lanes();
-        return 0;
-    }
-    if (kind == IN_SAM_BGZF) return sam_bgzf(nullptr); // (a regular file: the producer opens it)
-    if (kind == IN_STDIN || kind == IN_SAM) { // SAM text: the reader takes the descriptor from its first byte
-        const int fd = dash ? 0 : open(path, O_RDONLY);
-        if (fd < 0) { b->err = std::string("could not open ") + path; return BQC_ERR_IO; }
-        b->gsam.reset(new GpuSamReader());
-        if (dash) b->gsam->preload(first.data(), first.size());
-        if (!b->gsam->start(fd, 0, b->err)) { b->gsam.reset(); return BQC_ERR_IO; }
-        if (!b->gsam->open(device, 1u << 20, 256u << 20, b->err)) { b->gsam.reset(); return BQC_ERR_DEVICE; }
-        b->gsam->allow_kernels();
-        b->refresh_lanes();
-        return 0;
-    }
-    if (!b->bam.open(path, b->err, true)) return BQC_ERR_IO; // the header, on the host
-    b->gpu.reset(new GpuBamReader());
-    const uint64_t first_record = b->bam.stream_pos();
-    b->bam.close(); // (the host reader's read-ahead stops here)
-    if (!b->gpu->open(path, device, b->bam.header(), first_record, 1u << 20, 256u << 20, b->err)) { b->gpu.reset(); return BQC_ERR_DEVICE; }
-    b->gpu->allow_kernels();
-    b->refresh_lanes();
-    return 0;
-}
-extern "C" int bqc_bam_open_range(const char* path, uint64_t begin_hint, uint64_t end_hint, bqc_bam** out)
-{
-    if (!path || !out) return BQC_ERR_ARG;
-    auto* b = new bqc_bam();
-    *out = b;
-    if (bqc_input_is_sam_text(path)) { b->err = "SAM text cannot be read in shards"; return BQC_ERR_ARG; }
-    if (!b->bam.open_range(path, begin_hint, end_hint, b->err)) return BQC_ERR_IO;
-    b->refresh_lanes();
-    return 0;
-}
-// the block boundaries of a shard, as BamReader::open_range finds them; false: an empty shard (or an error: err set)
-static bool shard_blocks(const char* path, uint64_t begin_hint, uint64_t end_hint, uint64_t& b0, uint64_t& b1, std::string& err)
+// the block boundaries of a shard, as BamReader::open_range finds them (bgzf_find_block is a function of the hint), and the compressed bytes
+// between them; 0: an empty shard (or an error: err set)
+static uint64_t shard_blocks(const char* path, uint64_t begin_hint, uint64_t end_hint, uint64_t& b0, uint64_t& b1, std::string& err)
 {
     const uint64_t size = bgzf_file_size(path);
     b1 = end_hint >= size ? UINT64_MAX : bgzf_find_block(path, end_hint, err);
     if (b1 >= size) b1 = UINT64_MAX;
     b0 = begin_hint == 0 ? 0 : bgzf_find_block(path, begin_hint, err);
-    return err.empty() && b0 < std::min(b1, size);
+    return err.empty() && b0 < std::min(b1, size) ? std::min(b1, size) - b0 : 0;
 }
-extern "C" int bqc_bam_open_gpu_range(const char* path, int device, uint64_t begin_hint, uint64_t end_hint, bqc_bam** out)
+
+// One opener for every input: it carries out what input_route answers (host/input_route.h; DESIGN section 4.5d, "which reader takes it") for
+// the program and for bqc_bam_open*, in the three steps the program needs at three moments.  It owns the readers, the stdio stream of plain
+// text, the stream object and a shard's block boundaries; the reader of BAM on the card is its own or one lent to it (a session's, which
+// survives from job to job).
+struct InputOpener {
+    explicit InputOpener(GpuBamReader* lent = nullptr) : gpu_(lent ? lent : &own_gpu_) { if (lent) lent->set_anchor_context(nullptr); } // (the context of the job before may not outlive this one's set-up)
+    ~InputOpener() { if (fp_ && fp_ != stdin) fclose(fp_); }
+    // No device needed.  Gathers the facts `f` leaves open (one stat, the look at "-", what a BGZF stream carries, a shard's blocks), has the host
+    // reader of the route parse the header — from bytes that are kept, for a stream: nothing is read twice — holds a stream while the caller's
+    // runtime starts beside it, and prepares the reader the route ends at.  false: route().refuse, or err (an I/O error).
+    bool open(const char* path, bqc_route_facts f, uint64_t begin_hint, uint64_t end_hint, std::string& err)
+    {
+        path_ = path;
+        bool regular = false;
+        f.kind = input_kind(path, &regular, &f.size);
+        f.regular = regular;
+        f.gpu_decode = gpu_decode_env();
+        rt_ = input_route(f);
+        std::vector<uint8_t> first; // "-": its first bytes say what it carries
+        if (rt_.sniff == SNIFF_FD) { sniff_fd(0, first); f.dash_bgzf = is_bgzf_magic(first.data(), first.size()); }
+        if (rt_.sniff == SNIFF_STDIO) f.dash_bgzf = sniff_stdio_bgzf(stdin, first);
+        std::string blocks_err;
+        if (rt_.find_blocks) { f.shard_bytes = shard_blocks(path, begin_hint, end_hint, b0_, b1_, blocks_err); f.shard_found = f.shard_bytes != 0; }
+        rt_ = input_route(f);
+        if (rt_.refuse) {
+            err = rt_.refuse == REFUSE_STDIN_SHARD ? "a stream on stdin cannot be split between processes" : rt_.refuse == REFUSE_SAM_SHARD ? "SAM text cannot be read in shards" : blocks_err.empty() ? "empty shard" : blocks_err;
+            return false;
+        }
+        auto descriptor = [&]() { // (whoever takes it owns it from its first byte)
+            const int fd = f.kind == IN_STDIN ? 0 : ::open(path, O_RDONLY);
+            if (fd < 0) err = std::string("could not open ") + path;
+            return fd;
+        };
+        if (rt_.stream) { // a BGZF stream (DESIGN sections 4.5c, 4.5d): what it carries is looked at inside the bytes the stream object keeps
+            if (rt_.sniff == SNIFF_STDIO) src_ = std::make_shared<BgzfStream>(stdin);
+            else {
+                const int fd = descriptor();
+                if (fd < 0) return false;
+                src_ = std::make_shared<BgzfStream>(fd);
+            }
+            if (!first.empty()) src_->preload(first.data(), first.size());
+            stream_test_hold(*src_);
+            if (f.kind != IN_SAM_BGZF) { f.carries = bgzf_stream_carries(*src_); rt_ = input_route(f); }
+        }
+        const BamHeader* hdr = nullptr;
+        if (rt_.header_by == HDR_GSAM) { // plain text: the reader takes the descriptor, holds, and parses the header itself
+            const int fd = descriptor();
+            if (fd < 0) return false;
+            gsam_.preload(first.data(), first.size());
+            if (!gsam_.start(fd, (size_t)rt_.hold, err)) return false;
+            f.ended = gsam_.stream_ended();
+            hdr = &gsam_.header();
+        } else if (rt_.header_by == HDR_SAM_STDIO) {
+            fp_ = f.kind == IN_STDIN ? stdin : fopen(path, "r");
+            if (!fp_) { err = std::string("could not open ") + path; return false; }
+            if (!sam_.open(fp_, err)) return false;
+            hdr = &sam_.header();
+        } else if (rt_.header_by == HDR_SAM_BGZF) {
+            if (src_ ? !sam_.open_bgzf_stream(src_, err) : !sam_.open_bgzf(path, err)) return false;
+            hdr = &sam_.header();
+        } else if (f.shard && rt_.header_first) { // a shard the card may take: the header through a reader of its own, the range is opened below
+            BamReader whole;
+            if (!whole.open(path, err, true)) return false;
+            gpu_->header() = whole.header();
+            first_record_ = whole.stream_pos();
+            hdr = &gpu_->header();
+        } else {
+            if (src_ ? !bam_.open_stream(src_, err) : f.shard ? !bam_.open_range(path, begin_hint, end_hint, err) : !bam_.open(path, err, rt_.header_first != 0)) return false;
+            hdr = &bam_.header();
+        }
+        f.has_rg = hdr->lane_count != 0;
+        rt_ = input_route(f);
+        if (src_ && rt_.hold) { src_->hold((size_t)rt_.hold); f.ended = src_->has_ended(); rt_ = input_route(f); } // (the calling thread holds the stream meanwhile)
+        if (src_ && !route_on_card(rt_)) src_->release(); // the host reader goes on, over {what is held, then the descriptor}; nothing more is kept
+        if (rt_.reader == RD_GPU_BAM && hdr == &bam_.header()) {
+            gpu_->header() = bam_.header(); // (complete once opened on the device)
+            first_record_ = bam_.stream_pos();
+            bam_.close(); // (its read-ahead has inflated the first run of blocks for the header; no more.  Nobody is inside the stream object any more)
+        }
+        if (rt_.reader == RD_GPU_BAM && rt_.source == SRC_RANGE) gpu_->set_range(b0_, b1_);
+        if (rt_.reader == RD_BAM && hdr == &gpu_->header()) return bam_.open_range(path, begin_hint, end_hint, err); // (no @RG line: the host reader, over its range, decides what that means)
+        if (rt_.reader == RD_GPU_SAM_BGZF) {
+            gsam_.start_bgzf(sam_.header(), sam_.ref_index(), sam_.first_record_pos(), path);
+            sam_.close();
+        }
+        return true;
+    }
+    // The device side of a reader on the card (nothing to do for the others): a stream changes hands — descriptor and prefix, by move: the prefix is
+    // the first runs' input — and the reader opens.  false: err, and code says what the caller may do — GpuBamReader::kUnsupported for a BAM file
+    // (the host reader can take a second pass), BQC_ERR_DEVICE for a stream (it cannot be started over) and for SAM text.
+    bool start_card(int device, size_t batch_reads, size_t batch_bases, std::string& err, int& code)
+    {
+        bool ok = true;
+        if (rt_.reader == RD_GPU_BAM) {
+            if (src_) gpu_->set_stream(src_->release_fd(), std::move(src_->held), src_->has_ended());
+            ok = gpu_->open(path_.c_str(), device, gpu_->header(), first_record_, batch_reads, batch_bases, err);
+        } else if (route_gpu_sam(rt_)) {
+            if (src_) gsam_.producer().set_stream(src_->release_fd(), std::move(src_->held), src_->has_ended());
+            ok = gsam_.open(device, batch_reads, batch_bases, err);
+        }
+        code = ok ? 0 : rt_.reader == RD_GPU_BAM && !src_ ? GpuBamReader::kUnsupported : BQC_ERR_DEVICE;
+        started_ = ok && route_on_card(rt_);
+        return ok;
+    }
+    // The reader on the card may launch its first kernel (the caller's own device set-up is done); ctx: the batches' coverage anchors are made on
+    // the card from the first batch on (BQC_DEVICE_ANCHORS=0, or no context: the host's pass, columns and all)
+    void allow(bqc_ctx* ctx)
+    {
+        const char* da = getenv("BQC_DEVICE_ANCHORS");
+        auto go = [&](auto& r) { if (ctx && !(da && da[0] == '0')) r.set_anchor_context(ctx); r.allow_kernels(); };
+        if (rt_.reader == RD_GPU_BAM) go(*gpu_);
+        else if (route_gpu_sam(rt_)) go(gsam_);
+    }
+    const bqc_route& route() const { return rt_; }
+    RecordReader& reader()
+    {
+        if (rt_.reader == RD_GPU_BAM) return *gpu_;
+        if (route_any_gsam(rt_)) return gsam_;
+        return rt_.header_by == HDR_BAM ? static_cast<RecordReader&>(bam_) : sam_;
+    }
+    BamReader& bam() { return bam_; }
+    GpuBamReader& gpu() { return *gpu_; }
+    GpuSamReader& gsam() { return gsam_; }
+    bool on_card() const { return started_; }
+    uint64_t batches_handed_over() const { return rt_.reader == RD_GPU_BAM ? gpu_->batches_handed_over() : route_any_gsam(rt_) ? gsam_.batches_handed_over() : 0; }
+    uint64_t range_begin_block() const { return rt_.reader == RD_GPU_BAM ? b0_ : bam_.range_begin_block(); }
+    uint64_t range_end_block() const { return rt_.reader == RD_GPU_BAM ? b1_ : bam_.range_end_block(); }
+    uint64_t range_first() const { return rt_.reader == RD_GPU_BAM ? gpu_->range_first() : bam_.range_first(); }
+    uint64_t range_over() const { return rt_.reader == RD_GPU_BAM ? gpu_->range_over() : bam_.range_over(); }
+
+private:
+    bqc_route rt_{};
+    std::string path_;
+    BamReader bam_;
+    SamReader sam_;
+    FILE* fp_ = nullptr; // (plain text the host reader reads)
+    GpuSamReader gsam_;
+    std::shared_ptr<BgzfStream> src_;
+    GpuBamReader own_gpu_;
+    GpuBamReader* gpu_;
+    uint64_t b0_ = 0, b1_ = UINT64_MAX, first_record_ = 0;
+    bool started_ = false;
+};
+
+struct bqc_bam {
+    InputOpener in;
+    RecordReader& rd() { return in.reader(); }
+    const BamHeader& hdr() const { return const_cast<bqc_bam*>(this)->rd().header(); }
+    HostBatch hb;
+    bqc_batch view;
+    std::string err;
+    std::vector<std::string> lane_sorted;
+    std::vector<uint32_t> lane_idx;
+    void refresh_lanes()
+    {
+        lane_sorted.clear(); lane_idx.clear();
+        for (auto& kv : rd().header().lane_names) { lane_sorted.push_back(kv.first); lane_idx.push_back(kv.second); }
+    }
+};
+// bqc_bam_open*: *out is set on failure too, so that the message can be read
+static int bam_open_as(RouteCaller caller, const char* path, int device, bool shard, uint64_t begin_hint, uint64_t end_hint, bqc_bam** out)
 {
     if (!path || !out) return BQC_ERR_ARG;
     auto* b = new bqc_bam();
     *out = b;
-    if (const InputKind k = input_kind(path); k == IN_STDIN || k == IN_SAM || k == IN_SAM_BGZF) { b->err = "SAM text cannot be read in shards"; return BQC_ERR_ARG; }
-    if (!shard_blocks(path, begin_hint, end_hint, b->g_b0, b->g_b1, b->err)) { if (b->err.empty()) b->err = "empty shard"; return BQC_ERR_ARG; }
-    if (!b->bam.open(path, b->err, true)) return BQC_ERR_IO; // the header, on the host
-    b->gpu.reset(new GpuBamReader());
-    const uint64_t first_record = b->bam.stream_pos();
-    b->bam.close();
-    b->gpu->set_range(b->g_b0, b->g_b1);
-    if (!b->gpu->open(path, device, b->bam.header(), first_record, 1u << 20, 256u << 20, b->err)) { b->gpu.reset(); return BQC_ERR_DEVICE; }
-    b->gpu->allow_kernels();
+    bqc_route_facts f{};
+    f.caller = caller; f.shard = shard;
+    if (!b->in.open(path, f, begin_hint, end_hint, b->err)) return b->in.route().refuse ? BQC_ERR_ARG : BQC_ERR_IO;
+    int code = 0;
+    if (!b->in.start_card(device, 1u << 20, 256u << 20, b->err, code)) return BQC_ERR_DEVICE;
+    b->in.allow(nullptr);
     b->refresh_lanes();
     return 0;
 }
-extern "C" uint64_t bqc_bam_range_begin_block(const bqc_bam* b) { return b->gpu ? b->g_b0 : b->bam.range_begin_block(); }
-extern "C" uint64_t bqc_bam_range_end_block(const bqc_bam* b) { return b->gpu ? b->g_b1 : b->bam.range_end_block(); }
-extern "C" uint64_t bqc_bam_range_first(const bqc_bam* b) { return b->gpu ? b->gpu->range_first() : b->bam.range_first(); }
-extern "C" uint64_t bqc_bam_range_over(const bqc_bam* b) { return b->gpu ? b->gpu->range_over() : b->bam.range_over(); }
-extern "C" int bqc_bam_on_card(const bqc_bam* b) { return b && (b->gpu || (b->gsam && b->gsam->on_card())) ? 1 : 0; }
-extern "C" uint64_t bqc_bam_batches_handed_over(const bqc_bam* b) { return b && b->gpu ? b->gpu->batches_handed_over() : b && b->gsam ? b->gsam->batches_handed_over() : 0; }
+extern "C" int bqc_bam_open(const char* path, bqc_bam** out) { return bam_open_as(CALLER_LIB_HOST, path, 0, false, 0, 0, out); }
+extern "C" int bqc_bam_open_range(const char* path, uint64_t begin_hint, uint64_t end_hint, bqc_bam** out) { return bam_open_as(CALLER_LIB_HOST, path, 0, true, begin_hint, end_hint, out); }
+extern "C" int bqc_bam_open_gpu(const char* path, int device, bqc_bam** out) { return bam_open_as(CALLER_LIB_CARD, path, device, false, 0, 0, out); }
+extern "C" int bqc_bam_open_gpu_range(const char* path, int device, uint64_t begin_hint, uint64_t end_hint, bqc_bam** out) { return bam_open_as(CALLER_LIB_CARD, path, device, true, begin_hint, end_hint, out); }
+extern "C" uint64_t bqc_bam_range_begin_block(const bqc_bam* b) { return b->in.range_begin_block(); }
+extern "C" uint64_t bqc_bam_range_end_block(const bqc_bam* b) { return b->in.range_end_block(); }
+extern "C" uint64_t bqc_bam_range_first(const bqc_bam* b) { return b->in.range_first(); }
+extern "C" uint64_t bqc_bam_range_over(const bqc_bam* b) { return b->in.range_over(); }
+extern "C" int bqc_bam_on_card(const bqc_bam* b) { return b && b->in.on_card() ? 1 : 0; }
+extern "C" uint64_t bqc_bam_batches_handed_over(const bqc_bam* b) { return b ? b->in.batches_handed_over() : 0; }
 extern "C" uint64_t bqc_file_size(const char* path) { return path ? bgzf_file_size(path) : 0; }
 extern "C" void bqc_gpu_inflate_device(int device) { bgzf_gpu_inflate_device(device); }
 extern "C" uint64_t bqc_gpu_inflated_blocks(void) { return bgzf_gpu_inflated_blocks(); }
@@ -549,8 +523,8 @@ extern "C" int bqc_bam_set_main_chrom(bqc_bam* b, const uint8_t* mc)
 extern "C" int bqc_bam_set_rid_filter(bqc_bam* b, const uint8_t* keep, int keep_unplaced)
 {
     if (!b || !keep) return BQC_ERR_ARG;
-    if (b->is_sam || b->gsam) return BQC_ERR_ARG; // (chromosome sharding needs the BAM reader)
-    b->bam.set_rid_filter(std::vector<uint8_t>(keep, keep + b->hdr().ref_names.size()), keep_unplaced != 0);
+    if (b->in.route().header_by != HDR_BAM) return BQC_ERR_ARG; // (chromosome sharding needs the BAM reader)
+    b->in.bam().set_rid_filter(std::vector<uint8_t>(keep, keep + b->hdr().ref_names.size()), keep_unplaced != 0);
     return 0;
 }
 extern "C" int bqc_bam_next(bqc_bam* b, uint32_t max_reads, uint64_t max_bases, const bqc_batch** out)
@@ -1089,9 +1063,6 @@ struct bqc_session {
 };
 typedef bqc_session Session;
 
-// SAM text on stdin: streams at least this long go to the card.  Measured (profiles/sam_reader_ab.json): whole-program
-// time, host reader against the card, at 1 / 4 / 16 / 64 MB of text — the card is not slower from 64 MB on (0.19 against 0.29 s).
-static const size_t kSamCardFrom = 64u << 20;
 static int run_program(int argc, const char** argv, const ShardArgs* shard, bool host_reader_only = false, Session* S = nullptr)
 {
     ProgramOptions opt;
@@ -1125,135 +1096,35 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     });
     struct InflateOff { ~InflateOff() { bgzf_gpu_inflate_device(-1); bqc_raw_vector_pin_hook = nullptr; } } inflate_off; // (destroyed after the joiner below has joined the thread that sets it)
     struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } warm_joiner{warm};
-    // What the input is: input_kind.  "-": SAM text from stdin, or a BGZF stream; x.sam and x.sam.gz: SAM text, plain and
-    // inside BGZF (the reference opens every path as BAM, bamqualcheck.cpp:252-262: a .sam path fails to open there); anything else: BAM.
-    BamReader bam_rd;
-    SamReader sam_rd;
-    FILE* sam_fp = nullptr; // (a .sam file the host reader reads)
-    struct FpClose { FILE*& f; ~FpClose() { if (f && f != stdin) fclose(f); } } sam_fp_close{sam_fp};
-    GpuSamReader gsam_rd;
+    // The input becomes a reader (InputOpener; DESIGN section 4.5d, "which reader takes it").  The reference opens every path as BAM
+    // (bamqualcheck.cpp:252-262: a .sam path fails to open there).  A stream is held by this thread while the runtime starts beside it; a
+    // BAM file the card takes may still end this pass before anything has been reported (GpuBamReader::kUnsupported), and the program
+    // starts over with the host reader (host_reader_only).
+    InputOpener in(S ? &S->gpu_rd : nullptr);
     std::string err;
-    const InputKind kind = input_kind(opt.bamFile.c_str());
-    const bool from_stdin = kind == IN_STDIN;
-    // SAM text on stdin is decoded on the card (csrc/gpu_sam.hip) unless BQC_GPU_DECODE=0: the reader takes the descriptor from its
-    // first byte.  BQC_GPU_DECODE unset: a stream that ends within its first kSamCardFrom bytes (read here, while the runtime starts) is
-    // parsed on the host from memory, and no device reader is set up.
-    const char* const gd_stdin = getenv("BQC_GPU_DECODE");
     // a failure before the hook is reached must still reach it: the other processes wait for this one
     auto shard_abort = [&]() { if (shard) { bqc_shard_info si{}; si.status = 1; bqc_shard_result sr{}; (void)shard->hook(shard->user, &si, &sr); } return 1; };
-    if (shard && from_stdin) { fprintf(stderr, "ERROR: a stream on stdin cannot be split between processes\n"); return shard_abort(); }
-    if (shard && (kind == IN_SAM || kind == IN_SAM_BGZF)) { fprintf(stderr, "ERROR: SAM text cannot be read in shards\n"); return shard_abort(); } // (the front end of --gpus N says so before it forks)
-    // A BAM stream: an input that is not a regular file, or "-" whose first two bytes are a gzip member's (looked
-    // at inside the bytes the readers take anyway: the reader of SAM text gets them back).  Its header is parsed by the host reader from
-    // bytes that are kept; the card takes the stream, prefix first, or the host reader goes on from where it is.  Nothing is read twice.
-    std::shared_ptr<BgzfStream> bam_stream;
-    std::vector<uint8_t> stdin_first;
-    if (from_stdin && gd_stdin && atoi(gd_stdin) == 0) { // (the host's SAM parser reads stdin through stdio)
-        if (sniff_stdio_bgzf(stdin, stdin_first)) { bam_stream = std::make_shared<BgzfStream>(stdin); bam_stream->preload(stdin_first.data(), stdin_first.size()); }
-    }
-    else if (from_stdin) {
-        sniff_fd(0, stdin_first);
-        if (is_bgzf_magic(stdin_first.data(), stdin_first.size())) { bam_stream = std::make_shared<BgzfStream>(0); bam_stream->preload(stdin_first.data(), stdin_first.size()); }
-    } else if (!shard && (kind == IN_STREAM || (kind == IN_SAM_BGZF && !is_regular_file(opt.bamFile.c_str())))) { // (a FIFO named x.sam.gz is read once too)
-        const int fd = open(opt.bamFile.c_str(), O_RDONLY);
-        if (fd >= 0) bam_stream = std::make_shared<BgzfStream>(fd);
-    }
-    if (bam_stream) stream_test_hold(*bam_stream);
-    // SAM text inside BGZF: by its name, or a BGZF stream by its first inflated bytes — looked at inside what the stream object keeps
-    const bool sam_bgzf = kind == IN_SAM_BGZF || (bam_stream && bgzf_stream_carries(*bam_stream) == BGZF_SAM_TEXT);
-    const bool sam_stdin = (from_stdin && !bam_stream) || kind == IN_SAM; // plain SAM text: stdin, or a path that ends in ".sam"
-    // (plain SAM text goes to the card as a stream does; a regular file by its size against kSamCardFrom — a constant measured for streams,
-    // not for files — instead of holding bytes)
-    uint64_t sam_size = 0;
-    const bool sam_regular = kind == IN_SAM && is_regular_file(opt.bamFile.c_str(), &sam_size);
-    bool use_gsam = sam_stdin && !(gd_stdin && atoi(gd_stdin) == 0) && (!sam_regular || gd_stdin || sam_size >= kSamCardFrom);
-    bool stream_card = false; // the card takes the BAM stream
-    bool sam_bgzf_card = false; // ... or the SAM text inside BGZF, stream or file
-    bool opened;
-    // a shard of the file: its block boundaries are found here (BamReader::open_range finds the same ones: bgzf_find_block is a
-    // function of the hint), so that either reader can take the range
-    uint64_t shard_b0 = 0, shard_b1 = UINT64_MAX;
-    bool shard_gpu = false;
-    if (use_gsam) {
-        const int fd = from_stdin ? 0 : open(opt.bamFile.c_str(), O_RDONLY);
-        if (from_stdin) gsam_rd.preload(stdin_first.data(), stdin_first.size());
-        opened = fd >= 0 && gsam_rd.start(fd, gd_stdin || sam_regular ? 0 : kSamCardFrom, err);
-    }
-    else if (sam_stdin) { sam_fp = from_stdin ? stdin : fopen(opt.bamFile.c_str(), "r"); opened = sam_fp && sam_rd.open(sam_fp, err); }
-    else if (sam_bgzf) {
-        // The header on the host, from bytes that are kept (a stream) or through the reader's small first run (a file); then
-        // the card or the host reader by the rules of a BAM stream: BQC_GPU_DECODE=1 the card, =0 the host, no @RG line the host, unset: the size
-        uint64_t size = 0;
-        const bool card_allowed = !host_reader_only && !(gd_stdin && atoi(gd_stdin) == 0);
-        const bool file_card = !bam_stream && card_allowed && is_regular_file(opt.bamFile.c_str(), &size) && (gd_stdin || size >= kSamBgzfCardFrom);
-        opened = bam_stream ? sam_rd.open_bgzf_stream(bam_stream, err) : sam_rd.open_bgzf(opt.bamFile.c_str(), err);
-        if (opened) sam_bgzf_card = bam_stream ? stream_to_card(sam_rd.header(), *bam_stream, card_allowed, kSamBgzfCardFrom) : file_card && sam_rd.header().lane_count != 0;
-        if (sam_bgzf_card) {
-            gsam_rd.start_bgzf(sam_rd.header(), sam_rd.ref_index(), sam_rd.first_record_pos(), opt.bamFile.c_str());
-            sam_rd.close(); // (its read-ahead has inflated the first run for the header; nobody is inside the stream object any more)
-            use_gsam = true;
-        }
-    }
-    else if (bam_stream) {
-        opened = bam_rd.open_stream(bam_stream, err); // the header (a stream that is no BAM, or ends inside it, fails here in the host reader's words)
-        if (opened) stream_card = bam_stream_to_card(bam_rd, *bam_stream, !host_reader_only); // (the calling thread holds the stream meanwhile: the runtime starts beside it)
-    }
-    else if (shard) { // this process's part of the compressed file
+    bqc_route_facts facts{};
+    facts.caller = CALLER_PROGRAM; facts.host_reader_only = host_reader_only; facts.shard = shard != nullptr;
+    uint64_t shard_lo = 0, shard_hi = UINT64_MAX; // this process's part of the compressed file
+    if (shard) {
         const uint64_t size = bqc_file_size(opt.bamFile.c_str());
-        const uint64_t lo = size / shard->count * shard->index, hi = shard->index + 1 == shard->count ? UINT64_MAX : size / shard->count * (shard->index + 1);
-        const char* gd = getenv("BQC_GPU_DECODE");
-        struct stat st;
-        if (!host_reader_only && !(gd && atoi(gd) == 0) && stat(opt.bamFile.c_str(), &st) == 0 && S_ISREG(st.st_mode)) {
-            std::string e2;
-            // (an empty part, or a small one, is the host reader's: the GPU reader's set-up costs ~50 ms)
-            shard_gpu = shard_blocks(opt.bamFile.c_str(), lo, hi, shard_b0, shard_b1, e2) && (gd || std::min(shard_b1, size) - shard_b0 >= (256ull << 20));
-        }
-        opened = shard_gpu ? bam_rd.open(opt.bamFile.c_str(), err, true) /* the header; the records come from the card */ : bam_rd.open_range(opt.bamFile.c_str(), lo, hi, err);
-    } else {
-        // (a file the GPU reader will probably take: the host reader is only asked for the header — a small first run)
-        const char* gd = getenv("BQC_GPU_DECODE");
-        struct stat st;
-        const bool likely_gpu = !host_reader_only && !(gd && atoi(gd) == 0) && stat(opt.bamFile.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (gd || (uint64_t)st.st_size >= (256ull << 20));
-        opened = bam_rd.open(opt.bamFile.c_str(), err, likely_gpu);
+        shard_lo = size / shard->count * shard->index;
+        if (shard->index + 1 != shard->count) shard_hi = size / shard->count * (shard->index + 1);
     }
+    const bool opened = in.open(opt.bamFile.c_str(), facts, shard_lo, shard_hi, err);
+    const bqc_route& rt = in.route();
+    if (rt.refuse) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return shard_abort(); } // (SAM text: the front end of --gpus N says so before it forks)
     since_launch("input opened");
     if (!opened) {
         fprintf(stderr, "ERROR: Could not open %s for reading.\n", opt.bamFile.c_str()); // bamqualcheck.cpp:265
         return shard_abort();
     }
-    // A BAM file read as a whole is inflated and decoded on the GPU (csrc/gpu_bam.hip): the host reader has read the header, the
-    // records come from the card.  Whatever that reader does not decode itself (a read group that is not in the header, a record
-    // the host reader would report, ...) ends this pass before anything has been reported, and the program starts over with the
-    // host reader (host_reader_only).  BQC_GPU_DECODE=0: the host reader from the start.
-    GpuBamReader own_gpu_rd;
-    GpuBamReader& gpu_rd = S ? S->gpu_rd : own_gpu_rd;
-    if (S) gpu_rd.set_anchor_context(nullptr); // (the context of the job before may not outlive this one's set-up)
-    const char* gd_env = getenv("BQC_GPU_DECODE"); // 1: whenever possible, 0: never; unset: files of 256 MB and more (its set-up costs ~50 ms)
-    bool use_gpu_reader = !sam_stdin && !sam_bgzf && (!shard || shard_gpu) && !host_reader_only && bam_rd.header().lane_count != 0 && !(gd_env && atoi(gd_env) == 0);
-    if (shard && shard_gpu && !use_gpu_reader) { // (no @RG line: the host reader, over its range, decides what that means)
-        bam_rd.~BamReader();
-        new (&bam_rd) BamReader();
-        const uint64_t size = bqc_file_size(opt.bamFile.c_str());
-        const uint64_t lo = size / shard->count * shard->index, hi = shard->index + 1 == shard->count ? UINT64_MAX : size / shard->count * (shard->index + 1);
-        if (!bam_rd.open_range(opt.bamFile.c_str(), lo, hi, err)) { fprintf(stderr, "ERROR: Could not open %s for reading.\n", opt.bamFile.c_str()); return shard_abort(); }
-        shard_gpu = false;
-    }
-    if (bam_stream) use_gpu_reader = stream_card; // (false for SAM text inside BGZF: that is the reader of SAM text's)
-    else if (use_gpu_reader && !shard) { // a regular file: the reader opens it a second time
-        struct stat st;
-        use_gpu_reader = stat(opt.bamFile.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (gd_env || (uint64_t)st.st_size >= (256ull << 20));
-    }
-    uint64_t first_record_u = 0;
-    if (use_gpu_reader) {
-        first_record_u = bam_rd.stream_pos();
-        bam_rd.close(); // (its read-ahead has inflated the first run of blocks for the header; no more)
-        if (shard) gpu_rd.set_range(shard_b0, shard_b1);
-        bqc_raw_vector_free_hook = pin_free_hook;
-        bqc_raw_vector_pin_hook = pin_hook;
-    }
-    const bool gsam_card = sam_bgzf_card || (use_gsam && gsam_rd.header().lane_count != 0 && (gd_stdin || !gsam_rd.stream_ended()));
-    RecordReader& rd = use_gsam ? static_cast<RecordReader&>(gsam_rd) : sam_stdin || sam_bgzf ? static_cast<RecordReader&>(sam_rd) : use_gpu_reader ? static_cast<RecordReader&>(gpu_rd) : static_cast<RecordReader&>(bam_rd);
-    if (use_gpu_reader) gpu_rd.header() = bam_rd.header(); // (complete once opened, in the decode thread: the device is not up yet)
+    GpuBamReader& gpu_rd = in.gpu();
+    GpuSamReader& gsam_rd = in.gsam();
+    const bool bam_on_card = rt.reader == RD_GPU_BAM;
+    if (bam_on_card) { bqc_raw_vector_free_hook = pin_free_hook; bqc_raw_vector_pin_hook = pin_hook; } // (the reader page-locks the buffers the card copies into)
+    RecordReader& rd = in.reader();
     if (!shard || shard->index == 0) {
         FILE* of = fopen(opt.outputFile.c_str(), "wb"); // opened (truncated) before the scan, :278-283
         if (!of) { fprintf(stderr, "ERROR: Could not open output file %s\n", opt.outputFile.c_str()); return shard_abort(); }
@@ -1301,7 +1172,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     } spare_loan{Q, S};
     size_t n_spare_kept = 0;
     if (S) { n_spare_kept = S->spare.size(); Q.spare = std::move(S->spare); S->spare.clear(); }
-    struct ReaderEnd { GpuBamReader& r; bool on; ~ReaderEnd() { if (on) r.end_file(); } } reader_end{gpu_rd, S && use_gpu_reader}; // (the file is over on every way out)
+    struct ReaderEnd { GpuBamReader& r; bool on; ~ReaderEnd() { if (on) r.end_file(); } } reader_end{gpu_rd, S && bam_on_card}; // (the file is over on every way out)
     std::atomic<bool> gpu_reader_opened{false};
     std::thread dec;
     auto stop_decoder = [&]() {
@@ -1311,28 +1182,17 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         dec.join();
     };
     if (H.lane_count != 0) dec = std::thread([&]() {
-        if (use_gpu_reader) {
+        if (route_on_card(rt)) { // the device side of the reader opens here, beside the FASTA file and the context
             std::string e;
-            if (bam_stream) gpu_rd.set_stream(bam_stream->release_fd(), std::move(bam_stream->held), bam_stream->has_ended()); // (by move: the prefix is the first runs' input)
-            const bool ok = gpu_rd.open(opt.bamFile.c_str(), opt.device, gpu_rd.header(), first_record_u, opt.batch_reads, 256ull << 20, e);
+            int code = 0;
+            const bool ok = in.start_card(opt.device, opt.batch_reads, 256ull << 20, e, code);
             gpu_reader_opened = true; // (the context is created after this: see there)
             if (!ok) {
                 std::lock_guard<std::mutex> lk(Q.m);
-                Q.err = e; Q.err_code = bam_stream ? BQC_ERR_DEVICE : GpuBamReader::kUnsupported; Q.done = true; Q.cv.notify_all(); // (a stream cannot be started over)
+                Q.err = e; Q.err_code = code; Q.done = true; Q.cv.notify_all();
                 return;
             }
-            gpu_rd.set_main_chrom(main_chrom);
-        }
-        if (gsam_card) {
-            std::string e;
-            if (sam_bgzf_card && bam_stream) gsam_rd.producer().set_stream(bam_stream->release_fd(), std::move(bam_stream->held), bam_stream->has_ended()); // (as a BAM stream's: the prefix is the first runs' input)
-            const bool ok = gsam_rd.open(opt.device, opt.batch_reads, 256ull << 20, e);
-            gpu_reader_opened = true;
-            if (!ok) {
-                std::lock_guard<std::mutex> lk(Q.m);
-                Q.err = e; Q.err_code = BQC_ERR_DEVICE; Q.done = true; Q.cv.notify_all();
-                return;
-            }
+            rd.set_main_chrom(main_chrom);
         }
         for (;;) {
             std::unique_ptr<HostBatch> hb;
@@ -1458,18 +1318,9 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     // stream at this point, as a rule): a thread of its own says so, this one goes on to the references.
     std::thread allow_thr;
     struct AllowJoiner { std::thread& t; ~AllowJoiner() { if (t.joinable()) t.join(); } } allow_joiner{allow_thr};
-    if (use_gpu_reader) allow_thr = std::thread([&gpu_reader_opened, &gpu_rd, ctx, rc] {
+    if (route_on_card(rt)) allow_thr = std::thread([&gpu_reader_opened, &in, ctx, rc] {
         while (!gpu_reader_opened.load()) std::this_thread::sleep_for(std::chrono::microseconds(100));
-        // the batches' coverage anchors are made on the card from the first batch on (BQC_DEVICE_ANCHORS=0: the host's pass, columns and all)
-        const char* da = getenv("BQC_DEVICE_ANCHORS");
-        if (!rc && ctx && !(da && da[0] == '0')) gpu_rd.set_anchor_context(ctx);
-        gpu_rd.allow_kernels(); // (the context exists: the card may get busy)
-    });
-    if (gsam_card) allow_thr = std::thread([&gpu_reader_opened, &gsam_rd, ctx, rc] { // (the same for the reader of SAM text)
-        while (!gpu_reader_opened.load()) std::this_thread::sleep_for(std::chrono::microseconds(100));
-        const char* da = getenv("BQC_DEVICE_ANCHORS");
-        if (!rc && ctx && !(da && da[0] == '0')) gsam_rd.set_anchor_context(ctx);
-        gsam_rd.allow_kernels();
+        in.allow(rc ? nullptr : ctx); // (the context exists: the card may get busy)
     });
     const auto t_create = clk::now();
     // where a context goes on every way out: back to the session (the next job resets it, or takes its contigs, or destroys it)
@@ -1620,7 +1471,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
             // reader, which then prints them itself — i.e. behind the loop and in front of a record error: the lines of the batches BEFORE
             // a failing record all come first, where the reference interleaves them with nothing either; the failing batch's own lines
             // are the host decoder's to print)
-            if (use_gpu_reader) { n_noqual_deferred += n_noqual; n_noqual = 0; }
+            if (bam_on_card) { n_noqual_deferred += n_noqual; n_noqual = 0; }
             if (n_noqual) {
                 static const char msg[] = "ERROR: length of sequence and quality is not the same\n";
                 std::string out;
@@ -1657,9 +1508,9 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (ref_loader.joinable()) ref_loader.join();
     if (!status && (rc = bqc_sync(ctx))) { note_rc(rc); fprintf(stderr, "%s\n", bqc_last_error(ctx)); status = 1; } // what the device found in the last batches
     dec.join();
-    if (S && use_gpu_reader) gpu_rd.end_file(); // (its threads are gone and its streams idle: what it holds can be told, and the next file may open it)
+    if (S && bam_on_card) gpu_rd.end_file(); // (its threads are gone and its streams idle: what it holds can be told, and the next file may open it)
     note_rc(Q.err_code);
-    if (timing) fprintf(stderr, "[timing] records decoded %s\n", use_gpu_reader ? "on the GPU (csrc/gpu_bam.hip)" : gsam_card ? (sam_bgzf_card ? "on the GPU (csrc/gpu_inflate.hip + csrc/gpu_sam.hip)" : "on the GPU (csrc/gpu_sam.hip)") : "on the host");
+    if (timing) fprintf(stderr, "[timing] records decoded %s\n", bam_on_card ? "on the GPU (csrc/gpu_bam.hip)" : rt.reader == RD_GPU_SAM_BGZF ? "on the GPU (csrc/gpu_inflate.hip + csrc/gpu_sam.hip)" : rt.reader == RD_GPU_SAM ? "on the GPU (csrc/gpu_sam.hip)" : "on the host");
     if (timing) { // (every buffer of the run exists at this point: what is in use now is the run's peak)
         size_t free_b = 0, total_b = 0, pinned = 0;
         { std::lock_guard<std::mutex> lk(g_pins.m); for (auto& kv : g_pins.blocks) pinned += kv.second; }
@@ -1668,25 +1519,25 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     }
     if (timing && refs_beside_loop) fprintf(stderr, "[timing] references uploaded beside the record loop; the submitting thread waited %.3f s for them\n", t_wait_refs);
     if (timing && lazy_refs) fprintf(stderr, "[timing] %u of %u contigs loaded, when their first reads arrived: %.3f s\n", n_lazy_refs, n_refs, t_lazy_refs);
-    if (timing && use_gpu_reader) fprintf(stderr, "[timing] %llu batches anchored on the card (fixed columns never on the host) of %llu batches\n", (unsigned long long)gpu_rd.batches_anchored(), (unsigned long long)gpu_rd.batches());
-    if (timing && use_gpu_reader)
-        fprintf(stderr, bam_stream ? "[timing] reader on the card: a stream, read() and waiting for it %.2f s in its one reader thread, the producer waited %.2f s for chunks, the decode thread waited %.2f s for inflated runs\n"
+    if (timing && bam_on_card) fprintf(stderr, "[timing] %llu batches anchored on the card (fixed columns never on the host) of %llu batches\n", (unsigned long long)gpu_rd.batches_anchored(), (unsigned long long)gpu_rd.batches());
+    if (timing && bam_on_card)
+        fprintf(stderr, rt.stream ? "[timing] reader on the card: a stream, read() and waiting for it %.2f s in its one reader thread, the producer waited %.2f s for chunks, the decode thread waited %.2f s for inflated runs\n"
                                    : "[timing] reader on the card: pread %.2f s summed over its reader threads, the producer waited %.2f s for them, the decode thread waited %.2f s for inflated runs\n",
                 gpu_rd.seconds_reading(), gpu_rd.seconds_producer_waiting_for_chunks(), gpu_rd.seconds_waiting_for_runs());
-    if (timing && sam_bgzf_card)
+    if (timing && rt.reader == RD_GPU_SAM_BGZF)
         fprintf(stderr, "[sam reader] text inflated on the card: %s %.2f s in the producer's reader thread%s, the producer waited %.2f s for chunks, the decode thread waited %.2f s for inflated runs\n",
-                bam_stream ? "a stream, read() and waiting for it" : "pread", gsam_rd.seconds_producer_reading(), bam_stream ? "" : "s (summed)", gsam_rd.seconds_producer_waiting_for_chunks(), gsam_rd.seconds_waiting_for_runs());
-    if (timing && use_gsam) {
+                rt.stream ? "a stream, read() and waiting for it" : "pread", gsam_rd.seconds_producer_reading(), rt.stream ? "" : "s (summed)", gsam_rd.seconds_producer_waiting_for_chunks(), gsam_rd.seconds_waiting_for_runs());
+    if (timing && route_any_gsam(rt)) {
         fprintf(stderr, "[sam reader] %llu batches on the card, %llu handed over, %llu anchored\n", (unsigned long long)gsam_rd.batches(), (unsigned long long)gsam_rd.batches_handed_over(),
                 (unsigned long long)gsam_rd.batches_anchored());
         fprintf(stderr, "[sam reader] read() %.3f s in the reader thread; the decode thread waited %.3f s for input, copied text for %.3f s, ran kernels for %.3f s\n", gsam_rd.seconds_reading(),
                 gsam_rd.seconds_waiting_for_input(), gsam_rd.seconds_copying(), gsam_rd.seconds_in_kernels());
     }
-    if (timing && use_gpu_reader && gpu_rd.batches_handed_over()) fprintf(stderr, "[timing] %llu batches held records the card does not decode and went through the host decoder\n", (unsigned long long)gpu_rd.batches_handed_over());
+    if (timing && bam_on_card && gpu_rd.batches_handed_over()) fprintf(stderr, "[timing] %llu batches held records the card does not decode and went through the host decoder\n", (unsigned long long)gpu_rd.batches_handed_over());
     if (timing)
         fprintf(stderr, "[timing] %llu records: decode thread busy %.2f s, submit thread (host pass + enqueue; page-locking %.2f s) %.2f s, waiting for the decoder %.2f s, loop %.2f s\n",
                 (unsigned long long)n_total, t_decode, g_pins.t_register, t_submit, t_wait, secs(t_setup, clk::now()));
-    if (Q.err_code == GpuBamReader::kUnsupported && bam_stream) { // (cannot happen: the reader decides a stream's records itself — and there is no second pass over a stream)
+    if (Q.err_code == GpuBamReader::kUnsupported && rt.stream) { // (cannot happen: the reader decides a stream's records itself — and there is no second pass over a stream)
         fprintf(stderr, "ERROR: internal error: the reader on the card gave up a stream (%s)\n", Q.err.c_str());
         Q.err_code = 0; status = 1;
     }
@@ -1701,7 +1552,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     }
     if (timing && S) // what this job found in place: facts, told when everything it needed exists
         fprintf(stderr, "[timing] job %u of %u: context %s, %u of %u contigs already on the card, reader buffers %s\n", S->job, std::max(S->job, S->n_jobs), (S->started_over ? S->first_ctx_kept : ctx_kept) ? "kept" : "created",
-                S->started_over ? S->first_contigs : contigs_before, n_refs, use_gpu_reader ? gpu_rd.buffers_report() : n_spare_kept ? "kept" : "new");
+                S->started_over ? S->first_contigs : contigs_before, n_refs, bam_on_card ? gpu_rd.buffers_report() : n_spare_kept ? "kept" : "new");
     for (uint64_t k = 0; k < n_noqual_deferred; ++k) fputs("ERROR: length of sequence and quality is not the same\n", stderr);
     if (!status && Q.err_code) {
         if (Q.err_code == BQC_ERR_IO) fprintf(stderr, "ERROR: Could not read record from BAM File %s\n", opt.bamFile.c_str()); // :308
@@ -1715,8 +1566,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (shard) { // what needs the other processes: split check, coverage hand-over, sum of the state vectors, lane names
         bqc_shard_info si{};
         si.ctx = ctx; si.status = status;
-        if (use_gpu_reader) { si.begin_block = shard_b0; si.end_block = shard_b1; si.first = gpu_rd.range_first(); si.over = gpu_rd.range_over(); }
-        else { si.begin_block = bam_rd.range_begin_block(); si.end_block = bam_rd.range_end_block(); si.first = bam_rd.range_first(); si.over = bam_rd.range_over(); }
+        si.begin_block = in.range_begin_block(); si.end_block = in.range_end_block(); si.first = in.range_first(); si.over = in.range_over();
         si.sample_id = rd.header().sample_id.c_str();
         si.n_lane_names = (uint32_t)names.size(); si.lane_names = names.data(); si.lane_index = idx.data();
         bqc_shard_result sr{};

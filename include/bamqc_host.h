@@ -57,7 +57,7 @@ int bqc_sam_write(const char* path, const bqc_batch* b, uint32_t n_refs, const c
 
 /* ---- BAM / FASTA input (replaces SeqAn BamStream / SequenceStream) --------- */
 typedef struct bqc_bam bqc_bam;
-/* What a path is, for this function, bqc_bam_open_gpu and the program alike (one function of the driver states it):
+/* What a path is, for this function, bqc_bam_open_gpu and the program alike (input_kind states it, host/input_route.h):
  *   - a path that ends in ".sam" is plain SAM text, whatever kind of file it is (a FIFO too: read once, as ever);
  *   - a path that ends in ".sam.gz" is SAM text inside BGZF (bgzip, samtools view -O sam,level=N), whatever kind of file it is; plain
  *     gzip — one serial DEFLATE stream without BGZF's BC subfield — is not read: it fails to open in the BGZF layer's words;
