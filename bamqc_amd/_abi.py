@@ -41,7 +41,7 @@ class Options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_lanes", C.c_uint32), ("n_refs", C.c_uint32),
                 ("isize", C.c_int32), ("max_read_len", C.c_uint32), ("hist_cap", C.c_uint32),
                 ("main_chrom", u8p), ("fasta_index", i32p), ("device", C.c_int32),
-                ("sketch", SketchOptions), ("shard_tail", C.c_uint32)]
+                ("sketch", SketchOptions), ("shard_tail", C.c_uint32), ("qual_by_cycle", C.c_uint32)]
 
 
 class Batch(C.Structure):
@@ -99,6 +99,10 @@ class ShardResult(C.Structure):
 
 SHARD_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(ShardInfo), C.POINTER(ShardResult))
 SHARD_FAIL, SHARD_DONE, SHARD_FALLBACK, SHARD_WRITE = 0, 1, 2, 3  # (0 is what ctypes returns for a callback that raised)
+
+
+class QbcView(C.Structure):  # bqc_qbc_view: element [c][q] is hist[c * stride + q]
+    _fields_ = [("n_cycles", C.c_uint32), ("n_q", C.c_uint32), ("stride", C.c_uint32), ("hist", u64p)]
 
 
 class HeaderInfo(C.Structure):
@@ -166,7 +170,7 @@ def make_batch(cols):
 
 
 def make_options(n_lanes=1, n_refs=1, isize=1000, max_read_len=1024, hist_cap=4096, main_chrom=None,
-                 fasta_index=None, device=0, klist=(), qlist=(), e=0.01, seed=1, shard_tail=0):
+                 fasta_index=None, device=0, klist=(), qlist=(), e=0.01, seed=1, shard_tail=0, qual_by_cycle=0):
     keep = {}
     o = Options()
     o.struct_size = C.sizeof(Options)
@@ -189,6 +193,7 @@ def make_options(n_lanes=1, n_refs=1, isize=1000, max_read_len=1024, hist_cap=40
         o.sketch.qlist = _ptr(ql, u32p)
     o.sketch.e, o.sketch.seed = e, seed
     o.shard_tail = 1 if shard_tail else 0
+    o.qual_by_cycle = qual_by_cycle  # per-cycle base quality histograms: 0 = off, else the cycle capacity N
     return o, keep
 
 

@@ -116,9 +116,8 @@ class Aggregator:
     def finalize(self):
         return _abi.counts_to_dict(self.finalize_raw())
 
-    def write_bamqc(self, path, sample_id="", lane_names=("",), lane_index=None):
-        if self._counts is None:
-            self.finalize_raw()
+    @staticmethod
+    def _header(sample_id, lane_names, lane_index):
         hdr = _abi.HeaderInfo()
         names = (C.c_char_p * len(lane_names))(*[n.encode() for n in lane_names])
         idx = np.ascontiguousarray(lane_index if lane_index is not None else np.arange(len(lane_names)), np.uint32)
@@ -126,7 +125,31 @@ class Aggregator:
         hdr.n_names = len(lane_names)
         hdr.lane_names = names
         hdr.lane_index = idx.ctypes.data_as(_abi.u32p)
+        return hdr, (names, idx)
+
+    def write_bamqc(self, path, sample_id="", lane_names=("",), lane_index=None):
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_bamqc(self._counts, C.byref(hdr), path.encode()))
+
+    def qual_by_cycle(self, lane=0, mate=0):
+        """The per-cycle base quality histogram of a read group and mate (0 first, 1 second) as a (n_cycles, n_q) uint64 array
+        (option qual_by_cycle=N; valid after finalize)."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.QbcView()
+        self._chk(self.lib.bqc_qual_by_cycle(self.h, lane, mate, C.byref(v)))
+        if v.n_cycles == 0 or v.n_q == 0:
+            return np.zeros((v.n_cycles, v.n_q), np.uint64)
+        rows = np.ctypeslib.as_array(v.hist, shape=(v.n_cycles, v.stride))
+        return rows[:, :v.n_q].copy()
+
+    def write_qual_by_cycle(self, path, sample_id="", lane_names=("",), lane_index=None):
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        self._chk(self.lib.bqc_write_qual_by_cycle(self.h, C.byref(hdr), path.encode()))
 
     def close(self):
         if self.h:

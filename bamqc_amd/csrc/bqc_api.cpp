@@ -7,6 +7,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +25,7 @@ extern "C" {
 void bqc_launch_cov_final(const StateLayout&, uint64_t*, const uint32_t* carry, const uint32_t* parity, const uint8_t* started, const uint8_t* sel, uint32_t count_start, hipStream_t);
 void bqc_launch_ref_nibbles(const uint8_t* dna5, uint64_t len, uint32_t* out, uint64_t n_dwords, hipStream_t);
 uint32_t bqc_long_slots_cap(uint32_t max_read_len, uint32_t n_cu);
+uint64_t bqc_qcyc_words(uint32_t n_lanes, uint32_t N);
 hipError_t bqc_long_init();
 hipError_t bqc_short_init();
 }
@@ -70,17 +72,21 @@ static int reset_stream_records(bqc_ctx* c)
 extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
 {
     if (!opt || !out) return fail(nullptr, BQC_ERR_ARG, "bqc_create: null argument");
-    if (opt->struct_size != sizeof(bqc_options)) return fail(nullptr, BQC_ERR_ARG, "bqc_create: struct_size mismatch");
+    // (with qual_by_cycle, which lies in the former tail padding, or cut off in front of it: the module is off then)
+    if (opt->struct_size != sizeof(bqc_options) && opt->struct_size != offsetof(bqc_options, qual_by_cycle)) return fail(nullptr, BQC_ERR_ARG, "bqc_create: struct_size mismatch");
+    const uint32_t qbc_n = opt->struct_size > offsetof(bqc_options, qual_by_cycle) ? opt->qual_by_cycle : 0u;
     if (opt->n_lanes == 0 || opt->n_lanes > 256) return fail(nullptr, BQC_ERR_ARG, "bqc_create: n_lanes must be 1..256");
     if (opt->isize < 0) return fail(nullptr, BQC_ERR_ARG, "bqc_create: negative insert size");
     if (opt->max_read_len == 0 || opt->hist_cap == 0) return fail(nullptr, BQC_ERR_ARG, "bqc_create: zero capacity");
     if (opt->n_refs && !opt->main_chrom) return fail(nullptr, BQC_ERR_ARG, "bqc_create: main_chrom missing");
+    if (qbc_n > opt->max_read_len || qbc_n >= 1u << 30) return fail(nullptr, BQC_ERR_ARG, "bqc_create: qual_by_cycle %u exceeds max_read_len %u", qbc_n, opt->max_read_len);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, BQC_ERR_DEVICE, "bqc_create: no HIP device available (this library has no CPU fallback)");
     if (opt->device < 0 || opt->device >= ndev) return fail(nullptr, BQC_ERR_DEVICE, "bqc_create: device %d out of range", opt->device);
     bqc_ctx* c = new bqc_ctx();
-    c->opt = *opt;
+    memcpy(&c->opt, opt, std::min<size_t>(opt->struct_size, sizeof(bqc_options)));
+    c->opt.qual_by_cycle = qbc_n;
     c->device = opt->device;
     uint32_t nr = opt->n_refs ? opt->n_refs : 1;
     c->main_chrom.assign(nr, 0);
@@ -164,6 +170,20 @@ extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
         std::string e;
         c->sketch = sketch_create(opt->sketch, opt->n_lanes, c->stream, e);
         if (!c->sketch) { fail(nullptr, BQC_ERR_ARG, "bqc_create: sketch: %s", e.c_str()); bqc_destroy(c); return BQC_ERR_ARG; }
+    }
+    if (qbc_n) { // refused before allocating when it does not fit, as the sketch's tables are (1 GiB stays for the rest of the context)
+        c->qcyc_words = bqc_qcyc_words(opt->n_lanes, qbc_n);
+        size_t free_b = 0, total_b = 0;
+        CCHK(hipMemGetInfo(&free_b, &total_b));
+        if (c->qcyc_words * 8 + (1ull << 30) > free_b) {
+            fail(nullptr, BQC_ERR_ARG, "bqc_create: qual_by_cycle %u needs %llu bytes of tables (%u read groups x 2 x %u cycles x 224 qualities x 8 bytes), the device has %zu bytes free (%llu kept for the rest of the context)",
+                 qbc_n, (unsigned long long)(c->qcyc_words * 8), opt->n_lanes, qbc_n, free_b, 1ull << 30);
+            bqc_destroy(c);
+            return BQC_ERR_ARG;
+        }
+        CCHK(hipMalloc(&c->d_qcyc, c->qcyc_words * 8));
+        CCHK(hipMemsetAsync(c->d_qcyc, 0, c->qcyc_words * 8, c->stream));
+        CCHK(hipStreamSynchronize(c->stream));
     }
     cstamp(4);
     for (int i = 0; i < 16; ++i) {
@@ -270,6 +290,7 @@ extern "C" void bqc_destroy(bqc_ctx* c)
 
     (void)hipFree(c->d_refn_ptrs);
     if (c->sketch) sketch_destroy(c->sketch);
+    if (c->d_qcyc) (void)hipFree(c->d_qcyc);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
     (void)hipFree(c->d_started); (void)hipFree(c->d_ref_ptrs); (void)hipFree(c->d_ref_len); (void)hipFree(c->d_main);
     for (auto e : c->ev) (void)hipEventDestroy(e);
@@ -380,6 +401,8 @@ extern "C" int bqc_reset(bqc_ctx* c)
     HIPCHK(c, hipMemsetAsync(c->d_parity, 0, ((size_t)c->opt.n_lanes + 1) * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_started, 0, c->opt.n_lanes, c->stream));
     if (c->sketch) sketch_reset(c->sketch, c->stream);
+    if (c->d_qcyc) HIPCHK(c, hipMemsetAsync(c->d_qcyc, 0, c->qcyc_words * 8, c->stream));
+    c->qcyc_final = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -426,7 +449,9 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-extern "C" uint64_t bqc_state_words(const bqc_ctx* c) { return c ? c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0) : 0; }
+// the flat vector: [sl.words][sketch][qual by cycle]
+static uint64_t qcyc_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+extern "C" uint64_t bqc_state_words(const bqc_ctx* c) { return c ? qcyc_offset(c) + c->qcyc_words : 0; }
 
 extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
 {
@@ -436,6 +461,7 @@ extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
+    if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -447,6 +473,7 @@ extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
+    if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync(c->d_qcyc, (const uint64_t*)src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->flushed = true; // an imported vector is already flushed
     return 0;
@@ -468,6 +495,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
         HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_qcyc) HIPCHK(c, hipMemcpy(dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
@@ -487,6 +515,7 @@ extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_qcyc) HIPCHK(c, hipMemcpy(c->d_qcyc, src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyHostToDevice));
     c->flushed = true;
     return 0;
 }
@@ -574,8 +603,37 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
             L.sketch = c->sk_out[l].data();
         }
     }
+    if (c->d_qcyc) { // the printed sizes follow from the sums: cycles from the mate's read lengths, qualities from the table itself
+        const uint32_t N = c->opt.qual_by_cycle;
+        c->h_qcyc.resize(c->qcyc_words);
+        HIPCHK(c, hipMemcpy(c->h_qcyc.data(), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToHost));
+        c->qcyc_ncyc.assign((size_t)sl.n_lanes * 2, 0);
+        c->qcyc_nq.assign((size_t)sl.n_lanes * 2, 0);
+        for (uint32_t l = 0; l < sl.n_lanes; ++l)
+            for (uint32_t m = 0; m < 2; ++m) {
+                const uint64_t* H = c->h_qcyc.data() + ((uint64_t)l * 2 + m) * N * 224;
+                uint32_t nq = 0;
+                for (uint32_t cy = 0; cy < N; ++cy) nq = std::max(nq, last_nonzero_len(H + (uint64_t)cy * 224, 224));
+                c->qcyc_ncyc[l * 2 + m] = std::min(N, c->lanes[l].mate[m].n_cycles);
+                c->qcyc_nq[l * 2 + m] = nq;
+            }
+        c->qcyc_final = true;
+    }
     c->counts.n_lanes = sl.n_lanes;
     c->counts.lanes = c->lanes.data();
     *out = &c->counts;
+    return 0;
+}
+
+extern "C" int bqc_qual_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_qbc_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_qcyc) return fail(c, BQC_ERR_STATE, "bqc_qual_by_cycle: the context was created without qual_by_cycle");
+    if (!c->qcyc_final) return fail(c, BQC_ERR_STATE, "bqc_qual_by_cycle: nothing has been finalised");
+    if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_qual_by_cycle: lane %u / mate %u out of range", lane, mate);
+    out->n_cycles = c->qcyc_ncyc[lane * 2 + mate];
+    out->n_q = c->qcyc_nq[lane * 2 + mate];
+    out->stride = 224;
+    out->hist = c->h_qcyc.data() + ((uint64_t)lane * 2 + mate) * c->opt.qual_by_cycle * 224;
     return 0;
 }

@@ -203,6 +203,12 @@ struct bqc_ctx {
     AnchorEngine anchor;
     // sketch (N1)
     SketchDevice* sketch = nullptr;
+    // per-cycle base quality histograms (k_qcyc.hip; bqc_options.qual_by_cycle = N, 0: off — nothing below exists then)
+    uint64_t* d_qcyc = nullptr;        // [n_lanes][2][N][224], the module's words of the state vector (behind the sketch's)
+    uint64_t qcyc_words = 0;
+    std::vector<uint64_t> h_qcyc;      // bqc_finalize's copy, and per (lane, mate) the printed sizes
+    std::vector<uint32_t> qcyc_ncyc, qcyc_nq;
+    bool qcyc_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -32,6 +32,7 @@ uint32_t bqc_short_parts();
 void bqc_launch_t8_fold(const uint32_t* t8rows, const uint32_t* t8_used, uint32_t n_slots, const StateLayout&, uint64_t* state, uint32_t lane, hipStream_t);
 void bqc_launch_err_merge(ErrRec* dst, const ErrRec* src, hipStream_t);
 void bqc_launch_cov_final(const StateLayout&, uint64_t*, const uint32_t* carry, const uint32_t* parity, const uint8_t* started, const uint8_t* sel, uint32_t count_start, hipStream_t);
+void bqc_launch_qcyc(const DevBatch&, uint64_t* hist, uint32_t N, uint32_t n_lanes, uint32_t n_cu, uint32_t n_long, uint32_t longest, hipStream_t);
 }
 
 using clk = std::chrono::steady_clock;
@@ -608,6 +609,7 @@ static int enqueue_batch(bqc_ctx* c, BatchMem& m, bool& forked)
         tick(c, "k_cov");
     }
     if (c->sketch) { sketch_process(c->sketch, d, c->stream); tick(c, "k_sketch"); }
+    if (c->d_qcyc) { bqc_launch_qcyc(d, c->d_qcyc, c->opt.qual_by_cycle, c->opt.n_lanes, c->n_cu, m.n_slow, m.max_len_slow, c->stream); tick(c, "k_qcyc"); }
     if (side) { // the join, behind everything the compute stream has of this batch but its last launch
         const int rc = cov_join(c, forked);
         if (rc) return rc;

@@ -69,6 +69,14 @@ void avgqual(Out& o, const char* key, const bqc_mate_counts& m)
     for (uint32_t i = 0; i < m.n_cycles; ++i) { o.s.push_back(' '); o.dbl((double)m.qualcount[i] / nr); }
     o.s.push_back('\n');
 }
+int write_file(const Out& o, const char* path)
+{
+    FILE* f = fopen(path, "wb");
+    if (!f) return BQC_ERR_IO;
+    size_t w = fwrite(o.s.data(), 1, o.s.size(), f);
+    int rc = fclose(f);
+    return (w == o.s.size() && rc == 0) ? 0 : BQC_ERR_IO;
+}
 } // namespace
 
 extern "C" int bqc_write_bamqc(const bqc_counts* counts, const bqc_header_info* hdr, const char* path)
@@ -145,9 +153,32 @@ extern "C" int bqc_write_bamqc(const bqc_counts* counts, const bqc_header_info* 
                 o.array(key.c_str(), row.data(), 64);
             }
     }
-    FILE* f = fopen(path, "wb");
-    if (!f) return BQC_ERR_IO;
-    size_t w = fwrite(o.s.data(), 1, o.s.size(), f);
-    int rc = fclose(f);
-    return (w == o.s.size() && rc == 0) ? 0 : BQC_ERR_IO;
+    return write_file(o, path);
+}
+
+// The per-cycle base quality histograms as text (include/bamqc.h): per lane and mate a key line with the table's sizes, then one line
+// of n_q counts per cycle.
+extern "C" int bqc_write_qual_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path)
+{
+    if (!ctx || !hdr || !path) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 16);
+    static const char* keys[2] = {"base_qual_histogram_by_position_first", "base_qual_histogram_by_position_second"};
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        for (uint32_t m = 0; m < 2; ++m) {
+            bqc_qbc_view v;
+            const int rc = bqc_qual_by_cycle(ctx, hdr->lane_index[n], m, &v);
+            if (rc) return rc;
+            o.str(keys[m]); o.s.push_back(' '); o.u64(v.n_cycles); o.s.push_back(' '); o.u64(v.n_q); o.s.push_back('\n');
+            if (!v.n_q) continue; // no counted base: no rows
+            for (uint32_t c = 0; c < v.n_cycles; ++c) {
+                const uint64_t* row = v.hist + (uint64_t)c * v.stride;
+                for (uint32_t q = 0; q < v.n_q; ++q) { if (q) o.s.push_back(' '); o.u64(row[q]); }
+                o.s.push_back('\n');
+            }
+        }
+    }
+    return write_file(o, path);
 }

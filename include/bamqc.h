@@ -103,6 +103,10 @@ typedef struct bqc_options {
     bqc_sketch_options sketch;
     uint32_t shard_tail;       /* 1: this context processes a shard of the record stream that does NOT begin with the
                                   stream's first record (multi-GPU, see bqc_shard_resolve)              */
+    uint32_t qual_by_cycle;    /* per-cycle base quality histograms (bqc_qual_by_cycle): 0 = off, else the cycle capacity N,
+                                  1 <= N <= max_read_len; cycles at or behind N of a longer read are not counted.  (The field
+                                  lies in what was the structure's tail padding: bqc_create takes the structure with or
+                                  without it, and a caller that cleared the structure has the module off.)        */
 } bqc_options;
 
 /* ---- input batch (host, structure of arrays) -------------------------------
@@ -327,6 +331,23 @@ typedef struct bqc_header_info {
     const uint32_t* lane_index;     /* index into counts->lanes for each name               */
 } bqc_header_info;
 int bqc_write_bamqc(const bqc_counts* counts, const bqc_header_info* hdr, const char* path);
+
+/* ---- per-cycle base quality histograms (bqc_options.qual_by_cycle; not in the reference) -----------------------
+ * H[lane][mate][cycle][q] = number of bases with Phred value q at sequencing cycle `cycle` (stored byte j of a read of length L is
+ * cycle j, or L-1-j when 0x10 is set), over exactly the reads whose qualities enter qualcount: neither supplementary nor secondary,
+ * 0x40 set -> mate 0, else 0x80 set -> mate 1, BQC_FLAG_NO_QUAL clear.  For every cycle: sum_q q * H[..][cycle][q] == qualcount[cycle].
+ * Pure sums: the module's words lie behind the sketch's in the flat state vector, n_lanes x 2 x N x 224 of them (lane-major, then
+ * mate, cycle, quality), and add across shards.
+ *   n_cycles = min(N, the mate's n_cycles in bqc_mate_counts); n_q = 1 + the highest Phred value counted for the lane and mate (0: none)
+ *   element [c][q] is hist[c * stride + q]
+ * bqc_qual_by_cycle: valid after bqc_finalize; the view is owned by the context until the next finalize / destroy.  BQC_ERR_STATE:
+ * the module is off, or nothing has been finalised; BQC_ERR_ARG: lane or mate out of range.
+ * bqc_write_qual_by_cycle: the table as text, lanes in the order of `hdr` as in the `.bamqc`:
+ *   sample_id <id> / lane <name> / base_qual_histogram_by_position_first <n_cycles> <n_q> / one line of n_q counts per cycle /
+ *   base_qual_histogram_by_position_second <n_cycles> <n_q> / ... */
+typedef struct bqc_qbc_view { uint32_t n_cycles, n_q, stride; const uint64_t* hist; } bqc_qbc_view;
+int bqc_qual_by_cycle(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_qbc_view* out);
+int bqc_write_qual_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
 
 #ifdef __cplusplus
 }
