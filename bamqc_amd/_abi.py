@@ -41,7 +41,8 @@ class Options(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_lanes", C.c_uint32), ("n_refs", C.c_uint32),
                 ("isize", C.c_int32), ("max_read_len", C.c_uint32), ("hist_cap", C.c_uint32),
                 ("main_chrom", u8p), ("fasta_index", i32p), ("device", C.c_int32),
-                ("sketch", SketchOptions), ("shard_tail", C.c_uint32), ("qual_by_cycle", C.c_uint32)]
+                ("sketch", SketchOptions), ("shard_tail", C.c_uint32), ("qual_by_cycle", C.c_uint32),
+                ("mismatch_by_cycle", C.c_uint32), ("pad_tail", C.c_uint32)]
 
 
 class Batch(C.Structure):
@@ -103,6 +104,10 @@ SHARD_FAIL, SHARD_DONE, SHARD_FALLBACK, SHARD_WRITE = 0, 1, 2, 3  # (0 is what c
 
 class QbcView(C.Structure):  # bqc_qbc_view: element [c][q] is hist[c * stride + q]
     _fields_ = [("n_cycles", C.c_uint32), ("n_q", C.c_uint32), ("stride", C.c_uint32), ("hist", u64p)]
+
+
+class MbcView(C.Structure):  # bqc_mbc_view: element [c][q] is aligned[c * stride + q] / mismatch[c * stride + q]
+    _fields_ = [("n_cycles", C.c_uint32), ("n_q", C.c_uint32), ("stride", C.c_uint32), ("aligned", u64p), ("mismatch", u64p)]
 
 
 class HeaderInfo(C.Structure):
@@ -170,10 +175,11 @@ def make_batch(cols):
 
 
 def make_options(n_lanes=1, n_refs=1, isize=1000, max_read_len=1024, hist_cap=4096, main_chrom=None,
-                 fasta_index=None, device=0, klist=(), qlist=(), e=0.01, seed=1, shard_tail=0, qual_by_cycle=0):
+                 fasta_index=None, device=0, klist=(), qlist=(), e=0.01, seed=1, shard_tail=0, qual_by_cycle=0,
+                 mismatch_by_cycle=0, struct_size=None):
     keep = {}
     o = Options()
-    o.struct_size = C.sizeof(Options)
+    o.struct_size = C.sizeof(Options) if struct_size is None else struct_size  # (a smaller one: a caller built against an earlier header)
     o.n_lanes, o.n_refs, o.isize = n_lanes, n_refs, isize
     o.max_read_len, o.hist_cap, o.device = max_read_len, hist_cap, device
     mc = np.ones(max(n_refs, 1), np.uint8) if main_chrom is None else np.ascontiguousarray(main_chrom, np.uint8)
@@ -194,6 +200,7 @@ def make_options(n_lanes=1, n_refs=1, isize=1000, max_read_len=1024, hist_cap=40
     o.sketch.e, o.sketch.seed = e, seed
     o.shard_tail = 1 if shard_tail else 0
     o.qual_by_cycle = qual_by_cycle  # per-cycle base quality histograms: 0 = off, else the cycle capacity N
+    o.mismatch_by_cycle = mismatch_by_cycle  # compared bases and mismatches by cycle and quality: 0 = off, else the cycle capacity N
     return o, keep
 
 

@@ -56,6 +56,8 @@ _SIGNATURES = {
     "bqc_write_bamqc": (C.c_int, [C.POINTER(_abi.Counts), C.POINTER(_abi.HeaderInfo), C.c_char_p]),
     "bqc_qual_by_cycle": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(_abi.QbcView)]),
     "bqc_write_qual_by_cycle": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.c_char_p]),
+    "bqc_mismatch_by_cycle": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(_abi.MbcView)]),
+    "bqc_write_mismatch_by_cycle": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.c_char_p]),
     # include/bamqc_host.h
     "bqc_synth_reference": (C.c_int, [C.c_uint64, C.c_int32, C.c_uint64, _abi.u8p]),
     "bqc_synth_batch": (C.c_int, [C.POINTER(_abi.SynthParams), C.POINTER(_abi.u8p), C.POINTER(C.POINTER(_abi.Batch))]),

@@ -151,6 +151,23 @@ class Aggregator:
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_qual_by_cycle(self.h, C.byref(hdr), path.encode()))
 
+    def mismatch_by_cycle(self, lane=0, mate=0):
+        """(aligned, mismatch) of a read group and mate (0 first, 1 second): the bases compared with the genome and those of them
+        that differ from it, each a (n_cycles, n_q) uint64 array (option mismatch_by_cycle=N; valid after finalize)."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.MbcView()
+        self._chk(self.lib.bqc_mismatch_by_cycle(self.h, lane, mate, C.byref(v)))
+        if v.n_cycles == 0 or v.n_q == 0:
+            return np.zeros((v.n_cycles, v.n_q), np.uint64), np.zeros((v.n_cycles, v.n_q), np.uint64)
+        return tuple(np.ctypeslib.as_array(p, shape=(v.n_cycles, v.stride))[:, :v.n_q].copy() for p in (v.aligned, v.mismatch))
+
+    def write_mismatch_by_cycle(self, path, sample_id="", lane_names=("",), lane_index=None):
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        self._chk(self.lib.bqc_write_mismatch_by_cycle(self.h, C.byref(hdr), path.encode()))
+
     def close(self):
         if self.h:
             self.lib.bqc_destroy(self.h)

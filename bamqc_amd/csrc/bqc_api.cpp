@@ -26,6 +26,7 @@ void bqc_launch_cov_final(const StateLayout&, uint64_t*, const uint32_t* carry, 
 void bqc_launch_ref_nibbles(const uint8_t* dna5, uint64_t len, uint32_t* out, uint64_t n_dwords, hipStream_t);
 uint32_t bqc_long_slots_cap(uint32_t max_read_len, uint32_t n_cu);
 uint64_t bqc_qcyc_words(uint32_t n_lanes, uint32_t N);
+uint64_t bqc_mbc_words(uint32_t n_lanes, uint32_t N);
 hipError_t bqc_long_init();
 hipError_t bqc_short_init();
 }
@@ -73,20 +74,27 @@ extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
 {
     if (!opt || !out) return fail(nullptr, BQC_ERR_ARG, "bqc_create: null argument");
     // (with qual_by_cycle, which lies in the former tail padding, or cut off in front of it: the module is off then)
-    if (opt->struct_size != sizeof(bqc_options) && opt->struct_size != offsetof(bqc_options, qual_by_cycle)) return fail(nullptr, BQC_ERR_ARG, "bqc_create: struct_size mismatch");
+    // (and with mismatch_by_cycle behind it, or as it was before that field: that module is off then)
+    if (opt->struct_size != sizeof(bqc_options) && opt->struct_size != offsetof(bqc_options, mismatch_by_cycle) && opt->struct_size != offsetof(bqc_options, qual_by_cycle))
+        return fail(nullptr, BQC_ERR_ARG, "bqc_create: struct_size mismatch");
     const uint32_t qbc_n = opt->struct_size > offsetof(bqc_options, qual_by_cycle) ? opt->qual_by_cycle : 0u;
+    const uint32_t mbc_n = opt->struct_size > offsetof(bqc_options, mismatch_by_cycle) ? opt->mismatch_by_cycle : 0u;
     if (opt->n_lanes == 0 || opt->n_lanes > 256) return fail(nullptr, BQC_ERR_ARG, "bqc_create: n_lanes must be 1..256");
     if (opt->isize < 0) return fail(nullptr, BQC_ERR_ARG, "bqc_create: negative insert size");
     if (opt->max_read_len == 0 || opt->hist_cap == 0) return fail(nullptr, BQC_ERR_ARG, "bqc_create: zero capacity");
     if (opt->n_refs && !opt->main_chrom) return fail(nullptr, BQC_ERR_ARG, "bqc_create: main_chrom missing");
     if (qbc_n > opt->max_read_len || qbc_n >= 1u << 30) return fail(nullptr, BQC_ERR_ARG, "bqc_create: qual_by_cycle %u exceeds max_read_len %u", qbc_n, opt->max_read_len);
+    if (mbc_n > opt->max_read_len || mbc_n >= 1u << 30) return fail(nullptr, BQC_ERR_ARG, "bqc_create: mismatch_by_cycle %u exceeds max_read_len %u", mbc_n, opt->max_read_len);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, BQC_ERR_DEVICE, "bqc_create: no HIP device available (this library has no CPU fallback)");
     if (opt->device < 0 || opt->device >= ndev) return fail(nullptr, BQC_ERR_DEVICE, "bqc_create: device %d out of range", opt->device);
     bqc_ctx* c = new bqc_ctx();
+    memset(&c->opt, 0, sizeof(bqc_options));
     memcpy(&c->opt, opt, std::min<size_t>(opt->struct_size, sizeof(bqc_options)));
     c->opt.qual_by_cycle = qbc_n;
+    c->opt.mismatch_by_cycle = mbc_n;
+    c->opt.pad_tail = 0;
     c->device = opt->device;
     uint32_t nr = opt->n_refs ? opt->n_refs : 1;
     c->main_chrom.assign(nr, 0);
@@ -183,6 +191,20 @@ extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
         }
         CCHK(hipMalloc(&c->d_qcyc, c->qcyc_words * 8));
         CCHK(hipMemsetAsync(c->d_qcyc, 0, c->qcyc_words * 8, c->stream));
+        CCHK(hipStreamSynchronize(c->stream));
+    }
+    if (mbc_n) { // the same rule
+        c->mbc_words = bqc_mbc_words(opt->n_lanes, mbc_n);
+        size_t free_b = 0, total_b = 0;
+        CCHK(hipMemGetInfo(&free_b, &total_b));
+        if (c->mbc_words * 8 + (1ull << 30) > free_b) {
+            fail(nullptr, BQC_ERR_ARG, "bqc_create: mismatch_by_cycle %u needs %llu bytes of tables (%u read groups x 2 x 2 x %u cycles x 224 qualities x 8 bytes), the device has %zu bytes free (%llu kept for the rest of the context)",
+                 mbc_n, (unsigned long long)(c->mbc_words * 8), opt->n_lanes, mbc_n, free_b, 1ull << 30);
+            bqc_destroy(c);
+            return BQC_ERR_ARG;
+        }
+        CCHK(hipMalloc(&c->d_mbc, c->mbc_words * 8));
+        CCHK(hipMemsetAsync(c->d_mbc, 0, c->mbc_words * 8, c->stream));
         CCHK(hipStreamSynchronize(c->stream));
     }
     cstamp(4);
@@ -291,6 +313,7 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     (void)hipFree(c->d_refn_ptrs);
     if (c->sketch) sketch_destroy(c->sketch);
     if (c->d_qcyc) (void)hipFree(c->d_qcyc);
+    if (c->d_mbc) (void)hipFree(c->d_mbc);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
     (void)hipFree(c->d_started); (void)hipFree(c->d_ref_ptrs); (void)hipFree(c->d_ref_len); (void)hipFree(c->d_main);
     for (auto e : c->ev) (void)hipEventDestroy(e);
@@ -403,6 +426,8 @@ extern "C" int bqc_reset(bqc_ctx* c)
     if (c->sketch) sketch_reset(c->sketch, c->stream);
     if (c->d_qcyc) HIPCHK(c, hipMemsetAsync(c->d_qcyc, 0, c->qcyc_words * 8, c->stream));
     c->qcyc_final = false;
+    if (c->d_mbc) HIPCHK(c, hipMemsetAsync(c->d_mbc, 0, c->mbc_words * 8, c->stream));
+    c->mbc_final = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -449,8 +474,9 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-// the flat vector: [sl.words][sketch][qual by cycle]
-static uint64_t qcyc_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+// the flat vector: [sl.words][sketch][mismatch by cycle][qual by cycle]
+static uint64_t mbc_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+static uint64_t qcyc_offset(const bqc_ctx* c) { return mbc_offset(c) + c->mbc_words; }
 extern "C" uint64_t bqc_state_words(const bqc_ctx* c) { return c ? qcyc_offset(c) + c->qcyc_words : 0; }
 
 extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
@@ -461,6 +487,7 @@ extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
+    if (c->d_mbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + mbc_offset(c), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -473,6 +500,7 @@ extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
+    if (c->d_mbc) HIPCHK(c, hipMemcpyAsync(c->d_mbc, (const uint64_t*)src + mbc_offset(c), c->mbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync(c->d_qcyc, (const uint64_t*)src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->flushed = true; // an imported vector is already flushed
@@ -495,6 +523,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
         HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_mbc) HIPCHK(c, hipMemcpy(dst + mbc_offset(c), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToHost));
     if (c->d_qcyc) HIPCHK(c, hipMemcpy(dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -515,6 +544,7 @@ extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_mbc) HIPCHK(c, hipMemcpy(c->d_mbc, src + mbc_offset(c), c->mbc_words * 8, hipMemcpyHostToDevice));
     if (c->d_qcyc) HIPCHK(c, hipMemcpy(c->d_qcyc, src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyHostToDevice));
     c->flushed = true;
     return 0;
@@ -619,6 +649,22 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
             }
         c->qcyc_final = true;
     }
+    if (c->d_mbc) { // the same for the two tables of a lane and mate: the quality range is that of A (M <= A cell by cell)
+        const uint32_t N = c->opt.mismatch_by_cycle;
+        c->h_mbc.resize(c->mbc_words);
+        HIPCHK(c, hipMemcpy(c->h_mbc.data(), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToHost));
+        c->mbc_ncyc.assign((size_t)sl.n_lanes * 2, 0);
+        c->mbc_nq.assign((size_t)sl.n_lanes * 2, 0);
+        for (uint32_t l = 0; l < sl.n_lanes; ++l)
+            for (uint32_t m = 0; m < 2; ++m) {
+                const uint64_t* A = c->h_mbc.data() + ((uint64_t)l * 2 + m) * 2 * N * 224;
+                uint32_t nq = 0;
+                for (uint32_t cy = 0; cy < N; ++cy) nq = std::max(nq, last_nonzero_len(A + (uint64_t)cy * 224, 224));
+                c->mbc_ncyc[l * 2 + m] = std::min(N, c->lanes[l].mate[m].n_cycles);
+                c->mbc_nq[l * 2 + m] = nq;
+            }
+        c->mbc_final = true;
+    }
     c->counts.n_lanes = sl.n_lanes;
     c->counts.lanes = c->lanes.data();
     *out = &c->counts;
@@ -635,5 +681,20 @@ extern "C" int bqc_qual_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_q
     out->n_q = c->qcyc_nq[lane * 2 + mate];
     out->stride = 224;
     out->hist = c->h_qcyc.data() + ((uint64_t)lane * 2 + mate) * c->opt.qual_by_cycle * 224;
+    return 0;
+}
+
+extern "C" int bqc_mismatch_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_mbc_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_mbc) return fail(c, BQC_ERR_STATE, "bqc_mismatch_by_cycle: the context was created without mismatch_by_cycle");
+    if (!c->mbc_final) return fail(c, BQC_ERR_STATE, "bqc_mismatch_by_cycle: nothing has been finalised");
+    if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_mismatch_by_cycle: lane %u / mate %u out of range", lane, mate);
+    const uint64_t tbl = (uint64_t)c->opt.mismatch_by_cycle * 224;
+    out->n_cycles = c->mbc_ncyc[lane * 2 + mate];
+    out->n_q = c->mbc_nq[lane * 2 + mate];
+    out->stride = 224;
+    out->aligned = c->h_mbc.data() + ((uint64_t)lane * 2 + mate) * 2 * tbl;
+    out->mismatch = out->aligned + tbl;
     return 0;
 }

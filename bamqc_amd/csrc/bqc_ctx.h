@@ -209,6 +209,12 @@ struct bqc_ctx {
     std::vector<uint64_t> h_qcyc;      // bqc_finalize's copy, and per (lane, mate) the printed sizes
     std::vector<uint32_t> qcyc_ncyc, qcyc_nq;
     bool qcyc_final = false;
+    // mismatches by cycle and base quality (k_mbc.hip; bqc_options.mismatch_by_cycle = N, 0: off — nothing below exists then)
+    uint64_t* d_mbc = nullptr;         // [n_lanes][2][2: A, M][N][224], the module's words of the state vector (behind the sketch's, in front of d_qcyc's)
+    uint64_t mbc_words = 0;
+    std::vector<uint64_t> h_mbc;       // bqc_finalize's copy, and per (lane, mate) the printed sizes
+    std::vector<uint32_t> mbc_ncyc, mbc_nq;
+    bool mbc_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

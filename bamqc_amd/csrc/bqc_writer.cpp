@@ -182,3 +182,34 @@ extern "C" int bqc_write_qual_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr,
     }
     return write_file(o, path);
 }
+
+// The mismatches by cycle and base quality as text (include/bamqc.h): per lane and mate the table of compared bases, then the table of
+// mismatches, each a key line with the sizes and one line of n_q counts per cycle.
+extern "C" int bqc_write_mismatch_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path)
+{
+    if (!ctx || !hdr || !path) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 16);
+    static const char* keys[2][2] = {{"aligned_bases_by_position_and_qual_first", "mismatches_by_position_and_qual_first"},
+                                     {"aligned_bases_by_position_and_qual_second", "mismatches_by_position_and_qual_second"}};
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        for (uint32_t m = 0; m < 2; ++m) {
+            bqc_mbc_view v;
+            const int rc = bqc_mismatch_by_cycle(ctx, hdr->lane_index[n], m, &v);
+            if (rc) return rc;
+            for (uint32_t t = 0; t < 2; ++t) {
+                const uint64_t* tbl = t ? v.mismatch : v.aligned;
+                o.str(keys[m][t]); o.s.push_back(' '); o.u64(v.n_cycles); o.s.push_back(' '); o.u64(v.n_q); o.s.push_back('\n');
+                if (!v.n_q) continue; // no compared base: no rows
+                for (uint32_t c = 0; c < v.n_cycles; ++c) {
+                    const uint64_t* row = tbl + (uint64_t)c * v.stride;
+                    for (uint32_t q = 0; q < v.n_q; ++q) { if (q) o.s.push_back(' '); o.u64(row[q]); }
+                    o.s.push_back('\n');
+                }
+            }
+        }
+    }
+    return write_file(o, path);
+}

@@ -783,6 +783,7 @@ struct ProgramOptions {
     uint32_t batch_reads = [] { const char* e = getenv("BQC_BATCH_READS"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 1u << 20; }(); // (the variable: experiments; --batch-reads)
     bool no_sketch = false;
     uint32_t qual_by_cycle = 0; // --qual-by-cycle / --qual-by-cycle-len N: per-cycle base quality histograms into <output>.qbc (0: off, else N)
+    uint32_t mismatch_by_cycle = 0; // --mismatch-by-cycle / --mismatch-by-cycle-len N: compared bases and mismatches by cycle and quality into <output>.mbc
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -808,6 +809,9 @@ void usage(FILE* f)
             "    --qual-by-cycle\n          Per-cycle base quality histograms (read group x mate x cycle x Phred value) into OUT.qbc,\n"
             "          for the first 1024 cycles of every read.\n"
             "    --qual-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).\n"
+            "    --mismatch-by-cycle\n          Bases compared with the reference genome, and those that differ from it (read group x mate x\n"
+            "          cycle x Phred value), into OUT.mbc, for the first 1024 cycles of every read.\n"
+            "    --mismatch-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -923,6 +927,14 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
             if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--qual-by-cycle-len wants 1 or more)"; return 1; }
             o.qual_by_cycle = (uint32_t)x;
+        }
+        else if (key == "--mismatch-by-cycle") { if (!o.mismatch_by_cycle) o.mismatch_by_cycle = 1024; }
+        else if (key == "--mismatch-by-cycle-len") {
+            if (!need(i, key, v, inl)) return 1;
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--mismatch-by-cycle-len wants 1 or more)"; return 1; }
+            o.mismatch_by_cycle = (uint32_t)x;
         }
         else if (key == "--manifest") { if (!need(i, key, v, inl)) return 1; o.manifest = v; have_m = true; }
         else if (a[0] == '-') { err = "bamqualcheck: illegal option -- " + a.substr(a.rfind("--", 0) == 0 ? 2 : 1); return 1; }
@@ -1040,7 +1052,7 @@ RefKey make_ref_key(const std::string& fasta, const BamHeader& H)
 }
 // The options that size a context (bqc_options): equal ones mean bqc_reset instead of bqc_create.
 struct CtxKey {
-    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0;
+    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0;
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
     double e = 0;
@@ -1049,7 +1061,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1247,6 +1259,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     bo.main_chrom = main_chrom.data(); bo.fasta_index = nullptr; bo.device = opt.device; // (FASTA order: bqc_set_fasta_index below)
     bo.shard_tail = shard && shard->index > 0 ? 1u : 0u;
     bo.qual_by_cycle = opt.qual_by_cycle;
+    bo.mismatch_by_cycle = opt.mismatch_by_cycle;
     if (!opt.no_sketch) {
         bo.sketch.n_k = (uint32_t)opt.klist.size(); bo.sketch.klist = opt.klist.data();
         bo.sketch.n_q = (uint32_t)opt.q_cutoff.size(); bo.sketch.qlist = opt.q_cutoff.data();
@@ -1265,7 +1278,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (S) {
         ref_key = make_ref_key(opt.referenceFile, H);
         ctx_key.n_lanes = bo.n_lanes; ctx_key.n_refs = bo.n_refs; ctx_key.max_read_len = bo.max_read_len; ctx_key.hist_cap = bo.hist_cap; ctx_key.isize = bo.isize;
-        ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch; ctx_key.qual_by_cycle = bo.qual_by_cycle;
+        ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch; ctx_key.qual_by_cycle = bo.qual_by_cycle; ctx_key.mismatch_by_cycle = bo.mismatch_by_cycle;
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1607,10 +1620,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     rc = bqc_write_bamqc(counts, &hi, opt.outputFile.c_str());
     const std::string qbc_path = opt.outputFile + ".qbc"; // the table of --qual-by-cycle, right after the .bamqc (the context still exists)
     const int qbc_rc = !rc && opt.qual_by_cycle ? bqc_write_qual_by_cycle(ctx, &hi, qbc_path.c_str()) : 0;
+    const std::string mbc_path = opt.outputFile + ".mbc"; // the tables of --mismatch-by-cycle, behind the .qbc
+    const int mbc_rc = !rc && !qbc_rc && opt.mismatch_by_cycle ? bqc_write_mismatch_by_cycle(ctx, &hi, mbc_path.c_str()) : 0;
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1625,6 +1640,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     }
     if (rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", opt.outputFile.c_str()); return 1; }
     if (qbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", qbc_path.c_str()); return 1; }
+    if (mbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", mbc_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

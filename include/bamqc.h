@@ -107,6 +107,10 @@ typedef struct bqc_options {
                                   1 <= N <= max_read_len; cycles at or behind N of a longer read are not counted.  (The field
                                   lies in what was the structure's tail padding: bqc_create takes the structure with or
                                   without it, and a caller that cleared the structure has the module off.)        */
+    uint32_t mismatch_by_cycle;/* mismatches by cycle and base quality (bqc_mismatch_by_cycle): 0 = off, else the cycle capacity N,
+                                  1 <= N <= max_read_len.  bqc_create also takes the structure as it was before this field
+                                  (struct_size 8 smaller): the module is off then.                              */
+    uint32_t pad_tail;         /* keeps sizeof a multiple of 8; not read                                         */
 } bqc_options;
 
 /* ---- input batch (host, structure of arrays) -------------------------------
@@ -348,6 +352,36 @@ int bqc_write_bamqc(const bqc_counts* counts, const bqc_header_info* hdr, const 
 typedef struct bqc_qbc_view { uint32_t n_cycles, n_q, stride; const uint64_t* hist; } bqc_qbc_view;
 int bqc_qual_by_cycle(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_qbc_view* out);
 int bqc_write_qual_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
+
+/* ---- mismatches by cycle and base quality (bqc_options.mismatch_by_cycle; not in the reference) -----------------
+ * Two tables per read group and mate, for a capacity N:
+ *   A[lane][mate][cycle][q]  bases that were compared with the genome        M[lane][mate][cycle][q]  those of them that differ from it
+ * A read is counted iff  flag & 0x900 == 0;  a mate flag is set (0x40 -> mate 0, else 0x80 -> mate 1);  BQC_FLAG_NO_QUAL is clear;
+ * flag & 0x4 is clear;  0 <= rid < n_refs;  the contig rid has been given with bqc_set_reference;  n_cigar > 0.  No mapq or AS filter;
+ * duplicates and QC-fail reads count.
+ * The walk, in BAM orientation and 64-bit signed arithmetic: j = 0 (stored base index), r = pos (genome position); for each CIGAR
+ * operation of length n:  M, =, X (0, 7, 8): examine the pairs (j+t, r+t), t < n, then j += n, r += n;  I, S (1, 4): j += n;
+ * D, N (2, 3): r += n;  H, P and any code of 9 or more: nothing.  `=` and `X` are compared by their bases, not believed.
+ * A pair (jj, rr) is counted iff  jj < l_seq;  0 <= rr < the contig's length;  the read's 4-bit code is A, C, G or T (1, 2, 4, 8);
+ * the genome's Dna5 code is 3 or less;  the quality byte q is 222 or less;  the cycle c = jj (l_seq-1-jj when 0x10 is set) is below N.
+ * Hard clips do not shift cycles.  For a counted pair A[c][q] += 1, and M[c][q] += 1 if the read's base is not the genome's; a read
+ * base N, = or any ambiguity code, and a genome N, enter neither table.
+ * Pure sums: the module's words are [n_lanes][2 mates][2 tables: A then M][N][224] u64; they lie behind the sketch's words and IN
+ * FRONT OF qual_by_cycle's in the flat state vector, and add across shards.
+ *   n_cycles = min(N, the mate's n_cycles in bqc_mate_counts); n_q = 1 + the highest q with a non-zero A for the lane and mate (0: none)
+ *   element [c][q] is aligned[c * stride + q] / mismatch[c * stride + q]
+ * bqc_mismatch_by_cycle: valid after bqc_finalize; the view is owned by the context until the next finalize / destroy.  BQC_ERR_STATE:
+ * the module is off, or nothing has been finalised; BQC_ERR_ARG: lane or mate out of range.
+ * bqc_write_mismatch_by_cycle: the tables as text, lanes in the order of `hdr` as in the `.bamqc`:
+ *   sample_id <id> / lane <name> / aligned_bases_by_position_and_qual_first <n_cycles> <n_q> / one line of n_q counts per cycle /
+ *   mismatches_by_position_and_qual_first <n_cycles> <n_q> / ... / aligned_bases_by_position_and_qual_second ... /
+ *   mismatches_by_position_and_qual_second ...
+ * "The contig is on the card" is decided per batch at its launch.  The program uploads every contig of the FASTA file that is a BAM
+ * reference before a batch with a read on it is submitted, in every mode but the non-default BQC_BG_REFS=1 (the uploader beside the
+ * record loop), which is out of this module's scope. */
+typedef struct bqc_mbc_view { uint32_t n_cycles, n_q, stride; const uint64_t* aligned; const uint64_t* mismatch; } bqc_mbc_view;
+int bqc_mismatch_by_cycle(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_mbc_view* out);
+int bqc_write_mismatch_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
 
 #ifdef __cplusplus
 }
