@@ -110,6 +110,33 @@ class MbcView(C.Structure):  # bqc_mbc_view: element [c][q] is aligned[c * strid
     _fields_ = [("n_cycles", C.c_uint32), ("n_q", C.c_uint32), ("stride", C.c_uint32), ("aligned", u64p), ("mismatch", u64p)]
 
 
+class Adapter(C.Structure):  # bqc_adapter
+    _fields_ = [("name", C.c_char_p), ("seq", C.c_char_p)]
+
+
+class Modules(C.Structure):  # bqc_modules: the optional modules that bqc_create_ex takes beside bqc_options
+    _fields_ = [("struct_size", C.c_uint32), ("adapter_by_cycle", C.c_uint32), ("n_adapters", C.c_uint32), ("pad", C.c_uint32),
+                ("adapters", C.POINTER(Adapter))]
+
+
+class AdpView(C.Structure):  # bqc_adp_view: reads_by_length[c], first_hit[a * stride + c]
+    _fields_ = [("n_cycles", C.c_uint32), ("n_adapters", C.c_uint32), ("stride", C.c_uint32), ("reads_by_length", u64p),
+                ("first_hit", u64p), ("adapters", C.POINTER(Adapter))]
+
+
+def make_modules(adapter_by_cycle=0, adapters=None, struct_size=None):
+    """bqc_modules: adapter_by_cycle = the cycle capacity N (0: off), adapters = [(name, sequence), ...] or None for the built-in set."""
+    m = Modules()
+    m.struct_size = C.sizeof(Modules) if struct_size is None else struct_size
+    m.adapter_by_cycle = adapter_by_cycle
+    keep = None
+    if adapters:
+        keep = (Adapter * len(adapters))(*[Adapter(n.encode() if isinstance(n, str) else n, s.encode() if isinstance(s, str) else s) for n, s in adapters])
+        m.n_adapters = len(adapters)
+        m.adapters = keep
+    return m, keep
+
+
 class HeaderInfo(C.Structure):
     _fields_ = [("sample_id", C.c_char_p), ("n_names", C.c_uint32),
                 ("lane_names", C.POINTER(C.c_char_p)), ("lane_index", u32p)]

@@ -38,11 +38,15 @@ class DeviceBatch:
 
 
 class Aggregator:
-    def __init__(self, **options):
+    def __init__(self, adapter_by_cycle=None, adapters=None, **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
-        rc = self.lib.bqc_create(C.byref(self.opt), C.byref(self.h))
+        if adapter_by_cycle is None and adapters is None:
+            rc = self.lib.bqc_create(C.byref(self.opt), C.byref(self.h))
+        else:  # the modules that are configured beside bqc_options (adapter content by cycle)
+            mod, keep = _abi.make_modules(adapter_by_cycle or 0, adapters)
+            rc = self.lib.bqc_create_ex(C.byref(self.opt), C.byref(mod), C.byref(self.h))
         if rc:
             raise BamQCError(rc, (self.lib.bqc_last_error(None) or b"").decode())
         self._counts = None
@@ -167,6 +171,27 @@ class Aggregator:
             self.finalize_raw()
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_mismatch_by_cycle(self.h, C.byref(hdr), path.encode()))
+
+    def adapter_by_cycle(self, lane=0, mate=0):
+        """(reads_by_length, first_hit, adapters) of a read group and mate (0 first, 1 second): the examined reads by length, a
+        (n_cycles,) uint64 array; per adapter of the set the reads whose first occurrence of it starts at each cycle, a
+        (n_adapters, n_cycles) uint64 array; the set in use as [(name, sequence), ...] (option adapter_by_cycle=N; valid after finalize)."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.AdpView()
+        self._chk(self.lib.bqc_adapter_by_cycle(self.h, lane, mate, C.byref(v)))
+        names = [(v.adapters[a].name.decode(), v.adapters[a].seq.decode()) for a in range(v.n_adapters)]
+        if v.n_cycles == 0:
+            return np.zeros(0, np.uint64), np.zeros((v.n_adapters, 0), np.uint64), names
+        e = np.ctypeslib.as_array(v.reads_by_length, shape=(v.n_cycles,)).copy()
+        f = np.ctypeslib.as_array(v.first_hit, shape=(v.n_adapters, v.stride))[:, :v.n_cycles].copy()
+        return e, f, names
+
+    def write_adapter_by_cycle(self, path, sample_id="", lane_names=("",), lane_index=None):
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        self._chk(self.lib.bqc_write_adapter_by_cycle(self.h, C.byref(hdr), path.encode()))
 
     def close(self):
         if self.h:

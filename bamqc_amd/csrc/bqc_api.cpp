@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "bqc_ctx.h"
+#include "adapter_rule.h"
 #include "../host/parallel.h"
 
 extern "C" {
@@ -27,6 +28,7 @@ void bqc_launch_ref_nibbles(const uint8_t* dna5, uint64_t len, uint32_t* out, ui
 uint32_t bqc_long_slots_cap(uint32_t max_read_len, uint32_t n_cu);
 uint64_t bqc_qcyc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_mbc_words(uint32_t n_lanes, uint32_t N);
+uint64_t bqc_adp_words(uint32_t n_lanes, uint32_t N);
 hipError_t bqc_long_init();
 hipError_t bqc_short_init();
 }
@@ -70,7 +72,44 @@ static int reset_stream_records(bqc_ctx* c)
     return 0;
 }
 
-extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
+// The adapter set of bqc_modules, checked (include/bamqc.h: bqc_create_ex) and copied: names, sequences and the kernel's patterns.
+// n_adapters = 0: the built-in set.  Returns 0, or BQC_ERR_ARG with the message set.
+static int adapter_set(const bqc_modules* mod, std::vector<std::string>& names, std::vector<std::string>& seqs, AdpPatterns& P)
+{
+    static const bqc_adapter builtin[] = {{"Illumina_Universal", "AGATCGGAAGAG"}, {"Illumina_SmallRNA_3p", "TGGAATTCTCGG"}, {"Illumina_SmallRNA_5p", "GATCGTCGGACT"},
+                                          {"Nextera_Transposase", "CTGTCTCTTATA"}, {"PolyA", "AAAAAAAAAAAA"}, {"PolyG", "GGGGGGGGGGGG"}};
+    const bqc_adapter* set = mod->n_adapters ? mod->adapters : builtin;
+    const uint32_t n = mod->n_adapters ? mod->n_adapters : (uint32_t)(sizeof builtin / sizeof builtin[0]);
+    if (n > BQC_ADP_MAX) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: %u adapters given, at most %d are taken", n, BQC_ADP_MAX);
+    if (!set) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: n_adapters is %u and adapters is null", n);
+    memset(&P, 0, sizeof P);
+    P.n = n;
+    for (uint32_t a = 0; a < n; ++a) {
+        const char* nm = set[a].name;
+        const char* sq = set[a].seq;
+        const std::string fault = bqc_adapter_fault(nm, sq);
+        if (!fault.empty()) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: adapter %u: %s", a, fault.c_str());
+        for (uint32_t b = 0; b < a; ++b)
+            if (names[b] == nm) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: the adapter name '%s' is given twice", nm);
+        const size_t m = strlen(sq);
+        uint32_t fwd = 0, rc = 0;
+        for (size_t i = 0; i < m; ++i) {
+            const uint32_t code = (uint32_t)(strchr("ACGT", sq[i]) - "ACGT");
+            fwd |= code << (2 * i);
+            rc |= (3u - code) << (2 * (m - 1 - i)); // (the complement of letter i is letter m-1-i of the reverse complement)
+        }
+        names.push_back(nm);
+        seqs.push_back(sq);
+        P.len[a] = (uint32_t)m; P.fwd[a] = fwd; P.rc[a] = rc;
+        P.cmask[a] = (uint32_t)((1ull << (2 * m)) - 1); // (64-bit: m = 16 would be a 32-bit shift by 32)
+        P.vmask[a] = (1u << m) - 1u;
+    }
+    return 0;
+}
+
+extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out) { return bqc_create_ex(opt, nullptr, out); }
+
+extern "C" int bqc_create_ex(const bqc_options* opt, const bqc_modules* mod, bqc_ctx** out)
 {
     if (!opt || !out) return fail(nullptr, BQC_ERR_ARG, "bqc_create: null argument");
     // (with qual_by_cycle, which lies in the former tail padding, or cut off in front of it: the module is off then)
@@ -85,11 +124,29 @@ extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
     if (opt->n_refs && !opt->main_chrom) return fail(nullptr, BQC_ERR_ARG, "bqc_create: main_chrom missing");
     if (qbc_n > opt->max_read_len || qbc_n >= 1u << 30) return fail(nullptr, BQC_ERR_ARG, "bqc_create: qual_by_cycle %u exceeds max_read_len %u", qbc_n, opt->max_read_len);
     if (mbc_n > opt->max_read_len || mbc_n >= 1u << 30) return fail(nullptr, BQC_ERR_ARG, "bqc_create: mismatch_by_cycle %u exceeds max_read_len %u", mbc_n, opt->max_read_len);
+    uint32_t adp_n = 0;
+    std::vector<std::string> adp_names, adp_seqs;
+    AdpPatterns adp_pat{};
+    if (mod) {
+        if (mod->struct_size != sizeof(bqc_modules)) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: bqc_modules.struct_size is %u, not %zu", mod->struct_size, sizeof(bqc_modules));
+        adp_n = mod->adapter_by_cycle;
+        if (!adp_n && mod->n_adapters) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: %u adapters given with adapter_by_cycle 0", mod->n_adapters);
+        if (adp_n > opt->max_read_len || adp_n >= 1u << 30) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: adapter_by_cycle %u exceeds max_read_len %u", adp_n, opt->max_read_len);
+        if (adp_n) {
+            const int rc = adapter_set(mod, adp_names, adp_seqs, adp_pat);
+            if (rc) return rc;
+        }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, BQC_ERR_DEVICE, "bqc_create: no HIP device available (this library has no CPU fallback)");
     if (opt->device < 0 || opt->device >= ndev) return fail(nullptr, BQC_ERR_DEVICE, "bqc_create: device %d out of range", opt->device);
     bqc_ctx* c = new bqc_ctx();
+    c->adp_n = adp_n;
+    c->adp_names = std::move(adp_names);
+    c->adp_seqs = std::move(adp_seqs);
+    c->adp_pat = adp_pat;
+    for (size_t a = 0; a < c->adp_names.size(); ++a) c->adp_set.push_back(bqc_adapter{c->adp_names[a].c_str(), c->adp_seqs[a].c_str()});
     memset(&c->opt, 0, sizeof(bqc_options));
     memcpy(&c->opt, opt, std::min<size_t>(opt->struct_size, sizeof(bqc_options)));
     c->opt.qual_by_cycle = qbc_n;
@@ -207,6 +264,20 @@ extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out)
         CCHK(hipMemsetAsync(c->d_mbc, 0, c->mbc_words * 8, c->stream));
         CCHK(hipStreamSynchronize(c->stream));
     }
+    if (adp_n) { // the same rule
+        c->adp_words = bqc_adp_words(opt->n_lanes, adp_n);
+        size_t free_b = 0, total_b = 0;
+        CCHK(hipMemGetInfo(&free_b, &total_b));
+        if (c->adp_words * 8 + (1ull << 30) > free_b) {
+            fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: adapter_by_cycle %u needs %llu bytes of tables (%u read groups x 2 x 9 x %u cycles x 8 bytes), the device has %zu bytes free (%llu kept for the rest of the context)",
+                 adp_n, (unsigned long long)(c->adp_words * 8), opt->n_lanes, adp_n, free_b, 1ull << 30);
+            bqc_destroy(c);
+            return BQC_ERR_ARG;
+        }
+        CCHK(hipMalloc(&c->d_adp, c->adp_words * 8));
+        CCHK(hipMemsetAsync(c->d_adp, 0, c->adp_words * 8, c->stream));
+        CCHK(hipStreamSynchronize(c->stream));
+    }
     cstamp(4);
     for (int i = 0; i < 16; ++i) {
         hipEvent_t e;
@@ -314,6 +385,7 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (c->sketch) sketch_destroy(c->sketch);
     if (c->d_qcyc) (void)hipFree(c->d_qcyc);
     if (c->d_mbc) (void)hipFree(c->d_mbc);
+    if (c->d_adp) (void)hipFree(c->d_adp);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
     (void)hipFree(c->d_started); (void)hipFree(c->d_ref_ptrs); (void)hipFree(c->d_ref_len); (void)hipFree(c->d_main);
     for (auto e : c->ev) (void)hipEventDestroy(e);
@@ -428,6 +500,8 @@ extern "C" int bqc_reset(bqc_ctx* c)
     c->qcyc_final = false;
     if (c->d_mbc) HIPCHK(c, hipMemsetAsync(c->d_mbc, 0, c->mbc_words * 8, c->stream));
     c->mbc_final = false;
+    if (c->d_adp) HIPCHK(c, hipMemsetAsync(c->d_adp, 0, c->adp_words * 8, c->stream));
+    c->adp_final = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -474,8 +548,9 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-// the flat vector: [sl.words][sketch][mismatch by cycle][qual by cycle]
-static uint64_t mbc_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+// the flat vector: [sl.words][sketch][adapter by cycle][mismatch by cycle][qual by cycle]
+static uint64_t adp_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+static uint64_t mbc_offset(const bqc_ctx* c) { return adp_offset(c) + c->adp_words; }
 static uint64_t qcyc_offset(const bqc_ctx* c) { return mbc_offset(c) + c->mbc_words; }
 extern "C" uint64_t bqc_state_words(const bqc_ctx* c) { return c ? qcyc_offset(c) + c->qcyc_words : 0; }
 
@@ -487,6 +562,7 @@ extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
+    if (c->d_adp) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + adp_offset(c), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_mbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + mbc_offset(c), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -500,6 +576,7 @@ extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
+    if (c->d_adp) HIPCHK(c, hipMemcpyAsync(c->d_adp, (const uint64_t*)src + adp_offset(c), c->adp_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_mbc) HIPCHK(c, hipMemcpyAsync(c->d_mbc, (const uint64_t*)src + mbc_offset(c), c->mbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync(c->d_qcyc, (const uint64_t*)src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -523,6 +600,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
         HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_adp) HIPCHK(c, hipMemcpy(dst + adp_offset(c), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToHost));
     if (c->d_mbc) HIPCHK(c, hipMemcpy(dst + mbc_offset(c), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToHost));
     if (c->d_qcyc) HIPCHK(c, hipMemcpy(dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToHost));
     return 0;
@@ -544,6 +622,7 @@ extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_adp) HIPCHK(c, hipMemcpy(c->d_adp, src + adp_offset(c), c->adp_words * 8, hipMemcpyHostToDevice));
     if (c->d_mbc) HIPCHK(c, hipMemcpy(c->d_mbc, src + mbc_offset(c), c->mbc_words * 8, hipMemcpyHostToDevice));
     if (c->d_qcyc) HIPCHK(c, hipMemcpy(c->d_qcyc, src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyHostToDevice));
     c->flushed = true;
@@ -665,6 +744,16 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
             }
         c->mbc_final = true;
     }
+    if (c->d_adp) { // the printed length follows from the module's own sums: the longest examined read of the lane and mate, cut at N
+        const uint32_t N = c->adp_n;
+        c->h_adp.resize(c->adp_words);
+        HIPCHK(c, hipMemcpy(c->h_adp.data(), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToHost));
+        c->adp_ncyc.assign((size_t)sl.n_lanes * 2, 0);
+        for (uint32_t l = 0; l < sl.n_lanes; ++l)
+            for (uint32_t m = 0; m < 2; ++m)
+                c->adp_ncyc[l * 2 + m] = last_nonzero_len(c->h_adp.data() + (((uint64_t)l * 2 + m) * BQC_ADP_ROWS + BQC_ADP_MAX) * N, N);
+        c->adp_final = true;
+    }
     c->counts.n_lanes = sl.n_lanes;
     c->counts.lanes = c->lanes.data();
     *out = &c->counts;
@@ -696,5 +785,20 @@ extern "C" int bqc_mismatch_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, b
     out->stride = 224;
     out->aligned = c->h_mbc.data() + ((uint64_t)lane * 2 + mate) * 2 * tbl;
     out->mismatch = out->aligned + tbl;
+    return 0;
+}
+
+extern "C" int bqc_adapter_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_adp_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_adp) return fail(c, BQC_ERR_STATE, "bqc_adapter_by_cycle: the context was created without adapter_by_cycle");
+    if (!c->adp_final) return fail(c, BQC_ERR_STATE, "bqc_adapter_by_cycle: nothing has been finalised");
+    if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_adapter_by_cycle: lane %u / mate %u out of range", lane, mate);
+    out->n_cycles = c->adp_ncyc[lane * 2 + mate];
+    out->n_adapters = (uint32_t)c->adp_set.size();
+    out->stride = c->adp_n;
+    out->first_hit = c->h_adp.data() + ((uint64_t)lane * 2 + mate) * BQC_ADP_ROWS * c->adp_n;
+    out->reads_by_length = out->first_hit + (uint64_t)BQC_ADP_MAX * c->adp_n;
+    out->adapters = c->adp_set.data();
     return 0;
 }

@@ -215,6 +215,16 @@ struct bqc_ctx {
     std::vector<uint64_t> h_mbc;       // bqc_finalize's copy, and per (lane, mate) the printed sizes
     std::vector<uint32_t> mbc_ncyc, mbc_nq;
     bool mbc_final = false;
+    // adapter content by cycle (k_adp.hip; bqc_modules.adapter_by_cycle = N through bqc_create_ex, 0: off — nothing below exists then)
+    uint32_t adp_n = 0;                // the capacity N
+    std::vector<std::string> adp_names, adp_seqs; // the set in use: the context's own copies
+    std::vector<bqc_adapter> adp_set;  // ... as bqc_adp_view shows it
+    AdpPatterns adp_pat{};
+    uint64_t* d_adp = nullptr;         // [n_lanes][2][9: slots 0..7, then E][N], the module's words of the state vector (behind the sketch's, in front of d_mbc's)
+    uint64_t adp_words = 0;
+    std::vector<uint64_t> h_adp;       // bqc_finalize's copy, and per (lane, mate) the printed length
+    std::vector<uint32_t> adp_ncyc;
+    bool adp_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -213,3 +213,29 @@ extern "C" int bqc_write_mismatch_by_cycle(bqc_ctx* ctx, const bqc_header_info* 
     }
     return write_file(o, path);
 }
+
+// The adapter content by cycle as text (include/bamqc.h): per lane and mate the reads by length, then one line of first hits per adapter
+// of the set, key-then-values lines as in the `.bamqc`.
+extern "C" int bqc_write_adapter_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path)
+{
+    if (!ctx || !hdr || !path) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 16);
+    static const char* keys[2][2] = {{"adapter_reads_by_length_first", "adapter_first_hit_by_position_first"},
+                                     {"adapter_reads_by_length_second", "adapter_first_hit_by_position_second"}};
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        for (uint32_t m = 0; m < 2; ++m) {
+            bqc_adp_view v;
+            const int rc = bqc_adapter_by_cycle(ctx, hdr->lane_index[n], m, &v);
+            if (rc) return rc;
+            o.array(keys[m][0], v.reads_by_length, v.n_cycles);
+            for (uint32_t a = 0; a < v.n_adapters; ++a) {
+                const std::string key = std::string(keys[m][1]) + " " + v.adapters[a].name + " " + v.adapters[a].seq;
+                o.array(key.c_str(), v.first_hit + (uint64_t)a * v.stride, v.n_cycles);
+            }
+        }
+    }
+    return write_file(o, path);
+}

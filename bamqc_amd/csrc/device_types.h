@@ -150,6 +150,15 @@ struct DevBatch {
     const TripSeg* segs;       // triplet segments of fast reads with several CIGAR operations, at cigar_off[r] + j
 };
 
+// The adapter set of k_adp.hip as the kernel takes it, by value: adapter a of len[a] bases packed 2 bits a base (A 0, C 1, G 2, T 3),
+// base 0 lowest — as given (fwd) and as its reverse complement (rc), with the masks of 2 len and len set bits.  Packed by bqc_create_ex.
+#define BQC_ADP_MAX 8
+#define BQC_ADP_ROWS (BQC_ADP_MAX + 1) // rows of a (lane, mate) of the table: the first hits of slots 0..7, then the reads by length
+struct AdpPatterns {
+    uint32_t n;
+    uint32_t len[BQC_ADP_MAX], fwd[BQC_ADP_MAX], rc[BQC_ADP_MAX], cmask[BQC_ADP_MAX], vmask[BQC_ADP_MAX];
+};
+
 struct DevRefs {
     const uint8_t* const* ref; // [n_refs] Dna5 codes, nullptr if not loaded
     const uint64_t* len;

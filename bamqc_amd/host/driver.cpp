@@ -33,6 +33,7 @@
 #include "inflate_fast.h"
 #include "host_tools.h"
 #include "input_route.h"
+#include "../csrc/adapter_rule.h"
 #include "../csrc/gpu_bam.h"
 #include "../csrc/gpu_sam.h"
 #include <hip/hip_runtime_api.h>
@@ -784,6 +785,10 @@ struct ProgramOptions {
     bool no_sketch = false;
     uint32_t qual_by_cycle = 0; // --qual-by-cycle / --qual-by-cycle-len N: per-cycle base quality histograms into <output>.qbc (0: off, else N)
     uint32_t mismatch_by_cycle = 0; // --mismatch-by-cycle / --mismatch-by-cycle-len N: compared bases and mismatches by cycle and quality into <output>.mbc
+    // --adapter-by-cycle / --adapter-by-cycle-len N / --adapter NAME=SEQ: adapter content by cycle into <output>.adp (0: off, else N;
+    // adapters empty: the built-in set)
+    uint32_t adapter_by_cycle = 0;
+    std::vector<std::pair<std::string, std::string>> adapters;
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -812,6 +817,11 @@ void usage(FILE* f)
             "    --mismatch-by-cycle\n          Bases compared with the reference genome, and those that differ from it (read group x mate x\n"
             "          cycle x Phred value), into OUT.mbc, for the first 1024 cycles of every read.\n"
             "    --mismatch-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).\n"
+            "    --adapter-by-cycle\n          Adapter content by cycle: per read group, mate and adapter the reads whose first occurrence of the\n"
+            "          adapter starts at each cycle, and the reads by length, into OUT.adp, for the first 1024 cycles.\n"
+            "    --adapter-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).\n"
+            "    --adapter NAME=SEQ\n          An adapter to look for (repeatable, at most 8; the first one replaces the built-in set): NAME is 1 to 31\n"
+            "          characters of [A-Za-z0-9_.-], SEQ 8 to 16 letters of ACGT.  Implies --adapter-by-cycle.\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -873,6 +883,7 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
 {
     std::string kstr = "32", qstr = "17";
     bool have_r = false, have_o = false, have_m = false;
+    bool want_adp = false; // --adapter-by-cycle or an --adapter: the module at 1024 cycles unless --adapter-by-cycle-len says otherwise
     std::vector<std::string> pos;
     auto need = [&](int& i, const std::string& name, std::string& val, const char* inl) -> bool {
         if (inl) { val = inl; return true; }
@@ -936,10 +947,32 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--mismatch-by-cycle-len wants 1 or more)"; return 1; }
             o.mismatch_by_cycle = (uint32_t)x;
         }
+        else if (key == "--adapter-by-cycle") { want_adp = true; }
+        else if (key == "--adapter-by-cycle-len") {
+            if (!need(i, key, v, inl)) return 1;
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--adapter-by-cycle-len wants 1 or more)"; return 1; }
+            o.adapter_by_cycle = (uint32_t)x;
+        }
+        else if (key == "--adapter") {
+            if (!need(i, key, v, inl)) return 1;
+            const size_t eq = v.find('=');
+            if (eq == std::string::npos) { err = "bamqualcheck: the given value '" + v + "' is not an adapter (--adapter wants NAME=SEQ)"; return 1; }
+            const std::string nm = v.substr(0, eq), sq = v.substr(eq + 1);
+            const std::string fault = bqc_adapter_fault(nm.c_str(), sq.c_str());
+            if (!fault.empty()) { err = "bamqualcheck: --adapter " + v + ": " + fault; return 1; }
+            for (const auto& ad : o.adapters)
+                if (ad.first == nm) { err = "bamqualcheck: --adapter " + v + ": the adapter name '" + nm + "' is given twice"; return 1; }
+            if (o.adapters.size() == 8) { err = "bamqualcheck: --adapter " + v + ": at most 8 adapters are taken"; return 1; }
+            o.adapters.emplace_back(nm, sq);
+            want_adp = true;
+        }
         else if (key == "--manifest") { if (!need(i, key, v, inl)) return 1; o.manifest = v; have_m = true; }
         else if (a[0] == '-') { err = "bamqualcheck: illegal option -- " + a.substr(a.rfind("--", 0) == 0 ? 2 : 1); return 1; }
         else pos.push_back(a);
     }
+    if (want_adp && !o.adapter_by_cycle) o.adapter_by_cycle = 1024;
     if (!have_r) { err = "bamqualcheck: option requires an argument -- r (required option -r/--reference missing)"; return 1; }
     if (session_form) {
         if (have_o || have_m || !pos.empty()) { err = "bamqualcheck: a session takes the program's options without an input, -o and --manifest"; return 1; }
@@ -1052,7 +1085,8 @@ RefKey make_ref_key(const std::string& fasta, const BamHeader& H)
 }
 // The options that size a context (bqc_options): equal ones mean bqc_reset instead of bqc_create.
 struct CtxKey {
-    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0;
+    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0;
+    std::vector<std::pair<std::string, std::string>> adapters; // (empty: the built-in set)
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
     double e = 0;
@@ -1061,7 +1095,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1265,6 +1299,14 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         bo.sketch.n_q = (uint32_t)opt.q_cutoff.size(); bo.sketch.qlist = opt.q_cutoff.data();
         bo.sketch.e = opt.e; bo.sketch.seed = opt.seed;
     }
+    // the modules beside bqc_options (bqc_create_ex): adapter content by cycle
+    std::vector<bqc_adapter> adp_set;
+    for (const auto& ad : opt.adapters) adp_set.push_back(bqc_adapter{ad.first.c_str(), ad.second.c_str()});
+    bqc_modules bm;
+    memset(&bm, 0, sizeof bm);
+    bm.struct_size = sizeof bm;
+    bm.adapter_by_cycle = opt.adapter_by_cycle;
+    bm.n_adapters = (uint32_t)adp_set.size(); bm.adapters = adp_set.empty() ? nullptr : adp_set.data();
     bqc_ctx* ctx = nullptr;
     int rc = 0;
     std::string create_err;
@@ -1279,6 +1321,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         ref_key = make_ref_key(opt.referenceFile, H);
         ctx_key.n_lanes = bo.n_lanes; ctx_key.n_refs = bo.n_refs; ctx_key.max_read_len = bo.max_read_len; ctx_key.hist_cap = bo.hist_cap; ctx_key.isize = bo.isize;
         ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch; ctx_key.qual_by_cycle = bo.qual_by_cycle; ctx_key.mismatch_by_cycle = bo.mismatch_by_cycle;
+        ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters;
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1308,7 +1351,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         // go to the card while the reader still waits for its stream.
         const auto c1 = clk::now();
         const auto c2 = clk::now();
-        rc = bqc_create(&bo, &ctx);
+        rc = opt.adapter_by_cycle ? bqc_create_ex(&bo, &bm, &ctx) : bqc_create(&bo, &ctx);
         if (rc) create_err = bqc_last_error(nullptr);
         else if (old) { // the same genome under another context: its contigs change owner, nothing is uploaded
             rc = bqc_move_references(old, ctx);
@@ -1622,10 +1665,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const int qbc_rc = !rc && opt.qual_by_cycle ? bqc_write_qual_by_cycle(ctx, &hi, qbc_path.c_str()) : 0;
     const std::string mbc_path = opt.outputFile + ".mbc"; // the tables of --mismatch-by-cycle, behind the .qbc
     const int mbc_rc = !rc && !qbc_rc && opt.mismatch_by_cycle ? bqc_write_mismatch_by_cycle(ctx, &hi, mbc_path.c_str()) : 0;
+    const std::string adp_path = opt.outputFile + ".adp"; // the tables of --adapter-by-cycle, behind the .mbc
+    const int adp_rc = !rc && !qbc_rc && !mbc_rc && opt.adapter_by_cycle ? bqc_write_adapter_by_cycle(ctx, &hi, adp_path.c_str()) : 0;
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1641,6 +1686,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", opt.outputFile.c_str()); return 1; }
     if (qbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", qbc_path.c_str()); return 1; }
     if (mbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", mbc_path.c_str()); return 1; }
+    if (adp_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", adp_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

@@ -192,6 +192,20 @@ typedef struct bqc_dbatch bqc_dbatch; /* a batch resident in device memory */
 /* ---- aggregation (replaces bamqualcheck.cpp:303-453) ----------------------- */
 int bqc_abi_version(void);
 int bqc_create(const bqc_options* opt, bqc_ctx** out);
+/* Optional modules that are configured beside bqc_options, which stays as it is: bqc_create(opt, out) is bqc_create_ex(opt, NULL, out).
+ * `mod` is checked with the other arguments, before the device is looked at; each of these is BQC_ERR_ARG with a message that names the
+ * offending thing: a struct_size that is not sizeof(bqc_modules); adapter_by_cycle = 0 with adapters given; adapter_by_cycle >
+ * max_read_len; more than 8 adapters; a sequence shorter than 8 or longer than 16; a letter outside ACGT; a bad or repeated name.
+ * The context copies names and sequences: the caller's strings need not outlive the call.  (The adapter set: see bqc_adapter_by_cycle.) */
+typedef struct bqc_adapter { const char* name; const char* seq; } bqc_adapter;
+typedef struct bqc_modules {
+    uint32_t struct_size;        /* sizeof(bqc_modules) of the caller */
+    uint32_t adapter_by_cycle;   /* 0 = off, else the cycle capacity N, 1 <= N <= max_read_len */
+    uint32_t n_adapters;         /* 0 = the built-in set */
+    uint32_t pad;
+    const bqc_adapter* adapters;
+} bqc_modules;
+int bqc_create_ex(const bqc_options* opt, const bqc_modules* mod, bqc_ctx** out);
 /* Starts the HIP runtime on `device` (~0.06 s on a cold process) and makes the streams ahead that a context (and the program's reader)
  * will ask for (~0.05 s more, which then overlap with the caller's other set-up): callable from any thread, once per process, e.g.
  * while the inputs are opened. */
@@ -382,6 +396,45 @@ int bqc_write_qual_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char
 typedef struct bqc_mbc_view { uint32_t n_cycles, n_q, stride; const uint64_t* aligned; const uint64_t* mismatch; } bqc_mbc_view;
 int bqc_mismatch_by_cycle(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_mbc_view* out);
 int bqc_write_mismatch_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
+
+/* ---- adapter content by cycle (bqc_modules.adapter_by_cycle through bqc_create_ex; not in the reference) --------------------------
+ * Adapter set.  1 to 8 adapters.  Each has a name: 1 to 31 characters of [A-Za-z0-9_.-].  Each has a sequence: 8 to 16 letters of
+ * ACGT, upper case.  Built-in set, used when none is given, in this order:
+ *   Illumina_Universal AGATCGGAAGAG   Illumina_SmallRNA_3p TGGAATTCTCGG   Illumina_SmallRNA_5p GATCGTCGGACT
+ *   Nextera_Transposase CTGTCTCTTATA  PolyA AAAAAAAAAAAA                  PolyG GGGGGGGGGGGG
+ * Examined reads.  A read is examined when all of these hold:  flag & 0x900 == 0;  flag & 0xC0 != 0;  l_seq > 0;  lane < n_lanes.
+ * The mate is 0 with 0x40, else 1 (k_qcyc's rule).  There is no quality, mapping or duplicate condition: BQC_FLAG_NO_QUAL reads and
+ * unmapped reads are examined.
+ * Orientation.  For an examined read of length L, the base of cycle c is: stored base c, for a forward read; the complement of stored
+ * base L-1-c, when 0x10 is set.  Stored 4-bit codes 1, 2, 4 and 8 are A, C, G and T.  Every other code matches nothing: N, = and the
+ * ambiguity codes.
+ * Occurrence and first hit.  Adapter a of length m occurs at cycle c when both hold:  c + m <= L;  the bases of cycles c ... c+m-1
+ * equal a letter for letter.  An adapter cut off by the end of the read does not occur.  Its first hit is the lowest such c.
+ * Tables, for a capacity N:
+ *   F[lane][mate][slot][c] counts the examined reads whose first hit of adapter `slot` is c.  A first hit at or behind N is not counted.
+ *   E[lane][mate][min(L,N)-1] counts the examined reads by length.  This is what the fractions are taken of.
+ * The fraction of reads with adapter a at or before cycle c is  sum F[a][0..c] / sum E[c..].
+ * State.  All of it is pure sums.  The words are [n_lanes][2 mates][9 rows: slots 0...7, then E][N] u64.  They lie in the flat state
+ * vector behind the sketch's words and IN FRONT OF mismatch_by_cycle's and qual_by_cycle's.  Unused slots stay zero.  With the module
+ * off: no allocation, no launch, the same bqc_state_words.  With the module on: the `.bamqc`, `.qbc` and `.mbc` are the same bytes as
+ * without it.
+ *   n_cycles = 1 + the highest index with a non-zero E for the lane and mate, 0 when there is none (from the module's own sums, not
+ *   from bqc_mate_counts);  n_adapters, adapters: the set in use;  element [a][c] is first_hit[a * stride + c], [c] reads_by_length[c]
+ * bqc_adapter_by_cycle: valid after bqc_finalize; the view is owned by the context until the next finalize / destroy.  BQC_ERR_STATE:
+ * the module is off, or nothing has been finalised; BQC_ERR_ARG: lane or mate out of range.
+ * bqc_write_adapter_by_cycle: the tables as text, lanes in the order of `hdr`, key-then-values lines as in the `.bamqc`:
+ *   sample_id <id> / lane <name> / adapter_reads_by_length_first v0 ... v(n_cycles-1) /
+ *   adapter_first_hit_by_position_first <name> <sequence> v0 ... v(n_cycles-1), one such line per adapter in the set's order /
+ *   adapter_reads_by_length_second ... / adapter_first_hit_by_position_second <name> <sequence> ...
+ * With n_cycles = 0 the key lines stand without values. */
+typedef struct bqc_adp_view {
+    uint32_t n_cycles, n_adapters, stride;
+    const uint64_t* reads_by_length;   /* [c] */
+    const uint64_t* first_hit;         /* [a * stride + c] */
+    const bqc_adapter* adapters;       /* the set in use, n_adapters entries */
+} bqc_adp_view;
+int bqc_adapter_by_cycle(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_adp_view* out);
+int bqc_write_adapter_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
 
 #ifdef __cplusplus
 }
