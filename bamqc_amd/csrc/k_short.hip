@@ -51,6 +51,7 @@
 #define KS_RS    (KS_META + (KS_WAVES * 64 + 1) * KS_MW)  // (16 waves x 64 records + one dummy record); per-read statistics (read_stats.h)
 #define KS_WORDS (KS_RS + RS_WORDS)
 #define KS_T8_PERIOD 16                            // chunks between two flushes of the 8-mer counters (~35 counts per bin)
+#define KS_PARTS_ALL 15u                           // BQC_SHORT_PARTS with every part on, no XCD bit: the mask of every real run
 #define KS_BIAS  512u                              // seq / qual offsets in the records are biased so that they stay non-negative
 
 static_assert((KS_LUT % 4) == 0 && (KS_META % 4) == 0, "16-byte alignment of the LDS tables");
@@ -234,10 +235,16 @@ __device__ __forceinline__ Pre ks_prefetch(const uint32_t* rec, uint32_t w, cons
     return P;
 }
 
+// PARTS: the BQC_SHORT_PARTS mask (bqc_short_parts) fixed at compile time, or 0: the mask is the kernel argument.  The tests of the
+// mask below are then constants, the arms they switch off are not compiled, and the registers the group loop carries need no merge
+// with those arms (round 10: 22 register copies per group at the loop latch with the run-time mask, 6 without).  One body, two
+// instantiations: k_short<KS_PARTS_ALL> and k_short<0> (bqc_launch_short chooses, bqc_short_init prepares both).
+template <uint32_t PARTS>
 __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl, uint64_t* __restrict__ state, DevRefs refs,
-                                                         uint32_t* __restrict__ err, uint32_t parts, uint4* __restrict__ t8rows,
+                                                         uint32_t* __restrict__ err, uint32_t parts_arg, uint4* __restrict__ t8rows,
                                                          uint32_t* __restrict__ t8_used, uint32_t t8_period)
 {
+    const uint32_t parts = PARTS ? PARTS : parts_arg;
     extern __shared__ uint32_t lds[];
     if ((uint32_t)(uintptr_t)(lds_u32*)lds != 0u) { // the 8-mer atomics address LDS directly (KS_T8 at LDS address 0)
         if (threadIdx.x == 0) { atomicOr(err, BQC_DEVERR_INTERNAL); t8_used[blockIdx.x * BQC_T8_USED] = 0; }
@@ -415,7 +422,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
         __builtin_amdgcn_wave_barrier();
         // ---- phase B: groups of rpw reads; the next group's data is loaded while this one is processed
         const uint32_t n_groups = tn / rpw;
-        Pre cur = ks_prefetch(lane_used ? WM + slot * KS_MW : DUMMY, w, g_seq, g_qual);
+        const Pre first = ks_prefetch(lane_used ? WM + slot * KS_MW : DUMMY, w, g_seq, g_qual);
         // per-read statistics of the tile's reads, while the first group's data is on its way
         if ((parts & 8u) && __ballot(stat)) read_stats(b, sl, state, refs, err, lds + KS_RS, stat ? r : 0u, stat, stat);
         __builtin_amdgcn_s_setprio(0);
@@ -424,7 +431,10 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
         // registers, segment tiles never touch them, and no group decides that again at run time.
         auto groups = [&](auto tile_kind) __attribute__((always_inline)) {
         constexpr bool SEG = decltype(tile_kind)::seg; // a tile of triplet segments: triplets only
-        for (uint32_t g = 0; g < n_groups; ++g) {
+        // One group: computed from the raw data in `cur`, the loads of the next one issued into `nxt` on the way.  (Two named buffers, copied
+        // once per group below, instead of one that is overwritten in the middle of the body: the same six copies at the loop latch, but
+        // 13 spilled VGPRs in the kernel against 26, and 0.015 ms less per 10 M reads — round 10)
+        auto group = [&](const uint32_t g, const Pre& cur, Pre& nxt) __attribute__((always_inline)) {
             const uint32_t k = g * rpw + slot; // this lane's record (lanes behind the last slot: unused)
             const uint32_t m0 = cur.m0, w5 = cur.w5, L = (m0 >> 20) & 0xFFu; // L = 0 unless the record reaches get_count
             const bool rc = m0 & 0x10u;
@@ -473,7 +483,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
                 for (int h = 0; h < KS_NH; ++h) E[h] = rc ? __brev(F[KS_NH - 1 - h]) : F[h];
             }
             { // the raw registers are free again: issue the loads of this wave's next group
-                cur = ks_prefetch(lane_used && g + 1u < n_groups ? WM + (k + rpw) * KS_MW : DUMMY, w, g_seq, g_qual);
+                nxt = ks_prefetch(lane_used && g + 1u < n_groups ? WM + (k + rpw) * KS_MW : DUMMY, w, g_seq, g_qual);
             }
             Planes P[KS_NH];
 #pragma unroll
@@ -537,12 +547,14 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
 #pragma unroll
                     for (int h = 0; h < KS_NH; ++h) f[h] = ~(sb[h] | alignbit(sb[h], sb[h + 1], 16)); // nibble LSB set <=> the window starting there is counted
                 }
-                // Branch-free inside a batch of 16 windows: every lane with a valid cycle there issues all 16 returning atomics;
-                // a blocked window adds 0.  The address is the LDS byte address itself: KS_T8 = 0 and the dynamic LDS block
-                // starts at 0 (checked at kernel entry), which saves the base addition per window.
+                // Branch-free inside a batch of 16 windows: every lane with a counted window there issues all 16 returning atomics;
+                // a blocked window adds 0.  (A lane without one — the last lane of a 150-base read holds cycles 144..149, and every
+                // window from there crosses the read's end — would only add zeros, and bank conflicts for the others: 6 of the 60
+                // active lanes of every atomic at 150 bases.)  The address is the LDS byte address itself: KS_T8 = 0 and the dynamic
+                // LDS block starts at 0 (checked at kernel entry), which saves the base addition per window.
 #pragma unroll
                 for (int j = 0; j < KS_NH / 2; ++j) {
-                    if (nv > 16u * j) { // all 16 atomics are issued before the first returned value is looked at
+                    if ((f[2 * j] | f[2 * j + 1]) & M) { // all 16 atomics are issued before the first returned value is looked at
                         const uint32_t c32 = S[j], cx = S[j + 1];
                         uint32_t old[16];
 #pragma unroll
@@ -615,7 +627,9 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
                     }
                 }
             }
-        }
+        };
+        Pre cur = first, nxt;
+        for (uint32_t g = 0; g < n_groups; ++g) { group(g, cur, nxt); cur = nxt; }
         };
         if (seg_tile) groups(KsTile<true>{}); else groups(KsTile<false>{});
         asm volatile("" ::: "memory");
@@ -668,7 +682,7 @@ extern "C" void bqc_launch_ref_nibbles(const uint8_t* dna5, uint64_t len, uint32
 }
 
 // BQC_SHORT_PARTS: ablation switch for profiling (1 cycles + per-read sums, 2 8-mers, 4 triplets, 8 per-read statistics;
-// without 8 the caller runs k_reads over the fast chunks instead)
+// without 8 the caller runs k_reads over the fast chunks instead).  Any value but KS_PARTS_ALL runs k_short<0>.
 extern "C" uint32_t bqc_short_parts()
 {
     static uint32_t parts = 0xFFFFFFFFu;
@@ -683,7 +697,8 @@ extern "C" uint32_t bqc_short_parts()
 
 extern "C" hipError_t bqc_short_init()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_short), hipFuncAttributeMaxDynamicSharedMemorySize, KS_WORDS * 4);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_short<KS_PARTS_ALL>), hipFuncAttributeMaxDynamicSharedMemorySize, KS_WORDS * 4);
+    return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_short<0u>), hipFuncAttributeMaxDynamicSharedMemorySize, KS_WORDS * 4);
 }
 
 // Sum the packed rows the workgroups of one or more k_short launches have written (slot s: rows s * BQC_T8_SPW .. + used[s]) into
@@ -719,8 +734,11 @@ extern "C" void bqc_launch_short(const DevBatch& b, const StateLayout& sl, uint6
     (void)attr_once;                                      //  the compute stream, which has slack at a run's start, can take; bqc_create's caller cannot)
     static uint32_t env_period = 0xFFFFFFFFu;
     if (env_period == 0xFFFFFFFFu) { const char* e = getenv("BQC_T8_PERIOD"); env_period = e && atoi(e) > 0 ? (uint32_t)atoi(e) : 0u; } // tuning knob
-    hipLaunchKernelGGL(k_short, dim3(grid), dim3(KS_THREADS), KS_WORDS * 4, s, b, sl, state, refs, err, bqc_short_parts(), (uint4*)t8rows, t8_used,
-                       env_period ? env_period : KS_T8_PERIOD);
+    const uint32_t parts = bqc_short_parts(), period = env_period ? env_period : KS_T8_PERIOD;
+    if (parts == KS_PARTS_ALL) // every real run: the instantiation without the switch
+        hipLaunchKernelGGL(k_short<KS_PARTS_ALL>, dim3(grid), dim3(KS_THREADS), KS_WORDS * 4, s, b, sl, state, refs, err, parts, (uint4*)t8rows, t8_used, period);
+    else                       // ablations (BQC_SHORT_PARTS) and BQC_SHORT_XCD: the mask at run time
+        hipLaunchKernelGGL(k_short<0u>, dim3(grid), dim3(KS_THREADS), KS_WORDS * 4, s, b, sl, state, refs, err, parts, (uint4*)t8rows, t8_used, period);
 }
 
 // sum the rows of `n_slots` workgroup slots that belong to read group `lane` into its 8-mer counters
