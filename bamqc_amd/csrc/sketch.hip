@@ -398,26 +398,29 @@ __global__ void k_sketch_levels_commit(const DevSketch* __restrict__ dsk, const 
     D.misc[41] = 0;
 }
 
-// state vector <-> device tables: [sumCount][F2 table][counters as saturated bytes, 8 per word]
+// state vector <-> device tables: [sumCount][F2 table][counters clamped to 15, a 16-bit field each, four per word].
+// The fields are what the workers' vectors add in: the sum of up to 4 369 exported vectors (4 369 x 15 = 65 535) stays inside its
+// field, and the import's sum is clamped to 15 on use, which is StreamCounter::join's min(15, a + b) (StreamCounter.hpp:95-112) for any
+// number of joins.  (A byte per counter carried into the neighbouring counter from 18 summands on.)  More summands are outside the contract.
+#define SK_FIELDS 4u // counters per word of the vector
 __global__ void k_sketch_export(DevSketch D, uint64_t* __restrict__ dst, uint64_t f2size, uint64_t n_ctr)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) dst[0] = D.misc[0];
     if (i < f2size) dst[1 + i] = D.f2[i];
-    if (i < n_ctr / 8) {
-        uint64_t w = 0;
-        for (int k = 0; k < 8; ++k) { const uint32_t v = D.counters[i * 8 + k]; w |= (uint64_t)(v > 15u ? 15u : v) << (8 * k); }
-        dst[1 + f2size + i] = w;
+    if (i < n_ctr / SK_FIELDS) {
+        const uint4 v = ((const uint4*)D.counters)[i]; // (the counters of a sketch start 16-byte aligned: sketch_create)
+        dst[1 + f2size + i] = (uint64_t)min(v.x, 15u) | ((uint64_t)min(v.y, 15u) << 16) | ((uint64_t)min(v.z, 15u) << 32) | ((uint64_t)min(v.w, 15u) << 48);
     }
 }
-__global__ void k_sketch_import(DevSketch D, const uint64_t* __restrict__ src, uint64_t f2size, uint64_t n_ctr, uint64_t ctr_per_level)
+__global__ void k_sketch_import(DevSketch D, const uint64_t* __restrict__ src, uint64_t f2size, uint64_t n_ctr)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) D.misc[0] = src[0];
     if (i < f2size) D.f2[i] = src[1 + i];
-    if (i < n_ctr / 8) {
-        const uint64_t w = src[1 + f2size + i];
-        for (int k = 0; k < 8; ++k) D.counters[i * 8 + k] = (uint32_t)((w >> (8 * k)) & 255u); // sums of per-rank min(15, .) ; clamped on use
+    if (i < n_ctr / SK_FIELDS) {
+        const uint64_t w = src[1 + f2size + i]; // sums of per-worker min(15, .); clamped on use
+        ((uint4*)D.counters)[i] = make_uint4((uint32_t)w & 0xFFFFu, (uint32_t)(w >> 16) & 0xFFFFu, (uint32_t)(w >> 32) & 0xFFFFu, (uint32_t)(w >> 48));
     }
     if (i < 32) D.misc[1 + i] = 0; // successful-increment counts are not part of the vector: recomputed lazily (levels stay enabled)
     if (i == 0) { D.misc[40] = 0; D.misc[41] = 0; }
@@ -554,23 +557,22 @@ void sketch_process(SketchDevice* sk, const DevBatch& b, hipStream_t s)
     hipLaunchKernelGGL(k_sketch_levels_commit, dim3((n + 63) / 64), dim3(64), 0, s, sk->d_ds, sk->d_pp, sk->n_pairs, n);
 }
 
-static uint64_t words_per_sketch(const SketchDevice* sk) { return 1 + sk->f2size + sk->ctr_per_level * 32 / 8; }
+static uint64_t words_per_sketch(const SketchDevice* sk) { return 1 + sk->f2size + sk->ctr_per_level * 32 / SK_FIELDS; }
 uint64_t sketch_state_words(const SketchDevice* sk) { return words_per_sketch(sk) * sk->n_lanes * sk->n_pairs; }
 
 void sketch_state_export(SketchDevice* sk, uint64_t* dst, hipStream_t s)
 {
     const uint64_t n_ctr = sk->ctr_per_level * 32, wps = words_per_sketch(sk);
-    const uint32_t blocks = (uint32_t)((std::max<uint64_t>(n_ctr / 8, sk->f2size) + 255) / 256);
+    const uint32_t blocks = (uint32_t)((std::max<uint64_t>(n_ctr / SK_FIELDS, sk->f2size) + 255) / 256);
     for (size_t i = 0; i < sk->ds.size(); ++i)
         hipLaunchKernelGGL(k_sketch_export, dim3(blocks), dim3(256), 0, s, sk->ds[i], dst + i * wps, (uint64_t)sk->f2size, n_ctr);
 }
 void sketch_state_import(SketchDevice* sk, const uint64_t* src, hipStream_t s)
 {
     const uint64_t n_ctr = sk->ctr_per_level * 32, wps = words_per_sketch(sk);
-    const uint32_t blocks = (uint32_t)((std::max<uint64_t>(n_ctr / 8, sk->f2size) + 255) / 256);
+    const uint32_t blocks = (uint32_t)((std::max<uint64_t>(n_ctr / SK_FIELDS, sk->f2size) + 255) / 256);
     for (size_t i = 0; i < sk->ds.size(); ++i)
-        hipLaunchKernelGGL(k_sketch_import, dim3(blocks), dim3(256), 0, s, sk->ds[i], src + i * wps, (uint64_t)sk->f2size, n_ctr,
-                           (uint64_t)sk->ctr_per_level);
+        hipLaunchKernelGGL(k_sketch_import, dim3(blocks), dim3(256), 0, s, sk->ds[i], src + i * wps, (uint64_t)sk->f2size, n_ctr);
 }
 
 // per level: how many counters are 0, how many are 1 (all the estimators F0 / f1 need of the 16 M counters of a sketch)

@@ -4,6 +4,9 @@
 // taken at finalisation), so per-GPU vectors add: one RCCL all-reduce/reduce of
 // `words` uint64 is the whole multi-GPU merge.  The vector mirrors
 // `struct Counts` (reference src/bamqualcheck.cpp:14-38) lane by lane.
+// Behind these `words` the exported vector carries the k-mer sketches (sketch.hip: per lane and (q, k) pair
+// 1 + F2size + 8 R words — sumCount, the F2 table, 32 R counters as min(15, .) in 16-bit fields, four per word; at most
+// 4 369 such vectors may be summed) and the optional per-cycle modules (bqc_api.cpp).
 #pragma once
 #include <stdint.h>
 

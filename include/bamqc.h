@@ -324,7 +324,13 @@ int bqc_shard_export(bqc_ctx* ctx, void* state);
 
 /* Flat state vector (uint64 words, pure sums => additive across shards).
  * export/import take DEVICE pointers (e.g. a torch tensor's data_ptr) so a
- * caller can reduce them with RCCL between the two calls. */
+ * caller can reduce them with RCCL between the two calls.
+ * Behind the per-lane counters lie the k-mer sketches, [lane][pair = qi * n_k + ki], each
+ * [sumCount][F2 table, F2size words][32 levels x R counters], a counter exported as min(15, count) in a 16-bit field, four
+ * per word, counter j of level w in field w * R + j (F2size and R follow from sketch.e: 32768 and 524288 at 0.01, so
+ * 1 + F2size + 8 R = 4227073 words per sketch).  The import takes the SUM of exported vectors and uses min(15, sum) per
+ * counter, which is what one context counts over all the reads; a field holds 4369 x 15, so the sum of more than 4369
+ * exported vectors is outside the contract.  Behind the sketches: the optional modules (below). */
 uint64_t bqc_state_words(const bqc_ctx* ctx);
 int bqc_state_export(bqc_ctx* ctx, void* dev_dst_u64);
 int bqc_state_import(bqc_ctx* ctx, const void* dev_src_u64);

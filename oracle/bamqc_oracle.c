@@ -528,6 +528,12 @@ int orc_set_reference(struct orc_ctx* o, int32_t rid, const uint8_t* dna5, uint6
     return 0;
 }
 
+uint64_t orc_sketch_state_words(struct orc_ctx* o, uint32_t lane, uint32_t pair, uint64_t* out)
+{
+    if (!o || lane >= o->opt.n_lanes || !o->counts[lane].sketch) return 0;
+    return orc_sketch_state(o->counts[lane].sketch, pair, out);
+}
+
 static const char SEQ_DECODE[] = "=ACMGRSVTWYHKDBN"; /* SURVEY U8 */
 static const char CIG_DECODE[] = "MIDNSHP=X";
 

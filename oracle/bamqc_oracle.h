@@ -16,12 +16,16 @@ int orc_process_batch(struct orc_ctx* o, const bqc_batch* b); /* returns a BQC_E
 int orc_finalize(struct orc_ctx* o, const bqc_counts** out);
 void orc_destroy(struct orc_ctx* o);
 int orc_write_bamqc(const bqc_counts* counts, const bqc_header_info* hdr, const char* path);
+/* The k-mer sketch of one (read group, pair = qi * n_k + ki) as the words of the library's exported state vector
+   (see orc_sketch_state below); needs no orc_finalize.  Returns the word count (0: no such sketch); out may be NULL. */
+uint64_t orc_sketch_state_words(struct orc_ctx* o, uint32_t lane, uint32_t pair, uint64_t* out);
 
 /* sketch_oracle.c */
 void* orc_sketch_create(const bqc_sketch_options* so);
 void orc_sketch_destroy(void* sk);
 void orc_sketch_run(void* sk, const char* seq, size_t l, const char* qual, size_t ql);
 uint32_t orc_sketch_results(void* sk, bqc_sketch_counts* out);
+uint64_t orc_sketch_state(void* sk, uint32_t pair, uint64_t* out);
 void orc_rephash_table(int seed, uint64_t out[64]);
 uint32_t orc_rephash_sequence(int seed, int k, const char* s, uint32_t l, uint64_t* out);
 void orc_streamcounter_run(double e, const uint64_t* hashes, uint64_t n, uint64_t res[4]);

@@ -353,6 +353,30 @@ uint32_t orc_sketch_results(void* p, bqc_sketch_counts* out)
     return ss->n_q * ss->n_k;
 }
 
+/* The state of one (q, k) pair in the layout of the library's exported state vector:
+   [sumCount][F2table[0..F2size)][counters of level 0 .. 31], counter j of level w as field w * R + j
+   (R = size * countsPerLong counters per level), a 16-bit field each, four per word, field f in bits
+   16 (f & 3) of word f / 4.  Returns the number of words; out == NULL only asks for that number. */
+uint64_t orc_sketch_state(void* p, uint32_t pair, uint64_t* out)
+{
+    sketchset* ss = (sketchset*)p;
+    if (pair >= ss->n_q * ss->n_k) return 0;
+    const streamcounter* s = &ss->h[pair].sc;
+    size_t R = s->size * s->countsPerLong;
+    uint64_t words = 1 + s->F2size + R * s->MAX_TABLE / 4;
+    if (!out) return words;
+    out[0] = s->sumCount;
+    memcpy(out + 1, s->F2table, s->F2size * sizeof(uint64_t));
+    uint64_t* c = out + 1 + s->F2size;
+    memset(c, 0, R * s->MAX_TABLE / 4 * sizeof(uint64_t));
+    for (size_t w = 0; w < s->MAX_TABLE; ++w)
+        for (size_t j = 0; j < R; ++j) {
+            size_t f = w * R + j;
+            c[f >> 2] |= sc_getVal(s, j, w) << (16 * (f & 3));
+        }
+    return words;
+}
+
 /* ---- standalone entry points used by the pinning tests ----------------------- */
 /* hashes of every k-mer of s (no quality clipping): init at 0, then update */
 uint32_t orc_rephash_sequence(int seed, int k, const char* s, uint32_t l, uint64_t* out)

@@ -40,6 +40,8 @@ def lib():
     L.orc_rephash_sequence.restype = C.c_uint32
     L.orc_streamcounter_run.argtypes = [C.c_double, _abi.u64p, C.c_uint64, _abi.u64p]
     L.orc_streamcounter_run.restype = None
+    L.orc_sketch_state_words.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _abi.u64p]
+    L.orc_sketch_state_words.restype = C.c_uint64
     _LIB = L
     return L
 
@@ -72,6 +74,15 @@ class Oracle:
         assert rc == 0
         self.counts_ptr = p
         return _abi.counts_to_dict(p)
+
+    def sketch_state(self, lane, pair):
+        """The k-mer sketch of read group `lane` and pair qi * n_k + ki as the words of the library's exported state vector:
+        [sumCount][F2 table][counters of level 0 .. 31, a 16-bit field each, four per word] (np.uint64; no finalize needed)."""
+        n = int(self.L.orc_sketch_state_words(self.h, lane, pair, None))
+        assert n, "no sketch (read group %d, pair %d)" % (lane, pair)
+        a = np.empty(n, np.uint64)
+        assert self.L.orc_sketch_state_words(self.h, lane, pair, a.ctypes.data_as(_abi.u64p)) == n
+        return a
 
     def write_bamqc(self, path, sample_id="SYN", lane_names=("L1",), lane_index=None):
         if self.counts_ptr is None:
