@@ -124,6 +124,11 @@ class AdpView(C.Structure):  # bqc_adp_view: reads_by_length[c], first_hit[a * s
                 ("first_hit", u64p), ("adapters", C.POINTER(Adapter))]
 
 
+class GcbView(C.Structure):  # bqc_gcb_view: four arrays of n_bins = 101 entries, by GC bin
+    _fields_ = [("window", C.c_uint32), ("n_bins", C.c_uint32), ("genome_windows", u64p), ("read_starts", u64p), ("bases", u64p),
+                ("qual_sum", u64p)]
+
+
 def make_modules(adapter_by_cycle=0, adapters=None, struct_size=None):
     """bqc_modules: adapter_by_cycle = the cycle capacity N (0: off), adapters = [(name, sequence), ...] or None for the built-in set."""
     m = Modules()

@@ -38,7 +38,7 @@ class DeviceBatch:
 
 
 class Aggregator:
-    def __init__(self, adapter_by_cycle=None, adapters=None, **options):
+    def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
@@ -50,6 +50,15 @@ class Aggregator:
         if rc:
             raise BamQCError(rc, (self.lib.bqc_last_error(None) or b"").decode())
         self._counts = None
+        if gc_bias is not None:  # the module that is switched on behind the creation (GC bias, window gc_bias)
+            try:
+                self.enable_gc_bias(gc_bias)
+            except BamQCError:
+                self.close()
+                raise
+
+    def enable_gc_bias(self, window=100):
+        self._chk(self.lib.bqc_enable_gc_bias(self.h, window))
 
     def _chk(self, rc):
         if rc:
@@ -192,6 +201,23 @@ class Aggregator:
             self.finalize_raw()
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_adapter_by_cycle(self.h, C.byref(hdr), path.encode()))
+
+    def gc_bias(self, lane=0):
+        """(genome_windows, read_starts, bases, qual_sum) of a read group: four (101,) uint64 arrays by GC bin — the genome's windows
+        (the same for every read group), the counted reads, their bases and the sum of their quality bytes (option gc_bias=W; valid
+        after finalize).  The window length: gc_bias_window."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.GcbView()
+        self._chk(self.lib.bqc_gc_bias(self.h, lane, C.byref(v)))
+        self.gc_bias_window = int(v.window)
+        return tuple(np.ctypeslib.as_array(p, shape=(v.n_bins,)).copy() for p in (v.genome_windows, v.read_starts, v.bases, v.qual_sum))
+
+    def write_gc_bias(self, path, sample_id="", lane_names=("",), lane_index=None):
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        self._chk(self.lib.bqc_write_gc_bias(self.h, C.byref(hdr), path.encode()))
 
     def close(self):
         if self.h:

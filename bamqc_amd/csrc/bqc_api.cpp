@@ -29,6 +29,9 @@ uint32_t bqc_long_slots_cap(uint32_t max_read_len, uint32_t n_cu);
 uint64_t bqc_qcyc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_mbc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_adp_words(uint32_t n_lanes, uint32_t N);
+uint64_t bqc_gcb_words(uint32_t n_lanes);
+uint32_t bqc_gcb_share(void);
+void bqc_launch_gcb_genome(const GcbContig* tab, uint32_t n_contigs, uint64_t n_shares, uint32_t W, const GcbDiv& D, uint64_t* G, uint32_t n_cu, hipStream_t s);
 hipError_t bqc_long_init();
 hipError_t bqc_short_init();
 }
@@ -386,6 +389,9 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (c->d_qcyc) (void)hipFree(c->d_qcyc);
     if (c->d_mbc) (void)hipFree(c->d_mbc);
     if (c->d_adp) (void)hipFree(c->d_adp);
+    if (c->d_gcb) (void)hipFree(c->d_gcb);
+    if (c->d_gcb_g) (void)hipFree(c->d_gcb_g);
+    if (c->d_gcb_tab) (void)hipFree(c->d_gcb_tab);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
     (void)hipFree(c->d_started); (void)hipFree(c->d_ref_ptrs); (void)hipFree(c->d_ref_len); (void)hipFree(c->d_main);
     for (auto e : c->ev) (void)hipEventDestroy(e);
@@ -502,6 +508,8 @@ extern "C" int bqc_reset(bqc_ctx* c)
     c->mbc_final = false;
     if (c->d_adp) HIPCHK(c, hipMemsetAsync(c->d_adp, 0, c->adp_words * 8, c->stream));
     c->adp_final = false;
+    if (c->d_gcb) HIPCHK(c, hipMemsetAsync(c->d_gcb, 0, c->gcb_words * 8, c->stream)); // (R, B and Q; the genome table is bqc_finalize's)
+    c->gcb_final = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -548,8 +556,9 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-// the flat vector: [sl.words][sketch][adapter by cycle][mismatch by cycle][qual by cycle]
-static uint64_t adp_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+// the flat vector: [sl.words][sketch][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
+static uint64_t gcb_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+static uint64_t adp_offset(const bqc_ctx* c) { return gcb_offset(c) + c->gcb_words; }
 static uint64_t mbc_offset(const bqc_ctx* c) { return adp_offset(c) + c->adp_words; }
 static uint64_t qcyc_offset(const bqc_ctx* c) { return mbc_offset(c) + c->mbc_words; }
 extern "C" uint64_t bqc_state_words(const bqc_ctx* c) { return c ? qcyc_offset(c) + c->qcyc_words : 0; }
@@ -557,11 +566,13 @@ extern "C" uint64_t bqc_state_words(const bqc_ctx* c) { return c ? qcyc_offset(c
 extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
 {
     if (!c || !dst) return BQC_ERR_ARG;
+    c->gcb_closed = true;
     int rc = bqc_flush(c);
     if (rc) return rc;
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
+    if (c->d_gcb) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + gcb_offset(c), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_adp) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + adp_offset(c), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_mbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + mbc_offset(c), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -571,11 +582,13 @@ extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
 extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
 {
     if (!c || !src) return BQC_ERR_ARG;
+    c->gcb_closed = true;
     HIPCHK(c, hipSetDevice(c->device));
     (void)bqc_drain(c);
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
+    if (c->d_gcb) HIPCHK(c, hipMemcpyAsync(c->d_gcb, (const uint64_t*)src + gcb_offset(c), c->gcb_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_adp) HIPCHK(c, hipMemcpyAsync(c->d_adp, (const uint64_t*)src + adp_offset(c), c->adp_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_mbc) HIPCHK(c, hipMemcpyAsync(c->d_mbc, (const uint64_t*)src + mbc_offset(c), c->mbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync(c->d_qcyc, (const uint64_t*)src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -586,6 +599,7 @@ extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
 extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
 {
     if (!c || !dst) return BQC_ERR_ARG;
+    c->gcb_closed = true;
     int rc = bqc_flush(c);
     if (rc) return rc;
     bqc_state_ready(c);
@@ -600,6 +614,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
         HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_gcb) HIPCHK(c, hipMemcpy(dst + gcb_offset(c), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToHost));
     if (c->d_adp) HIPCHK(c, hipMemcpy(dst + adp_offset(c), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToHost));
     if (c->d_mbc) HIPCHK(c, hipMemcpy(dst + mbc_offset(c), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToHost));
     if (c->d_qcyc) HIPCHK(c, hipMemcpy(dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToHost));
@@ -608,6 +623,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
 extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
 {
     if (!c || !src) return BQC_ERR_ARG;
+    c->gcb_closed = true;
     HIPCHK(c, hipSetDevice(c->device));
     (void)bqc_drain(c);
     bqc_state_ready(c);
@@ -622,6 +638,7 @@ extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_gcb) HIPCHK(c, hipMemcpy(c->d_gcb, src + gcb_offset(c), c->gcb_words * 8, hipMemcpyHostToDevice));
     if (c->d_adp) HIPCHK(c, hipMemcpy(c->d_adp, src + adp_offset(c), c->adp_words * 8, hipMemcpyHostToDevice));
     if (c->d_mbc) HIPCHK(c, hipMemcpy(c->d_mbc, src + mbc_offset(c), c->mbc_words * 8, hipMemcpyHostToDevice));
     if (c->d_qcyc) HIPCHK(c, hipMemcpy(c->d_qcyc, src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyHostToDevice));
@@ -638,9 +655,63 @@ static uint32_t last_nonzero_len(const uint64_t* p, uint32_t n)
     return n;
 }
 
+// The genome table G of the GC bias (include/bamqc.h) from the contigs the context holds now: k_gcb_genome on the compute stream, into
+// d_gcb_g, and from there into h_gcb_g.
+static int gcb_genome_table(bqc_ctx* c)
+{
+    std::vector<GcbContig> tab;
+    uint64_t n_shares = 0;
+    const uint64_t share = bqc_gcb_share();
+    for (size_t r = 0; r < c->d_ref.size(); ++r) {
+        if (!c->d_ref[r] || c->ref_len[r] < c->gcb_w) continue; // (not given, or shorter than a window)
+        const uint64_t nstarts = c->ref_len[r] - c->gcb_w + 1;
+        tab.push_back(GcbContig{c->d_ref[r], nstarts, n_shares});
+        n_shares += (nstarts + share - 1) / share;
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_gcb_g, 0, BQC_GCB_BINS * 8, c->stream));
+    if (!tab.empty()) {
+        HIPCHK(c, hipMemcpyAsync(c->d_gcb_tab, tab.data(), tab.size() * sizeof(GcbContig), hipMemcpyHostToDevice, c->stream));
+        const bool timed = c->timing && c->ev.size() >= 2; // (bqc_last_timing then shows this launch: a batch's kernels are over)
+        if (timed) { c->n_timed = 0; c->tnames.clear(); (void)hipEventRecord(c->ev[0], c->stream); }
+        bqc_launch_gcb_genome(c->d_gcb_tab, (uint32_t)tab.size(), n_shares, c->gcb_w, c->gcb_div, c->d_gcb_g, c->n_cu, c->stream);
+        if (timed) { (void)hipEventRecord(c->ev[1], c->stream); c->tnames.push_back("k_gcb_genome"); c->n_timed = 1; }
+        HIPCHK(c, hipGetLastError());
+    }
+    c->h_gcb_g.resize(BQC_GCB_BINS);
+    HIPCHK(c, hipMemcpyAsync(c->h_gcb_g.data(), c->d_gcb_g, BQC_GCB_BINS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (also: `tab` is read to here)
+    return 0;
+}
+
+extern "C" int bqc_enable_gc_bias(bqc_ctx* c, uint32_t window)
+{
+    if (!c) return BQC_ERR_ARG;
+    if (window < BQC_GCB_WMIN || window > BQC_GCB_WMAX) return fail(c, BQC_ERR_ARG, "bqc_enable_gc_bias: window %u is outside %d ... %d", window, BQC_GCB_WMIN, BQC_GCB_WMAX);
+    if (c->d_gcb) return fail(c, BQC_ERR_STATE, "bqc_enable_gc_bias: the module is on already (window %u)", c->gcb_w);
+    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
+        return fail(c, BQC_ERR_STATE, "bqc_enable_gc_bias: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t words = bqc_gcb_words(c->opt.n_lanes);
+    uint64_t *d = nullptr, *g = nullptr;
+    GcbContig* tab = nullptr;
+    if (hipMalloc(&d, words * 8) != hipSuccess || hipMalloc(&g, BQC_GCB_BINS * 8) != hipSuccess ||
+        hipMalloc(&tab, std::max<size_t>(1, c->opt.n_refs) * sizeof(GcbContig)) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess ||
+        hipMemsetAsync(g, 0, BQC_GCB_BINS * 8, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d); (void)hipFree(g); (void)hipFree(tab);
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_gc_bias: the tables could not be allocated");
+    }
+    for (uint32_t n = 0; n < 5; ++n) c->gcb_div.m[n] = (uint32_t)(((1ull << 32) + (window - n) - 1) / (window - n)); // ceil(2^32 / (W - n))
+    c->gcb_w = window;
+    c->gcb_words = words;
+    c->d_gcb = d; c->d_gcb_g = g; c->d_gcb_tab = tab;
+    return 0;
+}
+
 extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
 {
     if (!c || !out) return BQC_ERR_ARG;
+    c->gcb_closed = true;
     int rc = bqc_flush(c);
     if (rc) return rc;
     const StateLayout& sl = c->sl;
@@ -754,6 +825,13 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
                 c->adp_ncyc[l * 2 + m] = last_nonzero_len(c->h_adp.data() + (((uint64_t)l * 2 + m) * BQC_ADP_ROWS + BQC_ADP_MAX) * N, N);
         c->adp_final = true;
     }
+    if (c->d_gcb) {
+        rc = gcb_genome_table(c);
+        if (rc) return rc;
+        c->h_gcb.resize(c->gcb_words);
+        HIPCHK(c, hipMemcpy(c->h_gcb.data(), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToHost));
+        c->gcb_final = true;
+    }
     c->counts.n_lanes = sl.n_lanes;
     c->counts.lanes = c->lanes.data();
     *out = &c->counts;
@@ -800,5 +878,20 @@ extern "C" int bqc_adapter_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bq
     out->first_hit = c->h_adp.data() + ((uint64_t)lane * 2 + mate) * BQC_ADP_ROWS * c->adp_n;
     out->reads_by_length = out->first_hit + (uint64_t)BQC_ADP_MAX * c->adp_n;
     out->adapters = c->adp_set.data();
+    return 0;
+}
+
+extern "C" int bqc_gc_bias(bqc_ctx* c, uint32_t lane, bqc_gcb_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_gcb) return fail(c, BQC_ERR_STATE, "bqc_gc_bias: bqc_enable_gc_bias has not been called for the context");
+    if (!c->gcb_final) return fail(c, BQC_ERR_STATE, "bqc_gc_bias: nothing has been finalised");
+    if (lane >= c->opt.n_lanes) return fail(c, BQC_ERR_ARG, "bqc_gc_bias: lane %u out of range", lane);
+    out->window = c->gcb_w;
+    out->n_bins = BQC_GCB_BINS;
+    out->genome_windows = c->h_gcb_g.data();
+    out->read_starts = c->h_gcb.data() + (uint64_t)lane * BQC_GCB_ROWS * BQC_GCB_BINS;
+    out->bases = out->read_starts + BQC_GCB_BINS;
+    out->qual_sum = out->bases + BQC_GCB_BINS;
     return 0;
 }

@@ -225,6 +225,16 @@ struct bqc_ctx {
     std::vector<uint64_t> h_adp;       // bqc_finalize's copy, and per (lane, mate) the printed length
     std::vector<uint32_t> adp_ncyc;
     bool adp_final = false;
+    // GC bias (k_gcb.hip; bqc_enable_gc_bias(W) after creation — nothing below exists without it)
+    uint32_t gcb_w = 0;                // the window length W
+    GcbDiv gcb_div{};                  // the reciprocals of W - n, n = 0..4
+    uint64_t* d_gcb = nullptr;         // [n_lanes][3: R, B, Q][101], the module's words of the state vector (behind the sketch's, in front of d_adp's)
+    uint64_t gcb_words = 0;
+    uint64_t* d_gcb_g = nullptr;       // [101] the genome table G: bqc_finalize's, not part of the state vector
+    GcbContig* d_gcb_tab = nullptr;    // [n_refs] the contigs of the genome table's launch
+    std::vector<uint64_t> h_gcb, h_gcb_g; // bqc_finalize's copies
+    bool gcb_final = false;
+    bool gcb_closed = false;           // state has been exported, imported or finalised: bqc_enable_gc_bias comes too late
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

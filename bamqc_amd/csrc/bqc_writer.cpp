@@ -239,3 +239,25 @@ extern "C" int bqc_write_adapter_by_cycle(bqc_ctx* ctx, const bqc_header_info* h
     }
     return write_file(o, path);
 }
+
+// The GC bias tables as text (include/bamqc.h): per lane the window length, the genome's windows by GC bin (the same line for every
+// lane: the table belongs to the genome) and the lane's three read tables, key-then-values lines as in the `.bamqc`.
+extern "C" int bqc_write_gc_bias(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path)
+{
+    if (!ctx || !hdr || !path) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 14);
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        bqc_gcb_view v;
+        const int rc = bqc_gc_bias(ctx, hdr->lane_index[n], &v);
+        if (rc) return rc;
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        o.line_u64("gc_bias_window", v.window);
+        o.array("genome_windows_by_gc", v.genome_windows, v.n_bins);
+        o.array("read_starts_by_gc", v.read_starts, v.n_bins);
+        o.array("bases_by_gc", v.bases, v.n_bins);
+        o.array("base_qual_sum_by_gc", v.qual_sum, v.n_bins);
+    }
+    return write_file(o, path);
+}

@@ -159,6 +159,23 @@ struct AdpPatterns {
     uint32_t len[BQC_ADP_MAX], fwd[BQC_ADP_MAX], rc[BQC_ADP_MAX], cmask[BQC_ADP_MAX], vmask[BQC_ADP_MAX];
 };
 
+// GC bias (k_gcb.hip; the statistic: include/bamqc.h).  A read group's words of the state vector: [3 rows: R, B, Q][101 bins], no padding.
+#define BQC_GCB_BINS 101
+#define BQC_GCB_ROWS 3
+#define BQC_GCB_WMIN 20
+#define BQC_GCB_WMAX 1000
+// floor(100 gc / (W - n)) for n = 0..4 without a divide: m[n] = ceil(2^32 / (W - n)), and the quotient is the high word of 100 gc * m[n].
+// Exact: with e = m d - 2^32 < d <= 1000 and x = 100 gc <= 100 000 the error term x e / (d 2^32) stays below 1 / d.
+struct GcbDiv {
+    uint32_t m[5];
+};
+// A contig of the genome table's launch: its bytes, its window starts (len - W + 1 >= 1) and the first of its shares among all shares
+struct GcbContig {
+    const uint8_t* ref;
+    uint64_t nstarts;
+    uint64_t share0;
+};
+
 struct DevRefs {
     const uint8_t* const* ref; // [n_refs] Dna5 codes, nullptr if not loaded
     const uint64_t* len;

@@ -789,6 +789,7 @@ struct ProgramOptions {
     // adapters empty: the built-in set)
     uint32_t adapter_by_cycle = 0;
     std::vector<std::pair<std::string, std::string>> adapters;
+    uint32_t gc_bias = 0; // --gc-bias / --gc-bias-window W: GC bias into <output>.gcb (0: off, else the window length W)
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -822,6 +823,9 @@ void usage(FILE* f)
             "    --adapter-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).\n"
             "    --adapter NAME=SEQ\n          An adapter to look for (repeatable, at most 8; the first one replaces the built-in set): NAME is 1 to 31\n"
             "          characters of [A-Za-z0-9_.-], SEQ 8 to 16 letters of ACGT.  Implies --adapter-by-cycle.\n"
+            "    --gc-bias\n          GC bias: the genome's windows of 100 bases by GC bin, and per read group the reads that start in a\n"
+            "          window of each bin, their bases and the sum of their base qualities, into OUT.gcb.  Not with --gpus.\n"
+            "    --gc-bias-window INT\n          The same for windows of INT bases (at least 20, at most 1000).  Implies --gc-bias.\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -884,6 +888,14 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
     std::string kstr = "32", qstr = "17";
     bool have_r = false, have_o = false, have_m = false;
     bool want_adp = false; // --adapter-by-cycle or an --adapter: the module at 1024 cycles unless --adapter-by-cycle-len says otherwise
+    bool want_gcb = false; // --gc-bias: the module with windows of 100 bases unless --gc-bias-window says otherwise
+    // (--gpus N is the front end's and never reaches this parser from it; given here, it is an illegal option — said in the option's
+    // own terms where the GC bias is asked for as well, which no worker of --gpus could compute)
+    auto gcb_somewhere = [&]() {
+        for (int k = 1; k < argc; ++k)
+            if (strcmp(argv[k], "--gc-bias") == 0 || strncmp(argv[k], "--gc-bias-window", 16) == 0) return true;
+        return false;
+    };
     std::vector<std::string> pos;
     auto need = [&](int& i, const std::string& name, std::string& val, const char* inl) -> bool {
         if (inl) { val = inl; return true; }
@@ -968,11 +980,21 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             o.adapters.emplace_back(nm, sq);
             want_adp = true;
         }
+        else if (key == "--gc-bias") { want_gcb = true; }
+        else if (key == "--gc-bias-window") {
+            if (!need(i, key, v, inl)) return 1;
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x < 20 || x > 1000) { err = "bamqualcheck: the given value '" + v + "' is not a window length (--gc-bias-window wants 20 to 1000)"; return 1; }
+            o.gc_bias = (uint32_t)x;
+        }
+        else if (key == "--gpus" && gcb_somewhere()) { err = "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)"; return 1; }
         else if (key == "--manifest") { if (!need(i, key, v, inl)) return 1; o.manifest = v; have_m = true; }
         else if (a[0] == '-') { err = "bamqualcheck: illegal option -- " + a.substr(a.rfind("--", 0) == 0 ? 2 : 1); return 1; }
         else pos.push_back(a);
     }
     if (want_adp && !o.adapter_by_cycle) o.adapter_by_cycle = 1024;
+    if (want_gcb && !o.gc_bias) o.gc_bias = 100;
     if (!have_r) { err = "bamqualcheck: option requires an argument -- r (required option -r/--reference missing)"; return 1; }
     if (session_form) {
         if (have_o || have_m || !pos.empty()) { err = "bamqualcheck: a session takes the program's options without an input, -o and --manifest"; return 1; }
@@ -1085,7 +1107,7 @@ RefKey make_ref_key(const std::string& fasta, const BamHeader& H)
 }
 // The options that size a context (bqc_options): equal ones mean bqc_reset instead of bqc_create.
 struct CtxKey {
-    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0;
+    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0, gc_bias = 0;
     std::vector<std::pair<std::string, std::string>> adapters; // (empty: the built-in set)
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
@@ -1095,7 +1117,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1128,6 +1150,8 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const int pr = parse_args(argc, argv, opt, perr);
     if (pr == 2) return 0;
     if (pr == 1) { fprintf(stderr, "%s\n", perr.c_str()); return 1; }
+    // (a worker of --gpus N holds only the contigs its batches touch: none has the genome table; the front end says so before it forks)
+    if (shard && opt.gc_bias) { fprintf(stderr, "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)\n"); return 1; }
     using clk = std::chrono::steady_clock;
     const bool timing = getenv("BQC_TIMING") && getenv("BQC_TIMING")[0] == '1'; // BQC_TIMING=1: where the wall time of a run goes (stderr)
     auto since_launch = [&](const char* what) { // (BQC_T0: the launcher's CLOCK_MONOTONIC seconds when it started the program)
@@ -1321,7 +1345,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         ref_key = make_ref_key(opt.referenceFile, H);
         ctx_key.n_lanes = bo.n_lanes; ctx_key.n_refs = bo.n_refs; ctx_key.max_read_len = bo.max_read_len; ctx_key.hist_cap = bo.hist_cap; ctx_key.isize = bo.isize;
         ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch; ctx_key.qual_by_cycle = bo.qual_by_cycle; ctx_key.mismatch_by_cycle = bo.mismatch_by_cycle;
-        ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters;
+        ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters; ctx_key.gc_bias = opt.gc_bias;
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1353,11 +1377,15 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         const auto c2 = clk::now();
         rc = opt.adapter_by_cycle ? bqc_create_ex(&bo, &bm, &ctx) : bqc_create(&bo, &ctx);
         if (rc) create_err = bqc_last_error(nullptr);
-        else if (old) { // the same genome under another context: its contigs change owner, nothing is uploaded
+        else if (opt.gc_bias) { // (the module that is switched on right behind the creation)
+            rc = bqc_enable_gc_bias(ctx, opt.gc_bias);
+            if (rc) create_err = bqc_last_error(ctx);
+        }
+        if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
             rc = bqc_move_references(old, ctx);
             if (rc) create_err = bqc_last_error(ctx);
         }
-        else if (!shard) { // one allocation for the contigs, sized from the BAM header, while nothing runs on the card yet (an allocation beside running kernels waits for them)
+        else if (!rc && !shard) { // one allocation for the contigs, sized from the BAM header, while nothing runs on the card yet (an allocation beside running kernels waits for them)
             uint64_t total = 0;
             for (uint32_t r = 0; r < n_refs; ++r) total += H.ref_lens[r];
             (void)bqc_reserve_references(ctx, total, n_refs);
@@ -1667,10 +1695,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const int mbc_rc = !rc && !qbc_rc && opt.mismatch_by_cycle ? bqc_write_mismatch_by_cycle(ctx, &hi, mbc_path.c_str()) : 0;
     const std::string adp_path = opt.outputFile + ".adp"; // the tables of --adapter-by-cycle, behind the .mbc
     const int adp_rc = !rc && !qbc_rc && !mbc_rc && opt.adapter_by_cycle ? bqc_write_adapter_by_cycle(ctx, &hi, adp_path.c_str()) : 0;
+    const std::string gcb_path = opt.outputFile + ".gcb"; // the tables of --gc-bias, behind the .adp
+    const int gcb_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && opt.gc_bias ? bqc_write_gc_bias(ctx, &hi, gcb_path.c_str()) : 0;
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1687,6 +1717,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (qbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", qbc_path.c_str()); return 1; }
     if (mbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", mbc_path.c_str()); return 1; }
     if (adp_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", adp_path.c_str()); return 1; }
+    if (gcb_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", gcb_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

@@ -487,6 +487,11 @@ extern "C" int bqc_main_multi(int argc, const char** argv, int n_gpus)
         const int pr = bqc_program_args(argc, argv, path, sizeof path);
         if (pr == 2) return 0;
         if (pr != 0) return 1;
+        for (int k = 1; k < argc; ++k) // (a worker holds only the contigs its batches touch: none has the genome table)
+            if (strcmp(argv[k], "--gc-bias") == 0 || strncmp(argv[k], "--gc-bias-window", 16) == 0) {
+                fprintf(stderr, "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)\n");
+                return 1;
+            }
         if (!path[0]) { fprintf(stderr, "bamqualcheck: --gpus with --manifest is not supported: run one process per card (--device), each with a list of its own\n"); return 1; }
         bam = path;
         // (said once, here, before any worker exists: every worker's run_program would say it too)

@@ -442,6 +442,49 @@ typedef struct bqc_adp_view {
 int bqc_adapter_by_cycle(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_adp_view* out);
 int bqc_write_adapter_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
 
+/* ---- GC bias: genome windows and read starts by GC (bqc_enable_gc_bias; not in the reference) ------------------------------------
+ * Window length W: 100 by default, 20 <= W <= 1000.  There are 101 bins, g = 0 ... 100.
+ * GC bin of a window.  For a window [s, s+W) of contig rid, with 0 <= s and s + W <= len(rid):
+ *   gc = number of bases with Dna5 code 1 or 2 (C, G);  n = number of bases with code 4 (N);
+ *   if n > 4 the window has no bin;  otherwise g = floor(100 * gc / (W - n)).
+ * Genome table G[g].  For every contig that has been given with bqc_set_reference (or moved in with bqc_move_references), every s in
+ * [0, len - W] whose window has a bin adds 1 to G[g].  A contig shorter than W adds nothing.  G belongs to the genome, not to the
+ * reads: it is not part of the state vector, it is not summed by import or the reduce, and bqc_reset does not touch it.  The context
+ * that finalises computes it at bqc_finalize from the contigs it holds at that moment, into a buffer of its own.
+ * Which reads count.  A read is examined iff all of these hold:  flag & 0x904 == 0 (primary and mapped);  n_cigar > 0;
+ * 0 <= rid < n_refs and the contig is on the card.  There is no mate-flag requirement, so single-end reads count.  There is no
+ * mapping-quality filter.  Duplicates and QC-fail reads count, as in the `.qbc` and `.mbc`.  A read group at or behind n_lanes cannot
+ * reach the kernel: the pre-pass refuses such a batch.
+ * A read's window.  Positions are 0-based and the arithmetic is 64-bit signed.  Forward read (0x10 clear): s = pos.  Reverse read:
+ * s = end - W, where end = pos + the sum of the lengths of the CIGAR operations M, D, N, =, X (0, 2, 3, 7, 8).  The read is counted iff
+ * 0 <= s, s + W <= len(rid), and the window has a bin g.  The read's own length plays no part: a read shorter than W still has a
+ * window of W genome bases.
+ * Read tables, per read group.  R[lane][g] += 1 for every counted read.  For a counted read without BQC_FLAG_NO_QUAL:
+ * B[lane][g] += l_seq;  Q[lane][g] += the sum of its quality bytes as stored, each 0 ... 255.  A counted read without qualities
+ * enters R only.
+ * What a consumer derives:  normalised coverage of bin g = (R[g] / sum R) / (G[g] / sum G);  mean base quality at GC g = Q[g] / B[g].
+ * bqc_enable_gc_bias switches the module on, after creation (bqc_options and bqc_modules stay as they are).  BQC_ERR_ARG, with a
+ * message that names the value: a window outside 20 ... 1000.  BQC_ERR_STATE: a second call; a call after the context has taken a
+ * batch (bqc_submit, bqc_submit_async, bqc_upload, bqc_anchor_enqueue / bqc_submit_anchored), has exported or imported state, or has
+ * been finalised.  The call allocates the tables: after it bqc_state_words is larger by n_lanes * 3 * 101 words, [n_lanes][3 rows: R,
+ * B, Q][101] u64 without padding, directly behind the sketch's words and IN FRONT OF adapter_by_cycle's, mismatch_by_cycle's and
+ * qual_by_cycle's.  All of them are pure sums: export / import, bqc_reset, shard hand-over and the reduce treat them as the other words.
+ * Two contexts exchange state only when both or neither have the module on (their bqc_state_words differ otherwise).  Without the
+ * call: no allocation, no launch, the same bqc_state_words and the same offsets.  With it: the `.bamqc`, `.qbc`, `.mbc` and `.adp` are
+ * the same bytes as without it.
+ * bqc_gc_bias: valid after bqc_finalize; the view (n_bins = 101 entries per array) is owned by the context until the next finalize /
+ * destroy.  BQC_ERR_STATE: the module is off, or nothing has been finalised; BQC_ERR_ARG: lane out of range.
+ * bqc_write_gc_bias: the tables as text, lanes in the order of `hdr`, key-then-values lines as in the `.bamqc`:
+ *   sample_id <id> / lane <name> / gc_bias_window <W> / genome_windows_by_gc v0 ... v100 / read_starts_by_gc v0 ... v100 /
+ *   bases_by_gc v0 ... v100 / base_qual_sum_by_gc v0 ... v100 */
+int bqc_enable_gc_bias(bqc_ctx* ctx, uint32_t window);   /* 20 <= window <= 1000 */
+typedef struct bqc_gcb_view {
+    uint32_t window, n_bins;
+    const uint64_t *genome_windows, *read_starts, *bases, *qual_sum;
+} bqc_gcb_view;
+int bqc_gc_bias(bqc_ctx* ctx, uint32_t lane, bqc_gcb_view* out);   /* after bqc_finalize; n_bins = 101 */
+int bqc_write_gc_bias(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
