@@ -129,6 +129,11 @@ class GcbView(C.Structure):  # bqc_gcb_view: four arrays of n_bins = 101 entries
                 ("qual_sum", u64p)]
 
 
+class IbcView(C.Structure):  # bqc_ibc_view: three arrays of n_cycles entries by cycle, two of n_len = 64 entries by length (entry i: i + 1)
+    _fields_ = [("n_cycles", C.c_uint32), ("n_len", C.c_uint32), ("reads_by_length", u64p), ("insertions", u64p), ("deletions", u64p),
+                ("insertion_lengths", u64p), ("deletion_lengths", u64p)]
+
+
 def make_modules(adapter_by_cycle=0, adapters=None, struct_size=None):
     """bqc_modules: adapter_by_cycle = the cycle capacity N (0: off), adapters = [(name, sequence), ...] or None for the built-in set."""
     m = Modules()

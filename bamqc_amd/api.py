@@ -38,7 +38,7 @@ class DeviceBatch:
 
 
 class Aggregator:
-    def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, **options):
+    def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, indel_by_cycle=None, **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
@@ -56,9 +56,18 @@ class Aggregator:
             except BamQCError:
                 self.close()
                 raise
+        if indel_by_cycle is not None:  # the same way: indels by cycle and by length, cycle capacity indel_by_cycle
+            try:
+                self.enable_indel_by_cycle(indel_by_cycle)
+            except BamQCError:
+                self.close()
+                raise
 
     def enable_gc_bias(self, window=100):
         self._chk(self.lib.bqc_enable_gc_bias(self.h, window))
+
+    def enable_indel_by_cycle(self, n_cycles=1024):
+        self._chk(self.lib.bqc_enable_indel_by_cycle(self.h, n_cycles))
 
     def _chk(self, rc):
         if rc:
@@ -218,6 +227,25 @@ class Aggregator:
             self.finalize_raw()
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_gc_bias(self.h, C.byref(hdr), path.encode()))
+
+    def indel_by_cycle(self, lane=0, mate=0):
+        """(reads_by_length, insertions, deletions, insertion_lengths, deletion_lengths) of a read group and mate (0 first, 1 second):
+        the examined reads by length and the insertion and deletion events by cycle, three (n_cycles,) uint64 arrays, and the events by
+        length, two (64,) uint64 arrays whose entry i counts length i + 1, the last one 64 and more (option indel_by_cycle=N; valid
+        after finalize)."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.IbcView()
+        self._chk(self.lib.bqc_indel_by_cycle(self.h, lane, mate, C.byref(v)))
+        by_cycle = tuple(np.ctypeslib.as_array(p, shape=(v.n_cycles,)).copy() if v.n_cycles else np.zeros(0, np.uint64)
+                         for p in (v.reads_by_length, v.insertions, v.deletions))
+        return by_cycle + tuple(np.ctypeslib.as_array(p, shape=(v.n_len,)).copy() for p in (v.insertion_lengths, v.deletion_lengths))
+
+    def write_indel_by_cycle(self, path, sample_id="", lane_names=("",), lane_index=None):
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        self._chk(self.lib.bqc_write_indel_by_cycle(self.h, C.byref(hdr), path.encode()))
 
     def close(self):
         if self.h:

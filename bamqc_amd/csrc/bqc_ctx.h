@@ -234,7 +234,14 @@ struct bqc_ctx {
     GcbContig* d_gcb_tab = nullptr;    // [n_refs] the contigs of the genome table's launch
     std::vector<uint64_t> h_gcb, h_gcb_g; // bqc_finalize's copies
     bool gcb_final = false;
-    bool gcb_closed = false;           // state has been exported, imported or finalised: bqc_enable_gc_bias comes too late
+    bool gcb_closed = false;           // state has been exported, imported or finalised: bqc_enable_gc_bias / _indel_by_cycle come too late
+    // indels by cycle and by length (k_ibc.hip; bqc_enable_indel_by_cycle(N) after creation — nothing below exists without it)
+    uint32_t ibc_n = 0;                // the cycle capacity N
+    uint64_t* d_ibc = nullptr;         // [n_lanes][2 mates]{[3: E, IC, DC][N], [2: IL, DL][64]}, the module's words of the state vector (behind the sketch's, in front of d_gcb's)
+    uint64_t ibc_words = 0;
+    std::vector<uint64_t> h_ibc;       // bqc_finalize's copy, and per (lane, mate) the printed length
+    std::vector<uint32_t> ibc_ncyc;
+    bool ibc_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

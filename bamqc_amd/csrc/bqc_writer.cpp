@@ -261,3 +261,29 @@ extern "C" int bqc_write_gc_bias(bqc_ctx* ctx, const bqc_header_info* hdr, const
     }
     return write_file(o, path);
 }
+
+// The indel tables as text (include/bamqc.h): per lane and mate the reads by length, the insertions and the deletions by cycle and
+// the two length histograms, key-then-values lines as in the `.bamqc`.
+extern "C" int bqc_write_indel_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path)
+{
+    if (!ctx || !hdr || !path) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 14);
+    static const char* const mates[2] = {"first", "second"};
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        for (uint32_t m = 0; m < 2; ++m) {
+            bqc_ibc_view v;
+            const int rc = bqc_indel_by_cycle(ctx, hdr->lane_index[n], m, &v);
+            if (rc) return rc;
+            const std::string sfx = std::string("_") + mates[m];
+            o.array(("indel_reads_by_length" + sfx).c_str(), v.reads_by_length, v.n_cycles);
+            o.array(("insertions_by_position" + sfx).c_str(), v.insertions, v.n_cycles);
+            o.array(("deletions_by_position" + sfx).c_str(), v.deletions, v.n_cycles);
+            o.array(("insertion_length_histogram" + sfx).c_str(), v.insertion_lengths, v.n_len);
+            o.array(("deletion_length_histogram" + sfx).c_str(), v.deletion_lengths, v.n_len);
+        }
+    }
+    return write_file(o, path);
+}

@@ -176,6 +176,12 @@ struct GcbContig {
     uint64_t share0;
 };
 
+// Indels by cycle and by length (k_ibc.hip; the statistic: include/bamqc.h).  The words of a read group and mate:
+// [3 rows: E, IC, DC][N] then [2 rows: IL, DL][64], no padding.
+#define BQC_IBC_ROWS 3
+#define BQC_IBC_K 64
+#define BQC_IBC_MATE_WORDS(N) ((uint64_t)BQC_IBC_ROWS * (N) + 2 * BQC_IBC_K)
+
 struct DevRefs {
     const uint8_t* const* ref; // [n_refs] Dna5 codes, nullptr if not loaded
     const uint64_t* len;

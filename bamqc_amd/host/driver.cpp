@@ -790,6 +790,7 @@ struct ProgramOptions {
     uint32_t adapter_by_cycle = 0;
     std::vector<std::pair<std::string, std::string>> adapters;
     uint32_t gc_bias = 0; // --gc-bias / --gc-bias-window W: GC bias into <output>.gcb (0: off, else the window length W)
+    uint32_t indel_by_cycle = 0; // --indel-by-cycle / --indel-by-cycle-len N: indels by cycle and by length into <output>.ibc (0: off, else N)
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -826,6 +827,9 @@ void usage(FILE* f)
             "    --gc-bias\n          GC bias: the genome's windows of 100 bases by GC bin, and per read group the reads that start in a\n"
             "          window of each bin, their bases and the sum of their base qualities, into OUT.gcb.  Not with --gpus.\n"
             "    --gc-bias-window INT\n          The same for windows of INT bases (at least 20, at most 1000).  Implies --gc-bias.\n"
+            "    --indel-by-cycle\n          Insertions and deletions by cycle (read group x mate x the first 1024 cycles) and by length (1 to 64\n"
+            "          and more), with the reads by length they are rates of, into OUT.ibc.\n"
+            "    --indel-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).  Implies --indel-by-cycle.\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -981,6 +985,14 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             want_adp = true;
         }
         else if (key == "--gc-bias") { want_gcb = true; }
+        else if (key == "--indel-by-cycle") { if (!o.indel_by_cycle) o.indel_by_cycle = 1024; }
+        else if (key == "--indel-by-cycle-len") {
+            if (!need(i, key, v, inl)) return 1;
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--indel-by-cycle-len wants 1 or more)"; return 1; }
+            o.indel_by_cycle = (uint32_t)x;
+        }
         else if (key == "--gc-bias-window") {
             if (!need(i, key, v, inl)) return 1;
             char* end = nullptr;
@@ -1107,7 +1119,7 @@ RefKey make_ref_key(const std::string& fasta, const BamHeader& H)
 }
 // The options that size a context (bqc_options): equal ones mean bqc_reset instead of bqc_create.
 struct CtxKey {
-    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0, gc_bias = 0;
+    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0, gc_bias = 0, indel_by_cycle = 0;
     std::vector<std::pair<std::string, std::string>> adapters; // (empty: the built-in set)
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
@@ -1117,7 +1129,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1345,7 +1357,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         ref_key = make_ref_key(opt.referenceFile, H);
         ctx_key.n_lanes = bo.n_lanes; ctx_key.n_refs = bo.n_refs; ctx_key.max_read_len = bo.max_read_len; ctx_key.hist_cap = bo.hist_cap; ctx_key.isize = bo.isize;
         ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch; ctx_key.qual_by_cycle = bo.qual_by_cycle; ctx_key.mismatch_by_cycle = bo.mismatch_by_cycle;
-        ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters; ctx_key.gc_bias = opt.gc_bias;
+        ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters; ctx_key.gc_bias = opt.gc_bias; ctx_key.indel_by_cycle = opt.indel_by_cycle;
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1379,6 +1391,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         if (rc) create_err = bqc_last_error(nullptr);
         else if (opt.gc_bias) { // (the module that is switched on right behind the creation)
             rc = bqc_enable_gc_bias(ctx, opt.gc_bias);
+            if (rc) create_err = bqc_last_error(ctx);
+        }
+        if (!rc && opt.indel_by_cycle) {
+            rc = bqc_enable_indel_by_cycle(ctx, opt.indel_by_cycle);
             if (rc) create_err = bqc_last_error(ctx);
         }
         if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
@@ -1697,10 +1713,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const int adp_rc = !rc && !qbc_rc && !mbc_rc && opt.adapter_by_cycle ? bqc_write_adapter_by_cycle(ctx, &hi, adp_path.c_str()) : 0;
     const std::string gcb_path = opt.outputFile + ".gcb"; // the tables of --gc-bias, behind the .adp
     const int gcb_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && opt.gc_bias ? bqc_write_gc_bias(ctx, &hi, gcb_path.c_str()) : 0;
+    const std::string ibc_path = opt.outputFile + ".ibc"; // the tables of --indel-by-cycle, behind the .gcb
+    const int ibc_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && opt.indel_by_cycle ? bqc_write_indel_by_cycle(ctx, &hi, ibc_path.c_str()) : 0;
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1718,6 +1736,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (mbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", mbc_path.c_str()); return 1; }
     if (adp_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", adp_path.c_str()); return 1; }
     if (gcb_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", gcb_path.c_str()); return 1; }
+    if (ibc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", ibc_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

@@ -467,8 +467,8 @@ int bqc_write_adapter_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const c
  * message that names the value: a window outside 20 ... 1000.  BQC_ERR_STATE: a second call; a call after the context has taken a
  * batch (bqc_submit, bqc_submit_async, bqc_upload, bqc_anchor_enqueue / bqc_submit_anchored), has exported or imported state, or has
  * been finalised.  The call allocates the tables: after it bqc_state_words is larger by n_lanes * 3 * 101 words, [n_lanes][3 rows: R,
- * B, Q][101] u64 without padding, directly behind the sketch's words and IN FRONT OF adapter_by_cycle's, mismatch_by_cycle's and
- * qual_by_cycle's.  All of them are pure sums: export / import, bqc_reset, shard hand-over and the reduce treat them as the other words.
+ * B, Q][101] u64 without padding, behind the sketch's words (and indel_by_cycle's, below) and IN FRONT OF adapter_by_cycle's,
+ * mismatch_by_cycle's and qual_by_cycle's.  All of them are pure sums: export / import, bqc_reset, shard hand-over and the reduce treat them as the other words.
  * Two contexts exchange state only when both or neither have the module on (their bqc_state_words differ otherwise).  Without the
  * call: no allocation, no launch, the same bqc_state_words and the same offsets.  With it: the `.bamqc`, `.qbc`, `.mbc` and `.adp` are
  * the same bytes as without it.
@@ -484,6 +484,56 @@ typedef struct bqc_gcb_view {
 } bqc_gcb_view;
 int bqc_gc_bias(bqc_ctx* ctx, uint32_t lane, bqc_gcb_view* out);   /* after bqc_finalize; n_bins = 101 */
 int bqc_write_gc_bias(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
+
+/* ---- indels by cycle and by length (bqc_enable_indel_by_cycle; not in the reference) ----------------------------------------------
+ * What the `.mbc` leaves out: where in the read insertions and deletions occur, and how long they are (samtools stats: IC and ID).
+ * Capacity N: 1 <= N <= max_read_len.  Length bins: K = 64.
+ * Examined reads.  A read is examined when all of these hold:  flag & 0x900 == 0;  flag & 0xC0 != 0;  flag & 0x4 is clear;
+ * n_cigar > 0;  l_seq > 0;  lane < n_lanes.  The mate is 0 with 0x40, else 1 (k_qcyc's rule).  There is no condition on mapping
+ * quality, on duplicates, on BQC_FLAG_NO_QUAL, on rid or on a loaded contig: the genome is not read.  A read group at or behind
+ * n_lanes and a primary read without a mate flag cannot reach the kernel: the pre-pass refuses such a batch.
+ * The walk, in stored (BAM) orientation and 64-bit arithmetic, for a read of L = l_seq bases: j = 0; for each CIGAR operation with code
+ * op and length n, in stored order:
+ *   M, =, X, S (0, 7, 8, 4):  j += n.
+ *   I (1):  an insertion of n bases at stored index j.  It is an event iff n >= 1 and j + n <= L.  Its cycle is c = j for a forward
+ *     read and c = L - j - n with 0x10 set: the first of the inserted bases in sequencing order.  Then j += n, event or not.
+ *   D (2):  a deletion of n genome bases between stored bases j-1 and j.  It is an event iff n >= 1 and 0 < j < L: a read base on both
+ *     sides.  Its cycle is the last cycle sequenced before the gap: c = j - 1 for a forward read, c = L - 1 - j with 0x10 set.
+ *     j is unchanged.
+ *   N, H, P (3, 5, 6) and every code of 9 or more:  nothing.  A reference skip is not a deletion.  Hard clips do not shift cycles.
+ * An event whose cycle is at or behind N enters NO table, the length tables included.
+ * Tables, per read group and mate:
+ *   E[min(L, N) - 1] += 1 for every examined read (the denominator);
+ *   IC[c] += 1 and IL[min(n, K) - 1] += 1 for an insertion event;  DC[c] += 1 and DL[min(n, K) - 1] += 1 for a deletion event.
+ * The last bin of a length table holds every length of K or more.  By construction sum IC = sum IL and sum DC = sum DL.  The insertion
+ * rate at cycle c is IC[c] / sum E[c..].
+ * State.  All of it is pure sums.  The words of a read group and mate are [3 rows: E, IC, DC][N] followed by [2 rows: IL, DL][64],
+ * all u64 without padding; in full [n_lanes][2 mates] of that, n_lanes * 2 * (3 N + 128) words.  They lie directly behind the sketch's
+ * words, IN FRONT OF gc-bias's, adapter_by_cycle's, mismatch_by_cycle's and qual_by_cycle's.  Export / import, bqc_reset, shard
+ * hand-over and the reduce treat them as the other words, so the module works across shards (--gpus N), unlike the GC bias.  Two
+ * contexts exchange state only when both or neither have the module on, with the same N.
+ * bqc_enable_indel_by_cycle switches the module on, after creation (bqc_options and bqc_modules stay as they are).  BQC_ERR_ARG, with
+ * a message that names the value: N = 0 or N > max_read_len.  BQC_ERR_STATE: a second call; a call after the context has taken a batch,
+ * has exported or imported state, or has been finalised (bqc_enable_gc_bias's conditions).  Both enable calls may be made on one
+ * context, in either order, with the same layout.  Without the call: no allocation, no launch, the same bqc_state_words and the same
+ * offsets.  With it: the `.bamqc`, `.qbc`, `.mbc`, `.adp` and `.gcb` are the same bytes as without it.
+ * bqc_indel_by_cycle: valid after bqc_finalize; the view is owned by the context until the next finalize / destroy.
+ *   n_cycles = 1 + the highest index with a non-zero E for the lane and mate, 0 when there is none (from the module's own sums, as in
+ *   the `.adp`): the entries of reads_by_length, insertions and deletions.  n_len = 64: the entries of the two length arrays, entry
+ *   i for length i + 1.
+ * BQC_ERR_STATE: the module is off, or nothing has been finalised; BQC_ERR_ARG: lane or mate out of range.
+ * bqc_write_indel_by_cycle: the tables as text, lanes in the order of `hdr`, key-then-values lines as in the `.bamqc`:
+ *   sample_id <id> / lane <name> / indel_reads_by_length_first v0 ... v(n_cycles-1) / insertions_by_position_first v0 ... /
+ *   deletions_by_position_first v0 ... / insertion_length_histogram_first v1 ... v64 / deletion_length_histogram_first v1 ... v64 /
+ *   the same five lines with _second.
+ * With n_cycles = 0 the three per-position keys stand without values; the two length lines always have 64 values. */
+int bqc_enable_indel_by_cycle(bqc_ctx* ctx, uint32_t n_cycles);   /* 1 <= n_cycles <= max_read_len */
+typedef struct bqc_ibc_view {
+    uint32_t n_cycles, n_len;
+    const uint64_t *reads_by_length, *insertions, *deletions, *insertion_lengths, *deletion_lengths;
+} bqc_ibc_view;
+int bqc_indel_by_cycle(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_ibc_view* out);   /* after bqc_finalize; n_len = 64 */
+int bqc_write_indel_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
 
 #ifdef __cplusplus
 }
