@@ -134,6 +134,10 @@ class IbcView(C.Structure):  # bqc_ibc_view: three arrays of n_cycles entries by
                 ("insertion_lengths", u64p), ("deletion_lengths", u64p)]
 
 
+class SbcView(C.Structure):  # bqc_sbc_view: by_context of 512 entries [s][ctx][b'], by_cycle of 16 n_cycles entries [c][t'][b']
+    _fields_ = [("n_cycles", C.c_uint32), ("min_base_qual", C.c_uint32), ("min_mapq", C.c_uint32), ("by_context", u64p), ("by_cycle", u64p)]
+
+
 def make_modules(adapter_by_cycle=0, adapters=None, struct_size=None):
     """bqc_modules: adapter_by_cycle = the cycle capacity N (0: off), adapters = [(name, sequence), ...] or None for the built-in set."""
     m = Modules()

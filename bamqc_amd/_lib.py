@@ -67,6 +67,9 @@ _SIGNATURES = {
     "bqc_enable_indel_by_cycle": (C.c_int, [C.c_void_p, C.c_uint32]),
     "bqc_indel_by_cycle": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(_abi.IbcView)]),
     "bqc_write_indel_by_cycle": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.c_char_p]),
+    "bqc_enable_substitutions": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bqc_substitutions": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(_abi.SbcView)]),
+    "bqc_write_substitutions": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.c_char_p]),
     # include/bamqc_host.h
     "bqc_synth_reference": (C.c_int, [C.c_uint64, C.c_int32, C.c_uint64, _abi.u8p]),
     "bqc_synth_batch": (C.c_int, [C.POINTER(_abi.SynthParams), C.POINTER(_abi.u8p), C.POINTER(C.POINTER(_abi.Batch))]),

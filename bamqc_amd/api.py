@@ -38,7 +38,8 @@ class DeviceBatch:
 
 
 class Aggregator:
-    def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, indel_by_cycle=None, **options):
+    def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, indel_by_cycle=None, substitutions=None, subst_min_qual=20, subst_min_mapq=30,
+                 **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
@@ -62,6 +63,16 @@ class Aggregator:
             except BamQCError:
                 self.close()
                 raise
+
+        if substitutions is not None:  # the same way: substitutions by context and by cycle, cycle capacity `substitutions`
+            try:
+                self.enable_substitutions(substitutions, subst_min_qual, subst_min_mapq)
+            except BamQCError:
+                self.close()
+                raise
+
+    def enable_substitutions(self, n_cycles=1024, min_base_qual=20, min_mapq=30):
+        self._chk(self.lib.bqc_enable_substitutions(self.h, n_cycles, min_base_qual, min_mapq))
 
     def enable_gc_bias(self, window=100):
         self._chk(self.lib.bqc_enable_gc_bias(self.h, window))
@@ -246,6 +257,24 @@ class Aggregator:
             self.finalize_raw()
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_indel_by_cycle(self.h, C.byref(hdr), path.encode()))
+
+    def substitutions(self, lane=0, mate=0):
+        """(by_context, by_cycle) of a read group and mate (0 first, 1 second), as sequenced: by_context[strand][context][read base],
+        (2, 64, 4) uint64, the context 16 * genome base before + 4 * genome base + genome base behind; by_cycle[cycle][genome base][read
+        base], (n_cycles, 4, 4) uint64 (option substitutions=N; valid after finalize)."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.SbcView()
+        self._chk(self.lib.bqc_substitutions(self.h, lane, mate, C.byref(v)))
+        by_context = np.ctypeslib.as_array(v.by_context, shape=(2, 64, 4)).copy()
+        by_cycle = np.ctypeslib.as_array(v.by_cycle, shape=(v.n_cycles, 4, 4)).copy() if v.n_cycles else np.zeros((0, 4, 4), np.uint64)
+        return by_context, by_cycle
+
+    def write_substitutions(self, path, sample_id="", lane_names=("",), lane_index=None):
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        self._chk(self.lib.bqc_write_substitutions(self.h, C.byref(hdr), path.encode()))
 
     def close(self):
         if self.h:

@@ -31,6 +31,7 @@ uint64_t bqc_mbc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_adp_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_gcb_words(uint32_t n_lanes);
 uint64_t bqc_ibc_words(uint32_t n_lanes, uint32_t N);
+uint64_t bqc_sbc_words(uint32_t n_lanes, uint32_t N);
 uint32_t bqc_gcb_share(void);
 void bqc_launch_gcb_genome(const GcbContig* tab, uint32_t n_contigs, uint64_t n_shares, uint32_t W, const GcbDiv& D, uint64_t* G, uint32_t n_cu, hipStream_t s);
 hipError_t bqc_long_init();
@@ -392,6 +393,7 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (c->d_adp) (void)hipFree(c->d_adp);
     if (c->d_gcb) (void)hipFree(c->d_gcb);
     if (c->d_ibc) (void)hipFree(c->d_ibc);
+    if (c->d_sbc) (void)hipFree(c->d_sbc);
     if (c->d_gcb_g) (void)hipFree(c->d_gcb_g);
     if (c->d_gcb_tab) (void)hipFree(c->d_gcb_tab);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
@@ -514,6 +516,8 @@ extern "C" int bqc_reset(bqc_ctx* c)
     c->gcb_final = false;
     if (c->d_ibc) HIPCHK(c, hipMemsetAsync(c->d_ibc, 0, c->ibc_words * 8, c->stream));
     c->ibc_final = false;
+    if (c->d_sbc) HIPCHK(c, hipMemsetAsync(c->d_sbc, 0, c->sbc_words * 8, c->stream));
+    c->sbc_final = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -560,8 +564,9 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-// the flat vector: [sl.words][sketch][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
-static uint64_t ibc_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+// the flat vector: [sl.words][sketch][substitutions][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
+static uint64_t sbc_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+static uint64_t ibc_offset(const bqc_ctx* c) { return sbc_offset(c) + c->sbc_words; }
 static uint64_t gcb_offset(const bqc_ctx* c) { return ibc_offset(c) + c->ibc_words; }
 static uint64_t adp_offset(const bqc_ctx* c) { return gcb_offset(c) + c->gcb_words; }
 static uint64_t mbc_offset(const bqc_ctx* c) { return adp_offset(c) + c->adp_words; }
@@ -577,6 +582,7 @@ extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
+    if (c->d_sbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_ibc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + ibc_offset(c), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_gcb) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + gcb_offset(c), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_adp) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + adp_offset(c), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -594,6 +600,7 @@ extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
+    if (c->d_sbc) HIPCHK(c, hipMemcpyAsync(c->d_sbc, (const uint64_t*)src + sbc_offset(c), c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_ibc) HIPCHK(c, hipMemcpyAsync(c->d_ibc, (const uint64_t*)src + ibc_offset(c), c->ibc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_gcb) HIPCHK(c, hipMemcpyAsync(c->d_gcb, (const uint64_t*)src + gcb_offset(c), c->gcb_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_adp) HIPCHK(c, hipMemcpyAsync(c->d_adp, (const uint64_t*)src + adp_offset(c), c->adp_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -621,6 +628,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
         HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_sbc) HIPCHK(c, hipMemcpy(dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToHost));
     if (c->d_ibc) HIPCHK(c, hipMemcpy(dst + ibc_offset(c), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToHost));
     if (c->d_gcb) HIPCHK(c, hipMemcpy(dst + gcb_offset(c), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToHost));
     if (c->d_adp) HIPCHK(c, hipMemcpy(dst + adp_offset(c), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToHost));
@@ -646,6 +654,7 @@ extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_sbc) HIPCHK(c, hipMemcpy(c->d_sbc, src + sbc_offset(c), c->sbc_words * 8, hipMemcpyHostToDevice));
     if (c->d_ibc) HIPCHK(c, hipMemcpy(c->d_ibc, src + ibc_offset(c), c->ibc_words * 8, hipMemcpyHostToDevice));
     if (c->d_gcb) HIPCHK(c, hipMemcpy(c->d_gcb, src + gcb_offset(c), c->gcb_words * 8, hipMemcpyHostToDevice));
     if (c->d_adp) HIPCHK(c, hipMemcpy(c->d_adp, src + adp_offset(c), c->adp_words * 8, hipMemcpyHostToDevice));
@@ -736,6 +745,30 @@ extern "C" int bqc_enable_indel_by_cycle(bqc_ctx* c, uint32_t n_cycles)
     c->ibc_n = n_cycles;
     c->ibc_words = words;
     c->d_ibc = d;
+    return 0;
+}
+
+extern "C" int bqc_enable_substitutions(bqc_ctx* c, uint32_t n_cycles, uint32_t min_base_qual, uint32_t min_mapq)
+{
+    if (!c) return BQC_ERR_ARG;
+    if (!n_cycles || n_cycles > c->opt.max_read_len || n_cycles >= 1u << 27)
+        return fail(c, BQC_ERR_ARG, "bqc_enable_substitutions: capacity %u is outside 1 ... max_read_len %u", n_cycles, c->opt.max_read_len);
+    if (min_base_qual > 222) return fail(c, BQC_ERR_ARG, "bqc_enable_substitutions: minimum base quality %u is outside 0 ... 222", min_base_qual);
+    if (min_mapq > 255) return fail(c, BQC_ERR_ARG, "bqc_enable_substitutions: minimum mapping quality %u is outside 0 ... 255", min_mapq);
+    if (c->d_sbc) return fail(c, BQC_ERR_STATE, "bqc_enable_substitutions: the module is on already (capacity %u)", c->sbc_n);
+    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
+        return fail(c, BQC_ERR_STATE, "bqc_enable_substitutions: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t words = bqc_sbc_words(c->opt.n_lanes, n_cycles);
+    uint64_t* d = nullptr;
+    if (hipMalloc(&d, words * 8) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d);
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_substitutions: the tables (%llu bytes) could not be allocated", (unsigned long long)(words * 8));
+    }
+    c->sbc_n = n_cycles; c->sbc_q = min_base_qual; c->sbc_mq = min_mapq;
+    c->sbc_words = words;
+    c->d_sbc = d;
     return 0;
 }
 
@@ -856,6 +889,16 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
                 c->adp_ncyc[l * 2 + m] = last_nonzero_len(c->h_adp.data() + (((uint64_t)l * 2 + m) * BQC_ADP_ROWS + BQC_ADP_MAX) * N, N);
         c->adp_final = true;
     }
+    if (c->d_sbc) {
+        c->h_sbc.resize(c->sbc_words);
+        HIPCHK(c, hipMemcpy(c->h_sbc.data(), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToHost));
+        const uint32_t N = c->sbc_n;
+        c->sbc_ncyc.assign((size_t)sl.n_lanes * 2, 0);
+        for (uint32_t l = 0; l < sl.n_lanes; ++l)
+            for (int m = 0; m < 2; ++m) // (Y of a (lane, mate): 16 words a cycle)
+                c->sbc_ncyc[l * 2 + m] = (last_nonzero_len(c->h_sbc.data() + ((uint64_t)l * 2 + m) * BQC_SBC_MATE_WORDS(N) + BQC_SBC_X_WORDS, 16 * N) + 15) / 16;
+        c->sbc_final = true;
+    }
     if (c->d_ibc) {
         c->h_ibc.resize(c->ibc_words);
         HIPCHK(c, hipMemcpy(c->h_ibc.data(), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToHost));
@@ -951,5 +994,19 @@ extern "C" int bqc_indel_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_
     out->deletions = out->insertions + N;
     out->insertion_lengths = out->deletions + N;
     out->deletion_lengths = out->insertion_lengths + BQC_IBC_K;
+    return 0;
+}
+
+extern "C" int bqc_substitutions(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_sbc_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_sbc) return fail(c, BQC_ERR_STATE, "bqc_substitutions: bqc_enable_substitutions has not been called for the context");
+    if (!c->sbc_final) return fail(c, BQC_ERR_STATE, "bqc_substitutions: nothing has been finalised");
+    if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_substitutions: lane %u / mate %u out of range", lane, mate);
+    out->n_cycles = c->sbc_ncyc[lane * 2 + mate];
+    out->min_base_qual = c->sbc_q;
+    out->min_mapq = c->sbc_mq;
+    out->by_context = c->h_sbc.data() + ((uint64_t)lane * 2 + mate) * BQC_SBC_MATE_WORDS(c->sbc_n);
+    out->by_cycle = out->by_context + BQC_SBC_X_WORDS;
     return 0;
 }

@@ -234,7 +234,7 @@ struct bqc_ctx {
     GcbContig* d_gcb_tab = nullptr;    // [n_refs] the contigs of the genome table's launch
     std::vector<uint64_t> h_gcb, h_gcb_g; // bqc_finalize's copies
     bool gcb_final = false;
-    bool gcb_closed = false;           // state has been exported, imported or finalised: bqc_enable_gc_bias / _indel_by_cycle come too late
+    bool gcb_closed = false;           // state has been exported, imported or finalised: bqc_enable_gc_bias / _indel_by_cycle / _substitutions come too late
     // indels by cycle and by length (k_ibc.hip; bqc_enable_indel_by_cycle(N) after creation — nothing below exists without it)
     uint32_t ibc_n = 0;                // the cycle capacity N
     uint64_t* d_ibc = nullptr;         // [n_lanes][2 mates]{[3: E, IC, DC][N], [2: IL, DL][64]}, the module's words of the state vector (behind the sketch's, in front of d_gcb's)
@@ -242,6 +242,13 @@ struct bqc_ctx {
     std::vector<uint64_t> h_ibc;       // bqc_finalize's copy, and per (lane, mate) the printed length
     std::vector<uint32_t> ibc_ncyc;
     bool ibc_final = false;
+    // substitutions by context and by cycle (k_sbc.hip; bqc_enable_substitutions(N, Q, MQ) after creation — nothing below exists without it)
+    uint32_t sbc_n = 0, sbc_q = 0, sbc_mq = 0; // the cycle capacity N, the minimum base quality, the minimum mapping quality
+    uint64_t* d_sbc = nullptr;         // [n_lanes][2 mates]{X [2 strands][64][4], Y [N][16]}, the module's words of the state vector (behind the sketch's, in front of d_ibc's)
+    uint64_t sbc_words = 0;
+    std::vector<uint64_t> h_sbc;       // bqc_finalize's copy, and per (lane, mate) the printed length
+    std::vector<uint32_t> sbc_ncyc;
+    bool sbc_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -287,3 +287,38 @@ extern "C" int bqc_write_indel_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr
     }
     return write_file(o, path);
 }
+
+// The substitution tables as text (include/bamqc.h): per lane the two thresholds, then per mate the contexts of the reads on the
+// forward and on the reverse strand, one line a context, and the base pairs by cycle, one line a cycle.
+extern "C" int bqc_write_substitutions(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path)
+{
+    if (!ctx || !hdr || !path) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 16);
+    static const char* const mates[2] = {"first", "second"};
+    static const char* const strands[2] = {"forward", "reverse"};
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        for (uint32_t m = 0; m < 2; ++m) {
+            bqc_sbc_view v;
+            const int rc = bqc_substitutions(ctx, hdr->lane_index[n], m, &v);
+            if (rc) return rc;
+            if (m == 0) {
+                o.line_u64("substitution_min_base_qual", v.min_base_qual);
+                o.line_u64("substitution_min_mapq", v.min_mapq);
+            }
+            for (uint32_t s = 0; s < 2; ++s)
+                for (uint32_t x = 0; x < 64; ++x) {
+                    const char name[4] = {"ACGT"[x >> 4], "ACGT"[(x >> 2) & 3], "ACGT"[x & 3], 0};
+                    o.array((std::string("substitutions_by_context_") + mates[m] + "_" + strands[s] + " " + name).c_str(), v.by_context + (s * 64 + x) * 4, 4);
+                }
+            o.str((std::string("substitutions_by_position_") + mates[m]).c_str()); o.s.push_back(' '); o.u64(v.n_cycles); o.str(" 16\n");
+            for (uint32_t c = 0; c < v.n_cycles; ++c) {
+                for (uint32_t k = 0; k < 16; ++k) { if (k) o.s.push_back(' '); o.u64(v.by_cycle[c * 16 + k]); }
+                o.s.push_back('\n');
+            }
+        }
+    }
+    return write_file(o, path);
+}

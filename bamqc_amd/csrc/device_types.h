@@ -182,6 +182,11 @@ struct GcbContig {
 #define BQC_IBC_K 64
 #define BQC_IBC_MATE_WORDS(N) ((uint64_t)BQC_IBC_ROWS * (N) + 2 * BQC_IBC_K)
 
+// Substitutions by context and by cycle (k_sbc.hip; the statistic: include/bamqc.h).  The words of a read group and mate:
+// X [2 strands][64 contexts][4 read bases] then Y [N][16: genome base x read base], no padding.
+#define BQC_SBC_X_WORDS 512
+#define BQC_SBC_MATE_WORDS(N) ((uint64_t)BQC_SBC_X_WORDS + 16ull * (N))
+
 struct DevRefs {
     const uint8_t* const* ref; // [n_refs] Dna5 codes, nullptr if not loaded
     const uint64_t* len;

@@ -791,6 +791,8 @@ struct ProgramOptions {
     std::vector<std::pair<std::string, std::string>> adapters;
     uint32_t gc_bias = 0; // --gc-bias / --gc-bias-window W: GC bias into <output>.gcb (0: off, else the window length W)
     uint32_t indel_by_cycle = 0; // --indel-by-cycle / --indel-by-cycle-len N: indels by cycle and by length into <output>.ibc (0: off, else N)
+    // --substitutions / --substitutions-len N / --substitutions-min-qual Q / --substitutions-min-mapq MQ: substitutions by context and by cycle into <output>.sbc
+    uint32_t substitutions = 0, subst_min_qual = 20, subst_min_mapq = 30; // (substitutions 0: off, else N)
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -830,6 +832,12 @@ void usage(FILE* f)
             "    --indel-by-cycle\n          Insertions and deletions by cycle (read group x mate x the first 1024 cycles) and by length (1 to 64\n"
             "          and more), with the reads by length they are rates of, into OUT.ibc.\n"
             "    --indel-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).  Implies --indel-by-cycle.\n"
+            "    --substitutions\n          Substitutions as sequenced: the pairs (genome base, read base) by trinucleotide context, per read group,\n"
+            "          mate and strand, and by cycle (the first 1024), over bases of quality 20 and more in reads of mapping\n"
+            "          quality 30 and more, into OUT.sbc (oxidation, deamination and strand artefacts are folds of it).\n"
+            "    --substitutions-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).  Implies --substitutions.\n"
+            "    --substitutions-min-qual INT\n          The same over bases of quality INT and more (0 to 222).  Implies --substitutions.\n"
+            "    --substitutions-min-mapq INT\n          The same over reads of mapping quality INT and more (0 to 255).  Implies --substitutions.\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -993,6 +1001,26 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--indel-by-cycle-len wants 1 or more)"; return 1; }
             o.indel_by_cycle = (uint32_t)x;
         }
+        else if (key == "--substitutions") { if (!o.substitutions) o.substitutions = 1024; }
+        else if (key == "--substitutions-len") {
+            if (!need(i, key, v, inl)) return 1;
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x == 0 || x > 0x7FFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--substitutions-len wants 1 or more)"; return 1; }
+            o.substitutions = (uint32_t)x;
+        }
+        else if (key == "--substitutions-min-qual" || key == "--substitutions-min-mapq") {
+            if (!need(i, key, v, inl)) return 1;
+            const bool qual = key == "--substitutions-min-qual";
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? ~0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x > (qual ? 222ull : 255ull)) {
+                err = "bamqualcheck: the given value '" + v + "' is not a " + (qual ? "base quality (--substitutions-min-qual wants 0 to 222)" : "mapping quality (--substitutions-min-mapq wants 0 to 255)");
+                return 1;
+            }
+            (qual ? o.subst_min_qual : o.subst_min_mapq) = (uint32_t)x;
+            if (!o.substitutions) o.substitutions = 1024;
+        }
         else if (key == "--gc-bias-window") {
             if (!need(i, key, v, inl)) return 1;
             char* end = nullptr;
@@ -1119,7 +1147,7 @@ RefKey make_ref_key(const std::string& fasta, const BamHeader& H)
 }
 // The options that size a context (bqc_options): equal ones mean bqc_reset instead of bqc_create.
 struct CtxKey {
-    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0, gc_bias = 0, indel_by_cycle = 0;
+    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0, gc_bias = 0, indel_by_cycle = 0, substitutions = 0, subst_min_qual = 0, subst_min_mapq = 0;
     std::vector<std::pair<std::string, std::string>> adapters; // (empty: the built-in set)
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
@@ -1129,7 +1157,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1358,6 +1386,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         ctx_key.n_lanes = bo.n_lanes; ctx_key.n_refs = bo.n_refs; ctx_key.max_read_len = bo.max_read_len; ctx_key.hist_cap = bo.hist_cap; ctx_key.isize = bo.isize;
         ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch; ctx_key.qual_by_cycle = bo.qual_by_cycle; ctx_key.mismatch_by_cycle = bo.mismatch_by_cycle;
         ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters; ctx_key.gc_bias = opt.gc_bias; ctx_key.indel_by_cycle = opt.indel_by_cycle;
+        ctx_key.substitutions = opt.substitutions; ctx_key.subst_min_qual = opt.subst_min_qual; ctx_key.subst_min_mapq = opt.subst_min_mapq;
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1395,6 +1424,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         }
         if (!rc && opt.indel_by_cycle) {
             rc = bqc_enable_indel_by_cycle(ctx, opt.indel_by_cycle);
+            if (rc) create_err = bqc_last_error(ctx);
+        }
+        if (!rc && opt.substitutions) {
+            rc = bqc_enable_substitutions(ctx, opt.substitutions, opt.subst_min_qual, opt.subst_min_mapq);
             if (rc) create_err = bqc_last_error(ctx);
         }
         if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
@@ -1715,10 +1748,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const int gcb_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && opt.gc_bias ? bqc_write_gc_bias(ctx, &hi, gcb_path.c_str()) : 0;
     const std::string ibc_path = opt.outputFile + ".ibc"; // the tables of --indel-by-cycle, behind the .gcb
     const int ibc_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && opt.indel_by_cycle ? bqc_write_indel_by_cycle(ctx, &hi, ibc_path.c_str()) : 0;
+    const std::string sbc_path = opt.outputFile + ".sbc"; // the tables of --substitutions, behind the .ibc
+    const int sbc_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && opt.substitutions ? bqc_write_substitutions(ctx, &hi, sbc_path.c_str()) : 0;
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1737,6 +1772,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (adp_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", adp_path.c_str()); return 1; }
     if (gcb_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", gcb_path.c_str()); return 1; }
     if (ibc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", ibc_path.c_str()); return 1; }
+    if (sbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sbc_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

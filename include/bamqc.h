@@ -508,8 +508,8 @@ int bqc_write_gc_bias(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path
  * The last bin of a length table holds every length of K or more.  By construction sum IC = sum IL and sum DC = sum DL.  The insertion
  * rate at cycle c is IC[c] / sum E[c..].
  * State.  All of it is pure sums.  The words of a read group and mate are [3 rows: E, IC, DC][N] followed by [2 rows: IL, DL][64],
- * all u64 without padding; in full [n_lanes][2 mates] of that, n_lanes * 2 * (3 N + 128) words.  They lie directly behind the sketch's
- * words, IN FRONT OF gc-bias's, adapter_by_cycle's, mismatch_by_cycle's and qual_by_cycle's.  Export / import, bqc_reset, shard
+ * all u64 without padding; in full [n_lanes][2 mates] of that, n_lanes * 2 * (3 N + 128) words.  They lie behind the sketch's
+ * words (and the substitutions', below), IN FRONT OF gc-bias's, adapter_by_cycle's, mismatch_by_cycle's and qual_by_cycle's.  Export / import, bqc_reset, shard
  * hand-over and the reduce treat them as the other words, so the module works across shards (--gpus N), unlike the GC bias.  Two
  * contexts exchange state only when both or neither have the module on, with the same N.
  * bqc_enable_indel_by_cycle switches the module on, after creation (bqc_options and bqc_modules stay as they are).  BQC_ERR_ARG, with
@@ -534,6 +534,58 @@ typedef struct bqc_ibc_view {
 } bqc_ibc_view;
 int bqc_indel_by_cycle(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_ibc_view* out);   /* after bqc_finalize; n_len = 64 */
 int bqc_write_indel_by_cycle(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
+
+/* ---- substitutions by sequence context and by cycle (bqc_enable_substitutions; not in the reference) -------------------------------
+ * What the `.mbc` leaves out: which base became which, and in what sequence context — the two tables that Picard's
+ * CollectSequencingArtifactMetrics, mapDamage's position curves and the 96-class substitution spectrum are folds of.
+ * Parameters.  Cycle capacity N, 1 <= N <= max_read_len.  Minimum base quality Q, 0 <= Q <= 222.  Minimum mapping quality MQ,
+ * 0 <= MQ <= 255; mapq is compared as a plain number, 255 is not special.  (The program's defaults: 1024, 20 and 30, the two last
+ * Picard's.)
+ * Examined reads.  mismatch_by_cycle's conditions exactly:  flag & 0x900 == 0;  a mate flag is set (0x40: mate 0, else 0x80: mate 1);
+ * BQC_FLAG_NO_QUAL is clear;  flag & 0x4 is clear;  l_seq > 0;  n_cigar > 0;  lane < n_lanes;  0 <= rid < n_refs and the contig is on
+ * the card (mismatch_by_cycle's meaning, and its BQC_BG_REFS=1 exclusion).  In addition mapq >= MQ.  Duplicates and QC-fail reads count.
+ * The walk is mismatch_by_cycle's, word for word: 64-bit signed arithmetic, j = 0 and r = pos;  M, =, X examine the pairs
+ * (j + t, r + t), t < n, and advance both;  I and S advance j;  D and N advance r;  H, P and every code of 9 or more do nothing.
+ * Examined pairs.  A pair (jj, rr) is examined iff all of these hold:  jj < l_seq;  0 <= rr < the contig's length;  the read's 4-bit
+ * code is 1, 2, 4 or 8;  the genome's Dna5 code g[rr] <= 3;  the quality byte q has Q <= q <= 222;  the cycle c < N, where c = jj, or
+ * l_seq - 1 - jj with 0x10 set.
+ * Orientation: as sequenced.  b = the read base as a code 0..3 (A, C, G, T), t = g[rr].  Forward read: b' = b, t' = t.  With 0x10
+ * set: b' = 3 - b, t' = 3 - t.  The strand index is s = (flag >> 4) & 1.
+ * Table Y, by cycle.  For every examined pair  Y[lane][mate][c][t'][b'] += 1:  sixteen bins a cycle.
+ * Table X, by context.  An examined pair enters X iff  1 <= rr  and  rr + 1 < the contig's length  and  g[rr-1] <= 3  and
+ * g[rr+1] <= 3.  The context as sequenced:  forward read  ctx = 16 g[rr-1] + 4 t + g[rr+1];  reverse read
+ * ctx = 16 (3 - g[rr+1]) + 4 (3 - t) + (3 - g[rr-1]).  Then  X[lane][mate][s][ctx][b'] += 1.
+ * The neighbours are GENOME bases: a run of one position, a base beside an insertion, a clip or a deletion has a context all the
+ * same, and the neighbour may lie outside the alignment.  By construction sum X <= sum Y per lane and mate; the difference is the
+ * examined pairs with a missing or N neighbour.
+ * State.  All of it is pure sums.  The words of a read group and mate are X [2 strands][64][4] then Y [N][16], u64 without padding:
+ * 512 + 16 N words; in full n_lanes * 2 * (512 + 16 N).  They lie directly behind the sketch's words, IN FRONT OF indel_by_cycle's,
+ * gc-bias's, adapter_by_cycle's, mismatch_by_cycle's and qual_by_cycle's: every other module's distance from the end of the vector
+ * stays what it is.  Export / import, bqc_reset, shard hand-over and the reduce treat them as the other words (--gpus N works).  Two
+ * contexts exchange state only when both or neither have the module on, with the same N (their bqc_state_words differ otherwise).
+ * bqc_enable_substitutions switches the module on, after creation (bqc_options and bqc_modules stay as they are; the ABI version
+ * stays 2).  BQC_ERR_ARG, with a message that names the value: N = 0, N > max_read_len, Q > 222, MQ > 255.  BQC_ERR_STATE: a second
+ * call; a call after the context has taken a batch, has exported or imported state, or has been finalised (bqc_enable_gc_bias's
+ * conditions).  The three enable calls may be made on one context in any order, with the same layout.  Without the call: no
+ * allocation, no launch, the same bqc_state_words and the same offsets.  With it: the `.bamqc`, `.qbc`, `.mbc`, `.adp`, `.gcb` and
+ * `.ibc` are the same bytes as without it.
+ * bqc_substitutions: valid after bqc_finalize; the view is owned by the context until the next finalize / destroy.
+ *   by_context: 512 entries, element [s][ctx][b'].  by_cycle: 16 n_cycles entries, element [c * 16 + t' * 4 + b'].
+ *   n_cycles = 1 + the highest cycle with a non-zero bin of Y for the lane and mate, 0 when there is none.
+ * BQC_ERR_STATE: the module is off, or nothing has been finalised; BQC_ERR_ARG: lane or mate out of range.
+ * bqc_write_substitutions: the tables as text, lanes in the order of `hdr`, key-then-values lines as in the `.bamqc`:
+ *   sample_id <id> / lane <name> / substitution_min_base_qual <Q> / substitution_min_mapq <MQ> /
+ *   substitutions_by_context_first_forward <CTX> vA vC vG vT   (64 lines, CTX = AAA, AAC, ... TTT: the genome as sequenced; the
+ *   values: the read base as sequenced) / substitutions_by_context_first_reverse <CTX> vA vC vG vT   (64 lines) /
+ *   substitutions_by_position_first <n_cycles> 16 / one line of 16 counts per cycle (template A -> read A C G T, template C -> ...) /
+ *   the same three blocks with _second. */
+int bqc_enable_substitutions(bqc_ctx* ctx, uint32_t n_cycles, uint32_t min_base_qual, uint32_t min_mapq);
+typedef struct bqc_sbc_view {
+    uint32_t n_cycles, min_base_qual, min_mapq;
+    const uint64_t *by_context, *by_cycle;
+} bqc_sbc_view;
+int bqc_substitutions(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_sbc_view* out);   /* after bqc_finalize */
+int bqc_write_substitutions(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
 
 #ifdef __cplusplus
 }
