@@ -138,6 +138,11 @@ class SbcView(C.Structure):  # bqc_sbc_view: by_context of 512 entries [s][ctx][
     _fields_ = [("n_cycles", C.c_uint32), ("min_base_qual", C.c_uint32), ("min_mapq", C.c_uint32), ("by_context", u64p), ("by_cycle", u64p)]
 
 
+class SacView(C.Structure):  # bqc_sac_view: rid and pos of n_sites entries, counts of 8 n_sites entries [site][strand][base]
+    _fields_ = [("n_sites", C.c_uint32), ("min_base_qual", C.c_uint32), ("min_mapq", C.c_uint32), ("rid", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32)),
+                ("counts", u64p)]
+
+
 def make_modules(adapter_by_cycle=0, adapters=None, struct_size=None):
     """bqc_modules: adapter_by_cycle = the cycle capacity N (0: off), adapters = [(name, sequence), ...] or None for the built-in set."""
     m = Modules()

@@ -39,7 +39,7 @@ class DeviceBatch:
 
 class Aggregator:
     def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, indel_by_cycle=None, substitutions=None, subst_min_qual=20, subst_min_mapq=30,
-                 **options):
+                 site_alleles=None, site_min_qual=20, site_min_mapq=20, **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
@@ -70,6 +70,19 @@ class Aggregator:
             except BamQCError:
                 self.close()
                 raise
+
+        if site_alleles is not None:  # the same way: allele counts at the sites (rid, pos), two arrays sorted by (rid, pos)
+            try:
+                self.enable_site_alleles(site_alleles[0], site_alleles[1], site_min_qual, site_min_mapq)
+            except BamQCError:
+                self.close()
+                raise
+
+    def enable_site_alleles(self, rid, pos, min_base_qual=20, min_mapq=20):
+        rid, pos = np.ascontiguousarray(rid, np.int32), np.ascontiguousarray(pos, np.int32)
+        assert rid.shape == pos.shape and rid.ndim == 1
+        i32p = C.POINTER(C.c_int32)
+        self._chk(self.lib.bqc_enable_site_alleles(self.h, len(rid), rid.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), min_base_qual, min_mapq))
 
     def enable_substitutions(self, n_cycles=1024, min_base_qual=20, min_mapq=30):
         self._chk(self.lib.bqc_enable_substitutions(self.h, n_cycles, min_base_qual, min_mapq))
@@ -275,6 +288,23 @@ class Aggregator:
             self.finalize_raw()
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_substitutions(self.h, C.byref(hdr), path.encode()))
+
+    def site_alleles(self, lane=0):
+        """The allele counts of a read group at the given sites: counts[site][strand][base], (S, 2, 4) uint64, strand 0 forward and 1
+        reverse, base A, C, G, T in genome orientation (option site_alleles=(rid, pos); valid after finalize)."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.SacView()
+        self._chk(self.lib.bqc_site_alleles(self.h, lane, C.byref(v)))
+        return np.ctypeslib.as_array(v.counts, shape=(v.n_sites, 2, 4)).copy()
+
+    def write_site_alleles(self, path, ref_names, sample_id="", lane_names=("",), lane_index=None):
+        """The `.sac` text; ref_names: the contigs' names by rid."""
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        names = (C.c_char_p * len(ref_names))(*[s.encode() for s in ref_names])
+        self._chk(self.lib.bqc_write_site_alleles(self.h, C.byref(hdr), names, len(ref_names), path.encode()))
 
     def close(self):
         if self.h:

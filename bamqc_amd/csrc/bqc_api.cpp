@@ -32,6 +32,7 @@ uint64_t bqc_adp_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_gcb_words(uint32_t n_lanes);
 uint64_t bqc_ibc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_sbc_words(uint32_t n_lanes, uint32_t N);
+uint64_t bqc_sac_words(uint32_t n_lanes, uint32_t S);
 uint32_t bqc_gcb_share(void);
 void bqc_launch_gcb_genome(const GcbContig* tab, uint32_t n_contigs, uint64_t n_shares, uint32_t W, const GcbDiv& D, uint64_t* G, uint32_t n_cu, hipStream_t s);
 hipError_t bqc_long_init();
@@ -394,6 +395,8 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (c->d_gcb) (void)hipFree(c->d_gcb);
     if (c->d_ibc) (void)hipFree(c->d_ibc);
     if (c->d_sbc) (void)hipFree(c->d_sbc);
+    if (c->d_sac) (void)hipFree(c->d_sac);
+    if (c->d_sac_tab) (void)hipFree(c->d_sac_tab);
     if (c->d_gcb_g) (void)hipFree(c->d_gcb_g);
     if (c->d_gcb_tab) (void)hipFree(c->d_gcb_tab);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
@@ -518,6 +521,8 @@ extern "C" int bqc_reset(bqc_ctx* c)
     c->ibc_final = false;
     if (c->d_sbc) HIPCHK(c, hipMemsetAsync(c->d_sbc, 0, c->sbc_words * 8, c->stream));
     c->sbc_final = false;
+    if (c->d_sac) HIPCHK(c, hipMemsetAsync(c->d_sac, 0, c->sac_words * 8, c->stream)); // (the table; the sites stay)
+    c->sac_final = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -564,8 +569,9 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-// the flat vector: [sl.words][sketch][substitutions][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
-static uint64_t sbc_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+// the flat vector: [sl.words][sketch][site alleles][substitutions][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
+static uint64_t sac_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+static uint64_t sbc_offset(const bqc_ctx* c) { return sac_offset(c) + c->sac_words; }
 static uint64_t ibc_offset(const bqc_ctx* c) { return sbc_offset(c) + c->sbc_words; }
 static uint64_t gcb_offset(const bqc_ctx* c) { return ibc_offset(c) + c->ibc_words; }
 static uint64_t adp_offset(const bqc_ctx* c) { return gcb_offset(c) + c->gcb_words; }
@@ -582,6 +588,7 @@ extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
+    if (c->d_sac) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sac_offset(c), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_ibc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + ibc_offset(c), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_gcb) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + gcb_offset(c), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -600,6 +607,7 @@ extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
+    if (c->d_sac) HIPCHK(c, hipMemcpyAsync(c->d_sac, (const uint64_t*)src + sac_offset(c), c->sac_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sbc) HIPCHK(c, hipMemcpyAsync(c->d_sbc, (const uint64_t*)src + sbc_offset(c), c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_ibc) HIPCHK(c, hipMemcpyAsync(c->d_ibc, (const uint64_t*)src + ibc_offset(c), c->ibc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_gcb) HIPCHK(c, hipMemcpyAsync(c->d_gcb, (const uint64_t*)src + gcb_offset(c), c->gcb_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -628,6 +636,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
         HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_sac) HIPCHK(c, hipMemcpy(dst + sac_offset(c), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToHost));
     if (c->d_sbc) HIPCHK(c, hipMemcpy(dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToHost));
     if (c->d_ibc) HIPCHK(c, hipMemcpy(dst + ibc_offset(c), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToHost));
     if (c->d_gcb) HIPCHK(c, hipMemcpy(dst + gcb_offset(c), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToHost));
@@ -654,6 +663,7 @@ extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_sac) HIPCHK(c, hipMemcpy(c->d_sac, src + sac_offset(c), c->sac_words * 8, hipMemcpyHostToDevice));
     if (c->d_sbc) HIPCHK(c, hipMemcpy(c->d_sbc, src + sbc_offset(c), c->sbc_words * 8, hipMemcpyHostToDevice));
     if (c->d_ibc) HIPCHK(c, hipMemcpy(c->d_ibc, src + ibc_offset(c), c->ibc_words * 8, hipMemcpyHostToDevice));
     if (c->d_gcb) HIPCHK(c, hipMemcpy(c->d_gcb, src + gcb_offset(c), c->gcb_words * 8, hipMemcpyHostToDevice));
@@ -769,6 +779,77 @@ extern "C" int bqc_enable_substitutions(bqc_ctx* c, uint32_t n_cycles, uint32_t 
     c->sbc_n = n_cycles; c->sbc_q = min_base_qual; c->sbc_mq = min_mapq;
     c->sbc_words = words;
     c->d_sbc = d;
+    return 0;
+}
+
+// The site tables of k_sac.hip (device_types.h: SacSites) from the checked list: one allocation, [pos S][first n_refs + 1][bkt_off
+// n_refs + 1][bkt].  The index comes from the sites alone: the library does not know contig lengths.
+extern "C" int bqc_enable_site_alleles(bqc_ctx* c, uint32_t n_sites, const int32_t* rid, const int32_t* pos, uint32_t min_base_qual, uint32_t min_mapq)
+{
+    if (!c) return BQC_ERR_ARG;
+    if (!n_sites) return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: the list holds 0 sites");
+    if ((uint64_t)c->opt.n_lanes * n_sites > 1ull << 24)
+        return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: %u sites x %u read groups are more than 16777216 (2^24) rows of counters", n_sites, c->opt.n_lanes);
+    if (!rid || !pos) return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: the list of %u sites is a null pointer", n_sites);
+    if (min_base_qual > 222) return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: minimum base quality %u is outside 0 ... 222", min_base_qual);
+    if (min_mapq > 255) return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: minimum mapping quality %u is outside 0 ... 255", min_mapq);
+    const uint32_t n_refs = c->opt.n_refs;
+    for (uint32_t i = 0; i < n_sites; ++i) {
+        if (rid[i] < 0 || (uint32_t)rid[i] >= n_refs) return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: site %u: contig %d is outside 0 ... %u", i, rid[i], n_refs - 1);
+        if (pos[i] < 0 || pos[i] > 0x7FFFFFFE) return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: site %u: position %d is outside 0 ... 2147483646", i, pos[i]);
+        if (i && (rid[i] < rid[i - 1] || (rid[i] == rid[i - 1] && pos[i] <= pos[i - 1])))
+            return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: site %u: (contig %d, position %d) does not lie behind its predecessor (%d, %d)", i, rid[i], pos[i], rid[i - 1], pos[i - 1]);
+    }
+    if (c->d_sac) return fail(c, BQC_ERR_STATE, "bqc_enable_site_alleles: the module is on already (%u sites)", c->sac_s);
+    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
+        return fail(c, BQC_ERR_STATE, "bqc_enable_site_alleles: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    std::vector<uint32_t> first(n_refs + 1, 0), bkt_off(n_refs + 1, 0);
+    for (uint32_t i = 0; i < n_sites; ++i) ++first[rid[i] + 1];
+    for (uint32_t r = 0; r < n_refs; ++r) first[r + 1] += first[r];
+    uint64_t n_bkt = 0;
+    for (uint32_t r = 0; r < n_refs; ++r) {
+        bkt_off[r] = (uint32_t)n_bkt;
+        if (first[r + 1] > first[r]) n_bkt += ((uint64_t)pos[first[r + 1] - 1] >> 12) + 2;
+        if (n_bkt > 0xFFFFFFFFull) return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: the index of the sites needs more than 2^32 buckets of 4096 bases");
+    }
+    bkt_off[n_refs] = (uint32_t)n_bkt;
+    std::vector<uint32_t> tab; // everything behind the positions
+    tab.reserve(2 * (size_t)(n_refs + 1) + n_bkt);
+    tab.insert(tab.end(), first.begin(), first.end());
+    tab.insert(tab.end(), bkt_off.begin(), bkt_off.end());
+    for (uint32_t r = 0; r < n_refs; ++r) {
+        const uint64_t nb = bkt_off[r + 1] - bkt_off[r];
+        uint32_t s = first[r];
+        for (uint64_t k = 0; k < nb; ++k) { // (the entry behind the last bucket: every site lies below its start, so it is first[r + 1])
+            while (s < first[r + 1] && (uint64_t)pos[s] < k << 12) ++s;
+            tab.push_back(s);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t words = bqc_sac_words(c->opt.n_lanes, n_sites);
+    const uint64_t tab_bytes = ((uint64_t)n_sites + tab.size()) * 4;
+    uint64_t* d = nullptr;
+    void* t = nullptr;
+    if (hipMalloc(&d, words * 8) != hipSuccess || hipMalloc(&t, tab_bytes) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess ||
+        hipMemcpy(t, pos, (uint64_t)n_sites * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy((uint32_t*)t + n_sites, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d);
+        (void)hipFree(t);
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_site_alleles: the table (%llu bytes) and the sites (%llu bytes) could not be allocated", (unsigned long long)(words * 8), (unsigned long long)tab_bytes);
+    }
+    c->sac_sites.pos = (const int32_t*)t;
+    c->sac_sites.first = (const uint32_t*)t + n_sites;
+    c->sac_sites.bkt_off = c->sac_sites.first + n_refs + 1;
+    c->sac_sites.bkt = c->sac_sites.bkt_off + n_refs + 1;
+    c->sac_sites.S = n_sites;
+    c->sac_sites.n_refs = n_refs;
+    c->sac_rid.assign(rid, rid + n_sites);
+    c->sac_pos.assign(pos, pos + n_sites);
+    c->sac_s = n_sites; c->sac_q = min_base_qual; c->sac_mq = min_mapq;
+    c->sac_words = words;
+    c->d_sac_tab = t;
+    c->d_sac = d;
     return 0;
 }
 
@@ -889,6 +970,11 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
                 c->adp_ncyc[l * 2 + m] = last_nonzero_len(c->h_adp.data() + (((uint64_t)l * 2 + m) * BQC_ADP_ROWS + BQC_ADP_MAX) * N, N);
         c->adp_final = true;
     }
+    if (c->d_sac) {
+        c->h_sac.resize(c->sac_words);
+        HIPCHK(c, hipMemcpy(c->h_sac.data(), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToHost));
+        c->sac_final = true;
+    }
     if (c->d_sbc) {
         c->h_sbc.resize(c->sbc_words);
         HIPCHK(c, hipMemcpy(c->h_sbc.data(), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToHost));
@@ -1008,5 +1094,20 @@ extern "C" int bqc_substitutions(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_s
     out->min_mapq = c->sbc_mq;
     out->by_context = c->h_sbc.data() + ((uint64_t)lane * 2 + mate) * BQC_SBC_MATE_WORDS(c->sbc_n);
     out->by_cycle = out->by_context + BQC_SBC_X_WORDS;
+    return 0;
+}
+
+extern "C" int bqc_site_alleles(bqc_ctx* c, uint32_t lane, bqc_sac_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_sac) return fail(c, BQC_ERR_STATE, "bqc_site_alleles: bqc_enable_site_alleles has not been called for the context");
+    if (!c->sac_final) return fail(c, BQC_ERR_STATE, "bqc_site_alleles: nothing has been finalised");
+    if (lane >= c->opt.n_lanes) return fail(c, BQC_ERR_ARG, "bqc_site_alleles: lane %u out of range", lane);
+    out->n_sites = c->sac_s;
+    out->min_base_qual = c->sac_q;
+    out->min_mapq = c->sac_mq;
+    out->rid = c->sac_rid.data();
+    out->pos = c->sac_pos.data();
+    out->counts = c->h_sac.data() + (uint64_t)lane * c->sac_s * 8;
     return 0;
 }

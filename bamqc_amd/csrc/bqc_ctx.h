@@ -249,6 +249,15 @@ struct bqc_ctx {
     std::vector<uint64_t> h_sbc;       // bqc_finalize's copy, and per (lane, mate) the printed length
     std::vector<uint32_t> sbc_ncyc;
     bool sbc_final = false;
+    // allele counts at given sites (k_sac.hip; bqc_enable_site_alleles(sites, Q, MQ) after creation — nothing below exists without it)
+    uint32_t sac_s = 0, sac_q = 0, sac_mq = 0; // the number of sites S, the minimum base quality, the minimum mapping quality
+    uint64_t* d_sac = nullptr;         // [n_lanes][S][8: strand x base], the module's words of the state vector (behind the sketch's, in front of d_sbc's)
+    uint64_t sac_words = 0;
+    void* d_sac_tab = nullptr;         // the site tables of `sac_sites`, one allocation
+    SacSites sac_sites{};
+    std::vector<int32_t> sac_rid, sac_pos; // the list as given (bqc_site_alleles' view)
+    std::vector<uint64_t> h_sac;       // bqc_finalize's copy
+    bool sac_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -38,6 +38,7 @@ void bqc_launch_adp(const DevBatch&, const AdpPatterns&, uint64_t* tables, uint3
 void bqc_launch_gcb_reads(const DevBatch&, const DevRefs&, uint64_t* tables, uint32_t W, const GcbDiv&, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_ibc(const DevBatch&, uint64_t* tables, uint32_t N, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_sbc(const DevBatch&, const DevRefs&, uint64_t* tables, uint32_t N, uint32_t Q, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
+void bqc_launch_sac(const DevBatch&, const SacSites&, uint64_t* table, uint32_t Q, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 }
 
 using clk = std::chrono::steady_clock;
@@ -617,6 +618,7 @@ static int enqueue_batch(bqc_ctx* c, BatchMem& m, bool& forked)
     if (c->d_qcyc) { bqc_launch_qcyc(d, c->d_qcyc, c->opt.qual_by_cycle, c->opt.n_lanes, c->n_cu, m.n_slow, m.max_len_slow, c->stream); tick(c, "k_qcyc"); }
     if (c->d_mbc) { bqc_launch_mbc(d, refs, c->d_mbc, c->opt.mismatch_by_cycle, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_mbc"); }
     if (c->d_sbc) { bqc_launch_sbc(d, refs, c->d_sbc, c->sbc_n, c->sbc_q, c->sbc_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sbc"); }
+    if (c->d_sac) { bqc_launch_sac(d, c->sac_sites, c->d_sac, c->sac_q, c->sac_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sac"); }
     if (c->d_adp) { bqc_launch_adp(d, c->adp_pat, c->d_adp, c->adp_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_adp"); }
     if (c->d_gcb) { bqc_launch_gcb_reads(d, refs, c->d_gcb, c->gcb_w, c->gcb_div, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_gcb_reads"); }
     if (c->d_ibc) { bqc_launch_ibc(d, c->d_ibc, c->ibc_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_ibc"); }

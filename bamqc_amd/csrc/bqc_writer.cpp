@@ -322,3 +322,29 @@ extern "C" int bqc_write_substitutions(bqc_ctx* ctx, const bqc_header_info* hdr,
     }
     return write_file(o, path);
 }
+
+// The allele counts at the given sites as text (include/bamqc.h): per lane the two thresholds and the number of sites, then one line a
+// site, in the table's order: the contig's name, the position counted from 1 and the eight counts, forward A C G T then reverse.
+extern "C" int bqc_write_site_alleles(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path)
+{
+    if (!ctx || !hdr || !path || (!ref_names && n_refs)) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 16);
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        bqc_sac_view v;
+        const int rc = bqc_site_alleles(ctx, hdr->lane_index[n], &v);
+        if (rc) return rc;
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        o.line_u64("site_allele_min_base_qual", v.min_base_qual);
+        o.line_u64("site_allele_min_mapq", v.min_mapq);
+        o.line_u64("site_alleles", v.n_sites);
+        for (uint32_t s = 0; s < v.n_sites; ++s) {
+            if ((uint32_t)v.rid[s] >= n_refs || !ref_names[v.rid[s]]) return BQC_ERR_ARG; // (a site's contig has no name)
+            o.str(ref_names[v.rid[s]]); o.s.push_back(' '); o.u64((uint64_t)v.pos[s] + 1);
+            for (uint32_t k = 0; k < 8; ++k) { o.s.push_back(' '); o.u64(v.counts[(uint64_t)s * 8 + k]); }
+            o.s.push_back('\n');
+        }
+    }
+    return write_file(o, path);
+}

@@ -187,6 +187,19 @@ struct GcbContig {
 #define BQC_SBC_X_WORDS 512
 #define BQC_SBC_MATE_WORDS(N) ((uint64_t)BQC_SBC_X_WORDS + 16ull * (N))
 
+// Allele counts at given sites (k_sac.hip; the statistic: include/bamqc.h).  The words of a read group: [S sites][8: strand x base], no
+// padding.  The site tables, made once by bqc_enable_site_alleles: the positions in the list's order, the contigs' runs of sites
+// first[r] .. first[r + 1], and per contig with sites an index of buckets of 4096 bases up to the bucket of its last site: entry k of
+// contig r, bkt[bkt_off[r] + k], is the first site at or behind base 4096 k, and one entry more closes the last bucket with
+// first[r + 1] (a contig without sites has no entries: bkt_off[r + 1] == bkt_off[r]).
+struct SacSites {
+    const int32_t* pos;      // [S]
+    const uint32_t* first;   // [n_refs + 1]
+    const uint32_t* bkt_off; // [n_refs + 1]
+    const uint32_t* bkt;     // [bkt_off[n_refs]]
+    uint32_t S, n_refs;
+};
+
 struct DevRefs {
     const uint8_t* const* ref; // [n_refs] Dna5 codes, nullptr if not loaded
     const uint64_t* len;

@@ -793,6 +793,9 @@ struct ProgramOptions {
     uint32_t indel_by_cycle = 0; // --indel-by-cycle / --indel-by-cycle-len N: indels by cycle and by length into <output>.ibc (0: off, else N)
     // --substitutions / --substitutions-len N / --substitutions-min-qual Q / --substitutions-min-mapq MQ: substitutions by context and by cycle into <output>.sbc
     uint32_t substitutions = 0, subst_min_qual = 20, subst_min_mapq = 30; // (substitutions 0: off, else N)
+    // --site-alleles FILE / --site-alleles-min-qual Q / --site-alleles-min-mapq MQ: allele counts at the sites of FILE into <output>.sac
+    std::string site_alleles; // (empty: off)
+    uint32_t site_min_qual = 20, site_min_mapq = 20;
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -838,6 +841,12 @@ void usage(FILE* f)
             "    --substitutions-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).  Implies --substitutions.\n"
             "    --substitutions-min-qual INT\n          The same over bases of quality INT and more (0 to 222).  Implies --substitutions.\n"
             "    --substitutions-min-mapq INT\n          The same over reads of mapping quality INT and more (0 to 255).  Implies --substitutions.\n"
+            "    --site-alleles FILE\n          Allele counts at given sites: per read group and site of FILE (lines CONTIG<TAB>POS, POS counted from 1,\n"
+            "          as the body lines of a VCF are), the reads that show A, C, G and T there, by strand, over bases of quality\n"
+            "          20 and more in reads of mapping quality 20 and more, into OUT.sac (fingerprint, lane swap and\n"
+            "          contamination checks are folds of it).\n"
+            "    --site-alleles-min-qual INT\n          The same over bases of quality INT and more (0 to 222).  Needs --site-alleles.\n"
+            "    --site-alleles-min-mapq INT\n          The same over reads of mapping quality INT and more (0 to 255).  Needs --site-alleles.\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -901,6 +910,7 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
     bool have_r = false, have_o = false, have_m = false;
     bool want_adp = false; // --adapter-by-cycle or an --adapter: the module at 1024 cycles unless --adapter-by-cycle-len says otherwise
     bool want_gcb = false; // --gc-bias: the module with windows of 100 bases unless --gc-bias-window says otherwise
+    std::string want_sac_value; // a threshold option of --site-alleles was given: it needs the sites
     // (--gpus N is the front end's and never reaches this parser from it; given here, it is an illegal option — said in the option's
     // own terms where the GC bias is asked for as well, which no worker of --gpus could compute)
     auto gcb_somewhere = [&]() {
@@ -1021,6 +1031,19 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             (qual ? o.subst_min_qual : o.subst_min_mapq) = (uint32_t)x;
             if (!o.substitutions) o.substitutions = 1024;
         }
+        else if (key == "--site-alleles") { if (!need(i, key, v, inl)) return 1; o.site_alleles = v; }
+        else if (key == "--site-alleles-min-qual" || key == "--site-alleles-min-mapq") {
+            if (!need(i, key, v, inl)) return 1;
+            const bool qual = key == "--site-alleles-min-qual";
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? ~0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x > (qual ? 222ull : 255ull)) {
+                err = "bamqualcheck: the given value '" + v + "' is not a " + (qual ? "base quality (--site-alleles-min-qual wants 0 to 222)" : "mapping quality (--site-alleles-min-mapq wants 0 to 255)");
+                return 1;
+            }
+            (qual ? o.site_min_qual : o.site_min_mapq) = (uint32_t)x;
+            want_sac_value = key;
+        }
         else if (key == "--gc-bias-window") {
             if (!need(i, key, v, inl)) return 1;
             char* end = nullptr;
@@ -1035,6 +1058,7 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
     }
     if (want_adp && !o.adapter_by_cycle) o.adapter_by_cycle = 1024;
     if (want_gcb && !o.gc_bias) o.gc_bias = 100;
+    if (!want_sac_value.empty() && o.site_alleles.empty()) { err = "bamqualcheck: option " + want_sac_value + " needs --site-alleles FILE (the sites it applies to)"; return 1; }
     if (!have_r) { err = "bamqualcheck: option requires an argument -- r (required option -r/--reference missing)"; return 1; }
     if (session_form) {
         if (have_o || have_m || !pos.empty()) { err = "bamqualcheck: a session takes the program's options without an input, -o and --manifest"; return 1; }
@@ -1149,6 +1173,8 @@ RefKey make_ref_key(const std::string& fasta, const BamHeader& H)
 struct CtxKey {
     uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0, gc_bias = 0, indel_by_cycle = 0, substitutions = 0, subst_min_qual = 0, subst_min_mapq = 0;
     std::vector<std::pair<std::string, std::string>> adapters; // (empty: the built-in set)
+    std::vector<int32_t> site_rid, site_pos; // --site-alleles: the list as mapped to the job's header (empty: off)
+    uint32_t site_min_qual = 0, site_min_mapq = 0;
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
     double e = 0;
@@ -1157,7 +1183,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1172,7 +1198,12 @@ struct bqc_session {
     RefKey ref_key;                // the genome whose contigs are on the card, in ctx
     std::vector<int32_t> fasta_index; // for ref_key: each BAM reference's position in the FASTA file (the cursor rule), -1: not there
     uint32_t contigs_on_card = 0;
-    GpuBamReader gpu_rd;           // opened again for every file it takes: its buffers stay
+    // --site-alleles: the file is read when a job's header lists other contigs than the job before's; the mapped list is kept with them
+    bool sites_loaded = false;
+    std::vector<std::string> sites_names;
+    std::vector<uint32_t> sites_lens;
+    std::vector<int32_t> sites_rid, sites_pos;
+    GpuBamReader gpu_rd;          // opened again for every file it takes: its buffers stay
     std::vector<std::unique_ptr<HostBatch>> spare; // the decoder's batch objects: their columns, page locks and device buffers
     std::atomic<bool> ended{false}; // a HIP error: nothing more is started on the card
     uint32_t job = 0, n_jobs = 0;  // the job that runs (1-based), and how many there will be if known
@@ -1268,6 +1299,29 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     }
     rd.set_main_chrom(main_chrom);
     since_launch("input opened, header read");
+    // --site-alleles: the sites as this header numbers the contigs (every worker of --gpus N loads the list itself)
+    std::vector<int32_t> site_rid, site_pos;
+    if (!opt.site_alleles.empty()) {
+        if (S && S->sites_loaded && S->sites_names == H.ref_names && S->sites_lens == H.ref_lens) { site_rid = S->sites_rid; site_pos = S->sites_pos; }
+        else {
+            std::vector<const char*> names;
+            for (const auto& nm : H.ref_names) names.push_back(nm.c_str());
+            uint32_t n_sites = 0;
+            int32_t *sr = nullptr, *sp = nullptr;
+            uint64_t given = 0, unnamed = 0;
+            char serr[1024];
+            if (bqc_sites_load(opt.site_alleles.c_str(), names.data(), H.ref_lens.data(), n_refs, &n_sites, &sr, &sp, &given, &unnamed, serr, sizeof serr)) {
+                fprintf(stderr, "ERROR: %s\n", serr);
+                return shard_abort();
+            }
+            site_rid.assign(sr, sr + n_sites);
+            site_pos.assign(sp, sp + n_sites);
+            bqc_sites_free(sr, sp);
+            if (unnamed && !host_reader_only && (!shard || shard->index == 0))
+                fprintf(stderr, "bamqualcheck: %llu of %llu sites of %s lie on contigs the header does not name\n", (unsigned long long)unnamed, (unsigned long long)given, opt.site_alleles.c_str());
+            if (S) { S->sites_loaded = true; S->sites_names = H.ref_names; S->sites_lens = H.ref_lens; S->sites_rid = site_rid; S->sites_pos = site_pos; }
+        }
+    }
     const auto t_begin = std::chrono::steady_clock::now(); // (BQC_TIMING=1 also reports the phases around the record loop)
     auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     double t_wait = 0, t_submit = 0, t_decode = 0;
@@ -1387,6 +1441,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch; ctx_key.qual_by_cycle = bo.qual_by_cycle; ctx_key.mismatch_by_cycle = bo.mismatch_by_cycle;
         ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters; ctx_key.gc_bias = opt.gc_bias; ctx_key.indel_by_cycle = opt.indel_by_cycle;
         ctx_key.substitutions = opt.substitutions; ctx_key.subst_min_qual = opt.subst_min_qual; ctx_key.subst_min_mapq = opt.subst_min_mapq;
+        if (!site_rid.empty()) { ctx_key.site_rid = site_rid; ctx_key.site_pos = site_pos; ctx_key.site_min_qual = opt.site_min_qual; ctx_key.site_min_mapq = opt.site_min_mapq; }
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1428,6 +1483,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         }
         if (!rc && opt.substitutions) {
             rc = bqc_enable_substitutions(ctx, opt.substitutions, opt.subst_min_qual, opt.subst_min_mapq);
+            if (rc) create_err = bqc_last_error(ctx);
+        }
+        if (!rc && !site_rid.empty()) {
+            rc = bqc_enable_site_alleles(ctx, (uint32_t)site_rid.size(), site_rid.data(), site_pos.data(), opt.site_min_qual, opt.site_min_mapq);
             if (rc) create_err = bqc_last_error(ctx);
         }
         if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
@@ -1750,10 +1809,14 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const int ibc_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && opt.indel_by_cycle ? bqc_write_indel_by_cycle(ctx, &hi, ibc_path.c_str()) : 0;
     const std::string sbc_path = opt.outputFile + ".sbc"; // the tables of --substitutions, behind the .ibc
     const int sbc_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && opt.substitutions ? bqc_write_substitutions(ctx, &hi, sbc_path.c_str()) : 0;
+    const std::string sac_path = opt.outputFile + ".sac"; // the table of --site-alleles, behind the .sbc
+    std::vector<const char*> sac_names;
+    for (const auto& nm : H.ref_names) sac_names.push_back(nm.c_str());
+    const int sac_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !site_rid.empty() ? bqc_write_site_alleles(ctx, &hi, sac_names.data(), n_refs, sac_path.c_str()) : 0;
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1773,6 +1836,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (gcb_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", gcb_path.c_str()); return 1; }
     if (ibc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", ibc_path.c_str()); return 1; }
     if (sbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sbc_path.c_str()); return 1; }
+    if (sac_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sac_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

@@ -130,6 +130,27 @@ def load_fasta(path):
     return out
 
 
+def load_sites(path, names, lens):
+    """The sites file of --site-alleles (lines CONTIG<TAB>POS, POS counted from 1; include/bamqc_host.h: bqc_sites_load) against a
+    header's contigs: (rid, pos, n_given, n_unnamed), rid and pos int32 arrays sorted by (rid, pos), pos counted from 0; n_unnamed of
+    the n_given sites lie on contigs that `names` does not hold and are left out.  IOError with "FILE: line N: reason"."""
+    lib = _lib.load()
+    rl = np.ascontiguousarray(lens, np.uint32)
+    assert len(rl) == len(names)
+    nm = (C.c_char_p * len(names))(*[s.encode() for s in names])
+    n = C.c_uint32()
+    rid, pos = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+    given, unnamed = C.c_uint64(), C.c_uint64()
+    err = C.create_string_buffer(1024)
+    rc = lib.bqc_sites_load(path.encode(), nm, rl.ctypes.data_as(_abi.u32p), len(rl), C.byref(n), C.byref(rid), C.byref(pos), C.byref(given), C.byref(unnamed),
+                            err, len(err))
+    if rc:
+        raise IOError(err.value.decode())
+    out = (np.ctypeslib.as_array(rid, shape=(n.value,)).copy(), np.ctypeslib.as_array(pos, shape=(n.value,)).copy(), int(given.value), int(unnamed.value))
+    lib.bqc_sites_free(rid, pos)
+    return out
+
+
 def synth_write(bam_path, fasta_path, seed, n_reads, ref_names, ref_lens, read_len=150, n_lanes=1, isize=1000, long_reads=False):
     lib = _lib.load()
     rl = np.ascontiguousarray(ref_lens, np.uint32)

@@ -587,6 +587,53 @@ typedef struct bqc_sbc_view {
 int bqc_substitutions(bqc_ctx* ctx, uint32_t lane, uint32_t mate, bqc_sbc_view* out);   /* after bqc_finalize */
 int bqc_write_substitutions(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
 
+/* ---- allele counts at given sites (bqc_enable_site_alleles; not in the reference) ---------------------------------------------------
+ * The other tables describe the chemistry; this one describes the sample.  Per read group and per site of a given list it counts the
+ * reads that show A, C, G and T there, by strand: the table that a fingerprint at known SNPs (Picard CheckFingerprint), the agreement
+ * of read groups (a lane swap) and the minor-allele fraction at homozygous sites (contamination, VerifyBamID's input) are folds of.
+ * Sites.  S sites (rid, pos), pos counted from 0, strictly increasing by (rid, pos);  0 <= rid < n_refs;  0 <= pos <= 2^31 - 2;
+ * 1 <= S and n_lanes * S <= 2^24 (at most 1 GiB of counters).
+ * Parameters.  Minimum base quality Q, 0 ... 222 (the program's default 20).  Minimum mapping quality MQ, 0 ... 255 (default 20); mapq
+ * is compared as a plain number, 255 is not special.
+ * Examined reads.  flag & 0xF04 == 0 (mapped, primary, not QC-fail, not a duplicate, not supplementary);  mapq >= MQ;  n_cigar > 0;
+ * l_seq > 0;  BQC_FLAG_NO_QUAL is clear;  lane < n_lanes;  0 <= rid < n_refs.  The mate flags are not looked at.  The genome is NOT
+ * read: no contig need be loaded.
+ * The walk, in stored orientation and 64-bit arithmetic: j = 0, g = pos; for every CIGAR operation (op, n) in stored order
+ *   M, =, X (0, 7, 8):  for every site (rid, p) with g <= p < g + n and i = j + (p - g) < l_seq take the read's 4-bit code at stored
+ *     index i and the quality q = qual[i]; if the code is 1, 2, 4 or 8 (A, C, G, T: b = 0 ... 3) and Q <= q <= 222 then
+ *     T[lane][site][4 s + b] += 1, where s = 1 with 0x10 set, else 0.  Then j += n and g += n.
+ *   I, S (1, 4):  j += n.      D, N (2, 3):  g += n; a site under a deletion or a skip gets nothing.
+ *   H, P and every code of 9 or more:  nothing.
+ * Bases are counted in genome orientation, as a pileup shows them (a reverse read's stored bases are that already).  The code `=`
+ * (0), N and the ambiguity codes count nowhere.  g only grows, so a read adds at most 1 to a site.  Two mates that overlap on a site
+ * BOTH count: read names are not on the card, and there is no overlap correction.
+ * State.  [n_lanes][S][8] u64, pure sums, no padding: n_lanes * S * 8 words directly behind the sketch's words, IN FRONT OF the
+ * substitutions' and every other module's: their distance from the end of the vector stays what it is.  Export / import, bqc_reset
+ * (the table goes back to zero, the sites stay), shard hand-over and the reduce treat them as the other words (--gpus N works).  Two
+ * contexts exchange state only when both have the module on with the same S (their bqc_state_words differ otherwise; the lists
+ * themselves are not compared).
+ * bqc_enable_site_alleles switches the module on, after creation, in any order with the other enable calls (bqc_options and
+ * bqc_modules stay as they are; the ABI version stays 2); the list is copied.  BQC_ERR_ARG, with a message that names the value and,
+ * for the list, the index of the first offending site: S = 0;  n_lanes * S > 2^24;  a rid or a pos out of range;  a site that does
+ * not lie strictly behind its predecessor;  Q > 222;  MQ > 255.  BQC_ERR_STATE: a second call; a call after the context has taken a
+ * batch, has exported or imported state, or has been finalised (bqc_enable_gc_bias's conditions).  Without the call: no allocation,
+ * no launch, the same bqc_state_words and the same offsets.  With it: every other output is the same bytes as without it.
+ * bqc_site_alleles: valid after bqc_finalize; the view is owned by the context until the next finalize / destroy.  rid and pos: the
+ * list as given; counts: S x 8 entries, element [site * 8 + 4 s + b].  BQC_ERR_STATE: the module is off, or nothing has been
+ * finalised; BQC_ERR_ARG: lane out of range.
+ * bqc_write_site_alleles: the table as text, lanes in the order of `hdr`, key-then-values lines as in the `.bamqc`.  bqc_header_info
+ * carries no contig names, hence ref_names[n_refs] (BQC_ERR_ARG when a site's contig has none):
+ *   sample_id <id> / lane <name> / site_allele_min_base_qual <Q> / site_allele_min_mapq <MQ> / site_alleles <S> /
+ *   <contig> <pos, counted from 1> fA fC fG fT rA rC rG rT     (one line per site, in the table's order) */
+int bqc_enable_site_alleles(bqc_ctx* ctx, uint32_t n_sites, const int32_t* rid, const int32_t* pos, uint32_t min_base_qual, uint32_t min_mapq);
+typedef struct bqc_sac_view {
+    uint32_t n_sites, min_base_qual, min_mapq;
+    const int32_t *rid, *pos;
+    const uint64_t* counts;
+} bqc_sac_view;
+int bqc_site_alleles(bqc_ctx* ctx, uint32_t lane, bqc_sac_view* out);   /* after bqc_finalize */
+int bqc_write_site_alleles(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path);
+
 #ifdef __cplusplus
 }
 #endif

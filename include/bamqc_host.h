@@ -135,6 +135,18 @@ int bqc_bam_next(bqc_bam* b, uint32_t max_reads, uint64_t max_bases, const bqc_b
 int bqc_fasta_load(const char* path, uint32_t* n_records, char*** names, uint8_t*** codes, uint64_t** lens);
 void bqc_fasta_free(uint32_t n_records, char** names, uint8_t** codes, uint64_t* lens);
 
+/* The sites file of --site-alleles (bqc_enable_site_alleles' list; no GPU is needed): text lines CONTIG<TAB>POS[<TAB>anything], POS
+ * counted from 1 and the rest of the line ignored, so the body lines of a VCF are such lines.  Lines that start with '#' and empty
+ * lines are skipped; "\r\n" is accepted.  The sites come back sorted by (index of the contig in ref_names, pos), pos counted from 0,
+ * in arrays that bqc_sites_free releases.  A site on a contig that ref_names does not hold is left out and counted: *n_given is the
+ * number of sites the file gives, *n_unnamed how many of them were left out (either pointer may be NULL).
+ * BQC_ERR_IO, with "FILE: line N: reason" in err[err_cap] (err may be NULL): the file cannot be opened or read; a line without a
+ * tab; a POS that is not a number of 1 or more; a POS behind the contig's length; a site given twice (the line of the second); no
+ * site left (the file's last line). */
+int bqc_sites_load(const char* path, const char* const* ref_names, const uint32_t* ref_lens, uint32_t n_refs, uint32_t* n_sites, int32_t** rid,
+                   int32_t** pos, uint64_t* n_given, uint64_t* n_unnamed, char* err, uint64_t err_cap);
+void bqc_sites_free(int32_t* rid, int32_t* pos);
+
 /* The BGZF reader's DEFLATE decoder on one raw deflate stream (host/inflate_fast.h; exposed for its tests): 1 when the
  * stream is valid, ends within in_n bytes and yields exactly out_n bytes, else 0.  The 8 bytes after in + in_n must be
  * readable (in a BGZF block: the CRC32 / ISIZE trailer). */
