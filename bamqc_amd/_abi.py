@@ -143,6 +143,13 @@ class SacView(C.Structure):  # bqc_sac_view: rid and pos of n_sites entries, cou
                 ("counts", u64p)]
 
 
+class RcvView(C.Structure):  # bqc_rcv_view: the list of n_regions entries, five scalars, thresholds, regions [n_regions][3 + n_thresholds], hist [depth_cap + 1]
+    _fields_ = [("n_regions", C.c_uint32), ("min_mapq", C.c_uint32), ("n_thresholds", C.c_uint32), ("depth_cap", C.c_uint32),
+                ("rid", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
+                ("reads_examined", C.c_uint64), ("reads_on_target", C.c_uint64), ("aligned_bases", C.c_uint64), ("bases_on_target", C.c_uint64),
+                ("target_bases", C.c_uint64), ("thresholds", u64p), ("regions", u64p), ("hist", u64p)]
+
+
 def make_modules(adapter_by_cycle=0, adapters=None, struct_size=None):
     """bqc_modules: adapter_by_cycle = the cycle capacity N (0: off), adapters = [(name, sequence), ...] or None for the built-in set."""
     m = Modules()

@@ -73,10 +73,18 @@ _SIGNATURES = {
     "bqc_enable_site_alleles": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_uint32]),
     "bqc_site_alleles": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(_abi.SacView)]),
     "bqc_write_site_alleles": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),
+    "bqc_enable_region_coverage": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_uint32,
+                                             C.POINTER(C.c_uint64), C.c_uint32]),
+    "bqc_region_coverage": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(_abi.RcvView)]),
+    "bqc_write_region_coverage": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),
     # include/bamqc_host.h
     "bqc_sites_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _abi.u32p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_int32)),
                                  C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
     "bqc_sites_free": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "bqc_regions_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _abi.u32p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_int32)),
+                                   C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
+    "bqc_regions_free": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "bqc_synth_reference": (C.c_int, [C.c_uint64, C.c_int32, C.c_uint64, _abi.u8p]),
     "bqc_synth_batch": (C.c_int, [C.POINTER(_abi.SynthParams), C.POINTER(_abi.u8p), C.POINTER(C.POINTER(_abi.Batch))]),
     "bqc_synth_batch_free": (None, [C.POINTER(_abi.Batch)]),

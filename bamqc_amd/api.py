@@ -39,7 +39,8 @@ class DeviceBatch:
 
 class Aggregator:
     def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, indel_by_cycle=None, substitutions=None, subst_min_qual=20, subst_min_mapq=30,
-                 site_alleles=None, site_min_qual=20, site_min_mapq=20, **options):
+                 site_alleles=None, site_min_qual=20, site_min_mapq=20, regions=None, region_min_mapq=20, region_thresholds=(1, 10, 20, 30, 50, 100),
+                 region_depth_cap=1000, **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
@@ -77,6 +78,21 @@ class Aggregator:
             except BamQCError:
                 self.close()
                 raise
+
+        if regions is not None:  # the same way: depth over the regions (rid, start, end), three arrays sorted by (rid, start), disjoint
+            try:
+                self.enable_region_coverage(regions[0], regions[1], regions[2], region_min_mapq, region_thresholds, region_depth_cap)
+            except BamQCError:
+                self.close()
+                raise
+
+    def enable_region_coverage(self, rid, start, end, min_mapq=20, thresholds=(1, 10, 20, 30, 50, 100), depth_cap=1000):
+        rid, start, end = (np.ascontiguousarray(a, np.int32) for a in (rid, start, end))
+        assert rid.shape == start.shape == end.shape and rid.ndim == 1
+        thr = np.ascontiguousarray(thresholds, np.uint64)
+        i32p = C.POINTER(C.c_int32)
+        self._chk(self.lib.bqc_enable_region_coverage(self.h, len(rid), rid.ctypes.data_as(i32p), start.ctypes.data_as(i32p), end.ctypes.data_as(i32p), min_mapq,
+                                                      len(thr), thr.ctypes.data_as(C.POINTER(C.c_uint64)), depth_cap))
 
     def enable_site_alleles(self, rid, pos, min_base_qual=20, min_mapq=20):
         rid, pos = np.ascontiguousarray(rid, np.int32), np.ascontiguousarray(pos, np.int32)
@@ -305,6 +321,30 @@ class Aggregator:
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         names = (C.c_char_p * len(ref_names))(*[s.encode() for s in ref_names])
         self._chk(self.lib.bqc_write_site_alleles(self.h, C.byref(hdr), names, len(ref_names), path.encode()))
+
+    def region_coverage(self, lane=0):
+        """The depth of a read group over the given regions (option regions=(rid, start, end); valid after finalize): a dict of
+        reads_examined, reads_on_target, aligned_bases, bases_on_target, target_bases, min_mapq, thresholds (n,), regions
+        (R, 3 + n) uint64 — a region's sum, min and max of the depth, then its positions at or above each threshold — and hist
+        (D + 1,), the positions by depth with the last bin open."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.RcvView()
+        self._chk(self.lib.bqc_region_coverage(self.h, lane, C.byref(v)))
+        n = v.n_thresholds
+        return {"reads_examined": int(v.reads_examined), "reads_on_target": int(v.reads_on_target), "aligned_bases": int(v.aligned_bases),
+                "bases_on_target": int(v.bases_on_target), "target_bases": int(v.target_bases), "min_mapq": int(v.min_mapq),
+                "thresholds": np.ctypeslib.as_array(v.thresholds, shape=(n,)).copy() if n else np.zeros(0, np.uint64),
+                "regions": np.ctypeslib.as_array(v.regions, shape=(v.n_regions, 3 + n)).copy(),
+                "hist": np.ctypeslib.as_array(v.hist, shape=(v.depth_cap + 1,)).copy()}
+
+    def write_region_coverage(self, path, ref_names, sample_id="", lane_names=("",), lane_index=None):
+        """The `.rcv` text; ref_names: the contigs' names by rid."""
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        names = (C.c_char_p * len(ref_names))(*[s.encode() for s in ref_names])
+        self._chk(self.lib.bqc_write_region_coverage(self.h, C.byref(hdr), names, len(ref_names), path.encode()))
 
     def close(self):
         if self.h:

@@ -33,6 +33,10 @@ uint64_t bqc_gcb_words(uint32_t n_lanes);
 uint64_t bqc_ibc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_sbc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_sac_words(uint32_t n_lanes, uint32_t S);
+uint64_t bqc_rcv_words(uint32_t n_lanes, uint64_t B, uint32_t R);
+uint32_t bqc_rcv_tiles(uint64_t B, uint32_t R);
+uint64_t bqc_rcv_out_words(uint32_t n_lanes, uint32_t R, uint32_t n_thr, uint32_t D);
+void bqc_launch_rcv_final(const uint64_t* state, const RcvRegions& rg, const RcvFinal& fp, uint32_t n_lanes, uint64_t* tsum, uint64_t* out, hipStream_t s);
 uint32_t bqc_gcb_share(void);
 void bqc_launch_gcb_genome(const GcbContig* tab, uint32_t n_contigs, uint64_t n_shares, uint32_t W, const GcbDiv& D, uint64_t* G, uint32_t n_cu, hipStream_t s);
 hipError_t bqc_long_init();
@@ -397,6 +401,9 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (c->d_sbc) (void)hipFree(c->d_sbc);
     if (c->d_sac) (void)hipFree(c->d_sac);
     if (c->d_sac_tab) (void)hipFree(c->d_sac_tab);
+    if (c->d_rcv) (void)hipFree(c->d_rcv);
+    if (c->d_rcv_tab) (void)hipFree(c->d_rcv_tab);
+    if (c->d_rcv_out) (void)hipFree(c->d_rcv_out);
     if (c->d_gcb_g) (void)hipFree(c->d_gcb_g);
     if (c->d_gcb_tab) (void)hipFree(c->d_gcb_tab);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
@@ -523,6 +530,8 @@ extern "C" int bqc_reset(bqc_ctx* c)
     c->sbc_final = false;
     if (c->d_sac) HIPCHK(c, hipMemsetAsync(c->d_sac, 0, c->sac_words * 8, c->stream)); // (the table; the sites stay)
     c->sac_final = false;
+    if (c->d_rcv) HIPCHK(c, hipMemsetAsync(c->d_rcv, 0, c->rcv_words * 8, c->stream)); // (the words; the regions stay)
+    c->rcv_final = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -569,8 +578,9 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-// the flat vector: [sl.words][sketch][site alleles][substitutions][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
-static uint64_t sac_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+// the flat vector: [sl.words][sketch][region coverage][site alleles][substitutions][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
+static uint64_t rcv_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+static uint64_t sac_offset(const bqc_ctx* c) { return rcv_offset(c) + c->rcv_words; }
 static uint64_t sbc_offset(const bqc_ctx* c) { return sac_offset(c) + c->sac_words; }
 static uint64_t ibc_offset(const bqc_ctx* c) { return sbc_offset(c) + c->sbc_words; }
 static uint64_t gcb_offset(const bqc_ctx* c) { return ibc_offset(c) + c->ibc_words; }
@@ -588,6 +598,7 @@ extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
+    if (c->d_rcv) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + rcv_offset(c), c->d_rcv, c->rcv_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sac) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sac_offset(c), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_ibc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + ibc_offset(c), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -607,6 +618,7 @@ extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
+    if (c->d_rcv) HIPCHK(c, hipMemcpyAsync(c->d_rcv, (const uint64_t*)src + rcv_offset(c), c->rcv_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sac) HIPCHK(c, hipMemcpyAsync(c->d_sac, (const uint64_t*)src + sac_offset(c), c->sac_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sbc) HIPCHK(c, hipMemcpyAsync(c->d_sbc, (const uint64_t*)src + sbc_offset(c), c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_ibc) HIPCHK(c, hipMemcpyAsync(c->d_ibc, (const uint64_t*)src + ibc_offset(c), c->ibc_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -636,6 +648,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
         HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_rcv) HIPCHK(c, hipMemcpy(dst + rcv_offset(c), c->d_rcv, c->rcv_words * 8, hipMemcpyDeviceToHost));
     if (c->d_sac) HIPCHK(c, hipMemcpy(dst + sac_offset(c), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToHost));
     if (c->d_sbc) HIPCHK(c, hipMemcpy(dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToHost));
     if (c->d_ibc) HIPCHK(c, hipMemcpy(dst + ibc_offset(c), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToHost));
@@ -663,6 +676,7 @@ extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_rcv) HIPCHK(c, hipMemcpy(c->d_rcv, src + rcv_offset(c), c->rcv_words * 8, hipMemcpyHostToDevice));
     if (c->d_sac) HIPCHK(c, hipMemcpy(c->d_sac, src + sac_offset(c), c->sac_words * 8, hipMemcpyHostToDevice));
     if (c->d_sbc) HIPCHK(c, hipMemcpy(c->d_sbc, src + sbc_offset(c), c->sbc_words * 8, hipMemcpyHostToDevice));
     if (c->d_ibc) HIPCHK(c, hipMemcpy(c->d_ibc, src + ibc_offset(c), c->ibc_words * 8, hipMemcpyHostToDevice));
@@ -853,6 +867,110 @@ extern "C" int bqc_enable_site_alleles(bqc_ctx* c, uint32_t n_sites, const int32
     return 0;
 }
 
+// The region tables of k_rcv.hip (device_types.h: RcvRegions) from the checked list: one allocation, [start R][end R][off R + 1][first
+// n_refs + 1][bkt_off n_refs + 1][bkt].  The index is over the regions' ends and comes from the list alone.
+extern "C" int bqc_enable_region_coverage(bqc_ctx* c, uint32_t n_regions, const int32_t* rid, const int32_t* start, const int32_t* end, uint32_t min_mapq,
+                                          uint32_t n_thresholds, const uint64_t* thresholds, uint32_t depth_cap)
+{
+    if (!c) return BQC_ERR_ARG;
+    static const uint64_t default_thr[6] = {1, 10, 20, 30, 50, 100};
+    if (!n_regions) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: the list holds 0 regions");
+    if (!rid || !start || !end) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: the list of %u regions is a null pointer", n_regions);
+    if (min_mapq > 255) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: minimum mapping quality %u is outside 0 ... 255", min_mapq);
+    if (n_thresholds > BQC_RCV_MAX_THRESHOLDS) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: %u depth thresholds are more than %d", n_thresholds, BQC_RCV_MAX_THRESHOLDS);
+    if (n_thresholds && !thresholds) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: the list of %u depth thresholds is a null pointer", n_thresholds);
+    if (!n_thresholds) { thresholds = default_thr; n_thresholds = 6; }
+    for (uint32_t t = 0; t < n_thresholds; ++t) {
+        if (thresholds[t] < 1 || thresholds[t] > 0xFFFFFFFFull)
+            return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: depth threshold %u: %llu is outside 1 ... 4294967295", t, (unsigned long long)thresholds[t]);
+        if (t && thresholds[t] <= thresholds[t - 1])
+            return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: depth threshold %u: %llu is not above its predecessor %llu", t, (unsigned long long)thresholds[t], (unsigned long long)thresholds[t - 1]);
+    }
+    if (depth_cap < 1 || depth_cap > 16383) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: histogram cap %u is outside 1 ... 16383", depth_cap);
+    const uint32_t n_refs = c->opt.n_refs;
+    uint64_t B = 0;
+    for (uint32_t i = 0; i < n_regions; ++i) {
+        if (rid[i] < 0 || (uint32_t)rid[i] >= n_refs) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: region %u: contig %d is outside 0 ... %u", i, rid[i], n_refs - 1);
+        if (start[i] < 0) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: region %u: start %d is outside 0 ... 2147483646", i, start[i]);
+        if (end[i] <= start[i]) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: region %u: end %d does not lie behind start %d", i, end[i], start[i]);
+        if (i && (rid[i] < rid[i - 1] || (rid[i] == rid[i - 1] && start[i] < end[i - 1])))
+            return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: region %u: (contig %d, start %d) does not lie at or behind its predecessor's end (%d, %d)", i, rid[i], start[i], rid[i - 1], end[i - 1]);
+        B += (uint64_t)((int64_t)end[i] - start[i]);
+    }
+    if ((uint64_t)c->opt.n_lanes * (B + n_regions + 4) > 1ull << 28)
+        return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: %llu bases in %u regions x %u read groups are more than 268435456 (2^28) words", (unsigned long long)B, n_regions, c->opt.n_lanes);
+    if (c->d_rcv) return fail(c, BQC_ERR_STATE, "bqc_enable_region_coverage: the module is on already (%u regions)", c->rcv_r);
+    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
+        return fail(c, BQC_ERR_STATE, "bqc_enable_region_coverage: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    std::vector<uint32_t> off(n_regions + 1, 0), first(n_refs + 1, 0), bkt_off(n_refs + 1, 0);
+    for (uint32_t i = 0; i < n_regions; ++i) {
+        off[i + 1] = off[i] + (uint32_t)(end[i] - start[i]) + 1u;
+        ++first[rid[i] + 1];
+    }
+    for (uint32_t r = 0; r < n_refs; ++r) first[r + 1] += first[r];
+    uint64_t n_bkt = 0;
+    for (uint32_t r = 0; r < n_refs; ++r) {
+        bkt_off[r] = (uint32_t)n_bkt;
+        if (first[r + 1] > first[r]) n_bkt += ((uint64_t)end[first[r + 1] - 1] >> 12) + 2;
+        if (n_bkt > 0xFFFFFFFFull) return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: the index of the regions needs more than 2^32 buckets of 4096 bases");
+    }
+    bkt_off[n_refs] = (uint32_t)n_bkt;
+    std::vector<uint32_t> tab; // everything behind the starts and ends
+    tab.reserve((size_t)n_regions + 1 + 2 * (size_t)(n_refs + 1) + n_bkt);
+    tab.insert(tab.end(), off.begin(), off.end());
+    tab.insert(tab.end(), first.begin(), first.end());
+    tab.insert(tab.end(), bkt_off.begin(), bkt_off.end());
+    for (uint32_t r = 0; r < n_refs; ++r) {
+        const uint64_t nb = bkt_off[r + 1] - bkt_off[r];
+        uint32_t s = first[r];
+        for (uint64_t k = 0; k < nb; ++k) { // entry k: the first region with end > 4096 k (behind the last bucket: none, first[r + 1])
+            while (s < first[r + 1] && (uint64_t)end[s] <= k << 12) ++s;
+            tab.push_back(s);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t words = bqc_rcv_words(c->opt.n_lanes, B, n_regions);
+    const uint64_t tab_bytes = (2 * (uint64_t)n_regions + tab.size()) * 4;
+    const uint64_t out_words = bqc_rcv_out_words(c->opt.n_lanes, n_regions, n_thresholds, depth_cap);
+    const uint64_t out_all = out_words + (uint64_t)c->opt.n_lanes * bqc_rcv_tiles(B, n_regions);
+    uint64_t *d = nullptr, *o = nullptr;
+    void* t = nullptr;
+    if (hipMalloc(&d, words * 8) != hipSuccess || hipMalloc(&t, tab_bytes) != hipSuccess || hipMalloc(&o, out_all * 8) != hipSuccess ||
+        hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess || hipMemcpy(t, start, (uint64_t)n_regions * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy((uint32_t*)t + n_regions, end, (uint64_t)n_regions * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy((uint32_t*)t + 2 * (uint64_t)n_regions, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d);
+        (void)hipFree(t);
+        (void)hipFree(o);
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_region_coverage: the words (%llu bytes), the regions (%llu bytes) and the products (%llu bytes) could not be allocated", (unsigned long long)(words * 8), (unsigned long long)tab_bytes, (unsigned long long)(out_all * 8));
+    }
+    RcvRegions& rg = c->rcv_regions;
+    rg.start = (const int32_t*)t;
+    rg.end = rg.start + n_regions;
+    rg.off = (const uint32_t*)(rg.end + n_regions);
+    rg.first = rg.off + n_regions + 1;
+    rg.bkt_off = rg.first + n_refs + 1;
+    rg.bkt = rg.bkt_off + n_refs + 1;
+    rg.R = n_regions;
+    rg.n_refs = n_refs;
+    rg.lane_words = 4 + B + n_regions;
+    c->rcv_fp.n_thr = n_thresholds;
+    c->rcv_fp.D = depth_cap;
+    for (uint32_t k = 0; k < BQC_RCV_MAX_THRESHOLDS; ++k) c->rcv_fp.thr[k] = k < n_thresholds ? (uint32_t)thresholds[k] : 0xFFFFFFFFu;
+    c->rcv_thr.assign(thresholds, thresholds + n_thresholds);
+    c->rcv_rid.assign(rid, rid + n_regions);
+    c->rcv_start.assign(start, start + n_regions);
+    c->rcv_end.assign(end, end + n_regions);
+    c->rcv_r = n_regions; c->rcv_mq = min_mapq; c->rcv_b = B;
+    c->rcv_words = words;
+    c->rcv_out_words = out_words;
+    c->d_rcv_tab = t;
+    c->d_rcv_out = o;
+    c->d_rcv = d;
+    return 0;
+}
+
 extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
 {
     if (!c || !out) return BQC_ERR_ARG;
@@ -969,6 +1087,32 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
             for (uint32_t m = 0; m < 2; ++m)
                 c->adp_ncyc[l * 2 + m] = last_nonzero_len(c->h_adp.data() + (((uint64_t)l * 2 + m) * BQC_ADP_ROWS + BQC_ADP_MAX) * N, N);
         c->adp_final = true;
+    }
+    if (c->d_rcv) { // k_rcv_final: the depths from the difference words, which it leaves as they are
+        const uint32_t n_lanes = c->opt.n_lanes, R = c->rcv_r;
+        c->rcv_final = false;
+        const bool timed = c->timing && c->ev.size() >= 2 && !c->d_gcb; // (bqc_last_timing then shows this pass, as it shows k_gcb_genome: a batch's kernels are over)
+        if (timed) { c->n_timed = 0; c->tnames.clear(); (void)hipEventRecord(c->ev[0], c->stream); }
+        bqc_launch_rcv_final(c->d_rcv, c->rcv_regions, c->rcv_fp, n_lanes, c->d_rcv_out + c->rcv_out_words, c->d_rcv_out, c->stream);
+        if (timed) { (void)hipEventRecord(c->ev[1], c->stream); c->tnames.push_back("k_rcv_final"); c->n_timed = 1; }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->h_rcv_out.resize(c->rcv_out_words);
+        HIPCHK(c, hipMemcpy(c->h_rcv_out.data(), c->d_rcv_out, c->rcv_out_words * 8, hipMemcpyDeviceToHost));
+        c->h_rcv_eta.assign((size_t)n_lanes * 4, 0);
+        HIPCHK(c, hipMemcpy2D(c->h_rcv_eta.data(), 32, c->d_rcv, c->rcv_regions.lane_words * 8, 32, n_lanes, hipMemcpyDeviceToHost));
+        const uint64_t bad = c->h_rcv_out[c->rcv_out_words - 1];
+        if (bad != ~0ull)
+            return fail(c, BQC_ERR_STATE, "bqc_finalize: region coverage: the words are not a difference array of this list of regions: region %llu (contig %d, %d ... %d) does not close at depth 0 (state imported from a context with another list?)",
+                        (unsigned long long)bad, c->rcv_rid[bad], c->rcv_start[bad], c->rcv_end[bad]);
+        const uint32_t C = 3 + c->rcv_fp.n_thr;
+        const uint64_t lane_out = (uint64_t)R * C + c->rcv_fp.D + 1;
+        for (uint32_t l = 0; l < n_lanes; ++l) { // (word 3 of a read group's header is 0 in the state; the view's copy holds the bases on target)
+            uint64_t on = 0;
+            for (uint32_t k = 0; k < R; ++k) on += c->h_rcv_out[l * lane_out + (uint64_t)k * C];
+            c->h_rcv_eta[(size_t)l * 4 + 3] = on;
+        }
+        c->rcv_final = true;
     }
     if (c->d_sac) {
         c->h_sac.resize(c->sac_words);
@@ -1109,5 +1253,32 @@ extern "C" int bqc_site_alleles(bqc_ctx* c, uint32_t lane, bqc_sac_view* out)
     out->rid = c->sac_rid.data();
     out->pos = c->sac_pos.data();
     out->counts = c->h_sac.data() + (uint64_t)lane * c->sac_s * 8;
+    return 0;
+}
+
+extern "C" int bqc_region_coverage(bqc_ctx* c, uint32_t lane, bqc_rcv_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_rcv) return fail(c, BQC_ERR_STATE, "bqc_region_coverage: bqc_enable_region_coverage has not been called for the context");
+    if (!c->rcv_final) return fail(c, BQC_ERR_STATE, "bqc_region_coverage: nothing has been finalised");
+    if (lane >= c->opt.n_lanes) return fail(c, BQC_ERR_ARG, "bqc_region_coverage: lane %u out of range", lane);
+    const uint32_t C = 3 + c->rcv_fp.n_thr;
+    const uint64_t lane_out = (uint64_t)c->rcv_r * C + c->rcv_fp.D + 1;
+    const uint64_t* eta = c->h_rcv_eta.data() + (size_t)lane * 4;
+    out->n_regions = c->rcv_r;
+    out->min_mapq = c->rcv_mq;
+    out->n_thresholds = c->rcv_fp.n_thr;
+    out->depth_cap = c->rcv_fp.D;
+    out->rid = c->rcv_rid.data();
+    out->start = c->rcv_start.data();
+    out->end = c->rcv_end.data();
+    out->reads_examined = eta[0];
+    out->reads_on_target = eta[1];
+    out->aligned_bases = eta[2];
+    out->bases_on_target = eta[3];
+    out->target_bases = c->rcv_b;
+    out->thresholds = c->rcv_thr.data();
+    out->regions = c->h_rcv_out.data() + lane * lane_out;
+    out->hist = out->regions + (uint64_t)c->rcv_r * C;
     return 0;
 }

@@ -258,6 +258,20 @@ struct bqc_ctx {
     std::vector<int32_t> sac_rid, sac_pos; // the list as given (bqc_site_alleles' view)
     std::vector<uint64_t> h_sac;       // bqc_finalize's copy
     bool sac_final = false;
+    // depth over given regions (k_rcv.hip; bqc_enable_region_coverage(regions, MQ, thresholds, D) after creation — nothing below exists without it)
+    uint32_t rcv_r = 0, rcv_mq = 0;    // the number of regions R, the minimum mapping quality
+    uint64_t rcv_b = 0;                // B: the regions' bases
+    uint64_t* d_rcv = nullptr;         // [n_lanes][4 + B + R], the module's words of the state vector (behind the sketch's, in front of d_sac's)
+    uint64_t rcv_words = 0;
+    void* d_rcv_tab = nullptr;         // the region tables of `rcv_regions`, one allocation
+    RcvRegions rcv_regions{};
+    RcvFinal rcv_fp{};                 // the finalize parameters: thresholds and the histogram's cap (not part of the state)
+    uint64_t* d_rcv_out = nullptr;     // k_rcv_final's products and, behind them, its tile sums
+    uint64_t rcv_out_words = 0;
+    std::vector<int32_t> rcv_rid, rcv_start, rcv_end; // the list as given (bqc_region_coverage's view)
+    std::vector<uint64_t> rcv_thr;     // the thresholds as the view shows them
+    std::vector<uint64_t> h_rcv_out, h_rcv_eta; // bqc_finalize's copies: the products, and [n_lanes][4: E, T, A, bases on target]
+    bool rcv_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

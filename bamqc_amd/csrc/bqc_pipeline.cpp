@@ -39,6 +39,7 @@ void bqc_launch_gcb_reads(const DevBatch&, const DevRefs&, uint64_t* tables, uin
 void bqc_launch_ibc(const DevBatch&, uint64_t* tables, uint32_t N, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_sbc(const DevBatch&, const DevRefs&, uint64_t* tables, uint32_t N, uint32_t Q, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_sac(const DevBatch&, const SacSites&, uint64_t* table, uint32_t Q, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
+void bqc_launch_rcv(const DevBatch&, const RcvRegions&, uint64_t* state, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 }
 
 using clk = std::chrono::steady_clock;
@@ -619,6 +620,7 @@ static int enqueue_batch(bqc_ctx* c, BatchMem& m, bool& forked)
     if (c->d_mbc) { bqc_launch_mbc(d, refs, c->d_mbc, c->opt.mismatch_by_cycle, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_mbc"); }
     if (c->d_sbc) { bqc_launch_sbc(d, refs, c->d_sbc, c->sbc_n, c->sbc_q, c->sbc_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sbc"); }
     if (c->d_sac) { bqc_launch_sac(d, c->sac_sites, c->d_sac, c->sac_q, c->sac_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sac"); }
+    if (c->d_rcv) { bqc_launch_rcv(d, c->rcv_regions, c->d_rcv, c->rcv_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_rcv"); }
     if (c->d_adp) { bqc_launch_adp(d, c->adp_pat, c->d_adp, c->adp_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_adp"); }
     if (c->d_gcb) { bqc_launch_gcb_reads(d, refs, c->d_gcb, c->gcb_w, c->gcb_div, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_gcb_reads"); }
     if (c->d_ibc) { bqc_launch_ibc(d, c->d_ibc, c->ibc_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_ibc"); }

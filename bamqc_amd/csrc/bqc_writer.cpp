@@ -348,3 +348,39 @@ extern "C" int bqc_write_site_alleles(bqc_ctx* ctx, const bqc_header_info* hdr, 
     }
     return write_file(o, path);
 }
+
+// The depth over the given regions as text (include/bamqc.h): per lane the scalars, the thresholds and the histogram (its length
+// first), then one line a region, in the list's order: the contig's name, start and end as a BED file gives them, the depth's sum, min
+// and max and the positions at or above each threshold.
+extern "C" int bqc_write_region_coverage(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path)
+{
+    if (!ctx || !hdr || !path || (!ref_names && n_refs)) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 16);
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        bqc_rcv_view v;
+        const int rc = bqc_region_coverage(ctx, hdr->lane_index[n], &v);
+        if (rc) return rc;
+        const uint32_t C = 3 + v.n_thresholds;
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        o.line_u64("region_min_mapq", v.min_mapq);
+        o.line_u64("region_reads_examined", v.reads_examined);
+        o.line_u64("region_reads_on_target", v.reads_on_target);
+        o.line_u64("region_aligned_bases", v.aligned_bases);
+        o.line_u64("region_bases_on_target", v.bases_on_target);
+        o.line_u64("region_target_bases", v.target_bases);
+        o.array("region_depth_thresholds", v.thresholds, v.n_thresholds);
+        o.str("region_depth_histogram "); o.u64((uint64_t)v.depth_cap + 1);
+        for (uint32_t d = 0; d <= v.depth_cap; ++d) { o.s.push_back(' '); o.u64(v.hist[d]); }
+        o.s.push_back('\n');
+        o.line_u64("regions", v.n_regions);
+        for (uint32_t k = 0; k < v.n_regions; ++k) {
+            if ((uint32_t)v.rid[k] >= n_refs || !ref_names[v.rid[k]]) return BQC_ERR_ARG; // (a region's contig has no name)
+            o.str(ref_names[v.rid[k]]); o.s.push_back(' '); o.u64((uint64_t)v.start[k]); o.s.push_back(' '); o.u64((uint64_t)v.end[k]);
+            for (uint32_t q = 0; q < C; ++q) { o.s.push_back(' '); o.u64(v.regions[(uint64_t)k * C + q]); }
+            o.s.push_back('\n');
+        }
+    }
+    return write_file(o, path);
+}

@@ -200,6 +200,28 @@ struct SacSites {
     uint32_t S, n_refs;
 };
 
+// Depth over given regions (k_rcv.hip; the statistic: include/bamqc.h).  The words of a read group: [E, T, A, 0] then the B + R
+// difference words, region k's len + 1 slots from off[k] (off[R] == B + R).  The region tables, made once by
+// bqc_enable_region_coverage: starts and ends in the list's order, the contigs' runs of regions first[r] .. first[r + 1], and per
+// contig with regions an index of buckets of 4096 bases over the regions' ENDS (a region may begin many buckets in front of the base
+// that is looked up; its end cannot lie in front of it): entry k of contig r, bkt[bkt_off[r] + k], is the first region with
+// end > 4096 k, up to the bucket of the contig's last end, and one entry more closes it with first[r + 1].
+struct RcvRegions {
+    const int32_t* start;    // [R]
+    const int32_t* end;      // [R]
+    const uint32_t* off;     // [R + 1]
+    const uint32_t* first;   // [n_refs + 1]
+    const uint32_t* bkt_off; // [n_refs + 1]
+    const uint32_t* bkt;     // [bkt_off[n_refs]]
+    uint32_t R, n_refs;
+    uint64_t lane_words;     // 4 + B + R
+};
+#define BQC_RCV_MAX_THRESHOLDS 8
+struct RcvFinal { // what k_rcv_final folds by
+    uint32_t n_thr, D;
+    uint32_t thr[BQC_RCV_MAX_THRESHOLDS];
+};
+
 struct DevRefs {
     const uint8_t* const* ref; // [n_refs] Dna5 codes, nullptr if not loaded
     const uint64_t* len;

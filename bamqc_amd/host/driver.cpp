@@ -796,6 +796,10 @@ struct ProgramOptions {
     // --site-alleles FILE / --site-alleles-min-qual Q / --site-alleles-min-mapq MQ: allele counts at the sites of FILE into <output>.sac
     std::string site_alleles; // (empty: off)
     uint32_t site_min_qual = 20, site_min_mapq = 20;
+    // --regions FILE / --regions-min-mapq MQ / --regions-thresholds LIST / --regions-depth-cap D: depth over the regions of FILE into <output>.rcv
+    std::string regions; // (empty: off)
+    uint32_t regions_min_mapq = 20, regions_depth_cap = 1000;
+    std::vector<uint64_t> regions_thresholds{1, 10, 20, 30, 50, 100};
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -847,6 +851,15 @@ void usage(FILE* f)
             "          contamination checks are folds of it).\n"
             "    --site-alleles-min-qual INT\n          The same over bases of quality INT and more (0 to 222).  Needs --site-alleles.\n"
             "    --site-alleles-min-mapq INT\n          The same over reads of mapping quality INT and more (0 to 255).  Needs --site-alleles.\n"
+            "    --regions FILE\n          Depth over given regions: FILE is a BED file (lines CONTIG<TAB>START<TAB>END, START counted from 0, END\n"
+            "          exclusive; regions that overlap or abut are merged).  Per read group the reads and aligned bases on the\n"
+            "          regions, a histogram of the depth over their bases and per region the depth's sum, minimum and maximum\n"
+            "          and the bases at depth 1, 10, 20, 30, 50 and 100 or more, over reads of mapping quality 20 and more,\n"
+            "          into OUT.rcv (on-target rate, mean target depth, fold-80 and the list of gaps are folds of it).\n"
+            "    --regions-min-mapq INT\n          The same over reads of mapping quality INT and more (0 to 255).  Needs --regions.\n"
+            "    --regions-thresholds LIST\n          The same with the depths of LIST: up to 8 numbers of 1 to 4294967295, increasing, separated by\n"
+            "          commas.  Needs --regions.\n"
+            "    --regions-depth-cap INT\n          The histogram's last bin: depth INT and more (1 to 16383, default 1000).  Needs --regions.\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -911,6 +924,7 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
     bool want_adp = false; // --adapter-by-cycle or an --adapter: the module at 1024 cycles unless --adapter-by-cycle-len says otherwise
     bool want_gcb = false; // --gc-bias: the module with windows of 100 bases unless --gc-bias-window says otherwise
     std::string want_sac_value; // a threshold option of --site-alleles was given: it needs the sites
+    std::string want_rcv_value; // a parameter option of --regions was given: it needs the regions
     // (--gpus N is the front end's and never reaches this parser from it; given here, it is an illegal option — said in the option's
     // own terms where the GC bias is asked for as well, which no worker of --gpus could compute)
     auto gcb_somewhere = [&]() {
@@ -1044,6 +1058,39 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             (qual ? o.site_min_qual : o.site_min_mapq) = (uint32_t)x;
             want_sac_value = key;
         }
+        else if (key == "--regions") { if (!need(i, key, v, inl)) return 1; o.regions = v; }
+        else if (key == "--regions-min-mapq" || key == "--regions-depth-cap") {
+            if (!need(i, key, v, inl)) return 1;
+            const bool mq = key == "--regions-min-mapq";
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? ~0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x > (mq ? 255ull : 16383ull) || (!mq && x < 1)) {
+                err = "bamqualcheck: the given value '" + v + "' is not a " + (mq ? "mapping quality (--regions-min-mapq wants 0 to 255)" : "histogram cap (--regions-depth-cap wants 1 to 16383)");
+                return 1;
+            }
+            (mq ? o.regions_min_mapq : o.regions_depth_cap) = (uint32_t)x;
+            want_rcv_value = key;
+        }
+        else if (key == "--regions-thresholds") {
+            if (!need(i, key, v, inl)) return 1;
+            std::vector<uint64_t> t;
+            bool ok = !v.empty();
+            for (size_t at = 0; ok && at <= v.size();) {
+                const size_t comma = std::min(v.find(',', at), v.size());
+                const std::string f = v.substr(at, comma - at);
+                char* end = nullptr;
+                const unsigned long long x = f.empty() || f[0] < '0' || f[0] > '9' || f.size() > 10 ? 0ull : strtoull(f.c_str(), &end, 10);
+                ok = end && !*end && x >= 1 && x <= 0xFFFFFFFFull && (t.empty() || x > t.back()) && t.size() < 8;
+                t.push_back(x);
+                at = comma + 1;
+            }
+            if (!ok) {
+                err = "bamqualcheck: the given value '" + v + "' is not a list of depths (--regions-thresholds wants up to 8 increasing numbers of 1 to 4294967295, separated by commas)";
+                return 1;
+            }
+            o.regions_thresholds = t;
+            want_rcv_value = key;
+        }
         else if (key == "--gc-bias-window") {
             if (!need(i, key, v, inl)) return 1;
             char* end = nullptr;
@@ -1059,6 +1106,7 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
     if (want_adp && !o.adapter_by_cycle) o.adapter_by_cycle = 1024;
     if (want_gcb && !o.gc_bias) o.gc_bias = 100;
     if (!want_sac_value.empty() && o.site_alleles.empty()) { err = "bamqualcheck: option " + want_sac_value + " needs --site-alleles FILE (the sites it applies to)"; return 1; }
+    if (!want_rcv_value.empty() && o.regions.empty()) { err = "bamqualcheck: option " + want_rcv_value + " needs --regions FILE (the regions it applies to)"; return 1; }
     if (!have_r) { err = "bamqualcheck: option requires an argument -- r (required option -r/--reference missing)"; return 1; }
     if (session_form) {
         if (have_o || have_m || !pos.empty()) { err = "bamqualcheck: a session takes the program's options without an input, -o and --manifest"; return 1; }
@@ -1175,6 +1223,9 @@ struct CtxKey {
     std::vector<std::pair<std::string, std::string>> adapters; // (empty: the built-in set)
     std::vector<int32_t> site_rid, site_pos; // --site-alleles: the list as mapped to the job's header (empty: off)
     uint32_t site_min_qual = 0, site_min_mapq = 0;
+    std::vector<int32_t> region_rid, region_start, region_end; // --regions: the list as mapped to the job's header (empty: off)
+    uint32_t regions_min_mapq = 0, regions_depth_cap = 0;
+    std::vector<uint64_t> regions_thresholds;
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
     double e = 0;
@@ -1183,7 +1234,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && region_rid == o.region_rid && region_start == o.region_start && region_end == o.region_end && regions_min_mapq == o.regions_min_mapq && regions_depth_cap == o.regions_depth_cap && regions_thresholds == o.regions_thresholds && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1203,6 +1254,11 @@ struct bqc_session {
     std::vector<std::string> sites_names;
     std::vector<uint32_t> sites_lens;
     std::vector<int32_t> sites_rid, sites_pos;
+    // --regions: the same for the BED file
+    bool regions_loaded = false;
+    std::vector<std::string> regions_names;
+    std::vector<uint32_t> regions_lens;
+    std::vector<int32_t> regions_rid, regions_start, regions_end;
     GpuBamReader gpu_rd;          // opened again for every file it takes: its buffers stay
     std::vector<std::unique_ptr<HostBatch>> spare; // the decoder's batch objects: their columns, page locks and device buffers
     std::atomic<bool> ended{false}; // a HIP error: nothing more is started on the card
@@ -1320,6 +1376,32 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
             if (unnamed && !host_reader_only && (!shard || shard->index == 0))
                 fprintf(stderr, "bamqualcheck: %llu of %llu sites of %s lie on contigs the header does not name\n", (unsigned long long)unnamed, (unsigned long long)given, opt.site_alleles.c_str());
             if (S) { S->sites_loaded = true; S->sites_names = H.ref_names; S->sites_lens = H.ref_lens; S->sites_rid = site_rid; S->sites_pos = site_pos; }
+        }
+    }
+    // --regions: the regions as this header numbers the contigs (every worker of --gpus N loads the list itself)
+    std::vector<int32_t> region_rid, region_start, region_end;
+    if (!opt.regions.empty()) {
+        if (S && S->regions_loaded && S->regions_names == H.ref_names && S->regions_lens == H.ref_lens) { region_rid = S->regions_rid; region_start = S->regions_start; region_end = S->regions_end; }
+        else {
+            std::vector<const char*> names;
+            for (const auto& nm : H.ref_names) names.push_back(nm.c_str());
+            uint32_t n_regions = 0;
+            int32_t *rr = nullptr, *rs = nullptr, *re = nullptr;
+            uint64_t given = 0, unnamed = 0, merged = 0;
+            char rerr[1024];
+            if (bqc_regions_load(opt.regions.c_str(), names.data(), H.ref_lens.data(), n_refs, &n_regions, &rr, &rs, &re, &given, &unnamed, &merged, rerr, sizeof rerr)) {
+                fprintf(stderr, "ERROR: %s\n", rerr);
+                return shard_abort();
+            }
+            region_rid.assign(rr, rr + n_regions);
+            region_start.assign(rs, rs + n_regions);
+            region_end.assign(re, re + n_regions);
+            bqc_regions_free(rr, rs, re);
+            if (!host_reader_only && (!shard || shard->index == 0)) {
+                if (unnamed) fprintf(stderr, "bamqualcheck: %llu of %llu regions of %s lie on contigs the header does not name\n", (unsigned long long)unnamed, (unsigned long long)given, opt.regions.c_str());
+                if (merged) fprintf(stderr, "bamqualcheck: %llu regions of %s overlap or abut their predecessor and were merged with it: %u regions are left\n", (unsigned long long)merged, opt.regions.c_str(), n_regions);
+            }
+            if (S) { S->regions_loaded = true; S->regions_names = H.ref_names; S->regions_lens = H.ref_lens; S->regions_rid = region_rid; S->regions_start = region_start; S->regions_end = region_end; }
         }
     }
     const auto t_begin = std::chrono::steady_clock::now(); // (BQC_TIMING=1 also reports the phases around the record loop)
@@ -1442,6 +1524,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters; ctx_key.gc_bias = opt.gc_bias; ctx_key.indel_by_cycle = opt.indel_by_cycle;
         ctx_key.substitutions = opt.substitutions; ctx_key.subst_min_qual = opt.subst_min_qual; ctx_key.subst_min_mapq = opt.subst_min_mapq;
         if (!site_rid.empty()) { ctx_key.site_rid = site_rid; ctx_key.site_pos = site_pos; ctx_key.site_min_qual = opt.site_min_qual; ctx_key.site_min_mapq = opt.site_min_mapq; }
+        if (!region_rid.empty()) { ctx_key.region_rid = region_rid; ctx_key.region_start = region_start; ctx_key.region_end = region_end; ctx_key.regions_min_mapq = opt.regions_min_mapq; ctx_key.regions_depth_cap = opt.regions_depth_cap; ctx_key.regions_thresholds = opt.regions_thresholds; }
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1487,6 +1570,11 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         }
         if (!rc && !site_rid.empty()) {
             rc = bqc_enable_site_alleles(ctx, (uint32_t)site_rid.size(), site_rid.data(), site_pos.data(), opt.site_min_qual, opt.site_min_mapq);
+            if (rc) create_err = bqc_last_error(ctx);
+        }
+        if (!rc && !region_rid.empty()) {
+            rc = bqc_enable_region_coverage(ctx, (uint32_t)region_rid.size(), region_rid.data(), region_start.data(), region_end.data(), opt.regions_min_mapq,
+                                            (uint32_t)opt.regions_thresholds.size(), opt.regions_thresholds.data(), opt.regions_depth_cap);
             if (rc) create_err = bqc_last_error(ctx);
         }
         if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
@@ -1813,10 +1901,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     std::vector<const char*> sac_names;
     for (const auto& nm : H.ref_names) sac_names.push_back(nm.c_str());
     const int sac_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !site_rid.empty() ? bqc_write_site_alleles(ctx, &hi, sac_names.data(), n_refs, sac_path.c_str()) : 0;
+    const std::string rcv_path = opt.outputFile + ".rcv"; // the table of --regions, behind the .sac
+    const int rcv_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !region_rid.empty() ? bqc_write_region_coverage(ctx, &hi, sac_names.data(), n_refs, rcv_path.c_str()) : 0;
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1837,6 +1927,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (ibc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", ibc_path.c_str()); return 1; }
     if (sbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sbc_path.c_str()); return 1; }
     if (sac_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sac_path.c_str()); return 1; }
+    if (rcv_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", rcv_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

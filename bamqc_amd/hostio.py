@@ -151,6 +151,28 @@ def load_sites(path, names, lens):
     return out
 
 
+def load_regions(path, names, lens):
+    """The BED file of --regions (lines CONTIG<TAB>START<TAB>END; include/bamqc_host.h: bqc_regions_load) against a header's contigs:
+    (rid, start, end, n_given, n_unnamed, n_merged), three int32 arrays sorted by (rid, start), disjoint and not abutting; n_unnamed of
+    the n_given regions lie on contigs that `names` does not hold and are left out, n_merged were merged into their predecessor.
+    IOError with "FILE: line N: reason"."""
+    lib = _lib.load()
+    rl = np.ascontiguousarray(lens, np.uint32)
+    assert len(rl) == len(names)
+    nm = (C.c_char_p * len(names))(*[s.encode() for s in names])
+    n = C.c_uint32()
+    rid, start, end = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+    given, unnamed, merged = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    err = C.create_string_buffer(1024)
+    rc = lib.bqc_regions_load(path.encode(), nm, rl.ctypes.data_as(_abi.u32p), len(rl), C.byref(n), C.byref(rid), C.byref(start), C.byref(end), C.byref(given),
+                              C.byref(unnamed), C.byref(merged), err, len(err))
+    if rc:
+        raise IOError(err.value.decode())
+    out = tuple(np.ctypeslib.as_array(a, shape=(n.value,)).copy() for a in (rid, start, end)) + (int(given.value), int(unnamed.value), int(merged.value))
+    lib.bqc_regions_free(rid, start, end)
+    return out
+
+
 def synth_write(bam_path, fasta_path, seed, n_reads, ref_names, ref_lens, read_len=150, n_lanes=1, isize=1000, long_reads=False):
     lib = _lib.load()
     rl = np.ascontiguousarray(ref_lens, np.uint32)

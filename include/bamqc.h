@@ -634,6 +634,67 @@ typedef struct bqc_sac_view {
 int bqc_site_alleles(bqc_ctx* ctx, uint32_t lane, bqc_sac_view* out);   /* after bqc_finalize */
 int bqc_write_site_alleles(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path);
 
+/* ---- depth over given regions (bqc_enable_region_coverage; not in the reference) ---------------------------------------------------
+ * What an exome, a gene panel or an amplicon run is judged by: how much of the sequencing landed on the targets, how deep each target
+ * is, which targets fall below a depth (Picard CollectHsMetrics, mosdepth --by).  The window histogram (poscov) stays the tool for a
+ * whole genome.
+ * Regions.  R regions (rid, start, end), counted from 0 and half-open;  0 <= rid < n_refs;  0 <= start < end <= 2^31 - 1;  sorted by
+ * (rid, start) and disjoint: within a contig start[k] >= end[k-1] (abutting regions are allowed).  len[k] = end - start, B = sum of
+ * len.  Region k owns len[k] + 1 slots from off[k] = sum over i < k of (len[i] + 1); the extra slot closes the region.  1 <= R and
+ * n_lanes * (B + R + 4) <= 2^28 (2 GiB of words): a whole genome as "regions" is refused.
+ * Parameters.  Minimum mapping quality MQ, 0 ... 255 (the program's default 20), compared as a plain number.  For finalize only, and
+ * not part of the state: up to 8 depth thresholds, strictly increasing, each 1 ... 2^32 - 1 (n_thresholds = 0: 1, 10, 20, 30, 50,
+ * 100), and a histogram cap D, 1 ... 16383 (the program's default 1000).
+ * Examined reads.  flag & 0xF04 == 0;  mapq >= MQ;  n_cigar > 0;  l_seq > 0;  lane < n_lanes;  0 <= rid < n_refs.
+ * BQC_FLAG_NO_QUAL is NOT looked at: no base or quality is read, only the CIGAR.  The mate flags are not looked at; two mates that
+ * overlap BOTH count, as in the site alleles.  The genome is not read.
+ * The walk, in stored order and 64-bit arithmetic: j = 0, g = pos, hit = false; for every CIGAR operation (op, n)
+ *   M, =, X (0, 7, 8):  m = min(n, max(0, l_seq - j)); the positions [g, g + m) are covered;  A[lane] += m;  for every region of the
+ *     read's contig with start < g + m and end > g:  lo = max(g, start), hi = min(g + m, end),
+ *     Diff[lane][off + lo - start] += 1, Diff[lane][off + hi - start] -= 1 (modulo 2^64), hit = true.  Then j += n and g += n.
+ *   I, S (1, 4):  j += n.      D, N (2, 3):  g += n; a deletion or a skip covers nothing (the .mbc / .sac convention, not mosdepth's).
+ *   H, P and every code of 9 or more:  nothing.
+ * Per read E[lane] += 1, and T[lane] += 1 when hit.
+ * State.  Per lane [E, T, A, 0][B + R difference words], u64, pure sums modulo 2^64: n_lanes * (4 + B + R) words directly behind the
+ * sketch's words, IN FRONT OF the site alleles' and every other module's: their distance from the end of the vector stays what it
+ * is.  A region's len + 1 slots always sum to 0, so a plain prefix sum over a lane's difference words is the depth inside every
+ * region and 0 on every closing slot.  Export / import, bqc_reset (the words go back to zero, the regions stay), shard hand-over and
+ * the reduce treat the words as the other words (--gpus N works).  Two contexts exchange state only when both have the module on with
+ * the same B + R (the lists themselves are not compared; see bqc_finalize below).
+ * Finalize products, per lane.  Per region: sum, min and max of the depth over its len positions and, per threshold t, the number of
+ * positions of depth >= t.  Over all B positions: the histogram H[0 ... D] (bin D: depth >= D).  bases_on_target = the sum of the
+ * regions' sums.  The state is left as it is: finalize can be called again, and an export after it still gives difference words.
+ * bqc_finalize fails with BQC_ERR_STATE and names the first such region when a closing slot's prefix is not 0: the words are not a
+ * difference array of this list (an import from a context with another list of the same B + R).
+ * bqc_enable_region_coverage switches the module on, after creation, in any order with the other enable calls (the ABI version stays
+ * 2); the lists are copied.  BQC_ERR_ARG, with a message that names the value and, for the list, the index of the first offending
+ * region, in this order: R = 0;  a null list;  MQ > 255;  more than 8 thresholds, a threshold out of range or not above its
+ * predecessor;  D out of range;  a rid out of range, a start below 0, an end not behind its start, a region that begins in front of
+ * its predecessor's end;  n_lanes * (B + R + 4) > 2^28.  BQC_ERR_STATE: a second call; a call after the context has taken a batch, has
+ * exported or imported state, or has been finalised.  Without the call: no allocation, no launch, the same bqc_state_words and the
+ * same offsets.  With it: every other output is the same bytes as without it.
+ * bqc_region_coverage: valid after bqc_finalize; the view is owned by the context until the next finalize / destroy.  regions:
+ * R x (3 + n_thresholds) entries, a region's sum, min, max, then its counts by threshold.  BQC_ERR_STATE: the module is off, or
+ * nothing has been finalised; BQC_ERR_ARG: lane out of range.
+ * bqc_write_region_coverage: the text, lanes in the order of `hdr`, key-then-values lines (BQC_ERR_ARG when a region's contig has no
+ * name):
+ *   sample_id <id> / lane <name> / region_min_mapq <MQ> / region_reads_examined <E> / region_reads_on_target <T> /
+ *   region_aligned_bases <A> / region_bases_on_target <sum of sums> / region_target_bases <B> / region_depth_thresholds t1 ... tn /
+ *   region_depth_histogram <D + 1> v0 ... vD / regions <R> /
+ *   <contig> <start> <end> <sum> <min> <max> <ge_t1> ... <ge_tn>     (one line per region, BED coordinates, the list's order) */
+int bqc_enable_region_coverage(bqc_ctx* ctx, uint32_t n_regions, const int32_t* rid, const int32_t* start, const int32_t* end, uint32_t min_mapq,
+                               uint32_t n_thresholds, const uint64_t* thresholds, uint32_t depth_cap);
+typedef struct bqc_rcv_view {
+    uint32_t n_regions, min_mapq, n_thresholds, depth_cap;
+    const int32_t *rid, *start, *end;
+    uint64_t reads_examined, reads_on_target, aligned_bases, bases_on_target, target_bases;
+    const uint64_t* thresholds; /* [n_thresholds] */
+    const uint64_t* regions;    /* [n_regions][3 + n_thresholds] */
+    const uint64_t* hist;       /* [depth_cap + 1] */
+} bqc_rcv_view;
+int bqc_region_coverage(bqc_ctx* ctx, uint32_t lane, bqc_rcv_view* out);   /* after bqc_finalize */
+int bqc_write_region_coverage(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,20 @@ int bqc_sites_load(const char* path, const char* const* ref_names, const uint32_
                    int32_t** pos, uint64_t* n_given, uint64_t* n_unnamed, char* err, uint64_t err_cap);
 void bqc_sites_free(int32_t* rid, int32_t* pos);
 
+/* The BED file of --regions (bqc_enable_region_coverage's list; no GPU is needed): text lines CONTIG<TAB>START<TAB>END[<TAB>anything],
+ * START counted from 0, END exclusive, the rest of the line ignored.  Lines that start with '#', "track" and "browser" lines and
+ * empty lines are skipped; "\r\n" is accepted; the order is free.  The regions come back sorted by (index of the contig in
+ * ref_names, start), in arrays that bqc_regions_free releases.  Regions of one contig that overlap OR ABUT are merged into one:
+ * *n_merged is the number of merges (regions given minus regions returned, among the named).  A region on a contig that ref_names
+ * does not hold is left out and counted: *n_given is the number of regions the file gives, *n_unnamed how many of them were left out
+ * (each of the three pointers may be NULL).
+ * BQC_ERR_IO, with "FILE: line N: reason" in err[err_cap] (err may be NULL): the file cannot be opened or read; a line without its
+ * two tabs; a START or END that is not a number; END <= START; an END behind the contig's length; no region left (the file's last
+ * line). */
+int bqc_regions_load(const char* path, const char* const* ref_names, const uint32_t* ref_lens, uint32_t n_refs, uint32_t* n_regions, int32_t** rid,
+                     int32_t** start, int32_t** end, uint64_t* n_given, uint64_t* n_unnamed, uint64_t* n_merged, char* err, uint64_t err_cap);
+void bqc_regions_free(int32_t* rid, int32_t* start, int32_t* end);
+
 /* The BGZF reader's DEFLATE decoder on one raw deflate stream (host/inflate_fast.h; exposed for its tests): 1 when the
  * stream is valid, ends within in_n bytes and yields exactly out_n bytes, else 0.  The 8 bytes after in + in_n must be
  * readable (in a BGZF block: the CRC32 / ISIZE trailer). */
