@@ -150,6 +150,11 @@ class RcvView(C.Structure):  # bqc_rcv_view: the list of n_regions entries, five
                 ("target_bases", C.c_uint64), ("thresholds", u64p), ("regions", u64p), ("hist", u64p)]
 
 
+class DupView(C.Structure):  # bqc_dup_view: by class (0 single, 1 pair) the sets, the largest set and 256 sets by size; lanes [n_lanes][5]
+    _fields_ = [("capacity", C.c_uint64), ("n_lanes", C.c_uint32), ("pad", C.c_uint32), ("sets", C.c_uint64 * 2), ("largest", C.c_uint64 * 2),
+                ("hist", u64p * 2), ("estimated_library_size", C.c_uint64), ("lanes", u64p)]
+
+
 def make_modules(adapter_by_cycle=0, adapters=None, struct_size=None):
     """bqc_modules: adapter_by_cycle = the cycle capacity N (0: off), adapters = [(name, sequence), ...] or None for the built-in set."""
     m = Modules()

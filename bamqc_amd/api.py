@@ -40,7 +40,7 @@ class DeviceBatch:
 class Aggregator:
     def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, indel_by_cycle=None, substitutions=None, subst_min_qual=20, subst_min_mapq=30,
                  site_alleles=None, site_min_qual=20, site_min_mapq=20, regions=None, region_min_mapq=20, region_thresholds=(1, 10, 20, 30, 50, 100),
-                 region_depth_cap=1000, **options):
+                 region_depth_cap=1000, duplicate_sets=None, **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
@@ -85,6 +85,16 @@ class Aggregator:
             except BamQCError:
                 self.close()
                 raise
+
+        if duplicate_sets is not None:  # the same way: duplicate sets by alignment signature, a table for `duplicate_sets` signatures
+            try:
+                self.enable_duplicate_sets(duplicate_sets)
+            except BamQCError:
+                self.close()
+                raise
+
+    def enable_duplicate_sets(self, capacity=1 << 26):
+        self._chk(self.lib.bqc_enable_duplicate_sets(self.h, capacity))
 
     def enable_region_coverage(self, rid, start, end, min_mapq=20, thresholds=(1, 10, 20, 30, 50, 100), depth_cap=1000):
         rid, start, end = (np.ascontiguousarray(a, np.int32) for a in (rid, start, end))
@@ -345,6 +355,26 @@ class Aggregator:
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         names = (C.c_char_p * len(ref_names))(*[s.encode() for s in ref_names])
         self._chk(self.lib.bqc_write_region_coverage(self.h, C.byref(hdr), names, len(ref_names), path.encode()))
+
+    def duplicate_sets(self):
+        """The duplicate sets by alignment signature over all read groups (option duplicate_sets=capacity; valid after finalize): a dict of
+        capacity, sets (2,), largest (2,) and hist (2, 256) by class (0 single, 1 pair; hist[c][i - 1]: the sets of i reads, the last bin
+        open), estimated_library_size, and lanes (n_lanes, 5): examined single, examined pair, flagged single, flagged pair, second ends."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.DupView()
+        self._chk(self.lib.bqc_duplicate_sets(self.h, C.byref(v)))
+        return {"capacity": int(v.capacity), "sets": np.array(list(v.sets), np.uint64), "largest": np.array(list(v.largest), np.uint64),
+                "hist": np.stack([np.ctypeslib.as_array(v.hist[k], shape=(256,)).copy() for k in range(2)]),
+                "estimated_library_size": int(v.estimated_library_size),
+                "lanes": np.ctypeslib.as_array(v.lanes, shape=(v.n_lanes, 5)).copy()}
+
+    def write_duplicate_sets(self, path, sample_id="", lane_names=("",), lane_index=None):
+        """The `.dup` text."""
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        self._chk(self.lib.bqc_write_duplicate_sets(self.h, C.byref(hdr), path.encode()))
 
     def close(self):
         if self.h:

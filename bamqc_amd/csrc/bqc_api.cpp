@@ -37,6 +37,10 @@ uint64_t bqc_rcv_words(uint32_t n_lanes, uint64_t B, uint32_t R);
 uint32_t bqc_rcv_tiles(uint64_t B, uint32_t R);
 uint64_t bqc_rcv_out_words(uint32_t n_lanes, uint32_t R, uint32_t n_thr, uint32_t D);
 void bqc_launch_rcv_final(const uint64_t* state, const RcvRegions& rg, const RcvFinal& fp, uint32_t n_lanes, uint64_t* tsum, uint64_t* out, hipStream_t s);
+uint64_t bqc_dup_slots(uint64_t capacity);
+uint64_t bqc_dup_out_words(void);
+void bqc_launch_dup_clear(const DupTable& T, uint64_t* sums, uint32_t n_lanes, uint32_t n_cu, hipStream_t s);
+void bqc_launch_dup_final(const DupTable& T, uint64_t* out, uint32_t n_cu, hipStream_t s);
 uint32_t bqc_gcb_share(void);
 void bqc_launch_gcb_genome(const GcbContig* tab, uint32_t n_contigs, uint64_t n_shares, uint32_t W, const GcbDiv& D, uint64_t* G, uint32_t n_cu, hipStream_t s);
 hipError_t bqc_long_init();
@@ -404,6 +408,7 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (c->d_rcv) (void)hipFree(c->d_rcv);
     if (c->d_rcv_tab) (void)hipFree(c->d_rcv_tab);
     if (c->d_rcv_out) (void)hipFree(c->d_rcv_out);
+    if (c->d_dup) (void)hipFree(c->d_dup);
     if (c->d_gcb_g) (void)hipFree(c->d_gcb_g);
     if (c->d_gcb_tab) (void)hipFree(c->d_gcb_tab);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
@@ -532,6 +537,11 @@ extern "C" int bqc_reset(bqc_ctx* c)
     c->sac_final = false;
     if (c->d_rcv) HIPCHK(c, hipMemsetAsync(c->d_rcv, 0, c->rcv_words * 8, c->stream)); // (the words; the regions stay)
     c->rcv_final = false;
+    if (c->d_dup) { // (the table and the sums go back to empty; the allocation stays)
+        bqc_launch_dup_clear(c->dup_tab, c->d_dup_sums, c->opt.n_lanes, c->n_cu, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
+    c->dup_final = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -971,6 +981,59 @@ extern "C" int bqc_enable_region_coverage(bqc_ctx* c, uint32_t n_regions, const 
     return 0;
 }
 
+// The table of k_dup.hip: one allocation, [C slots][the counter of sets, 7 spare words][n_lanes][5 sums][k_dup_final's products].  The
+// clear is left on the compute stream, in front of the first batch.
+extern "C" int bqc_enable_duplicate_sets(bqc_ctx* c, uint64_t capacity)
+{
+    if (!c) return BQC_ERR_ARG;
+    if (capacity < 16 || capacity > 1ull << 31)
+        return fail(c, BQC_ERR_ARG, "bqc_enable_duplicate_sets: capacity %llu is outside 16 ... 2147483648 (2^31) signatures", (unsigned long long)capacity);
+    if (c->d_dup) return fail(c, BQC_ERR_STATE, "bqc_enable_duplicate_sets: the module is on already (capacity %llu)", (unsigned long long)c->dup_tab.capacity);
+    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
+        return fail(c, BQC_ERR_STATE, "bqc_enable_duplicate_sets: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t C = bqc_dup_slots(capacity);
+    const uint64_t bytes = C * sizeof(DupSlot) + (8 + (uint64_t)c->opt.n_lanes * 5 + bqc_dup_out_words()) * 8;
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_duplicate_sets: the table of %llu slots for a capacity of %llu signatures (%llu bytes) could not be allocated", (unsigned long long)C, (unsigned long long)capacity, (unsigned long long)bytes);
+    }
+    DupTable& T = c->dup_tab;
+    T.slots = (DupSlot*)d;
+    T.n_sets = (uint64_t*)(T.slots + C);
+    T.mask = C - 1;
+    T.capacity = capacity;
+    c->d_dup_sums = T.n_sets + 8;
+    c->d_dup_out = c->d_dup_sums + (uint64_t)c->opt.n_lanes * 5;
+    bqc_launch_dup_clear(T, c->d_dup_sums, c->opt.n_lanes, c->n_cu, c->stream);
+    if (hipGetLastError() != hipSuccess) {
+        (void)hipFree(d);
+        T = DupTable{};
+        c->d_dup_sums = c->d_dup_out = nullptr;
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_duplicate_sets: the table could not be cleared");
+    }
+    c->d_dup = d;
+    return 0;
+}
+
+// Picard's estimateLibrarySize: the library size x with c = x (1 - exp(-n / x)) for n read pairs of which c are unique, by bisection
+static uint64_t dup_library_size(uint64_t n_reads, uint64_t n_unique)
+{
+    if (!n_unique || n_unique >= n_reads) return 0;
+    const double n = (double)n_reads, c = (double)n_unique;
+    auto f = [&](double x) { return c / x - 1 + exp(-n / x); };
+    double m = 1, M = 100;
+    while (f(M * c) > 0) M *= 10;
+    for (int i = 0; i < 40; ++i) {
+        const double r = (m + M) / 2, u = f(r * c);
+        if (u == 0) break;
+        if (u > 0) m = r;
+        else M = r;
+    }
+    return (uint64_t)(c * (m + M) / 2);
+}
+
 extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
 {
     if (!c || !out) return BQC_ERR_ARG;
@@ -1113,6 +1176,27 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
             c->h_rcv_eta[(size_t)l * 4 + 3] = on;
         }
         c->rcv_final = true;
+    }
+    if (c->d_dup) { // k_dup_final: the sets by class and size from the table, which it leaves as it is
+        c->dup_final = false;
+        const bool timed = c->timing && c->ev.size() >= 2 && !c->d_gcb && !c->d_rcv; // (as k_rcv_final)
+        if (timed) { c->n_timed = 0; c->tnames.clear(); (void)hipEventRecord(c->ev[0], c->stream); }
+        bqc_launch_dup_final(c->dup_tab, c->d_dup_out, c->n_cu, c->stream);
+        if (timed) { (void)hipEventRecord(c->ev[1], c->stream); c->tnames.push_back("k_dup_final"); c->n_timed = 1; }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->h_dup_out.resize(bqc_dup_out_words());
+        c->h_dup_sums.resize((size_t)c->opt.n_lanes * 5);
+        HIPCHK(c, hipMemcpy(c->h_dup_out.data(), c->d_dup_out, c->h_dup_out.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(c->h_dup_sums.data(), c->d_dup_sums, c->h_dup_sums.size() * 8, hipMemcpyDeviceToHost));
+        uint64_t pairs = 0;
+        for (uint32_t k = 0; k < 2; ++k) {
+            c->dup_sets[k] = 0;
+            for (uint32_t i = 0; i < BQC_DUP_BINS; ++i) c->dup_sets[k] += c->h_dup_out[(size_t)k * BQC_DUP_BINS + i];
+        }
+        for (uint32_t l = 0; l < c->opt.n_lanes; ++l) pairs += c->h_dup_sums[(size_t)l * 5 + 1];
+        c->dup_estimate = dup_library_size(pairs, c->dup_sets[1]);
+        c->dup_final = true;
     }
     if (c->d_sac) {
         c->h_sac.resize(c->sac_words);
@@ -1280,5 +1364,22 @@ extern "C" int bqc_region_coverage(bqc_ctx* c, uint32_t lane, bqc_rcv_view* out)
     out->thresholds = c->rcv_thr.data();
     out->regions = c->h_rcv_out.data() + lane * lane_out;
     out->hist = out->regions + (uint64_t)c->rcv_r * C;
+    return 0;
+}
+
+extern "C" int bqc_duplicate_sets(bqc_ctx* c, bqc_dup_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_dup) return fail(c, BQC_ERR_STATE, "bqc_duplicate_sets: bqc_enable_duplicate_sets has not been called for the context");
+    if (!c->dup_final) return fail(c, BQC_ERR_STATE, "bqc_duplicate_sets: nothing has been finalised");
+    out->capacity = c->dup_tab.capacity;
+    out->n_lanes = c->opt.n_lanes;
+    for (uint32_t k = 0; k < 2; ++k) {
+        out->sets[k] = c->dup_sets[k];
+        out->largest[k] = c->h_dup_out[2 * BQC_DUP_BINS + k];
+        out->hist[k] = c->h_dup_out.data() + (size_t)k * BQC_DUP_BINS;
+    }
+    out->estimated_library_size = c->dup_estimate;
+    out->lanes = c->h_dup_sums.data();
     return 0;
 }

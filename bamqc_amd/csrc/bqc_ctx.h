@@ -272,6 +272,15 @@ struct bqc_ctx {
     std::vector<uint64_t> rcv_thr;     // the thresholds as the view shows them
     std::vector<uint64_t> h_rcv_out, h_rcv_eta; // bqc_finalize's copies: the products, and [n_lanes][4: E, T, A, bases on target]
     bool rcv_final = false;
+    // duplicate sets by alignment signature (k_dup.hip; bqc_enable_duplicate_sets(capacity) after creation — nothing below exists without it,
+    // and none of it is part of the state vector)
+    DupTable dup_tab{};                // the table's slots (d_dup), the counter of sets behind them, C - 1 and the capacity
+    void* d_dup = nullptr;             // one allocation: [C slots][n_sets, 7 spare words][n_lanes][5 sums][k_dup_final's products]
+    uint64_t* d_dup_sums = nullptr;    // [n_lanes][5: E_single, E_pair, F_single, F_pair, second ends]
+    uint64_t* d_dup_out = nullptr;     // k_dup_final's products: [2][256] sets by size, the two largest sets
+    std::vector<uint64_t> h_dup_out, h_dup_sums; // bqc_finalize's copies
+    uint64_t dup_sets[2] = {0, 0}, dup_estimate = 0;
+    bool dup_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -40,6 +40,7 @@ void bqc_launch_ibc(const DevBatch&, uint64_t* tables, uint32_t N, uint32_t n_la
 void bqc_launch_sbc(const DevBatch&, const DevRefs&, uint64_t* tables, uint32_t N, uint32_t Q, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_sac(const DevBatch&, const SacSites&, uint64_t* table, uint32_t Q, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_rcv(const DevBatch&, const RcvRegions&, uint64_t* state, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
+void bqc_launch_dup(const DevBatch&, const DupTable&, uint64_t* sums, uint32_t* err, uint32_t n_lanes, uint32_t n_refs, uint32_t n_cu, hipStream_t);
 }
 
 using clk = std::chrono::steady_clock;
@@ -621,6 +622,7 @@ static int enqueue_batch(bqc_ctx* c, BatchMem& m, bool& forked)
     if (c->d_sbc) { bqc_launch_sbc(d, refs, c->d_sbc, c->sbc_n, c->sbc_q, c->sbc_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sbc"); }
     if (c->d_sac) { bqc_launch_sac(d, c->sac_sites, c->d_sac, c->sac_q, c->sac_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sac"); }
     if (c->d_rcv) { bqc_launch_rcv(d, c->rcv_regions, c->d_rcv, c->rcv_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_rcv"); }
+    if (c->d_dup) { bqc_launch_dup(d, c->dup_tab, c->d_dup_sums, err, c->opt.n_lanes, c->opt.n_refs, c->n_cu, c->stream); tick(c, "k_dup"); }
     if (c->d_adp) { bqc_launch_adp(d, c->adp_pat, c->d_adp, c->adp_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_adp"); }
     if (c->d_gcb) { bqc_launch_gcb_reads(d, refs, c->d_gcb, c->gcb_w, c->gcb_div, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_gcb_reads"); }
     if (c->d_ibc) { bqc_launch_ibc(d, c->d_ibc, c->ibc_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_ibc"); }
@@ -660,6 +662,8 @@ int bqc_report_errors(bqc_ctx* c, const ErrRec& e)
     if (!e.flags) return 0;
     if (e.flags & BQC_DEVERR_INTERNAL) return bqc_fail(c, BQC_ERR_DEVICE, "internal error: kernel layout assumption violated");
     if (e.flags & BQC_DEVERR_MATE) return bqc_fail(c, BQC_ERR_NO_MATE_FLAG, "ERROR: No first or second flag in read");
+    if (e.flags & BQC_DEVERR_DUP)
+        return bqc_fail(c, BQC_ERR_RANGE, "duplicate sets: the reads hold more than %llu different alignment signatures, the table's capacity (--duplicate-sets-capacity)", (unsigned long long)c->dup_tab.capacity);
     if (e.flags & BQC_DEVERR_RANGE) return bqc_fail(c, BQC_ERR_RANGE, "mismatch/deletion/insertion count exceeds hist_cap (or NM < D+I)");
     return bqc_fail(c, BQC_ERR_RANGE, "base quality above 222 cannot be represented by the reference (q+33 wraps)");
 }

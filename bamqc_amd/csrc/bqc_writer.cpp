@@ -384,3 +384,35 @@ extern "C" int bqc_write_region_coverage(bqc_ctx* ctx, const bqc_header_info* hd
     }
     return write_file(o, path);
 }
+
+// The duplicate sets as text (include/bamqc.h): the capacity, per lane of `hdr` the five sums, then the sets over all read groups.
+extern "C" int bqc_write_duplicate_sets(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path)
+{
+    if (!ctx || !hdr || !path) return BQC_ERR_ARG;
+    bqc_dup_view v;
+    const int rc = bqc_duplicate_sets(ctx, &v);
+    if (rc) return rc;
+    Out o;
+    o.s.reserve(1 << 14);
+    o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+    o.line_u64("duplicate_sets_capacity", v.capacity);
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        if (hdr->lane_index[n] >= v.n_lanes) return BQC_ERR_ARG;
+        const uint64_t* s = v.lanes + (uint64_t)hdr->lane_index[n] * 5;
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        o.line_u64("duplicate_reads_examined_single", s[0]);
+        o.line_u64("duplicate_reads_examined_pair", s[1]);
+        o.line_u64("duplicate_reads_flagged_single", s[2]);
+        o.line_u64("duplicate_reads_flagged_pair", s[3]);
+        o.line_u64("duplicate_reads_second_end", s[4]);
+    }
+    o.str("all_lanes\n");
+    o.line_u64("duplicate_sets_single", v.sets[0]);
+    o.line_u64("duplicate_sets_pair", v.sets[1]);
+    o.line_u64("duplicate_set_largest_single", v.largest[0]);
+    o.line_u64("duplicate_set_largest_pair", v.largest[1]);
+    o.array("duplicate_set_size_histogram_single", v.hist[0], 256);
+    o.array("duplicate_set_size_histogram_pair", v.hist[1], 256);
+    o.line_u64("duplicate_estimated_library_size", v.estimated_library_size);
+    return write_file(o, path);
+}

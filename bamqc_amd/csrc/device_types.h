@@ -24,6 +24,7 @@
 #define BQC_DEVERR_RANGE 2u      // mismatch / deletion / insertion count >= hist_cap
 #define BQC_DEVERR_MATE  4u      // neither first nor last flag
 #define BQC_DEVERR_INTERNAL 8u   // a kernel found its own layout assumptions violated (never expected)
+#define BQC_DEVERR_DUP 16u       // k_dup: more signatures than the table's capacity
 
 struct Chunk {        // lane-uniform run of reads (indices into perm, or read ids when perm == nullptr)
     uint32_t first, count, lane;
@@ -220,6 +221,19 @@ struct RcvRegions {
 struct RcvFinal { // what k_rcv_final folds by
     uint32_t n_thr, D;
     uint32_t thr[BQC_RCV_MAX_THRESHOLDS];
+};
+
+// Duplicate sets by alignment signature (k_dup.hip; the rule: include/bamqc.h).  A slot of the table: the two key words of a
+// signature — k0 = (u5 + 2^45) | class << 46 | strand << 47 | mate strand << 48, k1 = rid | tlen << 32, an empty word all ones — and
+// the reads of its set.  The table is no part of the state vector.
+#define BQC_DUP_EMPTY (~0ull)
+#define BQC_DUP_BINS 256
+struct DupSlot { uint64_t k0, k1, count; };
+struct DupTable {
+    DupSlot* slots;     // [mask + 1]
+    uint64_t* n_sets;   // the sets the table holds (added to once a workgroup and step)
+    uint64_t mask;      // C - 1, C a power of two >= 2 capacity
+    uint64_t capacity;  // the signatures asked for
 };
 
 struct DevRefs {

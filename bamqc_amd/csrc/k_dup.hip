@@ -1,0 +1,384 @@
+// k_dup.hip — duplicate sets by alignment signature (--duplicate-sets; the rule: include/bamqc.h): every examined
+// read has a signature (class, strand, mate strand, rid, unclipped 5' position, tlen), two reads with equal signatures are in one set,
+// and the sets are counted EXACTLY in a hash table in device memory.  An optional module beside k_rcv: its launches and its memory
+// exist only when bqc_enable_duplicate_sets has been called.  The genome is not read, nor any base or quality.  The module's state is
+// NOT part of the flat state vector: the table cannot be summed word by word.
+//
+// The table.  C slots (a power of two, at least twice the capacity in signatures) of DupSlot {k0, k1, count}, open addressing with
+// linear probing; an empty key word is all ones (k0 has 49 bits; k1's low half is a rid >= 0).  Every access to a key word or a count
+// while reads are inserted is an 8-byte agent-scope atomic: nothing is fenced, and no L1 can serve a stale key.
+// The insert never waits for another thread.  At a slot: (1) k0 is loaded, and if empty claimed by a compare-and-swap; (2) if the
+// slot's k0 is now this signature's, the same for k1; (3) if k1 is this signature's too the slot is the signature's, and its count is
+// added to — the thread whose compare-and-swap of k1 succeeded has made a new set; (4) otherwise both words are set, stay as they
+// are for good, and belong to another signature: the next slot.  k0 may be claimed by one thread and k1 by another with the same k0:
+// the slot then holds the second thread's signature and the first moves on.  Every thread of one signature sees the same immutable
+// words at every slot of its probe sequence, so all of them end in the same slot: no two signatures share a set, no signature has two.
+// The bound.  New sets are counted per workgroup and step in LDS and added to one word behind the table once a step.  A probe sequence
+// looks at that word every DP_CHECK slots and gives up when it has passed the capacity; it also gives up after C slots.  Giving up, or
+// a workgroup that finds the word above the capacity at its end (the last one sees every set), sets BQC_DEVERR_DUP in the batch's
+// error record: the stream fails with BQC_ERR_RANGE.  A launch that finds the word above the capacity at its start does nothing.
+//
+// k_dup, per batch.  About one workgroup per CU, DP_WAVES waves; a workgroup takes a contiguous share of the batch's processing order,
+// DP_STEP reads at a time, thread t of a step fetching the fixed columns of the step's read t (those of the next step before this
+// one is inserted).
+// Thread path.  A read of at most DP_T operations: its words are loaded together, lead, trail and reflen come from registers.  A
+// FORWARD read of more operations needs only its leading clips: where one of its first DP_T operations is no clip, it stays here.
+// Wave path.  Every other read of more than DP_T operations is listed in LDS and taken by a wave, 64 operations a pass; the sums are
+// exact (a length has 28 bits: its low 16 and high 12 bits are summed apart).  Lane 0 then inserts the read.
+// Equal signatures of a wave are combined by ballots before the table is touched, one insert with their number — in the waves where
+// some lane's signature is that of the lane beside it (mode bit 0: never; bit 2: in every wave).
+// The slot of a signature is a mix of the whole signature (mode bit 1: a mix of (rid, u5 >> 6, the rest) in the high bits and u5 & 63
+// in the low 6, so that sorted reads land in few rows of the table: measured, no gain).  The products do not depend on either.
+// The five sums of a read group (E and F by class, the second ends) are ballots by read group, added to the workgroup's LDS copy and
+// once, at the workgroup's end, to memory.
+//
+// k_dup_final, at bqc_finalize only: one pass over the C slots, which it only reads: the sets by class and size into LDS histograms
+// (one add a bin and workgroup to memory), the largest set by a maximum per wave.
+#include <algorithm>
+#include <cstdlib>
+#include "kernels_common.h"
+
+#define DP_THREADS 1024
+#define DP_WAVES (DP_THREADS / WAVE)
+#define DP_STEP DP_THREADS
+#define DP_T 8                       // operations up to which a read's CIGAR is summed by its own thread
+#define DP_CHECK 64                  // slots of a probe sequence between two looks at the counter of sets
+#define DP_LANES 256                 // read groups (the lane column is a byte)
+#define DP_NONE 0xFFFFFFFFu
+#define DP_FTHREADS 256
+
+typedef unsigned long long dp_u64;
+__device__ __forceinline__ dp_u64 dp_load(const uint64_t* p) { return __hip_atomic_load((const gmem_u64*)(uintptr_t)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// compare-and-swap of an empty word with `mine`: what the word holds afterwards; won: this thread's swap took place
+__device__ __forceinline__ dp_u64 dp_claim(uint64_t* p, dp_u64 mine, bool& won)
+{
+    dp_u64 seen = BQC_DUP_EMPTY;
+    won = __hip_atomic_compare_exchange_strong((gmem_u64*)(uintptr_t)p, &seen, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return won ? mine : seen;
+}
+
+__device__ __forceinline__ uint64_t dp_mix(uint64_t x)
+{
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
+    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
+    x ^= x >> 33;
+    return x;
+}
+__device__ __forceinline__ uint64_t dp_slot(uint64_t k0, uint64_t k1, uint64_t mask, uint32_t mode)
+{
+    if (!(mode & 2u)) return dp_mix(k0 ^ dp_mix(k1)) & mask;
+    return ((dp_mix((k0 >> 6) ^ dp_mix(k1)) << 6) | (k0 & 63u)) & mask; // (rid, u5 >> 6, the rest): k1 whole and k0 without u5's low 6 bits
+}
+
+// n reads of one signature.  Returns 1 when the set is new, 0 when it was there or the sequence gave up (`over`).
+__device__ __forceinline__ uint32_t dp_insert(const DupTable& T, uint64_t k0, uint64_t k1, uint64_t n, uint32_t mode, bool& over)
+{
+    uint64_t s = dp_slot(k0, k1, T.mask, mode);
+    for (uint64_t probes = 0; probes <= T.mask; ++probes, s = (s + 1u) & T.mask) {
+        if ((probes & (DP_CHECK - 1u)) == DP_CHECK - 1u && dp_load(T.n_sets) > T.capacity) break;
+        DupSlot* sl = T.slots + s;
+        bool won = false;
+        dp_u64 a = dp_load(&sl->k0);
+        if (a == BQC_DUP_EMPTY) a = dp_claim(&sl->k0, k0, won);
+        if (a != k0) continue;
+        won = false;
+        dp_u64 b = dp_load(&sl->k1);
+        if (b == BQC_DUP_EMPTY) b = dp_claim(&sl->k1, k1, won);
+        if (b != k1) continue;
+        gadd(&sl->count, n);
+        return won ? 1u : 0u;
+    }
+    over = true;
+    return 0;
+}
+
+__global__ void k_dup_clear(DupSlot* slots, uint64_t C)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t* w = (uint64_t*)slots;
+    for (uint64_t x = i; x < 3u * C; x += step) w[x] = x % 3u == 2u ? 0ull : BQC_DUP_EMPTY;
+}
+
+// Read i of the processing order.  cls: 0 single, 1 pair, 2 second end, DP_NONE not examined
+struct DpRead { uint32_t cls, r, nc, coff, lane, info; int32_t rid, pos, tlen; }; // info: strand | mate strand << 1 | flagged << 2
+__device__ __forceinline__ DpRead dp_read(const DevBatch& b, uint32_t r, uint32_t n_lanes, uint32_t n_refs)
+{
+    DpRead o{DP_NONE, r, 0u, 0u, 0u, 0u, 0, 0, 0};
+    const uint32_t f = b.flag[r], L = b.l_seq[r], g = b.lane[r], nc = b.n_cigar[r];
+    const int32_t rid = b.rid[r];
+    if ((f & 0xB04u) || !L || !nc || g >= n_lanes || rid < 0 || (uint32_t)rid >= n_refs) return o;
+    const int32_t tlen = b.tlen[r];
+    const bool both = (f & 1u) && !(f & 8u);
+    o.cls = both && tlen > 0 ? 1u : both && tlen < 0 ? 2u : 0u;
+    o.nc = nc; o.lane = g;
+    o.coff = b.cigar_off[r];
+    o.info = ((f >> 4) & 1u) | (o.cls == 1u ? (f >> 5) & 1u : 0u) << 1 | ((f >> 10) & 1u) << 2;
+    o.rid = rid;
+    o.pos = b.pos[r];
+    o.tlen = o.cls == 1u ? tlen : 0;
+    return o;
+}
+__device__ __forceinline__ DpRead dp_fetch(const DevBatch& b, uint64_t i, uint32_t end, uint32_t n_lanes, uint32_t n_refs)
+{
+    const DpRead none{DP_NONE, 0u, 0u, 0u, 0u, 0u, 0, 0, 0};
+    if (i >= end) return none;
+    const uint32_t r = b.order ? b.order[i] : (uint32_t)i;
+    if (r >= b.n_reads) return none;
+    return dp_read(b, r, n_lanes, n_refs);
+}
+
+__device__ __forceinline__ bool dp_clip(uint32_t op) { return op == 4u || op == 5u; }
+__device__ __forceinline__ uint32_t dp_glen(uint32_t op, uint32_t n) { return (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ? n : 0u; }
+__device__ __forceinline__ uint64_t dp_sum64(uint32_t v) { return ((uint64_t)wave_sum(v >> 16) << 16) + wave_sum(v & 0xFFFFu); } // v < 2^28, exact
+
+// the two key words of a read (cls 0 or 1) from its clips and its length on the genome
+__device__ __forceinline__ void dp_keys(const DpRead& me, uint64_t lead, uint64_t trail, uint64_t reflen, uint64_t& k0, uint64_t& k1)
+{
+    const bool rev = me.info & 1u;
+    const int64_t u5 = rev ? (int64_t)me.pos + (int64_t)reflen - 1 + (int64_t)trail : (int64_t)me.pos - (int64_t)lead; // |u5| < 2^31 + 2^44
+    k0 = (uint64_t)(u5 + (1ll << 45)) | (uint64_t)me.cls << 46 | (uint64_t)(me.info & 3u) << 47;
+    k1 = (uint64_t)(uint32_t)me.rid | (uint64_t)(uint32_t)me.tlen << 32;
+}
+
+__global__ __launch_bounds__(DP_THREADS) void k_dup(DevBatch b, DupTable T, uint64_t* __restrict__ sums, uint32_t* __restrict__ err, uint32_t n_lanes, uint32_t n_refs, uint32_t per, uint32_t mode)
+{
+    __shared__ uint32_t s_long[2][DP_STEP];                 // the long reads of a step: the threads that fetched them
+    __shared__ uint32_t s_r[2][DP_STEP];                    // their reads, by thread
+    __shared__ uint32_t s_cnt[3][2];                        // [step mod 3]: listed reads, new sets
+    __shared__ uint32_t s_full;                             // the table went over its capacity in an earlier batch
+    __shared__ unsigned long long s_sum[DP_LANES][5];       // the workgroup's sums by read group
+    if (b.desc->fatal) return;
+    if (threadIdx.x == 0) s_full = dp_load(T.n_sets) > T.capacity ? 1u : 0u;
+    block_sync();
+    if (s_full) return;                                     // (the stream has failed; one thread looks, so the whole workgroup leaves or stays)
+    const uint32_t tid = threadIdx.x, wave = tid / WAVE, ln = lane_id();
+    const uint64_t begin64 = (uint64_t)blockIdx.x * per;
+    if (begin64 >= b.n_reads) return;
+    const uint32_t begin = (uint32_t)begin64, end = (uint32_t)min((uint64_t)b.n_reads, begin64 + per);
+    const gmem_u32* cg = (const gmem_u32*)(uintptr_t)b.cigar;
+    if (tid < 6) s_cnt[tid / 2][tid % 2] = 0;
+    for (uint32_t t = tid; t < DP_LANES * 5; t += DP_THREADS) s_sum[t / 5][t % 5] = 0;
+    block_sync();
+    bool over = false;
+    DpRead nx = dp_fetch(b, (uint64_t)begin + tid, end, n_lanes, n_refs);
+    uint32_t par = 0, cnt = 0;
+    for (uint32_t base = begin; base < end; base += DP_STEP, par ^= 1u, cnt = cnt == 2u ? 0u : cnt + 1u) {
+        const DpRead me = nx;
+        if (end - base > DP_STEP) nx = dp_fetch(b, (uint64_t)base + DP_STEP + tid, end, n_lanes, n_refs); // (in flight while this step is inserted)
+        const bool ex = me.cls != DP_NONE, need = ex && me.cls < 2u, rev = me.info & 1u;
+        // the sums, by read group
+        {
+            uint64_t m = __ballot(ex);
+            while (m) {
+                const int leader = __ffsll((unsigned long long)m) - 1;
+                const uint32_t gl = __builtin_amdgcn_readlane(me.lane, leader);
+                const bool same = ex && me.lane == gl;
+                const uint64_t sm = __ballot(same);
+                const bool fl = (me.info >> 2) & 1u;
+                const uint32_t e0 = (uint32_t)__popcll((unsigned long long)__ballot(same && me.cls == 0u)), e1 = (uint32_t)__popcll((unsigned long long)__ballot(same && me.cls == 1u));
+                const uint32_t f0 = (uint32_t)__popcll((unsigned long long)__ballot(same && me.cls == 0u && fl)), f1 = (uint32_t)__popcll((unsigned long long)__ballot(same && me.cls == 1u && fl));
+                const uint32_t se = (uint32_t)__popcll((unsigned long long)__ballot(same && me.cls == 2u));
+                if ((int)ln == leader) {
+                    if (e0) atomicAdd(&s_sum[gl][0], (unsigned long long)e0);
+                    if (e1) atomicAdd(&s_sum[gl][1], (unsigned long long)e1);
+                    if (f0) atomicAdd(&s_sum[gl][2], (unsigned long long)f0);
+                    if (f1) atomicAdd(&s_sum[gl][3], (unsigned long long)f1);
+                    if (se) atomicAdd(&s_sum[gl][4], (unsigned long long)se);
+                }
+                m &= ~sm;
+            }
+        }
+        // the thread path: the first DP_T operations
+        uint64_t lead = 0, trail = 0, reflen = 0;
+        bool pre = true;
+        if (need) {
+            uint32_t w[DP_T];
+            w[0] = cg[me.coff];
+            if (me.nc > 1u) {
+#pragma unroll
+                for (uint32_t k = 1; k < DP_T; ++k) w[k] = k < me.nc ? cg[(uint64_t)me.coff + k] : 0u;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < DP_T; ++k) {
+                if (k < me.nc) {
+                    const uint32_t op = w[k] & 15u, n = w[k] >> 4;
+                    if (dp_clip(op)) { if (pre) lead += n; else trail += n; }
+                    else { pre = false; trail = 0; reflen += dp_glen(op, n); }
+                }
+            }
+        }
+        const bool lng = need && me.nc > DP_T && (rev || pre);
+        bool ins = need && !lng;
+        uint64_t k0 = 0, k1 = 0, n = 1;
+        if (ins) dp_keys(me, lead, trail, reflen, k0, k1);
+        // equal signatures of the wave: the first lane of each takes them all — where a lane's signature is its neighbour's (sorted
+        // input: duplicates arrive side by side; a wave of different signatures skips the loop, which costs it more than it saves)
+        const uint32_t digest = ins ? (uint32_t)k0 ^ (uint32_t)(k0 >> 32) ^ (uint32_t)k1 * 0x9E3779B1u ^ (uint32_t)(k1 >> 32) : ln;
+        const bool beside = ins && ln > 0 && (uint32_t)__shfl_up((int)digest, 1) == digest;
+        if ((mode & 4u) || (!(mode & 1u) && __ballot(beside))) {
+            uint64_t m = __ballot(ins);
+            while (m) {
+                const int leader = __ffsll((unsigned long long)m) - 1;
+                const uint32_t a0 = __builtin_amdgcn_readlane((uint32_t)k0, leader), a1 = __builtin_amdgcn_readlane((uint32_t)(k0 >> 32), leader);
+                const uint32_t b0 = __builtin_amdgcn_readlane((uint32_t)k1, leader), b1 = __builtin_amdgcn_readlane((uint32_t)(k1 >> 32), leader);
+                const bool same = ins && (uint32_t)k0 == a0 && (uint32_t)(k0 >> 32) == a1 && (uint32_t)k1 == b0 && (uint32_t)(k1 >> 32) == b1;
+                const uint64_t sm = __ballot(same);
+                if ((int)ln == leader) n = (uint64_t)__popcll((unsigned long long)sm);
+                else if (same) ins = false;
+                m &= ~sm;
+            }
+        }
+        uint32_t fresh = 0;
+        if (ins) fresh = dp_insert(T, k0, k1, n, mode, over);
+        {
+            const uint64_t fm = __ballot(fresh != 0u);
+            if (fm && ln == 0) atomicAdd(&s_cnt[cnt][1], (uint32_t)__popcll((unsigned long long)fm));
+        }
+        // the long reads are listed
+        const uint64_t bl = __ballot(lng);
+        if (bl) {
+            uint32_t at = 0;
+            if (ln == 0) at = atomicAdd(&s_cnt[cnt][0], (uint32_t)__popcll((unsigned long long)bl));
+            at = __builtin_amdgcn_readfirstlane(at);
+            if (lng) {
+                s_r[par][tid] = me.r;
+                s_long[par][at + (uint32_t)__popcll((unsigned long long)(bl & ((1ull << ln) - 1ull)))] = tid;
+            }
+        }
+        block_sync();
+        const uint32_t n_long = s_cnt[cnt][0];
+        if (tid == 0) { // the step before's counters: added to last in front of this barrier, added to again behind the next
+            const uint32_t pv = cnt ? cnt - 1u : 2u, v = s_cnt[pv][1];
+            if (v) gadd(T.n_sets, v);
+            s_cnt[pv][0] = 0; s_cnt[pv][1] = 0;
+        }
+        // the wave path: a wave per listed read
+        for (uint32_t e = wave; e < n_long; e += DP_WAVES) {
+            const DpRead rd = dp_read(b, __builtin_amdgcn_readfirstlane(s_r[par][s_long[par][e]]), n_lanes, n_refs);
+            const uint32_t nc = __builtin_amdgcn_readfirstlane(rd.nc), coff = __builtin_amdgcn_readfirstlane(rd.coff);
+            const bool rv = __builtin_amdgcn_readfirstlane(rd.info) & 1u;
+            uint64_t ld = 0, tr = 0, rl = 0;
+            bool pr = true;
+            uint32_t wd_n = ln < nc ? cg[(uint64_t)coff + ln] : 0u;
+            for (uint32_t p0 = 0; p0 < nc; p0 += WAVE) {
+                const uint32_t wd = wd_n;
+                const bool valid = p0 + ln < nc;
+                const uint32_t kn = p0 + WAVE + ln; // (nc <= 65 535: no wrap)
+                wd_n = kn < nc ? cg[(uint64_t)coff + kn] : 0u;
+                const uint32_t op = wd & 15u, len = wd >> 4;
+                const bool clip = valid && dp_clip(op), other = valid && !clip;
+                const uint64_t ob = __ballot(other);
+                const uint32_t cn = clip ? len : 0u;
+                rl += dp_sum64(other ? dp_glen(op, len) : 0u);
+                if (!ob) {
+                    const uint64_t tot = dp_sum64(cn);
+                    if (pr) ld += tot; else tr += tot;
+                } else {
+                    const uint32_t first = (uint32_t)__ffsll((unsigned long long)ob) - 1u, last = 63u - (uint32_t)__clzll((long long)ob);
+                    if (pr) ld += dp_sum64(ln < first ? cn : 0u);
+                    pr = false;
+                    tr = dp_sum64(ln > last ? cn : 0u);
+                }
+                if (!rv && !pr) break; // (a forward read needs its leading clips only)
+            }
+            uint32_t fr = 0;
+            if (ln == 0) {
+                uint64_t q0, q1;
+                dp_keys(rd, ld, tr, rl, q0, q1);
+                fr = dp_insert(T, q0, q1, 1, mode, over);
+                if (fr) atomicAdd(&s_cnt[cnt][1], 1u);
+            }
+        }
+        if (end - base <= DP_STEP) break; // (not left to the loop's test: base + DP_STEP may wrap)
+    }
+    if (over) atomicOr(err, BQC_DEVERR_DUP);
+    block_sync();
+    for (uint32_t t = tid; t < DP_LANES * 5; t += DP_THREADS) {
+        const unsigned long long v = s_sum[t / 5][t % 5];
+        if (v) gadd(sums + t, v); // (a read group with a sum is below n_lanes)
+    }
+    if (tid == 0) { // what is left of the counters, and the look at the whole
+        const uint64_t v = (uint64_t)s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1];
+        const dp_u64 before = __hip_atomic_fetch_add((gmem_u64*)(uintptr_t)T.n_sets, (dp_u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (before + v > T.capacity) atomicOr(err, BQC_DEVERR_DUP);
+    }
+}
+
+// ---- finalize ----------------------------------------------------------------------------------------------------------------------
+// out: [2 classes][BQC_DUP_BINS] sets by size, then the two largest sets; zero before the launch.
+__global__ __launch_bounds__(DP_FTHREADS) void k_dup_final(const DupSlot* __restrict__ slots, uint64_t C, uint64_t* __restrict__ out)
+{
+    __shared__ uint32_t s_h[2][BQC_DUP_BINS]; // (a workgroup takes fewer than 2^32 slots)
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t t = tid; t < 2 * BQC_DUP_BINS; t += DP_FTHREADS) s_h[t / BQC_DUP_BINS][t % BQC_DUP_BINS] = 0;
+    block_sync();
+    uint64_t big[2] = {0, 0};
+    const uint64_t step = (uint64_t)gridDim.x * DP_FTHREADS;
+    for (uint64_t x = (uint64_t)blockIdx.x * DP_FTHREADS + tid; x < C; x += step) {
+        const uint64_t k0 = slots[x].k0;
+        if (k0 == BQC_DUP_EMPTY) continue;
+        const uint64_t n = slots[x].count;
+        if (!n) continue; // (never: the add follows the claim of k1; a bin below the first does not exist)
+        const uint32_t cls = (uint32_t)(k0 >> 46) & 1u;
+        atomicAdd(&s_h[cls][(n < BQC_DUP_BINS ? (uint32_t)n : (uint32_t)BQC_DUP_BINS) - 1u], 1u);
+        big[cls] = n > big[cls] ? n : big[cls];
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < 2; ++c) {
+        uint64_t v = big[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t t = (uint64_t)__shfl_xor((unsigned long long)v, o);
+            v = t > v ? t : v;
+        }
+        if (lane_id() == 0 && v) __hip_atomic_fetch_max((gmem_u64*)(uintptr_t)(out + 2 * BQC_DUP_BINS + c), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    block_sync();
+    for (uint32_t t = tid; t < 2 * BQC_DUP_BINS; t += DP_FTHREADS) {
+        const uint32_t v = s_h[t / BQC_DUP_BINS][t % BQC_DUP_BINS];
+        if (v) gadd(out + t, v);
+    }
+}
+
+// the slots of a table for `capacity` signatures: the smallest power of two >= 2 capacity (capacity <= 2^31)
+extern "C" uint64_t bqc_dup_slots(uint64_t capacity)
+{
+    uint64_t C = 32;
+    while (C < 2 * capacity) C <<= 1;
+    return C;
+}
+extern "C" uint64_t bqc_dup_out_words(void) { return 2 * BQC_DUP_BINS + 2; }
+
+// The table, the counter of sets behind it and the sums: empty.
+extern "C" void bqc_launch_dup_clear(const DupTable& T, uint64_t* sums, uint32_t n_lanes, uint32_t n_cu, hipStream_t s)
+{
+    const uint64_t C = T.mask + 1u;
+    const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_cu * 8, (3 * C + 1023) / 1024));
+    hipLaunchKernelGGL(k_dup_clear, dim3(g), dim3(1024), 0, s, T.slots, C);
+    (void)hipMemsetAsync(T.n_sets, 0, 8, s);
+    (void)hipMemsetAsync(sums, 0, (uint64_t)n_lanes * 5 * 8, s);
+}
+
+// workgroups: about one per CU, a small batch gets fewer; each takes `per` consecutive reads of the processing order.
+// Measuring switches: BQC_DUP_COMBINE=0 leaves equal signatures of a wave uncombined, =2 combines them in every wave;
+// BQC_DUP_HASH=1 keeps u5's low bits in the slot instead of mixing the whole signature.
+extern "C" void bqc_launch_dup(const DevBatch& b, const DupTable& T, uint64_t* sums, uint32_t* err, uint32_t n_lanes, uint32_t n_refs, uint32_t n_cu, hipStream_t s)
+{
+    if (b.n_reads == 0) return;
+    static const uint32_t mode = [] {
+        const char *c = getenv("BQC_DUP_COMBINE"), *h = getenv("BQC_DUP_HASH");
+        return (c && c[0] == '0' && !c[1] ? 1u : 0u) | (c && c[0] == '2' && !c[1] ? 4u : 0u) | (h && h[0] == '1' && !h[1] ? 2u : 0u);
+    }();
+    const uint32_t g = std::max(1u, std::min(n_cu, (uint32_t)(((uint64_t)b.n_reads + 255) / 256)));
+    const uint32_t per = (uint32_t)(((uint64_t)b.n_reads + g - 1) / g);
+    hipLaunchKernelGGL(k_dup, dim3(g), dim3(DP_THREADS), 0, s, b, T, sums, err, n_lanes, n_refs, per, mode);
+}
+
+// The finalize pass: the table is read only; out holds bqc_dup_out_words words.
+extern "C" void bqc_launch_dup_final(const DupTable& T, uint64_t* out, uint32_t n_cu, hipStream_t s)
+{
+    const uint64_t C = T.mask + 1u;
+    (void)hipMemsetAsync(out, 0, bqc_dup_out_words() * 8, s);
+    const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_cu * 8, (C + DP_FTHREADS - 1) / DP_FTHREADS));
+    hipLaunchKernelGGL(k_dup_final, dim3(g), dim3(DP_FTHREADS), 0, s, T.slots, C, out);
+}

@@ -800,6 +800,9 @@ struct ProgramOptions {
     std::string regions; // (empty: off)
     uint32_t regions_min_mapq = 20, regions_depth_cap = 1000;
     std::vector<uint64_t> regions_thresholds{1, 10, 20, 30, 50, 100};
+    // --duplicate-sets / --duplicate-sets-capacity N: duplicate sets by alignment signature into <output>.dup
+    bool duplicate_sets = false;
+    uint64_t duplicate_sets_capacity = 1ull << 26; // signatures the table takes (3 GiB of slots)
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -860,6 +863,12 @@ void usage(FILE* f)
             "    --regions-thresholds LIST\n          The same with the depths of LIST: up to 8 numbers of 1 to 4294967295, increasing, separated by\n"
             "          commas.  Needs --regions.\n"
             "    --regions-depth-cap INT\n          The histogram's last bin: depth INT and more (1 to 16383, default 1000).  Needs --regions.\n"
+            "    --duplicate-sets\n          Duplicate sets: reads of equal alignment signature (class, strands, contig, unclipped 5' position and\n"
+            "          template length) are one set.  Per read group the examined and the flagged (0x400) reads, over all read\n"
+            "          groups the sets, the largest set, the sets by size and the estimated library size, into OUT.dup (the\n"
+            "          duplication rate and observed against flagged duplicates are folds of it).  Not with --gpus.\n"
+            "    --duplicate-sets-capacity INT\n          The different signatures the table takes (16 to 2147483648, default 67108864: 3 GiB on the card).\n"
+            "          Needs --duplicate-sets.\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -925,11 +934,17 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
     bool want_gcb = false; // --gc-bias: the module with windows of 100 bases unless --gc-bias-window says otherwise
     std::string want_sac_value; // a threshold option of --site-alleles was given: it needs the sites
     std::string want_rcv_value; // a parameter option of --regions was given: it needs the regions
+    std::string want_dup_value; // --duplicate-sets-capacity was given: it needs --duplicate-sets
     // (--gpus N is the front end's and never reaches this parser from it; given here, it is an illegal option — said in the option's
     // own terms where the GC bias is asked for as well, which no worker of --gpus could compute)
     auto gcb_somewhere = [&]() {
         for (int k = 1; k < argc; ++k)
             if (strcmp(argv[k], "--gc-bias") == 0 || strncmp(argv[k], "--gc-bias-window", 16) == 0) return true;
+        return false;
+    };
+    auto dup_somewhere = [&]() { // (the same for the duplicate sets: a set may have members in two workers' shards)
+        for (int k = 1; k < argc; ++k)
+            if (strcmp(argv[k], "--duplicate-sets") == 0 || strncmp(argv[k], "--duplicate-sets-capacity", 25) == 0) return true;
         return false;
     };
     std::vector<std::string> pos;
@@ -1091,6 +1106,18 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             o.regions_thresholds = t;
             want_rcv_value = key;
         }
+        else if (key == "--duplicate-sets") { o.duplicate_sets = true; }
+        else if (key == "--duplicate-sets-capacity") {
+            if (!need(i, key, v, inl)) return 1;
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' || v.size() > 10 ? 0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x < 16 || x > 1ull << 31) {
+                err = "bamqualcheck: the given value '" + v + "' is not a number of signatures (--duplicate-sets-capacity wants 16 to 2147483648)";
+                return 1;
+            }
+            o.duplicate_sets_capacity = x;
+            want_dup_value = key;
+        }
         else if (key == "--gc-bias-window") {
             if (!need(i, key, v, inl)) return 1;
             char* end = nullptr;
@@ -1098,6 +1125,7 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             if (!end || *end || x < 20 || x > 1000) { err = "bamqualcheck: the given value '" + v + "' is not a window length (--gc-bias-window wants 20 to 1000)"; return 1; }
             o.gc_bias = (uint32_t)x;
         }
+        else if (key == "--gpus" && dup_somewhere()) { err = "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)"; return 1; }
         else if (key == "--gpus" && gcb_somewhere()) { err = "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)"; return 1; }
         else if (key == "--manifest") { if (!need(i, key, v, inl)) return 1; o.manifest = v; have_m = true; }
         else if (a[0] == '-') { err = "bamqualcheck: illegal option -- " + a.substr(a.rfind("--", 0) == 0 ? 2 : 1); return 1; }
@@ -1107,6 +1135,7 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
     if (want_gcb && !o.gc_bias) o.gc_bias = 100;
     if (!want_sac_value.empty() && o.site_alleles.empty()) { err = "bamqualcheck: option " + want_sac_value + " needs --site-alleles FILE (the sites it applies to)"; return 1; }
     if (!want_rcv_value.empty() && o.regions.empty()) { err = "bamqualcheck: option " + want_rcv_value + " needs --regions FILE (the regions it applies to)"; return 1; }
+    if (!want_dup_value.empty() && !o.duplicate_sets) { err = "bamqualcheck: option " + want_dup_value + " needs --duplicate-sets (the table it sizes)"; return 1; }
     if (!have_r) { err = "bamqualcheck: option requires an argument -- r (required option -r/--reference missing)"; return 1; }
     if (session_form) {
         if (have_o || have_m || !pos.empty()) { err = "bamqualcheck: a session takes the program's options without an input, -o and --manifest"; return 1; }
@@ -1226,6 +1255,7 @@ struct CtxKey {
     std::vector<int32_t> region_rid, region_start, region_end; // --regions: the list as mapped to the job's header (empty: off)
     uint32_t regions_min_mapq = 0, regions_depth_cap = 0;
     std::vector<uint64_t> regions_thresholds;
+    uint64_t duplicate_sets = 0; // --duplicate-sets: the capacity (0: off)
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
     double e = 0;
@@ -1234,7 +1264,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && region_rid == o.region_rid && region_start == o.region_start && region_end == o.region_end && regions_min_mapq == o.regions_min_mapq && regions_depth_cap == o.regions_depth_cap && regions_thresholds == o.regions_thresholds && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && region_rid == o.region_rid && region_start == o.region_start && region_end == o.region_end && regions_min_mapq == o.regions_min_mapq && regions_depth_cap == o.regions_depth_cap && regions_thresholds == o.regions_thresholds && duplicate_sets == o.duplicate_sets && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1278,6 +1308,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (pr == 2) return 0;
     if (pr == 1) { fprintf(stderr, "%s\n", perr.c_str()); return 1; }
     // (a worker of --gpus N holds only the contigs its batches touch: none has the genome table; the front end says so before it forks)
+    if (shard && opt.duplicate_sets) { fprintf(stderr, "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)\n"); return 1; }
     if (shard && opt.gc_bias) { fprintf(stderr, "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)\n"); return 1; }
     using clk = std::chrono::steady_clock;
     const bool timing = getenv("BQC_TIMING") && getenv("BQC_TIMING")[0] == '1'; // BQC_TIMING=1: where the wall time of a run goes (stderr)
@@ -1525,6 +1556,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         ctx_key.substitutions = opt.substitutions; ctx_key.subst_min_qual = opt.subst_min_qual; ctx_key.subst_min_mapq = opt.subst_min_mapq;
         if (!site_rid.empty()) { ctx_key.site_rid = site_rid; ctx_key.site_pos = site_pos; ctx_key.site_min_qual = opt.site_min_qual; ctx_key.site_min_mapq = opt.site_min_mapq; }
         if (!region_rid.empty()) { ctx_key.region_rid = region_rid; ctx_key.region_start = region_start; ctx_key.region_end = region_end; ctx_key.regions_min_mapq = opt.regions_min_mapq; ctx_key.regions_depth_cap = opt.regions_depth_cap; ctx_key.regions_thresholds = opt.regions_thresholds; }
+        if (opt.duplicate_sets) ctx_key.duplicate_sets = opt.duplicate_sets_capacity;
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1575,6 +1607,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         if (!rc && !region_rid.empty()) {
             rc = bqc_enable_region_coverage(ctx, (uint32_t)region_rid.size(), region_rid.data(), region_start.data(), region_end.data(), opt.regions_min_mapq,
                                             (uint32_t)opt.regions_thresholds.size(), opt.regions_thresholds.data(), opt.regions_depth_cap);
+            if (rc) create_err = bqc_last_error(ctx);
+        }
+        if (!rc && opt.duplicate_sets) {
+            rc = bqc_enable_duplicate_sets(ctx, opt.duplicate_sets_capacity);
             if (rc) create_err = bqc_last_error(ctx);
         }
         if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
@@ -1903,10 +1939,12 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const int sac_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !site_rid.empty() ? bqc_write_site_alleles(ctx, &hi, sac_names.data(), n_refs, sac_path.c_str()) : 0;
     const std::string rcv_path = opt.outputFile + ".rcv"; // the table of --regions, behind the .sac
     const int rcv_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !region_rid.empty() ? bqc_write_region_coverage(ctx, &hi, sac_names.data(), n_refs, rcv_path.c_str()) : 0;
+    const std::string dup_path = opt.outputFile + ".dup"; // the table of --duplicate-sets, behind the .rcv
+    const int dup_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && opt.duplicate_sets ? bqc_write_duplicate_sets(ctx, &hi, dup_path.c_str()) : 0;
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && !dup_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1928,6 +1966,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (sbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sbc_path.c_str()); return 1; }
     if (sac_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sac_path.c_str()); return 1; }
     if (rcv_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", rcv_path.c_str()); return 1; }
+    if (dup_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", dup_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

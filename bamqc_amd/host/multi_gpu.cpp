@@ -492,6 +492,11 @@ extern "C" int bqc_main_multi(int argc, const char** argv, int n_gpus)
                 fprintf(stderr, "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)\n");
                 return 1;
             }
+        for (int k = 1; k < argc; ++k) // (a set may have members in two workers' shards, and the tables cannot be merged)
+            if (strcmp(argv[k], "--duplicate-sets") == 0 || strncmp(argv[k], "--duplicate-sets-capacity", 25) == 0) {
+                fprintf(stderr, "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)\n");
+                return 1;
+            }
         if (!path[0]) { fprintf(stderr, "bamqualcheck: --gpus with --manifest is not supported: run one process per card (--device), each with a list of its own\n"); return 1; }
         bam = path;
         // (said once, here, before any worker exists: every worker's run_program would say it too)

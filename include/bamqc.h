@@ -695,6 +695,62 @@ typedef struct bqc_rcv_view {
 int bqc_region_coverage(bqc_ctx* ctx, uint32_t lane, bqc_rcv_view* out);   /* after bqc_finalize */
 int bqc_write_region_coverage(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path);
 
+/* ---- duplicate sets by alignment signature (bqc_enable_duplicate_sets; not in the reference) ---------------------------------------
+ * How much of the library is PCR duplicates and how large the library is (Picard MarkDuplicates / EstimateLibraryComplexity, FastQC's
+ * duplication levels), computed from the alignments themselves and not from flag 0x400, which only repeats what an upstream tool
+ * wrote (BQC_S_DUPLICATES).  Read names and the mate's position are not looked at.
+ * Examined reads.  flag & 0xB04 == 0 (mapped, primary, not supplementary, not QC-fail);  n_cigar > 0;  l_seq > 0;  0 <= rid < n_refs;
+ * lane < n_lanes.  Mapping quality, BQC_FLAG_NO_QUAL, the mate flags 0x40 / 0x80 and 0x400 are NOT conditions.  The genome is not read.
+ * Class.  pair: 0x1 set, 0x8 clear, tlen > 0 (the leftmost end; it stands for its fragment).  second end: 0x1 set, 0x8 clear,
+ * tlen < 0: counted in a scalar and otherwise left out (its fragment is its mate's).  single: every other examined read (unpaired,
+ * the mate unmapped, tlen == 0).
+ * Unclipped 5' position u5, 64-bit signed arithmetic over the CIGAR in stored order: lead = the sum of the lengths of the maximal
+ * prefix of operations with code 4 or 5 (S, H); trail = the same for the maximal suffix, 0 when the prefix took every operation;
+ * reflen = the sum over M, D, N, =, X (0, 2, 3, 7, 8).  Forward read (0x10 clear): u5 = pos - lead.  Reverse read: u5 = pos + reflen -
+ * 1 + trail.  |u5| < 2^45 follows (at most 65 535 operations of fewer than 2^28 bases).
+ * Signature.  (class, strand = flag >> 4 & 1, mate strand = flag >> 5 & 1 for class pair else 0, rid, u5, tlen for class pair else 0).
+ * The read group is NOT part of it: a duplicate is a property of the library, and a library is spread over lanes.  Two reads are in one
+ * SET iff their signatures are equal; this is exact.  As two words: k0 = (u5 + 2^45) | class << 46 | strand << 47 | mate strand << 48
+ * (class: 0 single, 1 pair), k1 = rid | (uint32) tlen << 32.
+ * Products.  Per read group, pure sums: E_single, E_pair (examined reads of the class), F_single, F_pair (those of them with 0x400
+ * set), second_end.  Per context, over all read groups, for class c: U_c = the number of sets, largest_c = the reads of the largest
+ * set, H_c[i], i = 1 ... 256 = the sets of i reads (bin 256: 256 and more).  sum over lanes of E_c = sum over sets of their reads.  The
+ * observed duplicates of a class are sum E_c - U_c, to be set against sum F_c.
+ * Estimated library size, from class pair, Picard's estimateLibrarySize in double precision: n = sum E_pair, c = U_pair; c = 0 or
+ * c >= n: 0; otherwise f(x) = c / x - 1 + exp(-n / x);  m = 1, M = 100, while f(M c) > 0: M *= 10;  40 times: r = (m + M) / 2,
+ * u = f(r c), u == 0: stop, u > 0: m = r, else M = r;  the estimate is (uint64) (c (m + M) / 2).
+ * State.  A hash table in device memory, 24 bytes a slot, C = the smallest power of two >= 2 capacity (and >= 32) slots, and the
+ * per-lane sums.  NONE of it is part of the flat state vector (as the GC bias's genome table): bqc_state_words and every offset are
+ * the same with the module on, export and import carry none of it, shards cannot be merged (a set may have members in two shards:
+ * --gpus N is refused by the program).  bqc_reset empties the table and the sums and keeps the allocation.
+ * Overflow.  When the reads hold more than `capacity` different signatures (both classes together) the stream fails with
+ * BQC_ERR_RANGE where other errors found on the card surface (a later submit, sync, flush or finalize); the message names the
+ * capacity and --duplicate-sets-capacity.
+ * bqc_enable_duplicate_sets switches the module on, after creation, in any order with the other enable calls (the ABI version stays
+ * 2).  BQC_ERR_ARG, the message names the value: capacity outside 16 ... 2^31.  BQC_ERR_STATE: a second call; a call after the
+ * context has taken a batch, has exported or imported state, or has been finalised.  Without the call: no allocation, no launch.
+ * With it: every other output is the same bytes as without it.
+ * bqc_duplicate_sets: valid after bqc_finalize (which leaves the table as it is: it may be called again); the view is owned by the
+ * context until the next finalize / destroy.  BQC_ERR_STATE: the module is off, or nothing has been finalised.
+ * bqc_write_duplicate_sets: the text, lanes in the order of `hdr`, key-then-values lines:
+ *   sample_id <id> / duplicate_sets_capacity <capacity> /
+ *   lane <name> / duplicate_reads_examined_single <E> / duplicate_reads_examined_pair <E> / duplicate_reads_flagged_single <F> /
+ *   duplicate_reads_flagged_pair <F> / duplicate_reads_second_end <n>                                   (these six per read group)
+ *   all_lanes / duplicate_sets_single <U> / duplicate_sets_pair <U> / duplicate_set_largest_single <n> / duplicate_set_largest_pair <n> /
+ *   duplicate_set_size_histogram_single v1 ... v256 / duplicate_set_size_histogram_pair v1 ... v256 /
+ *   duplicate_estimated_library_size <L> */
+int bqc_enable_duplicate_sets(bqc_ctx* ctx, uint64_t capacity);
+typedef struct bqc_dup_view {
+    uint64_t capacity;
+    uint32_t n_lanes, pad;
+    uint64_t sets[2], largest[2];   /* [class: 0 single, 1 pair] */
+    const uint64_t* hist[2];        /* [256]: sets of 1 ... 255 reads, of 256 and more */
+    uint64_t estimated_library_size;
+    const uint64_t* lanes;          /* [n_lanes][5]: E_single, E_pair, F_single, F_pair, second_end */
+} bqc_dup_view;
+int bqc_duplicate_sets(bqc_ctx* ctx, bqc_dup_view* out);   /* after bqc_finalize */
+int bqc_write_duplicate_sets(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
