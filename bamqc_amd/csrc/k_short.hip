@@ -362,40 +362,71 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
         const uint32_t tn = min(tile_cap, p_n - tb); // entries of this wave's tile (a multiple of rpw)
         // ---- phase A: lane per read — per-read statistics, and the read's record for phase B into LDS
         __builtin_amdgcn_s_setprio(3); // few instructions between long waits: let them issue ahead of the other waves' phase B
-        uint32_t r;
         bool stat; // this lane's entry is a read (per-read statistics below)
+        RsRead rs{0, 0, 0, 0, 0, -1, 0, BQC_NM_ABSENT, 0, 0, 0, b.cigar}; // ... and what read_stats counts from
         {
+            // Three round trips, every load of one requested before the first of its values is looked at: the entry; the read's
+            // columns; the contig's tables and the ends of the CIGAR.  (A segment entry takes one more, for its TripSeg.)  All tests
+            // stand behind the last request and work on values: a load inside a condition made of loaded values waits where it stands.
             const uint32_t t = ch.first + p_first + tb + ln;
-            r = ln < tn ? b.perm[t] : 0xFFFFFFFFu;
+            uint32_t r = ln < tn ? b.perm[t] : 0xFFFFFFFFu;
             const bool live = r != 0xFFFFFFFFu;                // not a padding entry
             const bool seg = live && (r & BQC_ENTRY_SEG);      // triplet segment of a read (the read itself is another entry)
             stat = live && !seg;
             TripSeg sg{0, 0, 0, 0};
             if (seg) { sg = b.segs[r & ~BQC_ENTRY_SEG]; r = sg.r; }
+            // -- the read's columns.  Lanes past the tile's end and padding entries request nothing; for every other lane r (the entry's,
+            // or the segment's sg.r) is a read of the batch, and each column has n_reads elements.
+            uint32_t seq_off = 0, qual_off = 0, cigar_off = 0;
+            int32_t pos_col = 0;
+            if (live) {
+                rs.flag = b.flag[r]; rs.L = b.l_seq[r]; rs.rid = b.rid[r]; rs.ncig = b.n_cigar[r];
+                seq_off = b.seq_off[r]; qual_off = b.qual_off[r]; pos_col = b.pos[r]; cigar_off = b.cigar_off[r];
+            }
+            if (stat && (parts & 8u)) { rs.mapq = b.mapq[r]; rs.lane = b.lane[r]; rs.tlen = b.tlen[r]; rs.nm = b.nm[r]; } // read_stats' own four
+            // (the values pass through an empty asm: without it the compiler takes their first uses — an addition, a sign extension — into
+            // the block that requests them and waits there, in front of the requests that follow)
+            asm volatile("" : "+v"(rs.flag), "+v"(rs.L), "+v"(rs.rid), "+v"(rs.ncig), "+v"(seq_off), "+v"(qual_off), "+v"(pos_col), "+v"(cigar_off),
+                              "+v"(rs.mapq), "+v"(rs.lane), "+v"(rs.tlen), "+v"(rs.nm));
+            // -- the contig's tables and the ends of the CIGAR, under conditions made of the columns' values alone
+            const uint32_t* refn = nullptr;
+            uint64_t reflen_tab = 0;
+            // rid may be -1 or anything else: the three tables (n_refs elements each, never fewer than one) are read at rid only where
+            // 0 <= rid < n_refs, and not at all otherwise.  The table pointer that comes back may be null; it is not followed here.
+            if (live && rs.rid >= 0 && (uint32_t)rs.rid < refs.n_refs) {
+                refn = refs.refn[rs.rid]; reflen_tab = refs.len[rs.rid]; rs.main_chrom = refs.main_chrom[rs.rid];
+            }
+            // A read with n_cigar >= 1 owns the words cigar_off .. cigar_off + n_cigar - 1 of the CIGAR array.  A read without one
+            // requests nothing: its offset may be the array's end, and a batch may have no CIGAR words at all.  A segment needs neither word.
+            if (stat && rs.ncig > 0u) {
+                rs.cg = b.cigar + cigar_off;
+                rs.cg0 = rs.cg[0]; rs.cgl = rs.cg[rs.ncig - 1u];
+            }
+            asm volatile("" : "+v"(refn), "+v"(reflen_tab), "+v"(rs.main_chrom), "+v"(rs.cg0), "+v"(rs.cgl));
             uint4 R0 = make_uint4(0u, KS_BIAS, KS_BIAS, 8u * KS_NH - 1u);
             uint4 R1 = make_uint4(0u, 24u << 16, (uint32_t)(uintptr_t)state, (uint32_t)((uintptr_t)state >> 32));
             if (live) {
-                const uint32_t fl = b.flag[r];
+                const uint32_t fl = rs.flag;
                 R0.x = fl & 0xFFFFu;
                 if (!(fl & 0x900u) && (fl & 0xC0u)) { // reaches get_count / count8mers
-                    const uint32_t L = b.l_seq[r];
+                    const uint32_t L = rs.L;
                     const bool rc = fl & 0x10u, noq = fl & BQC_FLAG_NO_QUAL;
                     const int32_t o0 = rc ? (int32_t)L - KS_NB : 0;
                     R0.x |= (seg ? KM_SEG : KM_PRIM) | (L << 20);
-                    R0.y = b.seq_off[r] + (uint32_t)((o0 - 1) >> 1) + KS_BIAS; // the window is loaded from one byte (odd o0: one nibble) earlier
-                    R0.z = (noq ? 0u : b.qual_off[r]) + (uint32_t)o0 + KS_BIAS;
+                    R0.y = seq_off + (uint32_t)((o0 - 1) >> 1) + KS_BIAS; // the window is loaded from one byte (odd o0: one nibble) earlier
+                    R0.z = (noq ? 0u : qual_off) + (uint32_t)o0 + KS_BIAS;
                     R1.y = ((o0 & 1) ? 28u : 24u) << 16;
-                    const int32_t rid = b.rid[r];
-                    if ((fl & BQC_FLAG_TRIPLET) && b.n_cigar[r] >= 1 && L >= 3 && !noq && rid >= 0 && (uint32_t)rid < refs.n_refs &&
-                        refs.refn[rid] != nullptr) {
+                    const int32_t rid = rs.rid;
+                    if ((fl & BQC_FLAG_TRIPLET) && rs.ncig >= 1u && L >= 3 && !noq && rid >= 0 && (uint32_t)rid < refs.n_refs &&
+                        refn != nullptr) {
                         // read positions ia <= i < ib with chromPos = pos + i: inside the read (1 .. L-2), inside the first CIGAR
                         // operation (assumed match-like, TripletCounting.hpp:203) or the segment, context pos+i-1 .. pos+i+1 inside the contig
-                        const int64_t pos = seg ? (int64_t)sg.posv : (int64_t)b.pos[r];
-                        const int64_t reflen = (int64_t)refs.len[rid];
+                        const int64_t pos = seg ? (int64_t)sg.posv : (int64_t)pos_col;
+                        const int64_t reflen = (int64_t)reflen_tab;
                         int64_t ia = 1, ib = (int64_t)L - 1;
                         if (seg) { ia = sg.range & 0xFFu; ib = (sg.range >> 8) & 0xFFu; }
                         else {
-                            const uint32_t n0 = b.cigar[b.cigar_off[r]] >> 4;
+                            const uint32_t n0 = rs.cg0 >> 4;
                             if (n0 != 0u && (int64_t)n0 < ib) ib = n0;
                         }
                         if (1 - pos > ia) ia = 1 - pos;
@@ -407,7 +438,7 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
                             R0.w = (uint32_t)((int32_t)pos + o0 + 8 * KS_NH - 1);
                             R1.x = (uint32_t)(nd8 + KS_NH - 1);
                             R1.y |= ja | (jb << 8);
-                            const uint64_t rn = (uint64_t)(uintptr_t)refs.refn[rid];
+                            const uint64_t rn = (uint64_t)(uintptr_t)refn;
                             R1.z = (uint32_t)rn; R1.w = (uint32_t)(rn >> 32);
                         }
                     }
@@ -423,8 +454,9 @@ __global__ __launch_bounds__(KS_THREADS) void k_short(DevBatch b, StateLayout sl
         // ---- phase B: groups of rpw reads; the next group's data is loaded while this one is processed
         const uint32_t n_groups = tn / rpw;
         const Pre first = ks_prefetch(lane_used ? WM + slot * KS_MW : DUMMY, w, g_seq, g_qual);
-        // per-read statistics of the tile's reads, while the first group's data is on its way
-        if ((parts & 8u) && __ballot(stat)) read_stats(b, sl, state, refs, err, lds + KS_RS, stat ? r : 0u, stat, stat);
+        // per-read statistics of the tile's reads, while the first group's data is on its way: counted from the values phase A loaded
+        // (only the inner CIGAR words of a read with three or more operations are loaded there)
+        if ((parts & 8u) && __ballot(stat)) read_stats_counted(sl, state, err, lds + KS_RS, rs, stat, stat);
         __builtin_amdgcn_s_setprio(0);
         // A tile holds reads or triplet segments, never both (padding entries only fill the last group of the chunk's segment
         // part, behind at least one segment), so the group loop is compiled once per kind: read tiles always update the per-cycle

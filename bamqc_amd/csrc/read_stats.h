@@ -36,15 +36,31 @@ __device__ __forceinline__ void rs_hist(bool pred, bool use_lds, uint32_t bin, u
     wave_inc(pred && !in_lds, g_base + bin);
 }
 
-__device__ __forceinline__ void read_stats(const DevBatch& b, const StateLayout& sl, uint64_t* __restrict__ state, const DevRefs& refs,
-                                           uint32_t* __restrict__ err, uint32_t* lds, uint32_t r, bool live, bool use_lds)
+// length of CIGAR word c if its operation is `op`, else 0
+__device__ __forceinline__ uint32_t rs_oplen(uint32_t c, uint32_t op) { return (c & 15u) == op ? c >> 4 : 0u; }
+
+// A read's columns, its contig's main_chrom byte and the ends of its CIGAR as values: what read_stats counts from.  A caller that loads
+// the read's columns anyway (k_short, phase A) fills one beside its own loads and calls read_stats_counted; read_stats below loads it.
+struct RsRead {
+    uint32_t flag, L, mapq, ncig, lane;
+    int32_t rid, tlen, nm;
+    uint32_t main_chrom;  // refs.main_chrom[rid]; 0 where rid is no contig
+    uint32_t cg0, cgl;    // CIGAR words 0 and ncig - 1 (the same word at ncig == 1); unused at ncig == 0
+    const uint32_t* cg;   // b.cigar + b.cigar_off[r]: words 1 .. ncig - 2 are loaded here, for reads of three or more operations only
+};
+
+// the read's first-level columns: every index is r < n_reads; call for a live read only
+__device__ __forceinline__ void rs_load_columns(RsRead& v, const DevBatch& b, uint32_t r)
 {
-    uint32_t flag = 0, L = 0, mapq = 0, ncig = 0, lane = 0;
-    int32_t rid = -1, tlen = 0, nm = BQC_NM_ABSENT;
-    if (live) {
-        flag = b.flag[r]; L = b.l_seq[r]; mapq = b.mapq[r]; ncig = b.n_cigar[r]; lane = b.lane[r];
-        rid = b.rid[r]; tlen = b.tlen[r]; nm = b.nm[r];
-    }
+    v.flag = b.flag[r]; v.L = b.l_seq[r]; v.mapq = b.mapq[r]; v.ncig = b.n_cigar[r]; v.lane = b.lane[r];
+    v.rid = b.rid[r]; v.tlen = b.tlen[r]; v.nm = b.nm[r];
+}
+
+__device__ __forceinline__ void read_stats_counted(const StateLayout& sl, uint64_t* __restrict__ state, uint32_t* __restrict__ err, uint32_t* lds,
+                                                   const RsRead& v, bool live, bool use_lds)
+{
+    const uint32_t flag = v.flag, L = v.L, mapq = v.mapq, ncig = v.ncig, lane = v.lane;
+    const int32_t tlen = v.tlen, nm = v.nm;
     uint64_t* S = state + sl.lane_base(lane) + sl.o_scalars;
     uint32_t* LS = lds + RS_SCAL;
     const bool gl = live && !use_lds; // global path (other lane inside a mixed wave)
@@ -61,8 +77,7 @@ __device__ __forceinline__ void read_stats(const DevBatch& b, const StateLayout&
     const bool rc = flag & 0x10, nrc = flag & 0x20;
     const bool mated = first || last;
     const uint32_t mate = first ? 0u : 1u;
-    const int32_t nrefs = (int32_t)refs.n_refs;
-    const bool in_main = mated && rid >= 0 && rid < nrefs && refs.main_chrom[rid];
+    const bool in_main = mated && v.main_chrom;
     const bool fasm = first && in_main && (!unm || !nunm) && !(flag & 0x400);
     const bool autop = first && in_main && proper && !(flag & 0x400);
 #define RS_SC(pred, idx)                       \
@@ -95,7 +110,12 @@ __device__ __forceinline__ void read_stats(const DevBatch& b, const StateLayout&
         }
         if (prim && gl) gadd(S + BQC_S_TOTALBPS, L);
     }
-    uint64_t* M = state + sl.mate_base(lane, mate);
+    // (sl.mate_base(lane, mate) with a select of the two offsets as scalar values: o_mate[] indexed by a lane's own mate is a vector load
+    // from the kernel's arguments, and k_short's wait for it also waits for the first group's data, requested just before.  Through an
+    // empty asm, or the compiler turns the select of two loaded values back into one load at a selected address.)
+    uint32_t o_mate0 = sl.o_mate[0], o_mate1 = sl.o_mate[1];
+    asm volatile("" : "+s"(o_mate0), "+s"(o_mate1));
+    uint64_t* M = state + sl.lane_base(lane) + (first ? o_mate0 : o_mate1);
     uint32_t* LM = lds + RS_MATE + mate * RS_M_WORDS;
     // read_length + qualcount_readnr (QualityCheck.hpp:130,168-176)
     rs_count(first && use_lds, lds + RS_MATE + RS_M_READNR);              // rs_count: one address per call
@@ -108,10 +128,9 @@ __device__ __forceinline__ void read_stats(const DevBatch& b, const StateLayout&
     bool sc5 = false, sc3 = false;
     uint32_t n5 = 0, n3 = 0;
     if (mapped_main) { // cigar_count (QualityCheck.hpp:222-271) on the seq-oriented (reversed for RC) CIGAR
-        const uint32_t* cg = b.cigar + b.cigar_off[r];
         if (ncig > 0) {
-            const uint32_t c_first = rc ? cg[ncig - 1] : cg[0];
-            const uint32_t c_last = rc ? cg[0] : cg[ncig - 1];
+            const uint32_t c_first = rc ? v.cgl : v.cg0;
+            const uint32_t c_last = rc ? v.cg0 : v.cgl;
             if ((c_first & 15u) == 4u) { // 'S': sc5[j]++ for j < n  <=>  histogram of n, suffix-summed at finalize
                 sc5 = true;
                 n5 = min(c_first >> 4, L);
@@ -119,10 +138,11 @@ __device__ __forceinline__ void read_stats(const DevBatch& b, const StateLayout&
                 n3 = c_last >> 4;
                 sc3 = n3 <= L && n3 > 0;
             }
-            for (uint32_t k = 0; k < ncig; ++k) {
-                const uint32_t c = cg[k], op = c & 15u;
-                if (op == 2u) del += c >> 4;       // 'D'
-                else if (op == 1u) ins += c >> 4;  // 'I'
+            del = rs_oplen(v.cg0, 2u); ins = rs_oplen(v.cg0, 1u);                    // 'D' / 'I'
+            if (ncig > 1) { del += rs_oplen(v.cgl, 2u); ins += rs_oplen(v.cgl, 1u); }
+            for (uint32_t k = 1; k + 1 < ncig; ++k) { // the inner words: the only loads of this function
+                const uint32_t c = v.cg[k];
+                del += rs_oplen(c, 2u); ins += rs_oplen(c, 1u);
             }
         }
         if (del >= sl.hcap || ins >= sl.hcap) atomicOr(err, BQC_DEVERR_RANGE);
@@ -152,6 +172,22 @@ __device__ __forceinline__ void read_stats(const DevBatch& b, const StateLayout&
         if (use_lds && idx < RS_INS) atomicAdd(lds + RS_INSERT + idx, 1u);
         else gadd(M + sl.m_insert + idx, 1);
     }
+}
+
+// The loading form (k_reads): the read's columns, then its contig's byte and the ends of its CIGAR, then the counting above.
+__device__ __forceinline__ void read_stats(const DevBatch& b, const StateLayout& sl, uint64_t* __restrict__ state, const DevRefs& refs,
+                                           uint32_t* __restrict__ err, uint32_t* lds, uint32_t r, bool live, bool use_lds)
+{
+    RsRead v{0, 0, 0, 0, 0, -1, 0, BQC_NM_ABSENT, 0, 0, 0, b.cigar};
+    if (live) {
+        rs_load_columns(v, b, r);
+        if (v.rid >= 0 && (uint32_t)v.rid < refs.n_refs) v.main_chrom = refs.main_chrom[v.rid]; // rid is a contig: inside the table
+        if (v.ncig > 0) { // the read owns words cigar_off[r] .. + ncig - 1 (at ncig == 0 the offset may be the array's end)
+            v.cg = b.cigar + b.cigar_off[r];
+            v.cg0 = v.cg[0]; v.cgl = v.cg[v.ncig - 1];
+        }
+    }
+    read_stats_counted(sl, state, err, lds, v, live, use_lds);
 }
 
 // flush the privatised counters of `lane` to the global state and zero them (call block-uniformly,
