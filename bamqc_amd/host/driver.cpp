@@ -1365,6 +1365,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const bool bam_on_card = rt.reader == RD_GPU_BAM;
     if (bam_on_card) { bqc_raw_vector_free_hook = pin_free_hook; bqc_raw_vector_pin_hook = pin_hook; } // (the reader page-locks the buffers the card copies into)
     RecordReader& rd = in.reader();
+    if (rd.header().lane_count > 256) { // the lane column is a byte and bqc_create takes 256 at the most: said here in the input's terms, before the output file is opened
+        fprintf(stderr, "ERROR: %s: the header has %u @RG lines; at most 256 read groups are supported\n", opt.bamFile.c_str(), rd.header().lane_count);
+        return shard_abort();
+    }
     if (!shard || shard->index == 0) {
         FILE* of = fopen(opt.outputFile.c_str(), "wb"); // opened (truncated) before the scan, :278-283
         if (!of) { fprintf(stderr, "ERROR: Could not open output file %s\n", opt.outputFile.c_str()); return shard_abort(); }

@@ -54,9 +54,10 @@ def contexts(refs, n_lanes, **opts):
     return out
 
 
-def run_stream(batches, refs, n_lanes, may_fail=False, **opts):
+def run_stream(batches, refs, n_lanes, may_fail=False, state_words=False, **opts):
     """every batch anchored on the card (checked read by read) and submitted anchored; a second context gets the same batches through
-    bqc_submit; both against each other and against the oracle"""
+    bqc_submit; both against each other and against the oracle (state_words: the two contexts' exported state vectors are compared
+    word by word as well, before they are finalised)"""
     lib = _lib.load()
     hip = Hip()
     n_refs = len(refs)
@@ -79,6 +80,9 @@ def run_stream(batches, refs, n_lanes, may_fail=False, **opts):
                 host.submit(cols)
             except BamQCError:
                 assert may_fail
+        if state_words:
+            v_dev, v_host = dev.state_export_host(), host.state_export_host()
+            assert np.array_equal(v_dev, v_host), np.flatnonzero(v_dev != v_host)[:10]
         res = [finalize(dev), finalize(host)]
         if isinstance(res[0], int) or isinstance(res[1], int):
             assert res[0] == res[1] and may_fail, res
