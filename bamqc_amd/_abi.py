@@ -155,6 +155,12 @@ class DupView(C.Structure):  # bqc_dup_view: by class (0 single, 1 pair) the set
                 ("hist", u64p * 2), ("estimated_library_size", C.c_uint64), ("lanes", u64p)]
 
 
+class WdpView(C.Structure):  # bqc_wdp_view: W, MQ, NW, n_refs, woff [n_refs + 1], ref_len [n_refs], E, E_low, X, three planes [NW], contigs [n_refs][3], hist [1001]
+    _fields_ = [("window", C.c_uint32), ("min_mapq", C.c_uint32), ("n_windows", C.c_uint32), ("n_refs", C.c_uint32), ("woff", u32p), ("ref_len", u32p),
+                ("reads_examined", C.c_uint64), ("reads_low_mapq", C.c_uint64), ("bases_outside", C.c_uint64), ("reads", u64p), ("bases", u64p),
+                ("bases_low", u64p), ("contigs", u64p), ("hist", u64p)]
+
+
 def make_modules(adapter_by_cycle=0, adapters=None, struct_size=None):
     """bqc_modules: adapter_by_cycle = the cycle capacity N (0: off), adapters = [(name, sequence), ...] or None for the built-in set."""
     m = Modules()

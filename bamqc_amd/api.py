@@ -40,7 +40,7 @@ class DeviceBatch:
 class Aggregator:
     def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, indel_by_cycle=None, substitutions=None, subst_min_qual=20, subst_min_mapq=30,
                  site_alleles=None, site_min_qual=20, site_min_mapq=20, regions=None, region_min_mapq=20, region_thresholds=(1, 10, 20, 30, 50, 100),
-                 region_depth_cap=1000, duplicate_sets=None, **options):
+                 region_depth_cap=1000, duplicate_sets=None, window_depth=None, window_min_mapq=20, **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
@@ -92,6 +92,22 @@ class Aggregator:
             except BamQCError:
                 self.close()
                 raise
+
+        if window_depth is not None:  # the same way: depth in windows of window_depth[0] bases over contigs of the lengths window_depth[1]
+            try:
+                self.enable_window_depth(window_depth[0], window_depth[1], window_min_mapq)
+            except BamQCError:
+                self.close()
+                raise
+
+    def enable_window_depth(self, window=1000, ref_len=None, min_mapq=20):
+        """ref_len: the lengths of the context's n_refs contigs (None: a null list, which the library refuses)."""
+        if ref_len is None:
+            self._chk(self.lib.bqc_enable_window_depth(self.h, window, None, min_mapq))
+            return
+        ln = np.ascontiguousarray(ref_len, np.int32)
+        assert ln.shape == (self.opt.n_refs,)
+        self._chk(self.lib.bqc_enable_window_depth(self.h, window, ln.ctypes.data_as(C.POINTER(C.c_int32)), min_mapq))
 
     def enable_duplicate_sets(self, capacity=1 << 26):
         self._chk(self.lib.bqc_enable_duplicate_sets(self.h, capacity))
@@ -375,6 +391,31 @@ class Aggregator:
             self.finalize_raw()
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_duplicate_sets(self.h, C.byref(hdr), path.encode()))
+
+    def window_depth(self, lane=0):
+        """The depth of a read group in fixed genome windows (option window_depth=(W, ref_len); valid after finalize): a dict of window,
+        min_mapq, n_windows, woff (n_refs + 1,), ref_len (n_refs,), reads_examined, reads_low_mapq, bases_outside, the planes reads, bases
+        and bases_low (NW,) uint64, contigs (n_refs, 3) — a contig's sums of the three planes — and hist (1001,), the main contigs' windows
+        by floor(bases / length) with the last bin open."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.WdpView()
+        self._chk(self.lib.bqc_window_depth(self.h, lane, C.byref(v)))
+        nw, nr = v.n_windows, v.n_refs
+        arr = lambda p, shape, dt: np.ctypeslib.as_array(p, shape=shape).copy() if shape[0] else np.zeros(shape, dt)
+        return {"window": int(v.window), "min_mapq": int(v.min_mapq), "n_windows": int(nw), "woff": arr(v.woff, (nr + 1,), np.uint32),
+                "ref_len": arr(v.ref_len, (nr,), np.uint32), "reads_examined": int(v.reads_examined), "reads_low_mapq": int(v.reads_low_mapq),
+                "bases_outside": int(v.bases_outside), "reads": arr(v.reads, (nw,), np.uint64), "bases": arr(v.bases, (nw,), np.uint64),
+                "bases_low": arr(v.bases_low, (nw,), np.uint64), "contigs": arr(v.contigs, (nr, 3), np.uint64),
+                "hist": np.ctypeslib.as_array(v.hist, shape=(1001,)).copy()}
+
+    def write_window_depth(self, path, ref_names, sample_id="", lane_names=("",), lane_index=None):
+        """The `.wdp` text; ref_names: the contigs' names by rid."""
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        names = (C.c_char_p * len(ref_names))(*[s.encode() for s in ref_names])
+        self._chk(self.lib.bqc_write_window_depth(self.h, C.byref(hdr), names, len(ref_names), path.encode()))
 
     def close(self):
         if self.h:

@@ -34,6 +34,7 @@ uint64_t bqc_ibc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_sbc_words(uint32_t n_lanes, uint32_t N);
 uint64_t bqc_sac_words(uint32_t n_lanes, uint32_t S);
 uint64_t bqc_rcv_words(uint32_t n_lanes, uint64_t B, uint32_t R);
+uint64_t bqc_wdp_words(uint32_t n_lanes, uint64_t NW);
 uint32_t bqc_rcv_tiles(uint64_t B, uint32_t R);
 uint64_t bqc_rcv_out_words(uint32_t n_lanes, uint32_t R, uint32_t n_thr, uint32_t D);
 void bqc_launch_rcv_final(const uint64_t* state, const RcvRegions& rg, const RcvFinal& fp, uint32_t n_lanes, uint64_t* tsum, uint64_t* out, hipStream_t s);
@@ -405,6 +406,8 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (c->d_sbc) (void)hipFree(c->d_sbc);
     if (c->d_sac) (void)hipFree(c->d_sac);
     if (c->d_sac_tab) (void)hipFree(c->d_sac_tab);
+    if (c->d_wdp) (void)hipFree(c->d_wdp);
+    if (c->d_wdp_tab) (void)hipFree(c->d_wdp_tab);
     if (c->d_rcv) (void)hipFree(c->d_rcv);
     if (c->d_rcv_tab) (void)hipFree(c->d_rcv_tab);
     if (c->d_rcv_out) (void)hipFree(c->d_rcv_out);
@@ -535,6 +538,8 @@ extern "C" int bqc_reset(bqc_ctx* c)
     c->sbc_final = false;
     if (c->d_sac) HIPCHK(c, hipMemsetAsync(c->d_sac, 0, c->sac_words * 8, c->stream)); // (the table; the sites stay)
     c->sac_final = false;
+    if (c->d_wdp) HIPCHK(c, hipMemsetAsync(c->d_wdp, 0, c->wdp_words * 8, c->stream)); // (the words; the contigs' tables stay)
+    c->wdp_final = false;
     if (c->d_rcv) HIPCHK(c, hipMemsetAsync(c->d_rcv, 0, c->rcv_words * 8, c->stream)); // (the words; the regions stay)
     c->rcv_final = false;
     if (c->d_dup) { // (the table and the sums go back to empty; the allocation stays)
@@ -588,8 +593,9 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-// the flat vector: [sl.words][sketch][region coverage][site alleles][substitutions][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
-static uint64_t rcv_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+// the flat vector: [sl.words][sketch][window depth][region coverage][site alleles][substitutions][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
+static uint64_t wdp_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
+static uint64_t rcv_offset(const bqc_ctx* c) { return wdp_offset(c) + c->wdp_words; }
 static uint64_t sac_offset(const bqc_ctx* c) { return rcv_offset(c) + c->rcv_words; }
 static uint64_t sbc_offset(const bqc_ctx* c) { return sac_offset(c) + c->sac_words; }
 static uint64_t ibc_offset(const bqc_ctx* c) { return sbc_offset(c) + c->sbc_words; }
@@ -608,6 +614,7 @@ extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
+    if (c->d_wdp) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + wdp_offset(c), c->d_wdp, c->wdp_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_rcv) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + rcv_offset(c), c->d_rcv, c->rcv_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sac) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sac_offset(c), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -628,6 +635,7 @@ extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
     bqc_state_ready(c);
     HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
+    if (c->d_wdp) HIPCHK(c, hipMemcpyAsync(c->d_wdp, (const uint64_t*)src + wdp_offset(c), c->wdp_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_rcv) HIPCHK(c, hipMemcpyAsync(c->d_rcv, (const uint64_t*)src + rcv_offset(c), c->rcv_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sac) HIPCHK(c, hipMemcpyAsync(c->d_sac, (const uint64_t*)src + sac_offset(c), c->sac_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (c->d_sbc) HIPCHK(c, hipMemcpyAsync(c->d_sbc, (const uint64_t*)src + sbc_offset(c), c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -658,6 +666,7 @@ extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
         HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_wdp) HIPCHK(c, hipMemcpy(dst + wdp_offset(c), c->d_wdp, c->wdp_words * 8, hipMemcpyDeviceToHost));
     if (c->d_rcv) HIPCHK(c, hipMemcpy(dst + rcv_offset(c), c->d_rcv, c->rcv_words * 8, hipMemcpyDeviceToHost));
     if (c->d_sac) HIPCHK(c, hipMemcpy(dst + sac_offset(c), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToHost));
     if (c->d_sbc) HIPCHK(c, hipMemcpy(dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToHost));
@@ -686,6 +695,7 @@ extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(tmp));
     }
+    if (c->d_wdp) HIPCHK(c, hipMemcpy(c->d_wdp, src + wdp_offset(c), c->wdp_words * 8, hipMemcpyHostToDevice));
     if (c->d_rcv) HIPCHK(c, hipMemcpy(c->d_rcv, src + rcv_offset(c), c->rcv_words * 8, hipMemcpyHostToDevice));
     if (c->d_sac) HIPCHK(c, hipMemcpy(c->d_sac, src + sac_offset(c), c->sac_words * 8, hipMemcpyHostToDevice));
     if (c->d_sbc) HIPCHK(c, hipMemcpy(c->d_sbc, src + sbc_offset(c), c->sbc_words * 8, hipMemcpyHostToDevice));
@@ -981,6 +991,60 @@ extern "C" int bqc_enable_region_coverage(bqc_ctx* c, uint32_t n_regions, const 
     return 0;
 }
 
+// The tables of k_wdp.hip (device_types.h: WdpTab) from the contigs' lengths: one allocation, [len n_refs][woff n_refs + 1], and the
+// reciprocal of the window size.
+extern "C" int bqc_enable_window_depth(bqc_ctx* c, uint32_t window, const int32_t* ref_len, uint32_t min_mapq)
+{
+    if (!c) return BQC_ERR_ARG;
+    const uint32_t n_refs = c->opt.n_refs, n_lanes = c->opt.n_lanes;
+    if (window < 100 || window > 1u << 24) return fail(c, BQC_ERR_ARG, "bqc_enable_window_depth: window size %u is outside 100 ... 16777216 (2^24)", window);
+    if (min_mapq > 255) return fail(c, BQC_ERR_ARG, "bqc_enable_window_depth: minimum mapping quality %u is outside 0 ... 255", min_mapq);
+    if (!ref_len && n_refs) return fail(c, BQC_ERR_ARG, "bqc_enable_window_depth: the list of %u contig lengths is a null pointer", n_refs);
+    std::vector<uint32_t> tab(2 * (size_t)n_refs + 1, 0); // the lengths, then woff
+    uint64_t NW = 0;
+    for (uint32_t r = 0; r < n_refs; ++r) {
+        if (ref_len[r] < 0) return fail(c, BQC_ERR_ARG, "bqc_enable_window_depth: contig %u: length %d is negative", r, ref_len[r]);
+        tab[r] = (uint32_t)ref_len[r];
+        tab[n_refs + r] = (uint32_t)std::min<uint64_t>(NW, 0xFFFFFFFFull);
+        NW += ((uint64_t)ref_len[r] + window - 1) / window;
+    }
+    if ((uint64_t)n_lanes * (4 + 3 * NW) > 1ull << 28)
+        return fail(c, BQC_ERR_ARG, "bqc_enable_window_depth: %llu windows of %u bases x 3 planes x %u read groups are more than 268435456 (2^28) words", (unsigned long long)NW, window, n_lanes);
+    tab[2 * (size_t)n_refs] = (uint32_t)NW;
+    if (c->d_wdp) return fail(c, BQC_ERR_STATE, "bqc_enable_window_depth: the module is on already (windows of %u bases)", c->wdp_tab.W);
+    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
+        return fail(c, BQC_ERR_STATE, "bqc_enable_window_depth: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t words = bqc_wdp_words(n_lanes, NW);
+    uint64_t* d = nullptr;
+    void* t = nullptr;
+    if (hipMalloc(&d, words * 8) != hipSuccess || hipMalloc(&t, tab.size() * 4) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess ||
+        hipMemcpy(t, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d);
+        (void)hipFree(t);
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_window_depth: the words (%llu bytes) and the contigs' tables (%llu bytes) could not be allocated", (unsigned long long)(words * 8), (unsigned long long)(tab.size() * 4));
+    }
+    uint32_t l = 0; // ceil(log2 W)
+    while ((1u << l) < window) ++l;
+    WdpTab& T = c->wdp_tab;
+    T.len = (const uint32_t*)t;
+    T.woff = T.len + n_refs;
+    T.n_refs = n_refs;
+    T.NW = (uint32_t)NW;
+    T.W = window;
+    T.shift = 31 + l;
+    T.mul = (uint32_t)(((1ull << T.shift) + window - 1) / window); // (2^31 for a power of two, otherwise between 2^31 and 2^32)
+    T.lane_words = (uint32_t)(4 + 3 * NW);
+    c->wdp_len.assign(tab.begin(), tab.begin() + n_refs);
+    c->wdp_woff.assign(tab.begin() + n_refs, tab.end());
+    c->wdp_mq = min_mapq;
+    c->wdp_words = words;
+    c->d_wdp_tab = t;
+    c->d_wdp = d;
+    return 0;
+}
+
 // The table of k_dup.hip: one allocation, [C slots][the counter of sets, 7 spare words][n_lanes][5 sums][k_dup_final's products].  The
 // clear is left on the compute stream, in front of the first batch.
 extern "C" int bqc_enable_duplicate_sets(bqc_ctx* c, uint64_t capacity)
@@ -1198,6 +1262,34 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
         c->dup_estimate = dup_library_size(pairs, c->dup_sets[1]);
         c->dup_final = true;
     }
+    if (c->d_wdp) { // the sums by contig and the histogram over the main contigs' windows: one pass over a copy of the words, no kernel
+        const uint32_t n_lanes = c->opt.n_lanes, n_refs = c->opt.n_refs, W = c->wdp_tab.W;
+        const uint64_t NW = c->wdp_tab.NW, LW = c->wdp_tab.lane_words;
+        c->wdp_final = false;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->h_wdp.resize(c->wdp_words);
+        HIPCHK(c, hipMemcpy(c->h_wdp.data(), c->d_wdp, c->wdp_words * 8, hipMemcpyDeviceToHost));
+        c->h_wdp_contigs.assign((size_t)n_lanes * n_refs * 3, 0);
+        c->h_wdp_hist.assign((size_t)n_lanes * BQC_WDP_HIST_BINS, 0);
+        for (uint32_t l = 0; l < n_lanes; ++l) {
+            const uint64_t* reads = c->h_wdp.data() + l * LW + 4;
+            const uint64_t *bases = reads + NW, *low = bases + NW;
+            uint64_t* hist = c->h_wdp_hist.data() + (size_t)l * BQC_WDP_HIST_BINS;
+            for (uint32_t r = 0; r < n_refs; ++r) {
+                uint64_t* sum = c->h_wdp_contigs.data() + ((size_t)l * n_refs + r) * 3;
+                const bool main = r < c->main_chrom.size() && c->main_chrom[r] == 1;
+                for (uint32_t w = c->wdp_woff[r]; w < c->wdp_woff[r + 1]; ++w) {
+                    sum[0] += reads[w]; sum[1] += bases[w]; sum[2] += low[w];
+                    if (main) {
+                        const uint64_t k = w - c->wdp_woff[r], from = k * W, len = std::min<uint64_t>(from + W, c->wdp_len[r]) - from; // (>= 1)
+                        const uint64_t depth = bases[w] / len;
+                        ++hist[depth < BQC_WDP_HIST_BINS - 1 ? depth : BQC_WDP_HIST_BINS - 1];
+                    }
+                }
+            }
+        }
+        c->wdp_final = true;
+    }
     if (c->d_sac) {
         c->h_sac.resize(c->sac_words);
         HIPCHK(c, hipMemcpy(c->h_sac.data(), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToHost));
@@ -1381,5 +1473,29 @@ extern "C" int bqc_duplicate_sets(bqc_ctx* c, bqc_dup_view* out)
     }
     out->estimated_library_size = c->dup_estimate;
     out->lanes = c->h_dup_sums.data();
+    return 0;
+}
+
+extern "C" int bqc_window_depth(bqc_ctx* c, uint32_t lane, bqc_wdp_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_wdp) return fail(c, BQC_ERR_STATE, "bqc_window_depth: bqc_enable_window_depth has not been called for the context");
+    if (!c->wdp_final) return fail(c, BQC_ERR_STATE, "bqc_window_depth: nothing has been finalised");
+    if (lane >= c->opt.n_lanes) return fail(c, BQC_ERR_ARG, "bqc_window_depth: lane %u out of range", lane);
+    const uint64_t* w = c->h_wdp.data() + (uint64_t)lane * c->wdp_tab.lane_words;
+    out->window = c->wdp_tab.W;
+    out->min_mapq = c->wdp_mq;
+    out->n_windows = c->wdp_tab.NW;
+    out->n_refs = c->opt.n_refs;
+    out->woff = c->wdp_woff.data();
+    out->ref_len = c->wdp_len.data();
+    out->reads_examined = w[0];
+    out->reads_low_mapq = w[1];
+    out->bases_outside = w[2];
+    out->reads = w + 4;
+    out->bases = out->reads + c->wdp_tab.NW;
+    out->bases_low = out->bases + c->wdp_tab.NW;
+    out->contigs = c->h_wdp_contigs.data() + (size_t)lane * c->opt.n_refs * 3;
+    out->hist = c->h_wdp_hist.data() + (size_t)lane * BQC_WDP_HIST_BINS;
     return 0;
 }

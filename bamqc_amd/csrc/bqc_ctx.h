@@ -258,6 +258,15 @@ struct bqc_ctx {
     std::vector<int32_t> sac_rid, sac_pos; // the list as given (bqc_site_alleles' view)
     std::vector<uint64_t> h_sac;       // bqc_finalize's copy
     bool sac_final = false;
+    // depth in fixed genome windows (k_wdp.hip; bqc_enable_window_depth(W, lengths, MQ) after creation — nothing below exists without it)
+    uint64_t* d_wdp = nullptr;         // [n_lanes][4 + 3 NW], the module's words of the state vector (behind the sketch's, in front of d_rcv's)
+    uint64_t wdp_words = 0;
+    void* d_wdp_tab = nullptr;         // the tables of `wdp_tab`, one allocation
+    WdpTab wdp_tab{};
+    uint32_t wdp_mq = 0;               // the minimum mapping quality of the class `good`
+    std::vector<uint32_t> wdp_len, wdp_woff; // the contigs' lengths and first windows (n_refs + 1) as the view shows them
+    std::vector<uint64_t> h_wdp, h_wdp_contigs, h_wdp_hist; // bqc_finalize's copy of the words, [n_lanes][n_refs][3] and [n_lanes][1001]
+    bool wdp_final = false;
     // depth over given regions (k_rcv.hip; bqc_enable_region_coverage(regions, MQ, thresholds, D) after creation — nothing below exists without it)
     uint32_t rcv_r = 0, rcv_mq = 0;    // the number of regions R, the minimum mapping quality
     uint64_t rcv_b = 0;                // B: the regions' bases

@@ -40,6 +40,7 @@ void bqc_launch_ibc(const DevBatch&, uint64_t* tables, uint32_t N, uint32_t n_la
 void bqc_launch_sbc(const DevBatch&, const DevRefs&, uint64_t* tables, uint32_t N, uint32_t Q, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_sac(const DevBatch&, const SacSites&, uint64_t* table, uint32_t Q, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_rcv(const DevBatch&, const RcvRegions&, uint64_t* state, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
+void bqc_launch_wdp(const DevBatch&, const WdpTab&, uint64_t* state, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_dup(const DevBatch&, const DupTable&, uint64_t* sums, uint32_t* err, uint32_t n_lanes, uint32_t n_refs, uint32_t n_cu, hipStream_t);
 }
 
@@ -621,6 +622,7 @@ static int enqueue_batch(bqc_ctx* c, BatchMem& m, bool& forked)
     if (c->d_mbc) { bqc_launch_mbc(d, refs, c->d_mbc, c->opt.mismatch_by_cycle, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_mbc"); }
     if (c->d_sbc) { bqc_launch_sbc(d, refs, c->d_sbc, c->sbc_n, c->sbc_q, c->sbc_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sbc"); }
     if (c->d_sac) { bqc_launch_sac(d, c->sac_sites, c->d_sac, c->sac_q, c->sac_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sac"); }
+    if (c->d_wdp) { bqc_launch_wdp(d, c->wdp_tab, c->d_wdp, c->wdp_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_wdp"); }
     if (c->d_rcv) { bqc_launch_rcv(d, c->rcv_regions, c->d_rcv, c->rcv_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_rcv"); }
     if (c->d_dup) { bqc_launch_dup(d, c->dup_tab, c->d_dup_sums, err, c->opt.n_lanes, c->opt.n_refs, c->n_cu, c->stream); tick(c, "k_dup"); }
     if (c->d_adp) { bqc_launch_adp(d, c->adp_pat, c->d_adp, c->adp_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_adp"); }

@@ -416,3 +416,48 @@ extern "C" int bqc_write_duplicate_sets(bqc_ctx* ctx, const bqc_header_info* hdr
     o.line_u64("duplicate_estimated_library_size", v.estimated_library_size);
     return write_file(o, path);
 }
+
+// The depth in fixed genome windows as text (include/bamqc.h): per lane the scalars and the histogram (its length first), one line a
+// contig in the header's order — name, length, windows and the three sums — then one line for every window with a word that is not 0,
+// in order: the contig's name, the window's start and end, its reads, bases and bases of low mapping quality.
+extern "C" int bqc_write_window_depth(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path)
+{
+    if (!ctx || !hdr || !path || (!ref_names && n_refs)) return BQC_ERR_ARG;
+    Out o;
+    o.s.reserve(1 << 16);
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        bqc_wdp_view v;
+        const int rc = bqc_window_depth(ctx, hdr->lane_index[n], &v);
+        if (rc) return rc;
+        if (v.n_refs != n_refs) return BQC_ERR_ARG; // (a name for every contig of the context)
+        o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        o.line_u64("window_depth_window", v.window);
+        o.line_u64("window_depth_min_mapq", v.min_mapq);
+        o.line_u64("window_depth_reads_examined", v.reads_examined);
+        o.line_u64("window_depth_reads_low_mapq", v.reads_low_mapq);
+        o.line_u64("window_depth_bases_outside_contigs", v.bases_outside);
+        o.str("window_depth_histogram "); o.u64(BQC_WDP_HIST_BINS);
+        for (uint32_t d = 0; d < BQC_WDP_HIST_BINS; ++d) { o.s.push_back(' '); o.u64(v.hist[d]); }
+        o.s.push_back('\n');
+        o.line_u64("contigs", n_refs);
+        uint64_t lines = 0;
+        for (uint32_t r = 0; r < n_refs; ++r) {
+            if (!ref_names[r]) return BQC_ERR_ARG;
+            o.str(ref_names[r]); o.s.push_back(' '); o.u64(v.ref_len[r]); o.s.push_back(' '); o.u64(v.woff[r + 1] - v.woff[r]);
+            for (uint32_t q = 0; q < 3; ++q) { o.s.push_back(' '); o.u64(v.contigs[(size_t)r * 3 + q]); }
+            o.s.push_back('\n');
+        }
+        for (uint32_t w = 0; w < v.n_windows; ++w) lines += (v.reads[w] | v.bases[w] | v.bases_low[w]) != 0;
+        o.str("windows "); o.u64(lines); o.s.push_back(' '); o.u64(v.n_windows); o.s.push_back('\n');
+        for (uint32_t r = 0; r < n_refs; ++r)
+            for (uint32_t w = v.woff[r]; w < v.woff[r + 1]; ++w) {
+                if (!(v.reads[w] | v.bases[w] | v.bases_low[w])) continue;
+                const uint64_t from = (uint64_t)(w - v.woff[r]) * v.window, to = from + v.window < v.ref_len[r] ? from + v.window : v.ref_len[r];
+                o.str(ref_names[r]); o.s.push_back(' '); o.u64(from); o.s.push_back(' '); o.u64(to);
+                o.s.push_back(' '); o.u64(v.reads[w]); o.s.push_back(' '); o.u64(v.bases[w]); o.s.push_back(' '); o.u64(v.bases_low[w]);
+                o.s.push_back('\n');
+            }
+    }
+    return write_file(o, path);
+}

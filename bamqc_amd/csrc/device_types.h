@@ -223,6 +223,17 @@ struct RcvFinal { // what k_rcv_final folds by
     uint32_t thr[BQC_RCV_MAX_THRESHOLDS];
 };
 
+// Depth in fixed genome windows (k_wdp.hip; the statistic: include/bamqc.h).  The words of a read group: [E, E_low, X, 0] then three
+// planes of NW words, reads, bases and bases_low; contig r owns the windows woff[r] .. woff[r + 1] of every plane.  The tables, made
+// once by bqc_enable_window_depth: the contigs' lengths and the running sum of their window counts.  g / W for 0 <= g < 2^31 is
+// (g * mul) >> shift: mul = ceil(2^shift / W), shift = 31 + ceil(log2 W) (k_wdp.hip says for which range that is exact).
+struct WdpTab {
+    const uint32_t* len;     // [n_refs] (a length is at most 2^31 - 1)
+    const uint32_t* woff;    // [n_refs + 1]
+    uint32_t n_refs, NW, W, mul, shift;
+    uint32_t lane_words;     // 4 + 3 NW (n_lanes * lane_words <= 2^28)
+};
+
 // Duplicate sets by alignment signature (k_dup.hip; the rule: include/bamqc.h).  A slot of the table: the two key words of a
 // signature — k0 = (u5 + 2^45) | class << 46 | strand << 47 | mate strand << 48, k1 = rid | tlen << 32, an empty word all ones — and
 // the reads of its set.  The table is no part of the state vector.

@@ -803,6 +803,9 @@ struct ProgramOptions {
     // --duplicate-sets / --duplicate-sets-capacity N: duplicate sets by alignment signature into <output>.dup
     bool duplicate_sets = false;
     uint64_t duplicate_sets_capacity = 1ull << 26; // signatures the table takes (3 GiB of slots)
+    // --window-depth / --window-depth-size W / --window-depth-min-mapq MQ: depth in fixed genome windows into <output>.wdp
+    bool window_depth = false;
+    uint32_t window_depth_size = 1000, window_depth_min_mapq = 20;
     // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
     std::string manifest;
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -869,6 +872,14 @@ void usage(FILE* f)
             "          duplication rate and observed against flagged duplicates are folds of it).  Not with --gpus.\n"
             "    --duplicate-sets-capacity INT\n          The different signatures the table takes (16 to 2147483648, default 67108864: 3 GiB on the card).\n"
             "          Needs --duplicate-sets.\n"
+            "    --window-depth\n          Depth in fixed genome windows of 1000 bases over every contig of the header: per read group and window\n"
+            "          the reads that begin in it and the covered bases of reads of mapping quality 20 and more, the covered bases\n"
+            "          of the reads below it, the same summed by contig, and a histogram of the main contigs' window depths, into\n"
+            "          OUT.wdp (sex and aneuploidy checks, the share of reads off the main contigs and coverage evenness are\n"
+            "          folds of it).\n"
+            "    --window-depth-size INT\n          The same in windows of INT bases (100 to 16777216).  Implies --window-depth.\n"
+            "    --window-depth-min-mapq INT\n          The same with mapping quality INT as the border between the two classes (0 to 255).  Implies\n"
+            "          --window-depth.\n"
             "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
             "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
             "          job's input; in a single run the filename is taken as it is.\n\n"
@@ -1107,6 +1118,19 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             want_rcv_value = key;
         }
         else if (key == "--duplicate-sets") { o.duplicate_sets = true; }
+        else if (key == "--window-depth") { o.window_depth = true; }
+        else if (key == "--window-depth-size" || key == "--window-depth-min-mapq") {
+            if (!need(i, key, v, inl)) return 1;
+            const bool mq = key == "--window-depth-min-mapq";
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' || v.size() > 10 ? ~0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x > (mq ? 255ull : 1ull << 24) || (!mq && x < 100)) {
+                err = "bamqualcheck: the given value '" + v + "' is not a " + (mq ? "mapping quality (--window-depth-min-mapq wants 0 to 255)" : "window size (--window-depth-size wants 100 to 16777216)");
+                return 1;
+            }
+            (mq ? o.window_depth_min_mapq : o.window_depth_size) = (uint32_t)x;
+            o.window_depth = true;
+        }
         else if (key == "--duplicate-sets-capacity") {
             if (!need(i, key, v, inl)) return 1;
             char* end = nullptr;
@@ -1256,6 +1280,8 @@ struct CtxKey {
     uint32_t regions_min_mapq = 0, regions_depth_cap = 0;
     std::vector<uint64_t> regions_thresholds;
     uint64_t duplicate_sets = 0; // --duplicate-sets: the capacity (0: off)
+    uint32_t window_depth = 0, window_depth_min_mapq = 0; // --window-depth: the window size (0: off)
+    std::vector<int32_t> window_depth_lens;               // and the contigs' lengths of the job's header
     int isize = 0, seed = 0, device = 0;
     bool sketch = false;
     double e = 0;
@@ -1264,7 +1290,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && region_rid == o.region_rid && region_start == o.region_start && region_end == o.region_end && regions_min_mapq == o.regions_min_mapq && regions_depth_cap == o.regions_depth_cap && regions_thresholds == o.regions_thresholds && duplicate_sets == o.duplicate_sets && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && region_rid == o.region_rid && region_start == o.region_start && region_end == o.region_end && regions_min_mapq == o.regions_min_mapq && regions_depth_cap == o.regions_depth_cap && regions_thresholds == o.regions_thresholds && duplicate_sets == o.duplicate_sets && window_depth == o.window_depth && window_depth_min_mapq == o.window_depth_min_mapq && window_depth_lens == o.window_depth_lens && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1368,6 +1394,20 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (rd.header().lane_count > 256) { // the lane column is a byte and bqc_create takes 256 at the most: said here in the input's terms, before the output file is opened
         fprintf(stderr, "ERROR: %s: the header has %u @RG lines; at most 256 read groups are supported\n", opt.bamFile.c_str(), rd.header().lane_count);
         return shard_abort();
+    }
+    std::vector<int32_t> wdp_lens; // --window-depth: the contigs' lengths as this header gives them (every worker of --gpus N takes them from its own copy)
+    if (opt.window_depth) {
+        uint64_t NW = 0;
+        for (const uint32_t len : rd.header().ref_lens) {
+            wdp_lens.push_back((int32_t)std::min<uint32_t>(len, 0x7FFFFFFFu));
+            NW += ((uint64_t)len + opt.window_depth_size - 1) / opt.window_depth_size;
+        }
+        const uint64_t lanes = std::max(1u, rd.header().lane_count);
+        if (lanes * (4 + 3 * NW) > 1ull << 28) { // said here in the option's terms, before the output file is opened
+            fprintf(stderr, "ERROR: %s: %llu windows of %u bases x 3 planes x %llu read groups are more than 268435456 (2^28) words; --window-depth-size wants a larger window for this header\n",
+                    opt.bamFile.c_str(), (unsigned long long)NW, opt.window_depth_size, (unsigned long long)lanes);
+            return shard_abort();
+        }
     }
     if (!shard || shard->index == 0) {
         FILE* of = fopen(opt.outputFile.c_str(), "wb"); // opened (truncated) before the scan, :278-283
@@ -1561,6 +1601,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         if (!site_rid.empty()) { ctx_key.site_rid = site_rid; ctx_key.site_pos = site_pos; ctx_key.site_min_qual = opt.site_min_qual; ctx_key.site_min_mapq = opt.site_min_mapq; }
         if (!region_rid.empty()) { ctx_key.region_rid = region_rid; ctx_key.region_start = region_start; ctx_key.region_end = region_end; ctx_key.regions_min_mapq = opt.regions_min_mapq; ctx_key.regions_depth_cap = opt.regions_depth_cap; ctx_key.regions_thresholds = opt.regions_thresholds; }
         if (opt.duplicate_sets) ctx_key.duplicate_sets = opt.duplicate_sets_capacity;
+        if (opt.window_depth) { ctx_key.window_depth = opt.window_depth_size; ctx_key.window_depth_min_mapq = opt.window_depth_min_mapq; ctx_key.window_depth_lens = wdp_lens; }
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
@@ -1615,6 +1656,10 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         }
         if (!rc && opt.duplicate_sets) {
             rc = bqc_enable_duplicate_sets(ctx, opt.duplicate_sets_capacity);
+            if (rc) create_err = bqc_last_error(ctx);
+        }
+        if (!rc && opt.window_depth) {
+            rc = bqc_enable_window_depth(ctx, opt.window_depth_size, wdp_lens.data(), opt.window_depth_min_mapq);
             if (rc) create_err = bqc_last_error(ctx);
         }
         if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
@@ -1948,7 +1993,9 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && !dup_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const std::string wdp_path = opt.outputFile + ".wdp"; // the table of --window-depth, behind the .dup
+    const int wdp_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && !dup_rc && opt.window_depth ? bqc_write_window_depth(ctx, &hi, sac_names.data(), n_refs, wdp_path.c_str()) : 0;
+    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && !dup_rc && !wdp_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -1971,6 +2018,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (sac_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sac_path.c_str()); return 1; }
     if (rcv_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", rcv_path.c_str()); return 1; }
     if (dup_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", dup_path.c_str()); return 1; }
+    if (wdp_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", wdp_path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);

@@ -636,8 +636,8 @@ int bqc_write_site_alleles(bqc_ctx* ctx, const bqc_header_info* hdr, const char*
 
 /* ---- depth over given regions (bqc_enable_region_coverage; not in the reference) ---------------------------------------------------
  * What an exome, a gene panel or an amplicon run is judged by: how much of the sequencing landed on the targets, how deep each target
- * is, which targets fall below a depth (Picard CollectHsMetrics, mosdepth --by).  The window histogram (poscov) stays the tool for a
- * whole genome.
+ * is, which targets fall below a depth (Picard CollectHsMetrics, mosdepth --by).  For a whole genome: the window histogram (poscov), and the
+ * depth in fixed genome windows (bqc_enable_window_depth, below).
  * Regions.  R regions (rid, start, end), counted from 0 and half-open;  0 <= rid < n_refs;  0 <= start < end <= 2^31 - 1;  sorted by
  * (rid, start) and disjoint: within a contig start[k] >= end[k-1] (abutting regions are allowed).  len[k] = end - start, B = sum of
  * len.  Region k owns len[k] + 1 slots from off[k] = sum over i < k of (len[i] + 1); the extra slot closes the region.  1 <= R and
@@ -750,6 +750,65 @@ typedef struct bqc_dup_view {
 } bqc_dup_view;
 int bqc_duplicate_sets(bqc_ctx* ctx, bqc_dup_view* out);   /* after bqc_finalize */
 int bqc_write_duplicate_sets(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
+
+/* ---- depth in fixed genome windows (bqc_enable_window_depth; not in the reference) -------------------------------------------------
+ * What a whole-genome run is judged by: where the depth is (mosdepth --by 1000, samtools idxstats, the input of read-depth CNV
+ * callers).  The X : autosome and Y : autosome ratios, a chromosome at 1.5 x or 0.5 x of the median, the share of reads on chrM or
+ * decoys, the spread of the window depths and the low-mapping-quality depth beside the usable depth are folds of it.
+ * Windows.  W is the window size, 100 <= W <= 2^24 (the program's default 1000).  Contig rid of length len[rid] (>= 0; BAM stores it
+ * in 31 bits) has nw[rid] = ceil(len / W) windows, none when len is 0; window k is [k W, min((k + 1) W, len)).  woff[rid] is the
+ * running sum of nw[], NW = woff[n_refs].  n_lanes * (4 + 3 NW) <= 2^28 (2 GiB of words).
+ * Parameter.  Minimum mapping quality MQ, 0 ... 255 (the program's default 20), compared as a plain number: a read is of class GOOD
+ * when mapq >= MQ, otherwise LOW.
+ * Examined reads.  flag & 0xF04 == 0;  n_cigar > 0;  l_seq > 0;  lane < n_lanes;  0 <= rid < n_refs — the region coverage's
+ * conditions without the one on mapq.  BQC_FLAG_NO_QUAL and the mate flags are not looked at; two mates that overlap BOTH count.  The
+ * genome is not read, nor any base or quality.
+ * The walk, in stored order and 64-bit arithmetic: j = 0, g = pos; for every CIGAR operation (op, n)
+ *   M, =, X (0, 7, 8):  m = min(n, max(0, l_seq - j)); the positions [g, g + m) are covered.  A covered position p with
+ *     0 <= p < len[rid] belongs to window floor(p / W) of the contig and adds 1 to that window's word of the read's class, bases or
+ *     bases_low; every other covered position adds 1 to X[lane].  Then j += n and g += n.
+ *   I, S (1, 4):  j += n.      D, N (2, 3):  g += n; a deletion or a skip covers nothing.
+ *   H, P and every code of 9 or more:  nothing.
+ * Per read E[lane] += 1 (good) or E_low[lane] += 1 (low); a good read with 0 <= pos < len[rid] adds 1 to reads[floor(pos / W)] of
+ * its contig, any other read to no `reads` word.
+ * State.  Per lane [E, E_low, X, 0][reads NW][bases NW][bases_low NW], u64, pure sums modulo 2^64: n_lanes * (4 + 3 NW) words directly
+ * behind the sketch's words, IN FRONT OF the region coverage's and every other module's: their distance from the end of the vector
+ * stays what it is.  Export / import, bqc_reset (the words go back to zero, the tables stay), shard hand-over and the reduce treat the
+ * words as the other words (--gpus N works).  Two contexts exchange state only when both have the module on with the same NW.
+ * Finalize products, per lane, made on the host from a copy of the words: per contig the sums of reads, bases and bases_low over its
+ * windows; a histogram of floor(bases[w] / length(w)) with 1001 bins, the last open, over the windows of the contigs whose main_chrom
+ * entry is 1.  The state is left as it is: finalize can be called again and gives the same views.
+ * bqc_enable_window_depth switches the module on, after creation, in any order with the other enable calls (the ABI version stays
+ * 2); ref_len holds the n_refs lengths of the context's contigs and is copied.  BQC_ERR_ARG, with a message that names the value, in
+ * this order: W out of range;  MQ > 255;  a null list (n_refs > 0);  a negative length (with the contig's index);
+ * n_lanes * (4 + 3 NW) > 2^28 (the message names NW, W and the number of read groups).  BQC_ERR_STATE: a second call; a call after
+ * the context has taken a batch, has exported or imported state, or has been finalised.  Without the call: no allocation, no launch,
+ * the same bqc_state_words and the same offsets.  With it: every other output is the same bytes as without it.
+ * bqc_window_depth: valid after bqc_finalize; the view is owned by the context until the next finalize / destroy.  BQC_ERR_STATE: the
+ * module is off, or nothing has been finalised; BQC_ERR_ARG: lane out of range.
+ * bqc_write_window_depth: the text, lanes in the order of `hdr`, key-then-values lines (BQC_ERR_ARG when n_refs is not the
+ * context's or a contig has no name):
+ *   sample_id <id> / lane <name> / window_depth_window <W> / window_depth_min_mapq <MQ> / window_depth_reads_examined <E> /
+ *   window_depth_reads_low_mapq <E_low> / window_depth_bases_outside_contigs <X> / window_depth_histogram 1001 v0 ... v1000 /
+ *   contigs <n_refs> /
+ *   <contig> <length> <windows> <reads> <bases> <bases_low_mapq>     (one line per contig, the header's order) /
+ *   windows <lines that follow> <NW> /
+ *   <contig> <start> <end> <reads> <bases> <bases_low_mapq>          (only windows with a word that is not 0, in order) */
+#define BQC_WDP_HIST_BINS 1001
+int bqc_enable_window_depth(bqc_ctx* ctx, uint32_t window, const int32_t* ref_len, uint32_t min_mapq);
+typedef struct bqc_wdp_view {
+    uint32_t window, min_mapq, n_windows, n_refs;
+    const uint32_t* woff;      /* [n_refs + 1] */
+    const uint32_t* ref_len;   /* [n_refs] */
+    uint64_t reads_examined, reads_low_mapq, bases_outside;
+    const uint64_t* reads;     /* [n_windows] */
+    const uint64_t* bases;     /* [n_windows] */
+    const uint64_t* bases_low; /* [n_windows] */
+    const uint64_t* contigs;   /* [n_refs][3]: reads, bases, bases_low */
+    const uint64_t* hist;      /* [1001] */
+} bqc_wdp_view;
+int bqc_window_depth(bqc_ctx* ctx, uint32_t lane, bqc_wdp_view* out);   /* after bqc_finalize */
+int bqc_write_window_depth(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path);
 
 #ifdef __cplusplus
 }
