@@ -122,6 +122,37 @@ static int adapter_set(const bqc_modules* mod, std::vector<std::string>& names, 
     return 0;
 }
 
+// bqc_create_ex's device calls: a failure destroys the half-made context
+#define CCHK(call)                                                                                            \
+    do {                                                                                                      \
+        hipError_t e_ = (call);                                                                               \
+        if (e_ != hipSuccess) {                                                                               \
+            fail(nullptr, BQC_ERR_DEVICE, "bqc_create: %s failed: %s", #call, hipGetErrorString(e_));         \
+            bqc_destroy(c);                                                                                   \
+            return BQC_ERR_DEVICE;                                                                            \
+        }                                                                                                     \
+    } while (0)
+
+// A module's table of the creation (qual_by_cycle, mismatch_by_cycle, adapter_by_cycle; `option`: the call and the option's name, `shape`:
+// the table's dimensions) becomes segment `s`: refused before allocating when it does not fit, as the sketch's tables are (1 GiB stays
+// for the rest of the context).  A failure destroys the context, as CCHK does.
+static int create_segment(bqc_ctx* c, int s, uint64_t words, const char* option, uint32_t n, const char* shape)
+{
+    size_t free_b = 0, total_b = 0;
+    CCHK(hipMemGetInfo(&free_b, &total_b));
+    if (words * 8 + (1ull << 30) > free_b) {
+        fail(nullptr, BQC_ERR_ARG, "%s %u needs %llu bytes of tables (%s), the device has %zu bytes free (%llu kept for the rest of the context)",
+             option, n, (unsigned long long)(words * 8), shape, free_b, 1ull << 30);
+        bqc_destroy(c);
+        return BQC_ERR_ARG;
+    }
+    c->seg[s].words = words;
+    CCHK(hipMalloc(&c->seg[s].d, words * 8));
+    CCHK(hipMemsetAsync(c->seg[s].d, 0, words * 8, c->stream));
+    CCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 extern "C" int bqc_create(const bqc_options* opt, bqc_ctx** out) { return bqc_create_ex(opt, nullptr, out); }
 
 extern "C" int bqc_create_ex(const bqc_options* opt, const bqc_modules* mod, bqc_ctx** out)
@@ -188,15 +219,6 @@ extern "C" int bqc_create_ex(const bqc_options* opt, const bqc_modules* mod, bqc
     c->no_fast = v && v[0] == '1';
     const char* cs = getenv("BQC_COV_STREAM");
     c->cov_side = !(cs && cs[0] == '0');
-#define CCHK(call)                                                                                            \
-    do {                                                                                                      \
-        hipError_t e_ = (call);                                                                               \
-        if (e_ != hipSuccess) {                                                                               \
-            fail(nullptr, BQC_ERR_DEVICE, "bqc_create: %s failed: %s", #call, hipGetErrorString(e_));         \
-            bqc_destroy(c);                                                                                   \
-            return BQC_ERR_DEVICE;                                                                            \
-        }                                                                                                     \
-    } while (0)
     const bool ctiming = getenv("BQC_TIMING") && getenv("BQC_TIMING")[0] == '1';
     const auto ct0 = std::chrono::steady_clock::now();
     double cts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -251,47 +273,18 @@ extern "C" int bqc_create_ex(const bqc_options* opt, const bqc_modules* mod, bqc
         c->sketch = sketch_create(opt->sketch, opt->n_lanes, c->stream, e);
         if (!c->sketch) { fail(nullptr, BQC_ERR_ARG, "bqc_create: sketch: %s", e.c_str()); bqc_destroy(c); return BQC_ERR_ARG; }
     }
-    if (qbc_n) { // refused before allocating when it does not fit, as the sketch's tables are (1 GiB stays for the rest of the context)
-        c->qcyc_words = bqc_qcyc_words(opt->n_lanes, qbc_n);
-        size_t free_b = 0, total_b = 0;
-        CCHK(hipMemGetInfo(&free_b, &total_b));
-        if (c->qcyc_words * 8 + (1ull << 30) > free_b) {
-            fail(nullptr, BQC_ERR_ARG, "bqc_create: qual_by_cycle %u needs %llu bytes of tables (%u read groups x 2 x %u cycles x 224 qualities x 8 bytes), the device has %zu bytes free (%llu kept for the rest of the context)",
-                 qbc_n, (unsigned long long)(c->qcyc_words * 8), opt->n_lanes, qbc_n, free_b, 1ull << 30);
-            bqc_destroy(c);
-            return BQC_ERR_ARG;
-        }
-        CCHK(hipMalloc(&c->d_qcyc, c->qcyc_words * 8));
-        CCHK(hipMemsetAsync(c->d_qcyc, 0, c->qcyc_words * 8, c->stream));
-        CCHK(hipStreamSynchronize(c->stream));
+    char shape[128];
+    if (qbc_n) {
+        snprintf(shape, sizeof shape, "%u read groups x 2 x %u cycles x 224 qualities x 8 bytes", opt->n_lanes, qbc_n);
+        if (int rc = create_segment(c, SEG_QCYC, bqc_qcyc_words(opt->n_lanes, qbc_n), "bqc_create: qual_by_cycle", qbc_n, shape)) return rc;
     }
-    if (mbc_n) { // the same rule
-        c->mbc_words = bqc_mbc_words(opt->n_lanes, mbc_n);
-        size_t free_b = 0, total_b = 0;
-        CCHK(hipMemGetInfo(&free_b, &total_b));
-        if (c->mbc_words * 8 + (1ull << 30) > free_b) {
-            fail(nullptr, BQC_ERR_ARG, "bqc_create: mismatch_by_cycle %u needs %llu bytes of tables (%u read groups x 2 x 2 x %u cycles x 224 qualities x 8 bytes), the device has %zu bytes free (%llu kept for the rest of the context)",
-                 mbc_n, (unsigned long long)(c->mbc_words * 8), opt->n_lanes, mbc_n, free_b, 1ull << 30);
-            bqc_destroy(c);
-            return BQC_ERR_ARG;
-        }
-        CCHK(hipMalloc(&c->d_mbc, c->mbc_words * 8));
-        CCHK(hipMemsetAsync(c->d_mbc, 0, c->mbc_words * 8, c->stream));
-        CCHK(hipStreamSynchronize(c->stream));
+    if (mbc_n) {
+        snprintf(shape, sizeof shape, "%u read groups x 2 x 2 x %u cycles x 224 qualities x 8 bytes", opt->n_lanes, mbc_n);
+        if (int rc = create_segment(c, SEG_MBC, bqc_mbc_words(opt->n_lanes, mbc_n), "bqc_create: mismatch_by_cycle", mbc_n, shape)) return rc;
     }
-    if (adp_n) { // the same rule
-        c->adp_words = bqc_adp_words(opt->n_lanes, adp_n);
-        size_t free_b = 0, total_b = 0;
-        CCHK(hipMemGetInfo(&free_b, &total_b));
-        if (c->adp_words * 8 + (1ull << 30) > free_b) {
-            fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: adapter_by_cycle %u needs %llu bytes of tables (%u read groups x 2 x 9 x %u cycles x 8 bytes), the device has %zu bytes free (%llu kept for the rest of the context)",
-                 adp_n, (unsigned long long)(c->adp_words * 8), opt->n_lanes, adp_n, free_b, 1ull << 30);
-            bqc_destroy(c);
-            return BQC_ERR_ARG;
-        }
-        CCHK(hipMalloc(&c->d_adp, c->adp_words * 8));
-        CCHK(hipMemsetAsync(c->d_adp, 0, c->adp_words * 8, c->stream));
-        CCHK(hipStreamSynchronize(c->stream));
+    if (adp_n) {
+        snprintf(shape, sizeof shape, "%u read groups x 2 x 9 x %u cycles x 8 bytes", opt->n_lanes, adp_n);
+        if (int rc = create_segment(c, SEG_ADP, bqc_adp_words(opt->n_lanes, adp_n), "bqc_create_ex: adapter_by_cycle", adp_n, shape)) return rc;
     }
     cstamp(4);
     for (int i = 0; i < 16; ++i) {
@@ -398,17 +391,9 @@ extern "C" void bqc_destroy(bqc_ctx* c)
 
     (void)hipFree(c->d_refn_ptrs);
     if (c->sketch) sketch_destroy(c->sketch);
-    if (c->d_qcyc) (void)hipFree(c->d_qcyc);
-    if (c->d_mbc) (void)hipFree(c->d_mbc);
-    if (c->d_adp) (void)hipFree(c->d_adp);
-    if (c->d_gcb) (void)hipFree(c->d_gcb);
-    if (c->d_ibc) (void)hipFree(c->d_ibc);
-    if (c->d_sbc) (void)hipFree(c->d_sbc);
-    if (c->d_sac) (void)hipFree(c->d_sac);
+    for (const StateSeg& s : c->seg) if (s.d) (void)hipFree(s.d);
     if (c->d_sac_tab) (void)hipFree(c->d_sac_tab);
-    if (c->d_wdp) (void)hipFree(c->d_wdp);
     if (c->d_wdp_tab) (void)hipFree(c->d_wdp_tab);
-    if (c->d_rcv) (void)hipFree(c->d_rcv);
     if (c->d_rcv_tab) (void)hipFree(c->d_rcv_tab);
     if (c->d_rcv_out) (void)hipFree(c->d_rcv_out);
     if (c->d_dup) (void)hipFree(c->d_dup);
@@ -524,29 +509,13 @@ extern "C" int bqc_reset(bqc_ctx* c)
     HIPCHK(c, hipMemsetAsync(c->d_parity, 0, ((size_t)c->opt.n_lanes + 1) * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_started, 0, c->opt.n_lanes, c->stream));
     if (c->sketch) sketch_reset(c->sketch, c->stream);
-    if (c->d_qcyc) HIPCHK(c, hipMemsetAsync(c->d_qcyc, 0, c->qcyc_words * 8, c->stream));
-    c->qcyc_final = false;
-    if (c->d_mbc) HIPCHK(c, hipMemsetAsync(c->d_mbc, 0, c->mbc_words * 8, c->stream));
-    c->mbc_final = false;
-    if (c->d_adp) HIPCHK(c, hipMemsetAsync(c->d_adp, 0, c->adp_words * 8, c->stream));
-    c->adp_final = false;
-    if (c->d_gcb) HIPCHK(c, hipMemsetAsync(c->d_gcb, 0, c->gcb_words * 8, c->stream)); // (R, B and Q; the genome table is bqc_finalize's)
-    c->gcb_final = false;
-    if (c->d_ibc) HIPCHK(c, hipMemsetAsync(c->d_ibc, 0, c->ibc_words * 8, c->stream));
-    c->ibc_final = false;
-    if (c->d_sbc) HIPCHK(c, hipMemsetAsync(c->d_sbc, 0, c->sbc_words * 8, c->stream));
-    c->sbc_final = false;
-    if (c->d_sac) HIPCHK(c, hipMemsetAsync(c->d_sac, 0, c->sac_words * 8, c->stream)); // (the table; the sites stay)
-    c->sac_final = false;
-    if (c->d_wdp) HIPCHK(c, hipMemsetAsync(c->d_wdp, 0, c->wdp_words * 8, c->stream)); // (the words; the contigs' tables stay)
-    c->wdp_final = false;
-    if (c->d_rcv) HIPCHK(c, hipMemsetAsync(c->d_rcv, 0, c->rcv_words * 8, c->stream)); // (the words; the regions stay)
-    c->rcv_final = false;
+    for (const StateSeg& s : c->seg) // (the modules' words; their side tables — sites, regions, contigs — stay, the genome table is bqc_finalize's)
+        if (s.d) HIPCHK(c, hipMemsetAsync(s.d, 0, s.words * 8, c->stream));
     if (c->d_dup) { // (the table and the sums go back to empty; the allocation stays)
         bqc_launch_dup_clear(c->dup_tab, c->d_dup_sums, c->opt.n_lanes, c->n_cu, c->stream);
         HIPCHK(c, hipGetLastError());
     }
-    c->dup_final = false;
+    for (bool& f : c->finalised) f = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
     if (c->anchor.d_state) HIPCHK(c, bqc_anchor_fresh_state(c)); // (anchors made on the card: every read group's state starts over as well)
@@ -593,120 +562,61 @@ extern "C" int bqc_flush(bqc_ctx* c)
     return 0;
 }
 
-// the flat vector: [sl.words][sketch][window depth][region coverage][site alleles][substitutions][indels by cycle][GC bias][adapter by cycle][mismatch by cycle][qual by cycle]
-static uint64_t wdp_offset(const bqc_ctx* c) { return c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0); }
-static uint64_t rcv_offset(const bqc_ctx* c) { return wdp_offset(c) + c->wdp_words; }
-static uint64_t sac_offset(const bqc_ctx* c) { return rcv_offset(c) + c->rcv_words; }
-static uint64_t sbc_offset(const bqc_ctx* c) { return sac_offset(c) + c->sac_words; }
-static uint64_t ibc_offset(const bqc_ctx* c) { return sbc_offset(c) + c->sbc_words; }
-static uint64_t gcb_offset(const bqc_ctx* c) { return ibc_offset(c) + c->ibc_words; }
-static uint64_t adp_offset(const bqc_ctx* c) { return gcb_offset(c) + c->gcb_words; }
-static uint64_t mbc_offset(const bqc_ctx* c) { return adp_offset(c) + c->adp_words; }
-static uint64_t qcyc_offset(const bqc_ctx* c) { return mbc_offset(c) + c->mbc_words; }
-extern "C" uint64_t bqc_state_words(const bqc_ctx* c) { return c ? qcyc_offset(c) + c->qcyc_words : 0; }
+// where segment `s` begins in the flat vector (s = N_SEG: the vector's length): behind sl.words, the sketch's words and the segments in front of it
+static uint64_t seg_start(const bqc_ctx* c, int s)
+{
+    uint64_t off = c->sl.words + (c->sketch ? sketch_state_words(c->sketch) : 0);
+    for (int k = 0; k < s; ++k) off += c->seg[k].words;
+    return off;
+}
+extern "C" uint64_t bqc_state_words(const bqc_ctx* c) { return c ? seg_start(c, N_SEG) : 0; }
 
-extern "C" int bqc_state_export(bqc_ctx* c, void* dst)
+// The four exchange calls: the whole vector between the context and `buf` (only read when `incoming`), which lies in device memory — copies
+// on the compute stream — or, `host`, in host memory: blocking copies, the sketch's words through a staging buffer on the card.
+static int state_transfer(bqc_ctx* c, uint64_t* buf, bool incoming, bool host)
 {
-    if (!c || !dst) return BQC_ERR_ARG;
-    c->gcb_closed = true;
-    int rc = bqc_flush(c);
-    if (rc) return rc;
-    bqc_state_ready(c);
-    HIPCHK(c, hipMemcpyAsync(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->sketch) sketch_state_export(c->sketch, (uint64_t*)dst + c->sl.words, c->stream);
-    if (c->d_wdp) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + wdp_offset(c), c->d_wdp, c->wdp_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_rcv) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + rcv_offset(c), c->d_rcv, c->rcv_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_sac) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sac_offset(c), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_sbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_ibc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + ibc_offset(c), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_gcb) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + gcb_offset(c), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_adp) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + adp_offset(c), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_mbc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + mbc_offset(c), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync((uint64_t*)dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-extern "C" int bqc_state_import(bqc_ctx* c, const void* src)
-{
-    if (!c || !src) return BQC_ERR_ARG;
-    c->gcb_closed = true;
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)bqc_drain(c);
-    bqc_state_ready(c);
-    HIPCHK(c, hipMemcpyAsync(c->d_state, src, c->sl.words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->sketch) sketch_state_import(c->sketch, (const uint64_t*)src + c->sl.words, c->stream);
-    if (c->d_wdp) HIPCHK(c, hipMemcpyAsync(c->d_wdp, (const uint64_t*)src + wdp_offset(c), c->wdp_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_rcv) HIPCHK(c, hipMemcpyAsync(c->d_rcv, (const uint64_t*)src + rcv_offset(c), c->rcv_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_sac) HIPCHK(c, hipMemcpyAsync(c->d_sac, (const uint64_t*)src + sac_offset(c), c->sac_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_sbc) HIPCHK(c, hipMemcpyAsync(c->d_sbc, (const uint64_t*)src + sbc_offset(c), c->sbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_ibc) HIPCHK(c, hipMemcpyAsync(c->d_ibc, (const uint64_t*)src + ibc_offset(c), c->ibc_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_gcb) HIPCHK(c, hipMemcpyAsync(c->d_gcb, (const uint64_t*)src + gcb_offset(c), c->gcb_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_adp) HIPCHK(c, hipMemcpyAsync(c->d_adp, (const uint64_t*)src + adp_offset(c), c->adp_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_mbc) HIPCHK(c, hipMemcpyAsync(c->d_mbc, (const uint64_t*)src + mbc_offset(c), c->mbc_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    if (c->d_qcyc) HIPCHK(c, hipMemcpyAsync(c->d_qcyc, (const uint64_t*)src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->flushed = true; // an imported vector is already flushed
-    return 0;
-}
-extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst)
-{
-    if (!c || !dst) return BQC_ERR_ARG;
-    c->gcb_closed = true;
-    int rc = bqc_flush(c);
-    if (rc) return rc;
-    bqc_state_ready(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dst, c->d_state, c->sl.words * 8, hipMemcpyDeviceToHost));
-    if (c->sketch) {
-        uint64_t* tmp = nullptr;
-        const uint64_t w = sketch_state_words(c->sketch);
-        HIPCHK(c, hipMalloc(&tmp, w * 8));
-        sketch_state_export(c->sketch, tmp, c->stream);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(dst + c->sl.words, tmp, w * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipFree(tmp));
+    c->modules_closed = true;
+    if (incoming) {
+        HIPCHK(c, hipSetDevice(c->device));
+        (void)bqc_drain(c);
+    } else {
+        const int rc = bqc_flush(c);
+        if (rc) return rc;
     }
-    if (c->d_wdp) HIPCHK(c, hipMemcpy(dst + wdp_offset(c), c->d_wdp, c->wdp_words * 8, hipMemcpyDeviceToHost));
-    if (c->d_rcv) HIPCHK(c, hipMemcpy(dst + rcv_offset(c), c->d_rcv, c->rcv_words * 8, hipMemcpyDeviceToHost));
-    if (c->d_sac) HIPCHK(c, hipMemcpy(dst + sac_offset(c), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToHost));
-    if (c->d_sbc) HIPCHK(c, hipMemcpy(dst + sbc_offset(c), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToHost));
-    if (c->d_ibc) HIPCHK(c, hipMemcpy(dst + ibc_offset(c), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToHost));
-    if (c->d_gcb) HIPCHK(c, hipMemcpy(dst + gcb_offset(c), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToHost));
-    if (c->d_adp) HIPCHK(c, hipMemcpy(dst + adp_offset(c), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToHost));
-    if (c->d_mbc) HIPCHK(c, hipMemcpy(dst + mbc_offset(c), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToHost));
-    if (c->d_qcyc) HIPCHK(c, hipMemcpy(dst + qcyc_offset(c), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src)
-{
-    if (!c || !src) return BQC_ERR_ARG;
-    c->gcb_closed = true;
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)bqc_drain(c);
     bqc_state_ready(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(c->d_state, src, c->sl.words * 8, hipMemcpyHostToDevice));
+    if (host) HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipMemcpyKind kind = !host ? hipMemcpyDeviceToDevice : incoming ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    auto copy_words = [&](uint64_t* dev, uint64_t off, uint64_t words) {
+        void* dst = incoming ? dev : buf + off;
+        const void* src = incoming ? buf + off : dev;
+        return host ? hipMemcpy(dst, src, words * 8, kind) : hipMemcpyAsync(dst, src, words * 8, kind, c->stream);
+    };
+    HIPCHK(c, copy_words(c->d_state, 0, c->sl.words));
     if (c->sketch) {
-        uint64_t* tmp = nullptr;
+        uint64_t *sk = buf + c->sl.words, *tmp = nullptr;
         const uint64_t w = sketch_state_words(c->sketch);
-        HIPCHK(c, hipMalloc(&tmp, w * 8));
-        HIPCHK(c, hipMemcpy(tmp, src + c->sl.words, w * 8, hipMemcpyHostToDevice));
-        sketch_state_import(c->sketch, tmp, c->stream);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(tmp));
+        if (host) {
+            HIPCHK(c, hipMalloc(&tmp, w * 8));
+            if (incoming) HIPCHK(c, hipMemcpy(tmp, sk, w * 8, hipMemcpyHostToDevice));
+        }
+        if (incoming) sketch_state_import(c->sketch, host ? tmp : sk, c->stream);
+        else sketch_state_export(c->sketch, host ? tmp : sk, c->stream);
+        if (host) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (!incoming) HIPCHK(c, hipMemcpy(sk, tmp, w * 8, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipFree(tmp));
+        }
     }
-    if (c->d_wdp) HIPCHK(c, hipMemcpy(c->d_wdp, src + wdp_offset(c), c->wdp_words * 8, hipMemcpyHostToDevice));
-    if (c->d_rcv) HIPCHK(c, hipMemcpy(c->d_rcv, src + rcv_offset(c), c->rcv_words * 8, hipMemcpyHostToDevice));
-    if (c->d_sac) HIPCHK(c, hipMemcpy(c->d_sac, src + sac_offset(c), c->sac_words * 8, hipMemcpyHostToDevice));
-    if (c->d_sbc) HIPCHK(c, hipMemcpy(c->d_sbc, src + sbc_offset(c), c->sbc_words * 8, hipMemcpyHostToDevice));
-    if (c->d_ibc) HIPCHK(c, hipMemcpy(c->d_ibc, src + ibc_offset(c), c->ibc_words * 8, hipMemcpyHostToDevice));
-    if (c->d_gcb) HIPCHK(c, hipMemcpy(c->d_gcb, src + gcb_offset(c), c->gcb_words * 8, hipMemcpyHostToDevice));
-    if (c->d_adp) HIPCHK(c, hipMemcpy(c->d_adp, src + adp_offset(c), c->adp_words * 8, hipMemcpyHostToDevice));
-    if (c->d_mbc) HIPCHK(c, hipMemcpy(c->d_mbc, src + mbc_offset(c), c->mbc_words * 8, hipMemcpyHostToDevice));
-    if (c->d_qcyc) HIPCHK(c, hipMemcpy(c->d_qcyc, src + qcyc_offset(c), c->qcyc_words * 8, hipMemcpyHostToDevice));
-    c->flushed = true;
+    for (int s = 0; s < N_SEG; ++s)
+        if (c->seg[s].d) HIPCHK(c, copy_words(c->seg[s].d, seg_start(c, s), c->seg[s].words));
+    if (!host) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (incoming) c->flushed = true; // an imported vector is already flushed
     return 0;
 }
+extern "C" int bqc_state_export(bqc_ctx* c, void* dst) { return c && dst ? state_transfer(c, (uint64_t*)dst, false, false) : BQC_ERR_ARG; }
+extern "C" int bqc_state_import(bqc_ctx* c, const void* src) { return c && src ? state_transfer(c, (uint64_t*)src, true, false) : BQC_ERR_ARG; }
+extern "C" int bqc_state_export_host(bqc_ctx* c, uint64_t* dst) { return c && dst ? state_transfer(c, dst, false, true) : BQC_ERR_ARG; }
+extern "C" int bqc_state_import_host(bqc_ctx* c, const uint64_t* src) { return c && src ? state_transfer(c, (uint64_t*)src, true, true) : BQC_ERR_ARG; }
 
 // ---------------------------------------------------------------------------------------------------
 // finalize
@@ -715,6 +625,24 @@ static uint32_t last_nonzero_len(const uint64_t* p, uint32_t n)
 {
     while (n > 0 && p[n - 1] == 0) --n;
     return n;
+}
+
+// A kernel of bqc_finalize (k_gcb_genome, k_rcv_final, k_dup_final).  With timing on, bqc_last_timing shows it afterwards, as it shows a
+// batch's kernels, which are over; `shown`: of several in one bqc_finalize the GC bias's comes first, then the regions', then the sets'.
+template <class Launch> static void timed_launch(bqc_ctx* c, bool shown, const char* name, Launch&& launch)
+{
+    const bool timed = shown && c->timing && c->ev.size() >= 2;
+    if (timed) { c->n_timed = 0; c->tnames.clear(); (void)hipEventRecord(c->ev[0], c->stream); }
+    launch();
+    if (timed) { (void)hipEventRecord(c->ev[1], c->stream); c->tnames.push_back(name); c->n_timed = 1; }
+}
+
+// bqc_finalize's copy of a module's words
+static int fetch_segment(bqc_ctx* c, int s, std::vector<uint64_t>& h)
+{
+    h.resize(c->seg[s].words);
+    HIPCHK(c, hipMemcpy(h.data(), c->seg[s].d, h.size() * 8, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // The genome table G of the GC bias (include/bamqc.h) from the contigs the context holds now: k_gcb_genome on the compute stream, into
@@ -733,10 +661,7 @@ static int gcb_genome_table(bqc_ctx* c)
     HIPCHK(c, hipMemsetAsync(c->d_gcb_g, 0, BQC_GCB_BINS * 8, c->stream));
     if (!tab.empty()) {
         HIPCHK(c, hipMemcpyAsync(c->d_gcb_tab, tab.data(), tab.size() * sizeof(GcbContig), hipMemcpyHostToDevice, c->stream));
-        const bool timed = c->timing && c->ev.size() >= 2; // (bqc_last_timing then shows this launch: a batch's kernels are over)
-        if (timed) { c->n_timed = 0; c->tnames.clear(); (void)hipEventRecord(c->ev[0], c->stream); }
-        bqc_launch_gcb_genome(c->d_gcb_tab, (uint32_t)tab.size(), n_shares, c->gcb_w, c->gcb_div, c->d_gcb_g, c->n_cu, c->stream);
-        if (timed) { (void)hipEventRecord(c->ev[1], c->stream); c->tnames.push_back("k_gcb_genome"); c->n_timed = 1; }
+        timed_launch(c, true, "k_gcb_genome", [&] { bqc_launch_gcb_genome(c->d_gcb_tab, (uint32_t)tab.size(), n_shares, c->gcb_w, c->gcb_div, c->d_gcb_g, c->n_cu, c->stream); });
         HIPCHK(c, hipGetLastError());
     }
     c->h_gcb_g.resize(BQC_GCB_BINS);
@@ -745,28 +670,44 @@ static int gcb_genome_table(bqc_ctx* c)
     return 0;
 }
 
+// The bqc_enable_* calls belong right behind bqc_create: `fn` comes too late (BQC_ERR_STATE) once the context has done anything else.
+static int too_late(bqc_ctx* c, const char* fn)
+{
+    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->modules_closed)
+        return fail(c, BQC_ERR_STATE, "%s: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)", fn);
+    return 0;
+}
+
+// `words` words of device memory, cleared on the compute stream and waited for: a module's segment in the making (nullptr: not to be
+// had, and nothing stays allocated).  The caller registers it in bqc_ctx::seg once its side tables exist as well.
+static uint64_t* zeroed_words(bqc_ctx* c, uint64_t words)
+{
+    uint64_t* d = nullptr;
+    if (hipMalloc(&d, words * 8) == hipSuccess && hipMemsetAsync(d, 0, words * 8, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess) return d;
+    (void)hipGetLastError();
+    (void)hipFree(d);
+    return nullptr;
+}
+
 extern "C" int bqc_enable_gc_bias(bqc_ctx* c, uint32_t window)
 {
     if (!c) return BQC_ERR_ARG;
     if (window < BQC_GCB_WMIN || window > BQC_GCB_WMAX) return fail(c, BQC_ERR_ARG, "bqc_enable_gc_bias: window %u is outside %d ... %d", window, BQC_GCB_WMIN, BQC_GCB_WMAX);
-    if (c->d_gcb) return fail(c, BQC_ERR_STATE, "bqc_enable_gc_bias: the module is on already (window %u)", c->gcb_w);
-    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
-        return fail(c, BQC_ERR_STATE, "bqc_enable_gc_bias: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    if (c->seg[SEG_GCB].d) return fail(c, BQC_ERR_STATE, "bqc_enable_gc_bias: the module is on already (window %u)", c->gcb_w);
+    if (int rc = too_late(c, __func__)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t words = bqc_gcb_words(c->opt.n_lanes);
-    uint64_t *d = nullptr, *g = nullptr;
+    uint64_t *d = zeroed_words(c, words), *g = zeroed_words(c, BQC_GCB_BINS);
     GcbContig* tab = nullptr;
-    if (hipMalloc(&d, words * 8) != hipSuccess || hipMalloc(&g, BQC_GCB_BINS * 8) != hipSuccess ||
-        hipMalloc(&tab, std::max<size_t>(1, c->opt.n_refs) * sizeof(GcbContig)) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess ||
-        hipMemsetAsync(g, 0, BQC_GCB_BINS * 8, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (!d || !g || hipMalloc(&tab, std::max<size_t>(1, c->opt.n_refs) * sizeof(GcbContig)) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(d); (void)hipFree(g); (void)hipFree(tab);
         return fail(c, BQC_ERR_DEVICE, "bqc_enable_gc_bias: the tables could not be allocated");
     }
     for (uint32_t n = 0; n < 5; ++n) c->gcb_div.m[n] = (uint32_t)(((1ull << 32) + (window - n) - 1) / (window - n)); // ceil(2^32 / (W - n))
     c->gcb_w = window;
-    c->gcb_words = words;
-    c->d_gcb = d; c->d_gcb_g = g; c->d_gcb_tab = tab;
+    c->seg[SEG_GCB] = {d, words};
+    c->d_gcb_g = g; c->d_gcb_tab = tab;
     return 0;
 }
 
@@ -775,20 +716,14 @@ extern "C" int bqc_enable_indel_by_cycle(bqc_ctx* c, uint32_t n_cycles)
     if (!c) return BQC_ERR_ARG;
     if (!n_cycles || n_cycles > c->opt.max_read_len || n_cycles >= 1u << 30)
         return fail(c, BQC_ERR_ARG, "bqc_enable_indel_by_cycle: capacity %u is outside 1 ... max_read_len %u", n_cycles, c->opt.max_read_len);
-    if (c->d_ibc) return fail(c, BQC_ERR_STATE, "bqc_enable_indel_by_cycle: the module is on already (capacity %u)", c->ibc_n);
-    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
-        return fail(c, BQC_ERR_STATE, "bqc_enable_indel_by_cycle: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    if (c->seg[SEG_IBC].d) return fail(c, BQC_ERR_STATE, "bqc_enable_indel_by_cycle: the module is on already (capacity %u)", c->ibc_n);
+    if (int rc = too_late(c, __func__)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t words = bqc_ibc_words(c->opt.n_lanes, n_cycles);
-    uint64_t* d = nullptr;
-    if (hipMalloc(&d, words * 8) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(d);
-        return fail(c, BQC_ERR_DEVICE, "bqc_enable_indel_by_cycle: the tables (%llu bytes) could not be allocated", (unsigned long long)(words * 8));
-    }
+    uint64_t* d = zeroed_words(c, words);
+    if (!d) return fail(c, BQC_ERR_DEVICE, "bqc_enable_indel_by_cycle: the tables (%llu bytes) could not be allocated", (unsigned long long)(words * 8));
     c->ibc_n = n_cycles;
-    c->ibc_words = words;
-    c->d_ibc = d;
+    c->seg[SEG_IBC] = {d, words};
     return 0;
 }
 
@@ -799,20 +734,14 @@ extern "C" int bqc_enable_substitutions(bqc_ctx* c, uint32_t n_cycles, uint32_t 
         return fail(c, BQC_ERR_ARG, "bqc_enable_substitutions: capacity %u is outside 1 ... max_read_len %u", n_cycles, c->opt.max_read_len);
     if (min_base_qual > 222) return fail(c, BQC_ERR_ARG, "bqc_enable_substitutions: minimum base quality %u is outside 0 ... 222", min_base_qual);
     if (min_mapq > 255) return fail(c, BQC_ERR_ARG, "bqc_enable_substitutions: minimum mapping quality %u is outside 0 ... 255", min_mapq);
-    if (c->d_sbc) return fail(c, BQC_ERR_STATE, "bqc_enable_substitutions: the module is on already (capacity %u)", c->sbc_n);
-    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
-        return fail(c, BQC_ERR_STATE, "bqc_enable_substitutions: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    if (c->seg[SEG_SBC].d) return fail(c, BQC_ERR_STATE, "bqc_enable_substitutions: the module is on already (capacity %u)", c->sbc_n);
+    if (int rc = too_late(c, __func__)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t words = bqc_sbc_words(c->opt.n_lanes, n_cycles);
-    uint64_t* d = nullptr;
-    if (hipMalloc(&d, words * 8) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(d);
-        return fail(c, BQC_ERR_DEVICE, "bqc_enable_substitutions: the tables (%llu bytes) could not be allocated", (unsigned long long)(words * 8));
-    }
+    uint64_t* d = zeroed_words(c, words);
+    if (!d) return fail(c, BQC_ERR_DEVICE, "bqc_enable_substitutions: the tables (%llu bytes) could not be allocated", (unsigned long long)(words * 8));
     c->sbc_n = n_cycles; c->sbc_q = min_base_qual; c->sbc_mq = min_mapq;
-    c->sbc_words = words;
-    c->d_sbc = d;
+    c->seg[SEG_SBC] = {d, words};
     return 0;
 }
 
@@ -834,9 +763,8 @@ extern "C" int bqc_enable_site_alleles(bqc_ctx* c, uint32_t n_sites, const int32
         if (i && (rid[i] < rid[i - 1] || (rid[i] == rid[i - 1] && pos[i] <= pos[i - 1])))
             return fail(c, BQC_ERR_ARG, "bqc_enable_site_alleles: site %u: (contig %d, position %d) does not lie behind its predecessor (%d, %d)", i, rid[i], pos[i], rid[i - 1], pos[i - 1]);
     }
-    if (c->d_sac) return fail(c, BQC_ERR_STATE, "bqc_enable_site_alleles: the module is on already (%u sites)", c->sac_s);
-    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
-        return fail(c, BQC_ERR_STATE, "bqc_enable_site_alleles: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    if (c->seg[SEG_SAC].d) return fail(c, BQC_ERR_STATE, "bqc_enable_site_alleles: the module is on already (%u sites)", c->sac_s);
+    if (int rc = too_late(c, __func__)) return rc;
     std::vector<uint32_t> first(n_refs + 1, 0), bkt_off(n_refs + 1, 0);
     for (uint32_t i = 0; i < n_sites; ++i) ++first[rid[i] + 1];
     for (uint32_t r = 0; r < n_refs; ++r) first[r + 1] += first[r];
@@ -862,11 +790,10 @@ extern "C" int bqc_enable_site_alleles(bqc_ctx* c, uint32_t n_sites, const int32
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t words = bqc_sac_words(c->opt.n_lanes, n_sites);
     const uint64_t tab_bytes = ((uint64_t)n_sites + tab.size()) * 4;
-    uint64_t* d = nullptr;
+    uint64_t* d = zeroed_words(c, words);
     void* t = nullptr;
-    if (hipMalloc(&d, words * 8) != hipSuccess || hipMalloc(&t, tab_bytes) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess ||
-        hipMemcpy(t, pos, (uint64_t)n_sites * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy((uint32_t*)t + n_sites, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (!d || hipMalloc(&t, tab_bytes) != hipSuccess || hipMemcpy(t, pos, (uint64_t)n_sites * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy((uint32_t*)t + n_sites, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(d);
         (void)hipFree(t);
@@ -881,9 +808,8 @@ extern "C" int bqc_enable_site_alleles(bqc_ctx* c, uint32_t n_sites, const int32
     c->sac_rid.assign(rid, rid + n_sites);
     c->sac_pos.assign(pos, pos + n_sites);
     c->sac_s = n_sites; c->sac_q = min_base_qual; c->sac_mq = min_mapq;
-    c->sac_words = words;
     c->d_sac_tab = t;
-    c->d_sac = d;
+    c->seg[SEG_SAC] = {d, words};
     return 0;
 }
 
@@ -919,9 +845,8 @@ extern "C" int bqc_enable_region_coverage(bqc_ctx* c, uint32_t n_regions, const 
     }
     if ((uint64_t)c->opt.n_lanes * (B + n_regions + 4) > 1ull << 28)
         return fail(c, BQC_ERR_ARG, "bqc_enable_region_coverage: %llu bases in %u regions x %u read groups are more than 268435456 (2^28) words", (unsigned long long)B, n_regions, c->opt.n_lanes);
-    if (c->d_rcv) return fail(c, BQC_ERR_STATE, "bqc_enable_region_coverage: the module is on already (%u regions)", c->rcv_r);
-    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
-        return fail(c, BQC_ERR_STATE, "bqc_enable_region_coverage: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    if (c->seg[SEG_RCV].d) return fail(c, BQC_ERR_STATE, "bqc_enable_region_coverage: the module is on already (%u regions)", c->rcv_r);
+    if (int rc = too_late(c, __func__)) return rc;
     std::vector<uint32_t> off(n_regions + 1, 0), first(n_refs + 1, 0), bkt_off(n_refs + 1, 0);
     for (uint32_t i = 0; i < n_regions; ++i) {
         off[i + 1] = off[i] + (uint32_t)(end[i] - start[i]) + 1u;
@@ -953,12 +878,12 @@ extern "C" int bqc_enable_region_coverage(bqc_ctx* c, uint32_t n_regions, const 
     const uint64_t tab_bytes = (2 * (uint64_t)n_regions + tab.size()) * 4;
     const uint64_t out_words = bqc_rcv_out_words(c->opt.n_lanes, n_regions, n_thresholds, depth_cap);
     const uint64_t out_all = out_words + (uint64_t)c->opt.n_lanes * bqc_rcv_tiles(B, n_regions);
-    uint64_t *d = nullptr, *o = nullptr;
+    uint64_t *d = zeroed_words(c, words), *o = nullptr;
     void* t = nullptr;
-    if (hipMalloc(&d, words * 8) != hipSuccess || hipMalloc(&t, tab_bytes) != hipSuccess || hipMalloc(&o, out_all * 8) != hipSuccess ||
-        hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess || hipMemcpy(t, start, (uint64_t)n_regions * 4, hipMemcpyHostToDevice) != hipSuccess ||
+    if (!d || hipMalloc(&t, tab_bytes) != hipSuccess || hipMalloc(&o, out_all * 8) != hipSuccess ||
+        hipMemcpy(t, start, (uint64_t)n_regions * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy((uint32_t*)t + n_regions, end, (uint64_t)n_regions * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy((uint32_t*)t + 2 * (uint64_t)n_regions, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+        hipMemcpy((uint32_t*)t + 2 * (uint64_t)n_regions, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(d);
         (void)hipFree(t);
@@ -983,11 +908,10 @@ extern "C" int bqc_enable_region_coverage(bqc_ctx* c, uint32_t n_regions, const 
     c->rcv_start.assign(start, start + n_regions);
     c->rcv_end.assign(end, end + n_regions);
     c->rcv_r = n_regions; c->rcv_mq = min_mapq; c->rcv_b = B;
-    c->rcv_words = words;
     c->rcv_out_words = out_words;
     c->d_rcv_tab = t;
     c->d_rcv_out = o;
-    c->d_rcv = d;
+    c->seg[SEG_RCV] = {d, words};
     return 0;
 }
 
@@ -1011,15 +935,13 @@ extern "C" int bqc_enable_window_depth(bqc_ctx* c, uint32_t window, const int32_
     if ((uint64_t)n_lanes * (4 + 3 * NW) > 1ull << 28)
         return fail(c, BQC_ERR_ARG, "bqc_enable_window_depth: %llu windows of %u bases x 3 planes x %u read groups are more than 268435456 (2^28) words", (unsigned long long)NW, window, n_lanes);
     tab[2 * (size_t)n_refs] = (uint32_t)NW;
-    if (c->d_wdp) return fail(c, BQC_ERR_STATE, "bqc_enable_window_depth: the module is on already (windows of %u bases)", c->wdp_tab.W);
-    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
-        return fail(c, BQC_ERR_STATE, "bqc_enable_window_depth: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    if (c->seg[SEG_WDP].d) return fail(c, BQC_ERR_STATE, "bqc_enable_window_depth: the module is on already (windows of %u bases)", c->wdp_tab.W);
+    if (int rc = too_late(c, __func__)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t words = bqc_wdp_words(n_lanes, NW);
-    uint64_t* d = nullptr;
+    uint64_t* d = zeroed_words(c, words);
     void* t = nullptr;
-    if (hipMalloc(&d, words * 8) != hipSuccess || hipMalloc(&t, tab.size() * 4) != hipSuccess || hipMemsetAsync(d, 0, words * 8, c->stream) != hipSuccess ||
-        hipMemcpy(t, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (!d || hipMalloc(&t, tab.size() * 4) != hipSuccess || hipMemcpy(t, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(d);
         (void)hipFree(t);
@@ -1039,9 +961,8 @@ extern "C" int bqc_enable_window_depth(bqc_ctx* c, uint32_t window, const int32_
     c->wdp_len.assign(tab.begin(), tab.begin() + n_refs);
     c->wdp_woff.assign(tab.begin() + n_refs, tab.end());
     c->wdp_mq = min_mapq;
-    c->wdp_words = words;
     c->d_wdp_tab = t;
-    c->d_wdp = d;
+    c->seg[SEG_WDP] = {d, words};
     return 0;
 }
 
@@ -1053,8 +974,7 @@ extern "C" int bqc_enable_duplicate_sets(bqc_ctx* c, uint64_t capacity)
     if (capacity < 16 || capacity > 1ull << 31)
         return fail(c, BQC_ERR_ARG, "bqc_enable_duplicate_sets: capacity %llu is outside 16 ... 2147483648 (2^31) signatures", (unsigned long long)capacity);
     if (c->d_dup) return fail(c, BQC_ERR_STATE, "bqc_enable_duplicate_sets: the module is on already (capacity %llu)", (unsigned long long)c->dup_tab.capacity);
-    if (c->upload_counter || c->next_ticket > 1 || c->anchor.mode.load() == 1 || c->gcb_closed)
-        return fail(c, BQC_ERR_STATE, "bqc_enable_duplicate_sets: the context has taken a batch, exchanged state or been finalised (the call belongs right behind bqc_create)");
+    if (int rc = too_late(c, __func__)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t C = bqc_dup_slots(capacity);
     const uint64_t bytes = C * sizeof(DupSlot) + (8 + (uint64_t)c->opt.n_lanes * 5 + bqc_dup_out_words()) * 8;
@@ -1101,7 +1021,7 @@ static uint64_t dup_library_size(uint64_t n_reads, uint64_t n_unique)
 extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    c->gcb_closed = true;
+    c->modules_closed = true;
     int rc = bqc_flush(c);
     if (rc) return rc;
     const StateLayout& sl = c->sl;
@@ -1173,10 +1093,9 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
             L.sketch = c->sk_out[l].data();
         }
     }
-    if (c->d_qcyc) { // the printed sizes follow from the sums: cycles from the mate's read lengths, qualities from the table itself
+    if (c->seg[SEG_QCYC].d) { // the printed sizes follow from the sums: cycles from the mate's read lengths, qualities from the table itself
         const uint32_t N = c->opt.qual_by_cycle;
-        c->h_qcyc.resize(c->qcyc_words);
-        HIPCHK(c, hipMemcpy(c->h_qcyc.data(), c->d_qcyc, c->qcyc_words * 8, hipMemcpyDeviceToHost));
+        if ((rc = fetch_segment(c, SEG_QCYC, c->h_qcyc))) return rc;
         c->qcyc_ncyc.assign((size_t)sl.n_lanes * 2, 0);
         c->qcyc_nq.assign((size_t)sl.n_lanes * 2, 0);
         for (uint32_t l = 0; l < sl.n_lanes; ++l)
@@ -1187,12 +1106,11 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
                 c->qcyc_ncyc[l * 2 + m] = std::min(N, c->lanes[l].mate[m].n_cycles);
                 c->qcyc_nq[l * 2 + m] = nq;
             }
-        c->qcyc_final = true;
+        c->finalised[SEG_QCYC] = true;
     }
-    if (c->d_mbc) { // the same for the two tables of a lane and mate: the quality range is that of A (M <= A cell by cell)
+    if (c->seg[SEG_MBC].d) { // the same for the two tables of a lane and mate: the quality range is that of A (M <= A cell by cell)
         const uint32_t N = c->opt.mismatch_by_cycle;
-        c->h_mbc.resize(c->mbc_words);
-        HIPCHK(c, hipMemcpy(c->h_mbc.data(), c->d_mbc, c->mbc_words * 8, hipMemcpyDeviceToHost));
+        if ((rc = fetch_segment(c, SEG_MBC, c->h_mbc))) return rc;
         c->mbc_ncyc.assign((size_t)sl.n_lanes * 2, 0);
         c->mbc_nq.assign((size_t)sl.n_lanes * 2, 0);
         for (uint32_t l = 0; l < sl.n_lanes; ++l)
@@ -1203,31 +1121,27 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
                 c->mbc_ncyc[l * 2 + m] = std::min(N, c->lanes[l].mate[m].n_cycles);
                 c->mbc_nq[l * 2 + m] = nq;
             }
-        c->mbc_final = true;
+        c->finalised[SEG_MBC] = true;
     }
-    if (c->d_adp) { // the printed length follows from the module's own sums: the longest examined read of the lane and mate, cut at N
+    if (c->seg[SEG_ADP].d) { // the printed length follows from the module's own sums: the longest examined read of the lane and mate, cut at N
         const uint32_t N = c->adp_n;
-        c->h_adp.resize(c->adp_words);
-        HIPCHK(c, hipMemcpy(c->h_adp.data(), c->d_adp, c->adp_words * 8, hipMemcpyDeviceToHost));
+        if ((rc = fetch_segment(c, SEG_ADP, c->h_adp))) return rc;
         c->adp_ncyc.assign((size_t)sl.n_lanes * 2, 0);
         for (uint32_t l = 0; l < sl.n_lanes; ++l)
             for (uint32_t m = 0; m < 2; ++m)
                 c->adp_ncyc[l * 2 + m] = last_nonzero_len(c->h_adp.data() + (((uint64_t)l * 2 + m) * BQC_ADP_ROWS + BQC_ADP_MAX) * N, N);
-        c->adp_final = true;
+        c->finalised[SEG_ADP] = true;
     }
-    if (c->d_rcv) { // k_rcv_final: the depths from the difference words, which it leaves as they are
+    if (c->seg[SEG_RCV].d) { // k_rcv_final: the depths from the difference words, which it leaves as they are
         const uint32_t n_lanes = c->opt.n_lanes, R = c->rcv_r;
-        c->rcv_final = false;
-        const bool timed = c->timing && c->ev.size() >= 2 && !c->d_gcb; // (bqc_last_timing then shows this pass, as it shows k_gcb_genome: a batch's kernels are over)
-        if (timed) { c->n_timed = 0; c->tnames.clear(); (void)hipEventRecord(c->ev[0], c->stream); }
-        bqc_launch_rcv_final(c->d_rcv, c->rcv_regions, c->rcv_fp, n_lanes, c->d_rcv_out + c->rcv_out_words, c->d_rcv_out, c->stream);
-        if (timed) { (void)hipEventRecord(c->ev[1], c->stream); c->tnames.push_back("k_rcv_final"); c->n_timed = 1; }
+        c->finalised[SEG_RCV] = false;
+        timed_launch(c, !c->seg[SEG_GCB].d, "k_rcv_final", [&] { bqc_launch_rcv_final(c->seg[SEG_RCV].d, c->rcv_regions, c->rcv_fp, n_lanes, c->d_rcv_out + c->rcv_out_words, c->d_rcv_out, c->stream); });
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->h_rcv_out.resize(c->rcv_out_words);
         HIPCHK(c, hipMemcpy(c->h_rcv_out.data(), c->d_rcv_out, c->rcv_out_words * 8, hipMemcpyDeviceToHost));
         c->h_rcv_eta.assign((size_t)n_lanes * 4, 0);
-        HIPCHK(c, hipMemcpy2D(c->h_rcv_eta.data(), 32, c->d_rcv, c->rcv_regions.lane_words * 8, 32, n_lanes, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy2D(c->h_rcv_eta.data(), 32, c->seg[SEG_RCV].d, c->rcv_regions.lane_words * 8, 32, n_lanes, hipMemcpyDeviceToHost));
         const uint64_t bad = c->h_rcv_out[c->rcv_out_words - 1];
         if (bad != ~0ull)
             return fail(c, BQC_ERR_STATE, "bqc_finalize: region coverage: the words are not a difference array of this list of regions: region %llu (contig %d, %d ... %d) does not close at depth 0 (state imported from a context with another list?)",
@@ -1239,14 +1153,11 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
             for (uint32_t k = 0; k < R; ++k) on += c->h_rcv_out[l * lane_out + (uint64_t)k * C];
             c->h_rcv_eta[(size_t)l * 4 + 3] = on;
         }
-        c->rcv_final = true;
+        c->finalised[SEG_RCV] = true;
     }
     if (c->d_dup) { // k_dup_final: the sets by class and size from the table, which it leaves as it is
-        c->dup_final = false;
-        const bool timed = c->timing && c->ev.size() >= 2 && !c->d_gcb && !c->d_rcv; // (as k_rcv_final)
-        if (timed) { c->n_timed = 0; c->tnames.clear(); (void)hipEventRecord(c->ev[0], c->stream); }
-        bqc_launch_dup_final(c->dup_tab, c->d_dup_out, c->n_cu, c->stream);
-        if (timed) { (void)hipEventRecord(c->ev[1], c->stream); c->tnames.push_back("k_dup_final"); c->n_timed = 1; }
+        c->finalised[MOD_DUP] = false;
+        timed_launch(c, !c->seg[SEG_GCB].d && !c->seg[SEG_RCV].d, "k_dup_final", [&] { bqc_launch_dup_final(c->dup_tab, c->d_dup_out, c->n_cu, c->stream); });
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->h_dup_out.resize(bqc_dup_out_words());
@@ -1260,15 +1171,14 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
         }
         for (uint32_t l = 0; l < c->opt.n_lanes; ++l) pairs += c->h_dup_sums[(size_t)l * 5 + 1];
         c->dup_estimate = dup_library_size(pairs, c->dup_sets[1]);
-        c->dup_final = true;
+        c->finalised[MOD_DUP] = true;
     }
-    if (c->d_wdp) { // the sums by contig and the histogram over the main contigs' windows: one pass over a copy of the words, no kernel
+    if (c->seg[SEG_WDP].d) { // the sums by contig and the histogram over the main contigs' windows: one pass over a copy of the words, no kernel
         const uint32_t n_lanes = c->opt.n_lanes, n_refs = c->opt.n_refs, W = c->wdp_tab.W;
         const uint64_t NW = c->wdp_tab.NW, LW = c->wdp_tab.lane_words;
-        c->wdp_final = false;
+        c->finalised[SEG_WDP] = false;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->h_wdp.resize(c->wdp_words);
-        HIPCHK(c, hipMemcpy(c->h_wdp.data(), c->d_wdp, c->wdp_words * 8, hipMemcpyDeviceToHost));
+        if ((rc = fetch_segment(c, SEG_WDP, c->h_wdp))) return rc;
         c->h_wdp_contigs.assign((size_t)n_lanes * n_refs * 3, 0);
         c->h_wdp_hist.assign((size_t)n_lanes * BQC_WDP_HIST_BINS, 0);
         for (uint32_t l = 0; l < n_lanes; ++l) {
@@ -1288,39 +1198,35 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
                 }
             }
         }
-        c->wdp_final = true;
+        c->finalised[SEG_WDP] = true;
     }
-    if (c->d_sac) {
-        c->h_sac.resize(c->sac_words);
-        HIPCHK(c, hipMemcpy(c->h_sac.data(), c->d_sac, c->sac_words * 8, hipMemcpyDeviceToHost));
-        c->sac_final = true;
+    if (c->seg[SEG_SAC].d) {
+        if ((rc = fetch_segment(c, SEG_SAC, c->h_sac))) return rc;
+        c->finalised[SEG_SAC] = true;
     }
-    if (c->d_sbc) {
-        c->h_sbc.resize(c->sbc_words);
-        HIPCHK(c, hipMemcpy(c->h_sbc.data(), c->d_sbc, c->sbc_words * 8, hipMemcpyDeviceToHost));
+    if (c->seg[SEG_SBC].d) {
+        if ((rc = fetch_segment(c, SEG_SBC, c->h_sbc))) return rc;
         const uint32_t N = c->sbc_n;
         c->sbc_ncyc.assign((size_t)sl.n_lanes * 2, 0);
         for (uint32_t l = 0; l < sl.n_lanes; ++l)
             for (int m = 0; m < 2; ++m) // (Y of a (lane, mate): 16 words a cycle)
                 c->sbc_ncyc[l * 2 + m] = (last_nonzero_len(c->h_sbc.data() + ((uint64_t)l * 2 + m) * BQC_SBC_MATE_WORDS(N) + BQC_SBC_X_WORDS, 16 * N) + 15) / 16;
-        c->sbc_final = true;
+        c->finalised[SEG_SBC] = true;
     }
-    if (c->d_ibc) {
-        c->h_ibc.resize(c->ibc_words);
-        HIPCHK(c, hipMemcpy(c->h_ibc.data(), c->d_ibc, c->ibc_words * 8, hipMemcpyDeviceToHost));
+    if (c->seg[SEG_IBC].d) {
+        if ((rc = fetch_segment(c, SEG_IBC, c->h_ibc))) return rc;
         const uint32_t N = c->ibc_n;
         c->ibc_ncyc.assign((size_t)sl.n_lanes * 2, 0);
         for (uint32_t l = 0; l < sl.n_lanes; ++l)
             for (int m = 0; m < 2; ++m) // (row 0 of a (lane, mate): E)
                 c->ibc_ncyc[l * 2 + m] = last_nonzero_len(c->h_ibc.data() + ((uint64_t)l * 2 + m) * BQC_IBC_MATE_WORDS(N), N);
-        c->ibc_final = true;
+        c->finalised[SEG_IBC] = true;
     }
-    if (c->d_gcb) {
+    if (c->seg[SEG_GCB].d) {
         rc = gcb_genome_table(c);
         if (rc) return rc;
-        c->h_gcb.resize(c->gcb_words);
-        HIPCHK(c, hipMemcpy(c->h_gcb.data(), c->d_gcb, c->gcb_words * 8, hipMemcpyDeviceToHost));
-        c->gcb_final = true;
+        if ((rc = fetch_segment(c, SEG_GCB, c->h_gcb))) return rc;
+        c->finalised[SEG_GCB] = true;
     }
     c->counts.n_lanes = sl.n_lanes;
     c->counts.lanes = c->lanes.data();
@@ -1331,8 +1237,8 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
 extern "C" int bqc_qual_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_qbc_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_qcyc) return fail(c, BQC_ERR_STATE, "bqc_qual_by_cycle: the context was created without qual_by_cycle");
-    if (!c->qcyc_final) return fail(c, BQC_ERR_STATE, "bqc_qual_by_cycle: nothing has been finalised");
+    if (!c->seg[SEG_QCYC].d) return fail(c, BQC_ERR_STATE, "bqc_qual_by_cycle: the context was created without qual_by_cycle");
+    if (!c->finalised[SEG_QCYC]) return fail(c, BQC_ERR_STATE, "bqc_qual_by_cycle: nothing has been finalised");
     if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_qual_by_cycle: lane %u / mate %u out of range", lane, mate);
     out->n_cycles = c->qcyc_ncyc[lane * 2 + mate];
     out->n_q = c->qcyc_nq[lane * 2 + mate];
@@ -1344,8 +1250,8 @@ extern "C" int bqc_qual_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_q
 extern "C" int bqc_mismatch_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_mbc_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_mbc) return fail(c, BQC_ERR_STATE, "bqc_mismatch_by_cycle: the context was created without mismatch_by_cycle");
-    if (!c->mbc_final) return fail(c, BQC_ERR_STATE, "bqc_mismatch_by_cycle: nothing has been finalised");
+    if (!c->seg[SEG_MBC].d) return fail(c, BQC_ERR_STATE, "bqc_mismatch_by_cycle: the context was created without mismatch_by_cycle");
+    if (!c->finalised[SEG_MBC]) return fail(c, BQC_ERR_STATE, "bqc_mismatch_by_cycle: nothing has been finalised");
     if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_mismatch_by_cycle: lane %u / mate %u out of range", lane, mate);
     const uint64_t tbl = (uint64_t)c->opt.mismatch_by_cycle * 224;
     out->n_cycles = c->mbc_ncyc[lane * 2 + mate];
@@ -1359,8 +1265,8 @@ extern "C" int bqc_mismatch_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, b
 extern "C" int bqc_adapter_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_adp_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_adp) return fail(c, BQC_ERR_STATE, "bqc_adapter_by_cycle: the context was created without adapter_by_cycle");
-    if (!c->adp_final) return fail(c, BQC_ERR_STATE, "bqc_adapter_by_cycle: nothing has been finalised");
+    if (!c->seg[SEG_ADP].d) return fail(c, BQC_ERR_STATE, "bqc_adapter_by_cycle: the context was created without adapter_by_cycle");
+    if (!c->finalised[SEG_ADP]) return fail(c, BQC_ERR_STATE, "bqc_adapter_by_cycle: nothing has been finalised");
     if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_adapter_by_cycle: lane %u / mate %u out of range", lane, mate);
     out->n_cycles = c->adp_ncyc[lane * 2 + mate];
     out->n_adapters = (uint32_t)c->adp_set.size();
@@ -1374,8 +1280,8 @@ extern "C" int bqc_adapter_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bq
 extern "C" int bqc_gc_bias(bqc_ctx* c, uint32_t lane, bqc_gcb_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_gcb) return fail(c, BQC_ERR_STATE, "bqc_gc_bias: bqc_enable_gc_bias has not been called for the context");
-    if (!c->gcb_final) return fail(c, BQC_ERR_STATE, "bqc_gc_bias: nothing has been finalised");
+    if (!c->seg[SEG_GCB].d) return fail(c, BQC_ERR_STATE, "bqc_gc_bias: bqc_enable_gc_bias has not been called for the context");
+    if (!c->finalised[SEG_GCB]) return fail(c, BQC_ERR_STATE, "bqc_gc_bias: nothing has been finalised");
     if (lane >= c->opt.n_lanes) return fail(c, BQC_ERR_ARG, "bqc_gc_bias: lane %u out of range", lane);
     out->window = c->gcb_w;
     out->n_bins = BQC_GCB_BINS;
@@ -1389,8 +1295,8 @@ extern "C" int bqc_gc_bias(bqc_ctx* c, uint32_t lane, bqc_gcb_view* out)
 extern "C" int bqc_indel_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_ibc_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_ibc) return fail(c, BQC_ERR_STATE, "bqc_indel_by_cycle: bqc_enable_indel_by_cycle has not been called for the context");
-    if (!c->ibc_final) return fail(c, BQC_ERR_STATE, "bqc_indel_by_cycle: nothing has been finalised");
+    if (!c->seg[SEG_IBC].d) return fail(c, BQC_ERR_STATE, "bqc_indel_by_cycle: bqc_enable_indel_by_cycle has not been called for the context");
+    if (!c->finalised[SEG_IBC]) return fail(c, BQC_ERR_STATE, "bqc_indel_by_cycle: nothing has been finalised");
     if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_indel_by_cycle: lane %u / mate %u out of range", lane, mate);
     const uint32_t N = c->ibc_n;
     out->n_cycles = c->ibc_ncyc[lane * 2 + mate];
@@ -1406,8 +1312,8 @@ extern "C" int bqc_indel_by_cycle(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_
 extern "C" int bqc_substitutions(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_sbc_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_sbc) return fail(c, BQC_ERR_STATE, "bqc_substitutions: bqc_enable_substitutions has not been called for the context");
-    if (!c->sbc_final) return fail(c, BQC_ERR_STATE, "bqc_substitutions: nothing has been finalised");
+    if (!c->seg[SEG_SBC].d) return fail(c, BQC_ERR_STATE, "bqc_substitutions: bqc_enable_substitutions has not been called for the context");
+    if (!c->finalised[SEG_SBC]) return fail(c, BQC_ERR_STATE, "bqc_substitutions: nothing has been finalised");
     if (lane >= c->opt.n_lanes || mate > 1) return fail(c, BQC_ERR_ARG, "bqc_substitutions: lane %u / mate %u out of range", lane, mate);
     out->n_cycles = c->sbc_ncyc[lane * 2 + mate];
     out->min_base_qual = c->sbc_q;
@@ -1420,8 +1326,8 @@ extern "C" int bqc_substitutions(bqc_ctx* c, uint32_t lane, uint32_t mate, bqc_s
 extern "C" int bqc_site_alleles(bqc_ctx* c, uint32_t lane, bqc_sac_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_sac) return fail(c, BQC_ERR_STATE, "bqc_site_alleles: bqc_enable_site_alleles has not been called for the context");
-    if (!c->sac_final) return fail(c, BQC_ERR_STATE, "bqc_site_alleles: nothing has been finalised");
+    if (!c->seg[SEG_SAC].d) return fail(c, BQC_ERR_STATE, "bqc_site_alleles: bqc_enable_site_alleles has not been called for the context");
+    if (!c->finalised[SEG_SAC]) return fail(c, BQC_ERR_STATE, "bqc_site_alleles: nothing has been finalised");
     if (lane >= c->opt.n_lanes) return fail(c, BQC_ERR_ARG, "bqc_site_alleles: lane %u out of range", lane);
     out->n_sites = c->sac_s;
     out->min_base_qual = c->sac_q;
@@ -1435,8 +1341,8 @@ extern "C" int bqc_site_alleles(bqc_ctx* c, uint32_t lane, bqc_sac_view* out)
 extern "C" int bqc_region_coverage(bqc_ctx* c, uint32_t lane, bqc_rcv_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_rcv) return fail(c, BQC_ERR_STATE, "bqc_region_coverage: bqc_enable_region_coverage has not been called for the context");
-    if (!c->rcv_final) return fail(c, BQC_ERR_STATE, "bqc_region_coverage: nothing has been finalised");
+    if (!c->seg[SEG_RCV].d) return fail(c, BQC_ERR_STATE, "bqc_region_coverage: bqc_enable_region_coverage has not been called for the context");
+    if (!c->finalised[SEG_RCV]) return fail(c, BQC_ERR_STATE, "bqc_region_coverage: nothing has been finalised");
     if (lane >= c->opt.n_lanes) return fail(c, BQC_ERR_ARG, "bqc_region_coverage: lane %u out of range", lane);
     const uint32_t C = 3 + c->rcv_fp.n_thr;
     const uint64_t lane_out = (uint64_t)c->rcv_r * C + c->rcv_fp.D + 1;
@@ -1463,7 +1369,7 @@ extern "C" int bqc_duplicate_sets(bqc_ctx* c, bqc_dup_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
     if (!c->d_dup) return fail(c, BQC_ERR_STATE, "bqc_duplicate_sets: bqc_enable_duplicate_sets has not been called for the context");
-    if (!c->dup_final) return fail(c, BQC_ERR_STATE, "bqc_duplicate_sets: nothing has been finalised");
+    if (!c->finalised[MOD_DUP]) return fail(c, BQC_ERR_STATE, "bqc_duplicate_sets: nothing has been finalised");
     out->capacity = c->dup_tab.capacity;
     out->n_lanes = c->opt.n_lanes;
     for (uint32_t k = 0; k < 2; ++k) {
@@ -1479,8 +1385,8 @@ extern "C" int bqc_duplicate_sets(bqc_ctx* c, bqc_dup_view* out)
 extern "C" int bqc_window_depth(bqc_ctx* c, uint32_t lane, bqc_wdp_view* out)
 {
     if (!c || !out) return BQC_ERR_ARG;
-    if (!c->d_wdp) return fail(c, BQC_ERR_STATE, "bqc_window_depth: bqc_enable_window_depth has not been called for the context");
-    if (!c->wdp_final) return fail(c, BQC_ERR_STATE, "bqc_window_depth: nothing has been finalised");
+    if (!c->seg[SEG_WDP].d) return fail(c, BQC_ERR_STATE, "bqc_window_depth: bqc_enable_window_depth has not been called for the context");
+    if (!c->finalised[SEG_WDP]) return fail(c, BQC_ERR_STATE, "bqc_window_depth: nothing has been finalised");
     if (lane >= c->opt.n_lanes) return fail(c, BQC_ERR_ARG, "bqc_window_depth: lane %u out of range", lane);
     const uint64_t* w = c->h_wdp.data() + (uint64_t)lane * c->wdp_tab.lane_words;
     out->window = c->wdp_tab.W;

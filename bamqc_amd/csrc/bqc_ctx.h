@@ -139,6 +139,28 @@ struct AnchorEngine {
     std::string err;
 };
 
+// The optional modules' segments of the flat state vector, in the vector's order: [sl.words][sketch], then these.  The order is ABI
+// (vectors are exchanged between processes) and is stated here and nowhere else: bqc_state_words, the four exchange calls, bqc_reset
+// and bqc_destroy walk bqc_ctx::seg, and a segment's offset is the sum of the words in front of it (bqc_api.cpp: seg_start).
+enum Seg {
+    SEG_WDP,  // depth in fixed genome windows: [n_lanes][4 + 3 NW]
+    SEG_RCV,  // depth over given regions: [n_lanes][4 + B + R]
+    SEG_SAC,  // allele counts at given sites: [n_lanes][S][8: strand x base]
+    SEG_SBC,  // substitutions: [n_lanes][2 mates]{X [2 strands][64][4], Y [N][16]}
+    SEG_IBC,  // indels: [n_lanes][2 mates]{[3: E, IC, DC][N], [2: IL, DL][64]}
+    SEG_GCB,  // GC bias: [n_lanes][3: R, B, Q][101]
+    SEG_ADP,  // adapter content by cycle: [n_lanes][2][9: slots 0..7, then E][N]
+    SEG_MBC,  // mismatches by cycle and base quality: [n_lanes][2][2: A, M][N][224]
+    SEG_QCYC, // base quality by cycle: [n_lanes][2][N][224]
+    N_SEG,
+    MOD_DUP = N_SEG, // the duplicate sets: a module with views (bqc_ctx::finalised), no part of the vector
+    N_MOD
+};
+struct StateSeg {
+    uint64_t* d = nullptr; // the module's words in device memory (nullptr: the module is off)
+    uint64_t words = 0;
+};
+
 struct bqc_ctx {
     bqc_options opt{};
     std::vector<uint8_t> main_chrom;
@@ -203,75 +225,52 @@ struct bqc_ctx {
     AnchorEngine anchor;
     // sketch (N1)
     SketchDevice* sketch = nullptr;
+    // the optional modules (each: nothing of it exists while it is off)
+    StateSeg seg[N_SEG];               // their words of the state vector
+    bool finalised[N_MOD] = {};        // per module: bqc_finalize has made its views since the last bqc_reset
+    bool modules_closed = false;       // state has been exported, imported or finalised: the bqc_enable_* calls come too late
     // per-cycle base quality histograms (k_qcyc.hip; bqc_options.qual_by_cycle = N, 0: off — nothing below exists then)
-    uint64_t* d_qcyc = nullptr;        // [n_lanes][2][N][224], the module's words of the state vector (behind the sketch's)
-    uint64_t qcyc_words = 0;
     std::vector<uint64_t> h_qcyc;      // bqc_finalize's copy, and per (lane, mate) the printed sizes
     std::vector<uint32_t> qcyc_ncyc, qcyc_nq;
-    bool qcyc_final = false;
     // mismatches by cycle and base quality (k_mbc.hip; bqc_options.mismatch_by_cycle = N, 0: off — nothing below exists then)
-    uint64_t* d_mbc = nullptr;         // [n_lanes][2][2: A, M][N][224], the module's words of the state vector (behind the sketch's, in front of d_qcyc's)
-    uint64_t mbc_words = 0;
     std::vector<uint64_t> h_mbc;       // bqc_finalize's copy, and per (lane, mate) the printed sizes
     std::vector<uint32_t> mbc_ncyc, mbc_nq;
-    bool mbc_final = false;
     // adapter content by cycle (k_adp.hip; bqc_modules.adapter_by_cycle = N through bqc_create_ex, 0: off — nothing below exists then)
     uint32_t adp_n = 0;                // the capacity N
     std::vector<std::string> adp_names, adp_seqs; // the set in use: the context's own copies
     std::vector<bqc_adapter> adp_set;  // ... as bqc_adp_view shows it
     AdpPatterns adp_pat{};
-    uint64_t* d_adp = nullptr;         // [n_lanes][2][9: slots 0..7, then E][N], the module's words of the state vector (behind the sketch's, in front of d_mbc's)
-    uint64_t adp_words = 0;
     std::vector<uint64_t> h_adp;       // bqc_finalize's copy, and per (lane, mate) the printed length
     std::vector<uint32_t> adp_ncyc;
-    bool adp_final = false;
     // GC bias (k_gcb.hip; bqc_enable_gc_bias(W) after creation — nothing below exists without it)
     uint32_t gcb_w = 0;                // the window length W
     GcbDiv gcb_div{};                  // the reciprocals of W - n, n = 0..4
-    uint64_t* d_gcb = nullptr;         // [n_lanes][3: R, B, Q][101], the module's words of the state vector (behind the sketch's, in front of d_adp's)
-    uint64_t gcb_words = 0;
     uint64_t* d_gcb_g = nullptr;       // [101] the genome table G: bqc_finalize's, not part of the state vector
     GcbContig* d_gcb_tab = nullptr;    // [n_refs] the contigs of the genome table's launch
     std::vector<uint64_t> h_gcb, h_gcb_g; // bqc_finalize's copies
-    bool gcb_final = false;
-    bool gcb_closed = false;           // state has been exported, imported or finalised: bqc_enable_gc_bias / _indel_by_cycle / _substitutions come too late
     // indels by cycle and by length (k_ibc.hip; bqc_enable_indel_by_cycle(N) after creation — nothing below exists without it)
     uint32_t ibc_n = 0;                // the cycle capacity N
-    uint64_t* d_ibc = nullptr;         // [n_lanes][2 mates]{[3: E, IC, DC][N], [2: IL, DL][64]}, the module's words of the state vector (behind the sketch's, in front of d_gcb's)
-    uint64_t ibc_words = 0;
     std::vector<uint64_t> h_ibc;       // bqc_finalize's copy, and per (lane, mate) the printed length
     std::vector<uint32_t> ibc_ncyc;
-    bool ibc_final = false;
     // substitutions by context and by cycle (k_sbc.hip; bqc_enable_substitutions(N, Q, MQ) after creation — nothing below exists without it)
     uint32_t sbc_n = 0, sbc_q = 0, sbc_mq = 0; // the cycle capacity N, the minimum base quality, the minimum mapping quality
-    uint64_t* d_sbc = nullptr;         // [n_lanes][2 mates]{X [2 strands][64][4], Y [N][16]}, the module's words of the state vector (behind the sketch's, in front of d_ibc's)
-    uint64_t sbc_words = 0;
     std::vector<uint64_t> h_sbc;       // bqc_finalize's copy, and per (lane, mate) the printed length
     std::vector<uint32_t> sbc_ncyc;
-    bool sbc_final = false;
     // allele counts at given sites (k_sac.hip; bqc_enable_site_alleles(sites, Q, MQ) after creation — nothing below exists without it)
     uint32_t sac_s = 0, sac_q = 0, sac_mq = 0; // the number of sites S, the minimum base quality, the minimum mapping quality
-    uint64_t* d_sac = nullptr;         // [n_lanes][S][8: strand x base], the module's words of the state vector (behind the sketch's, in front of d_sbc's)
-    uint64_t sac_words = 0;
     void* d_sac_tab = nullptr;         // the site tables of `sac_sites`, one allocation
     SacSites sac_sites{};
     std::vector<int32_t> sac_rid, sac_pos; // the list as given (bqc_site_alleles' view)
     std::vector<uint64_t> h_sac;       // bqc_finalize's copy
-    bool sac_final = false;
     // depth in fixed genome windows (k_wdp.hip; bqc_enable_window_depth(W, lengths, MQ) after creation — nothing below exists without it)
-    uint64_t* d_wdp = nullptr;         // [n_lanes][4 + 3 NW], the module's words of the state vector (behind the sketch's, in front of d_rcv's)
-    uint64_t wdp_words = 0;
     void* d_wdp_tab = nullptr;         // the tables of `wdp_tab`, one allocation
     WdpTab wdp_tab{};
     uint32_t wdp_mq = 0;               // the minimum mapping quality of the class `good`
     std::vector<uint32_t> wdp_len, wdp_woff; // the contigs' lengths and first windows (n_refs + 1) as the view shows them
     std::vector<uint64_t> h_wdp, h_wdp_contigs, h_wdp_hist; // bqc_finalize's copy of the words, [n_lanes][n_refs][3] and [n_lanes][1001]
-    bool wdp_final = false;
     // depth over given regions (k_rcv.hip; bqc_enable_region_coverage(regions, MQ, thresholds, D) after creation — nothing below exists without it)
     uint32_t rcv_r = 0, rcv_mq = 0;    // the number of regions R, the minimum mapping quality
     uint64_t rcv_b = 0;                // B: the regions' bases
-    uint64_t* d_rcv = nullptr;         // [n_lanes][4 + B + R], the module's words of the state vector (behind the sketch's, in front of d_sac's)
-    uint64_t rcv_words = 0;
     void* d_rcv_tab = nullptr;         // the region tables of `rcv_regions`, one allocation
     RcvRegions rcv_regions{};
     RcvFinal rcv_fp{};                 // the finalize parameters: thresholds and the histogram's cap (not part of the state)
@@ -280,7 +279,6 @@ struct bqc_ctx {
     std::vector<int32_t> rcv_rid, rcv_start, rcv_end; // the list as given (bqc_region_coverage's view)
     std::vector<uint64_t> rcv_thr;     // the thresholds as the view shows them
     std::vector<uint64_t> h_rcv_out, h_rcv_eta; // bqc_finalize's copies: the products, and [n_lanes][4: E, T, A, bases on target]
-    bool rcv_final = false;
     // duplicate sets by alignment signature (k_dup.hip; bqc_enable_duplicate_sets(capacity) after creation — nothing below exists without it,
     // and none of it is part of the state vector)
     DupTable dup_tab{};                // the table's slots (d_dup), the counter of sets behind them, C - 1 and the capacity
@@ -289,7 +287,6 @@ struct bqc_ctx {
     uint64_t* d_dup_out = nullptr;     // k_dup_final's products: [2][256] sets by size, the two largest sets
     std::vector<uint64_t> h_dup_out, h_dup_sums; // bqc_finalize's copies
     uint64_t dup_sets[2] = {0, 0}, dup_estimate = 0;
-    bool dup_final = false;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

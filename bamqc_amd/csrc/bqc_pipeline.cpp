@@ -618,16 +618,16 @@ static int enqueue_batch(bqc_ctx* c, BatchMem& m, bool& forked)
         tick(c, "k_cov");
     }
     if (c->sketch) { sketch_process(c->sketch, d, c->stream); tick(c, "k_sketch"); }
-    if (c->d_qcyc) { bqc_launch_qcyc(d, c->d_qcyc, c->opt.qual_by_cycle, c->opt.n_lanes, c->n_cu, m.n_slow, m.max_len_slow, c->stream); tick(c, "k_qcyc"); }
-    if (c->d_mbc) { bqc_launch_mbc(d, refs, c->d_mbc, c->opt.mismatch_by_cycle, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_mbc"); }
-    if (c->d_sbc) { bqc_launch_sbc(d, refs, c->d_sbc, c->sbc_n, c->sbc_q, c->sbc_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sbc"); }
-    if (c->d_sac) { bqc_launch_sac(d, c->sac_sites, c->d_sac, c->sac_q, c->sac_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sac"); }
-    if (c->d_wdp) { bqc_launch_wdp(d, c->wdp_tab, c->d_wdp, c->wdp_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_wdp"); }
-    if (c->d_rcv) { bqc_launch_rcv(d, c->rcv_regions, c->d_rcv, c->rcv_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_rcv"); }
+    if (c->seg[SEG_QCYC].d) { bqc_launch_qcyc(d, c->seg[SEG_QCYC].d, c->opt.qual_by_cycle, c->opt.n_lanes, c->n_cu, m.n_slow, m.max_len_slow, c->stream); tick(c, "k_qcyc"); }
+    if (c->seg[SEG_MBC].d) { bqc_launch_mbc(d, refs, c->seg[SEG_MBC].d, c->opt.mismatch_by_cycle, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_mbc"); }
+    if (c->seg[SEG_SBC].d) { bqc_launch_sbc(d, refs, c->seg[SEG_SBC].d, c->sbc_n, c->sbc_q, c->sbc_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sbc"); }
+    if (c->seg[SEG_SAC].d) { bqc_launch_sac(d, c->sac_sites, c->seg[SEG_SAC].d, c->sac_q, c->sac_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_sac"); }
+    if (c->seg[SEG_WDP].d) { bqc_launch_wdp(d, c->wdp_tab, c->seg[SEG_WDP].d, c->wdp_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_wdp"); }
+    if (c->seg[SEG_RCV].d) { bqc_launch_rcv(d, c->rcv_regions, c->seg[SEG_RCV].d, c->rcv_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_rcv"); }
     if (c->d_dup) { bqc_launch_dup(d, c->dup_tab, c->d_dup_sums, err, c->opt.n_lanes, c->opt.n_refs, c->n_cu, c->stream); tick(c, "k_dup"); }
-    if (c->d_adp) { bqc_launch_adp(d, c->adp_pat, c->d_adp, c->adp_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_adp"); }
-    if (c->d_gcb) { bqc_launch_gcb_reads(d, refs, c->d_gcb, c->gcb_w, c->gcb_div, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_gcb_reads"); }
-    if (c->d_ibc) { bqc_launch_ibc(d, c->d_ibc, c->ibc_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_ibc"); }
+    if (c->seg[SEG_ADP].d) { bqc_launch_adp(d, c->adp_pat, c->seg[SEG_ADP].d, c->adp_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_adp"); }
+    if (c->seg[SEG_GCB].d) { bqc_launch_gcb_reads(d, refs, c->seg[SEG_GCB].d, c->gcb_w, c->gcb_div, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_gcb_reads"); }
+    if (c->seg[SEG_IBC].d) { bqc_launch_ibc(d, c->seg[SEG_IBC].d, c->ibc_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_ibc"); }
     if (side) { // the join, behind everything the compute stream has of this batch but its last launch
         const int rc = cov_join(c, forked);
         if (rc) return rc;

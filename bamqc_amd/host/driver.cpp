@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <set>
@@ -1633,33 +1634,16 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         const auto c2 = clk::now();
         rc = opt.adapter_by_cycle ? bqc_create_ex(&bo, &bm, &ctx) : bqc_create(&bo, &ctx);
         if (rc) create_err = bqc_last_error(nullptr);
-        else if (opt.gc_bias) { // (the module that is switched on right behind the creation)
-            rc = bqc_enable_gc_bias(ctx, opt.gc_bias);
-            if (rc) create_err = bqc_last_error(ctx);
-        }
-        if (!rc && opt.indel_by_cycle) {
-            rc = bqc_enable_indel_by_cycle(ctx, opt.indel_by_cycle);
-            if (rc) create_err = bqc_last_error(ctx);
-        }
-        if (!rc && opt.substitutions) {
-            rc = bqc_enable_substitutions(ctx, opt.substitutions, opt.subst_min_qual, opt.subst_min_mapq);
-            if (rc) create_err = bqc_last_error(ctx);
-        }
-        if (!rc && !site_rid.empty()) {
-            rc = bqc_enable_site_alleles(ctx, (uint32_t)site_rid.size(), site_rid.data(), site_pos.data(), opt.site_min_qual, opt.site_min_mapq);
-            if (rc) create_err = bqc_last_error(ctx);
-        }
-        if (!rc && !region_rid.empty()) {
-            rc = bqc_enable_region_coverage(ctx, (uint32_t)region_rid.size(), region_rid.data(), region_start.data(), region_end.data(), opt.regions_min_mapq,
-                                            (uint32_t)opt.regions_thresholds.size(), opt.regions_thresholds.data(), opt.regions_depth_cap);
-            if (rc) create_err = bqc_last_error(ctx);
-        }
-        if (!rc && opt.duplicate_sets) {
-            rc = bqc_enable_duplicate_sets(ctx, opt.duplicate_sets_capacity);
-            if (rc) create_err = bqc_last_error(ctx);
-        }
-        if (!rc && opt.window_depth) {
-            rc = bqc_enable_window_depth(ctx, opt.window_depth_size, wdp_lens.data(), opt.window_depth_min_mapq);
+        else { // the modules that are switched on right behind the creation, to the first that fails
+            if (opt.gc_bias) rc = bqc_enable_gc_bias(ctx, opt.gc_bias);
+            if (!rc && opt.indel_by_cycle) rc = bqc_enable_indel_by_cycle(ctx, opt.indel_by_cycle);
+            if (!rc && opt.substitutions) rc = bqc_enable_substitutions(ctx, opt.substitutions, opt.subst_min_qual, opt.subst_min_mapq);
+            if (!rc && !site_rid.empty()) rc = bqc_enable_site_alleles(ctx, (uint32_t)site_rid.size(), site_rid.data(), site_pos.data(), opt.site_min_qual, opt.site_min_mapq);
+            if (!rc && !region_rid.empty())
+                rc = bqc_enable_region_coverage(ctx, (uint32_t)region_rid.size(), region_rid.data(), region_start.data(), region_end.data(), opt.regions_min_mapq,
+                                                (uint32_t)opt.regions_thresholds.size(), opt.regions_thresholds.data(), opt.regions_depth_cap);
+            if (!rc && opt.duplicate_sets) rc = bqc_enable_duplicate_sets(ctx, opt.duplicate_sets_capacity);
+            if (!rc && opt.window_depth) rc = bqc_enable_window_depth(ctx, opt.window_depth_size, wdp_lens.data(), opt.window_depth_min_mapq);
             if (rc) create_err = bqc_last_error(ctx);
         }
         if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
@@ -1970,32 +1954,33 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     hi.lane_names = names.data();
     hi.lane_index = idx.data();
     rc = bqc_write_bamqc(counts, &hi, opt.outputFile.c_str());
-    const std::string qbc_path = opt.outputFile + ".qbc"; // the table of --qual-by-cycle, right after the .bamqc (the context still exists)
-    const int qbc_rc = !rc && opt.qual_by_cycle ? bqc_write_qual_by_cycle(ctx, &hi, qbc_path.c_str()) : 0;
-    const std::string mbc_path = opt.outputFile + ".mbc"; // the tables of --mismatch-by-cycle, behind the .qbc
-    const int mbc_rc = !rc && !qbc_rc && opt.mismatch_by_cycle ? bqc_write_mismatch_by_cycle(ctx, &hi, mbc_path.c_str()) : 0;
-    const std::string adp_path = opt.outputFile + ".adp"; // the tables of --adapter-by-cycle, behind the .mbc
-    const int adp_rc = !rc && !qbc_rc && !mbc_rc && opt.adapter_by_cycle ? bqc_write_adapter_by_cycle(ctx, &hi, adp_path.c_str()) : 0;
-    const std::string gcb_path = opt.outputFile + ".gcb"; // the tables of --gc-bias, behind the .adp
-    const int gcb_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && opt.gc_bias ? bqc_write_gc_bias(ctx, &hi, gcb_path.c_str()) : 0;
-    const std::string ibc_path = opt.outputFile + ".ibc"; // the tables of --indel-by-cycle, behind the .gcb
-    const int ibc_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && opt.indel_by_cycle ? bqc_write_indel_by_cycle(ctx, &hi, ibc_path.c_str()) : 0;
-    const std::string sbc_path = opt.outputFile + ".sbc"; // the tables of --substitutions, behind the .ibc
-    const int sbc_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && opt.substitutions ? bqc_write_substitutions(ctx, &hi, sbc_path.c_str()) : 0;
-    const std::string sac_path = opt.outputFile + ".sac"; // the table of --site-alleles, behind the .sbc
+    // the modules' tables, each in a file of its own beside the .bamqc (the context still exists), in this order, to the first that fails
     std::vector<const char*> sac_names;
     for (const auto& nm : H.ref_names) sac_names.push_back(nm.c_str());
-    const int sac_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !site_rid.empty() ? bqc_write_site_alleles(ctx, &hi, sac_names.data(), n_refs, sac_path.c_str()) : 0;
-    const std::string rcv_path = opt.outputFile + ".rcv"; // the table of --regions, behind the .sac
-    const int rcv_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !region_rid.empty() ? bqc_write_region_coverage(ctx, &hi, sac_names.data(), n_refs, rcv_path.c_str()) : 0;
-    const std::string dup_path = opt.outputFile + ".dup"; // the table of --duplicate-sets, behind the .rcv
-    const int dup_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && opt.duplicate_sets ? bqc_write_duplicate_sets(ctx, &hi, dup_path.c_str()) : 0;
+    struct ModuleFile { bool on; const char* suffix; std::function<int(const char*)> write; };
+    const ModuleFile module_files[] = {
+        {opt.qual_by_cycle != 0, ".qbc", [&](const char* p) { return bqc_write_qual_by_cycle(ctx, &hi, p); }},
+        {opt.mismatch_by_cycle != 0, ".mbc", [&](const char* p) { return bqc_write_mismatch_by_cycle(ctx, &hi, p); }},
+        {opt.adapter_by_cycle != 0, ".adp", [&](const char* p) { return bqc_write_adapter_by_cycle(ctx, &hi, p); }},
+        {opt.gc_bias != 0, ".gcb", [&](const char* p) { return bqc_write_gc_bias(ctx, &hi, p); }},
+        {opt.indel_by_cycle != 0, ".ibc", [&](const char* p) { return bqc_write_indel_by_cycle(ctx, &hi, p); }},
+        {opt.substitutions != 0, ".sbc", [&](const char* p) { return bqc_write_substitutions(ctx, &hi, p); }},
+        {!site_rid.empty(), ".sac", [&](const char* p) { return bqc_write_site_alleles(ctx, &hi, sac_names.data(), n_refs, p); }},
+        {!region_rid.empty(), ".rcv", [&](const char* p) { return bqc_write_region_coverage(ctx, &hi, sac_names.data(), n_refs, p); }},
+        {opt.duplicate_sets != 0, ".dup", [&](const char* p) { return bqc_write_duplicate_sets(ctx, &hi, p); }},
+        {opt.window_depth != 0, ".wdp", [&](const char* p) { return bqc_write_window_depth(ctx, &hi, sac_names.data(), n_refs, p); }},
+    };
+    std::string path = opt.outputFile; // the file last written: where rc, the one that failed
+    for (const ModuleFile& f : module_files) {
+        if (rc) break;
+        if (!f.on) continue;
+        path = opt.outputFile + f.suffix;
+        rc = f.write(path.c_str());
+    }
     const auto t_write = clk::now();
     // the program proper (tools/bamqualcheck.cpp sets BQC_FAST_EXIT) leaves without the static destructors of the HIP runtime:
     // the output file is complete and closed, the process is about to end anyway
-    const std::string wdp_path = opt.outputFile + ".wdp"; // the table of --window-depth, behind the .dup
-    const int wdp_rc = !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && !dup_rc && opt.window_depth ? bqc_write_window_depth(ctx, &hi, sac_names.data(), n_refs, wdp_path.c_str()) : 0;
-    const bool fast_exit = !S && !rc && !qbc_rc && !mbc_rc && !adp_rc && !gcb_rc && !ibc_rc && !sbc_rc && !sac_rc && !rcv_rc && !dup_rc && !wdp_rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
+    const bool fast_exit = !S && !rc && getenv("BQC_FAST_EXIT") && getenv("BQC_FAST_EXIT")[0] == '1'; // (a session: its owner leaves, behind the last job)
     const char* done_fd = fast_exit ? getenv("BQC_DONE_FD") : nullptr; // the front end (tools/bamqualcheck.cpp) waits for a byte there
     auto teardown = [&]() { // (device memory and page locks are released explicitly: left to the kernel's process teardown they cost 0.2 s more)
         destroy_ctx();
@@ -2008,17 +1993,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
                 secs(t_begin, t_fasta), t_create_s, secs(t_fasta, t_create), secs(t_create, t_setup), secs(t_setup, t_loop_end), secs(t_loop_end, t_final), secs(t_final, t_write),
                 secs(t_write, clk::now()), done_fd ? " (the context is released after the run has been reported complete)" : "");
     }
-    if (rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", opt.outputFile.c_str()); return 1; }
-    if (qbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", qbc_path.c_str()); return 1; }
-    if (mbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", mbc_path.c_str()); return 1; }
-    if (adp_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", adp_path.c_str()); return 1; }
-    if (gcb_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", gcb_path.c_str()); return 1; }
-    if (ibc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", ibc_path.c_str()); return 1; }
-    if (sbc_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sbc_path.c_str()); return 1; }
-    if (sac_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", sac_path.c_str()); return 1; }
-    if (rcv_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", rcv_path.c_str()); return 1; }
-    if (dup_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", dup_path.c_str()); return 1; }
-    if (wdp_rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", wdp_path.c_str()); return 1; }
+    if (rc) { fprintf(stderr, "ERROR: Could not write output file %s\n", path.c_str()); return 1; }
     since_launch("done");
     if (fast_exit) { // the program proper leaves without the static destructors of the HIP runtime: the output file is complete and closed
         fflush(stdout); fflush(stderr);
