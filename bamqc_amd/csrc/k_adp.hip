@@ -22,6 +22,7 @@
 // address, which serialises (profiles/r4_lds_atomic.txt) — equal (mate, length) pairs of a wave are counted by ballot and added once.
 #include <algorithm>
 #include "kernels_common.h"
+#include "cigar_walk.h" // share_grid: the launch geometry of a kernel that shares the reads out
 
 #define AD_THREADS 1024
 #define AD_WAVES (AD_THREADS / WAVE)
@@ -218,7 +219,7 @@ extern "C" void bqc_launch_adp(const DevBatch& b, const AdpPatterns& P, uint64_t
     if (b.n_reads == 0) return;
     static const hipError_t attr_once = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_adp), hipFuncAttributeMaxDynamicSharedMemorySize, AD_WORDS * 4);
     (void)attr_once;
-    const uint32_t g = std::max(1u, std::min(n_cu, (uint32_t)(((uint64_t)b.n_reads + 255) / 256)));
-    const uint32_t per = (uint32_t)(((uint64_t)b.n_reads + g - 1) / g);
+    uint32_t per;
+    const uint32_t g = share_grid(b.n_reads, n_cu, &per);
     hipLaunchKernelGGL(k_adp, dim3(g), dim3(AD_THREADS), AD_WORDS * 4, s, b, P, tab, N, n_lanes, per);
 }

@@ -18,13 +18,13 @@
 // a workgroup that finds the word above the capacity at its end (the last one sees every set), sets BQC_DEVERR_DUP in the batch's
 // error record: the stream fails with BQC_ERR_RANGE.  A launch that finds the word above the capacity at its start does nothing.
 //
-// k_dup, per batch.  About one workgroup per CU, DP_WAVES waves; a workgroup takes a contiguous share of the batch's processing order,
-// DP_STEP reads at a time, thread t of a step fetching the fixed columns of the step's read t (those of the next step before this
-// one is inserted).
+// k_dup, per batch.  The walk frame of cigar_walk.h: about one workgroup per CU, DP_WAVES waves; a workgroup takes a contiguous share
+// of the batch's processing order, DP_STEP reads at a time, thread t of a step fetching the fixed columns of the step's read t (those
+// of the next step before this one is inserted).
 // Thread path.  A read of at most DP_T operations: its words are loaded together, lead, trail and reflen come from registers.  A
 // FORWARD read of more operations needs only its leading clips: where one of its first DP_T operations is no clip, it stays here.
-// Wave path.  Every other read of more than DP_T operations is listed in LDS and taken by a wave, 64 operations a pass; the sums are
-// exact (a length has 28 bits: its low 16 and high 12 bits are summed apart).  Lane 0 then inserts the read.
+// Wave path.  Every other read of more than DP_T operations is listed in LDS (StepList) and taken by a wave, 64 operations a pass
+// (CigWalk's loads; the sums are wave_sum_split's, exact).  Lane 0 then inserts the read.
 // Equal signatures of a wave are combined by ballots before the table is touched, one insert with their number — in the waves where
 // some lane's signature is that of the lane beside it (mode bit 0: never; bit 2: in every wave).
 // The slot of a signature is a mix of the whole signature (mode bit 1: a mix of (rid, u5 >> 6, the rest) in the high bits and u5 & 63
@@ -34,9 +34,7 @@
 //
 // k_dup_final, at bqc_finalize only: one pass over the C slots, which it only reads: the sets by class and size into LDS histograms
 // (one add a bin and workgroup to memory), the largest set by a maximum per wave.
-#include <algorithm>
-#include <cstdlib>
-#include "kernels_common.h"
+#include "cigar_walk.h"
 
 #define DP_THREADS 1024
 #define DP_WAVES (DP_THREADS / WAVE)
@@ -44,7 +42,7 @@
 #define DP_T 8                       // operations up to which a read's CIGAR is summed by its own thread
 #define DP_CHECK 64                  // slots of a probe sequence between two looks at the counter of sets
 #define DP_LANES 256                 // read groups (the lane column is a byte)
-#define DP_NONE 0xFFFFFFFFu
+#define DP_NONE WALK_NONE
 #define DP_FTHREADS 256
 
 typedef unsigned long long dp_u64;
@@ -121,15 +119,11 @@ __device__ __forceinline__ DpRead dp_read(const DevBatch& b, uint32_t r, uint32_
 __device__ __forceinline__ DpRead dp_fetch(const DevBatch& b, uint64_t i, uint32_t end, uint32_t n_lanes, uint32_t n_refs)
 {
     const DpRead none{DP_NONE, 0u, 0u, 0u, 0u, 0u, 0, 0, 0};
-    if (i >= end) return none;
-    const uint32_t r = b.order ? b.order[i] : (uint32_t)i;
-    if (r >= b.n_reads) return none;
-    return dp_read(b, r, n_lanes, n_refs);
+    const uint32_t r = batch_read(b, i, end);
+    return r == WALK_NONE ? none : dp_read(b, r, n_lanes, n_refs);
 }
 
 __device__ __forceinline__ bool dp_clip(uint32_t op) { return op == 4u || op == 5u; }
-__device__ __forceinline__ uint32_t dp_glen(uint32_t op, uint32_t n) { return (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ? n : 0u; }
-__device__ __forceinline__ uint64_t dp_sum64(uint32_t v) { return ((uint64_t)wave_sum(v >> 16) << 16) + wave_sum(v & 0xFFFFu); } // v < 2^28, exact
 
 // the two key words of a read (cls 0 or 1) from its clips and its length on the genome
 __device__ __forceinline__ void dp_keys(const DpRead& me, uint64_t lead, uint64_t trail, uint64_t reflen, uint64_t& k0, uint64_t& k1)
@@ -142,9 +136,8 @@ __device__ __forceinline__ void dp_keys(const DpRead& me, uint64_t lead, uint64_
 
 __global__ __launch_bounds__(DP_THREADS) void k_dup(DevBatch b, DupTable T, uint64_t* __restrict__ sums, uint32_t* __restrict__ err, uint32_t n_lanes, uint32_t n_refs, uint32_t per, uint32_t mode)
 {
-    __shared__ uint32_t s_long[2][DP_STEP];                 // the long reads of a step: the threads that fetched them
-    __shared__ uint32_t s_r[2][DP_STEP];                    // their reads, by thread
-    __shared__ uint32_t s_cnt[3][2];                        // [step mod 3]: listed reads, new sets
+    __shared__ StepList<DP_STEP> s_long;                    // the long reads of a step
+    __shared__ uint32_t s_new[3];                           // [step mod 3] new sets: rotated with the list's counters
     __shared__ uint32_t s_full;                             // the table went over its capacity in an earlier batch
     __shared__ unsigned long long s_sum[DP_LANES][5];       // the workgroup's sums by read group
     if (b.desc->fatal) return;
@@ -152,19 +145,19 @@ __global__ __launch_bounds__(DP_THREADS) void k_dup(DevBatch b, DupTable T, uint
     block_sync();
     if (s_full) return;                                     // (the stream has failed; one thread looks, so the whole workgroup leaves or stays)
     const uint32_t tid = threadIdx.x, wave = tid / WAVE, ln = lane_id();
-    const uint64_t begin64 = (uint64_t)blockIdx.x * per;
-    if (begin64 >= b.n_reads) return;
-    const uint32_t begin = (uint32_t)begin64, end = (uint32_t)min((uint64_t)b.n_reads, begin64 + per);
+    uint32_t begin, end;
+    if (!wg_share(b.n_reads, per, begin, end)) return;
     const gmem_u32* cg = (const gmem_u32*)(uintptr_t)b.cigar;
-    if (tid < 6) s_cnt[tid / 2][tid % 2] = 0;
+    s_long.zero();
+    if (tid < 3) s_new[tid] = 0;
     for (uint32_t t = tid; t < DP_LANES * 5; t += DP_THREADS) s_sum[t / 5][t % 5] = 0;
     block_sync();
     bool over = false;
     DpRead nx = dp_fetch(b, (uint64_t)begin + tid, end, n_lanes, n_refs);
-    uint32_t par = 0, cnt = 0;
-    for (uint32_t base = begin; base < end; base += DP_STEP, par ^= 1u, cnt = cnt == 2u ? 0u : cnt + 1u) {
+    StepTurn turn;
+    for (uint32_t base = begin; base < end; base += DP_STEP, turn.next()) {
         const DpRead me = nx;
-        if (end - base > DP_STEP) nx = dp_fetch(b, (uint64_t)base + DP_STEP + tid, end, n_lanes, n_refs); // (in flight while this step is inserted)
+        if (!last_step(base, end, DP_STEP)) nx = dp_fetch(b, (uint64_t)base + DP_STEP + tid, end, n_lanes, n_refs); // (in flight while this step is inserted)
         const bool ex = me.cls != DP_NONE, need = ex && me.cls < 2u, rev = me.info & 1u;
         // the sums, by read group
         {
@@ -203,7 +196,7 @@ __global__ __launch_bounds__(DP_THREADS) void k_dup(DevBatch b, DupTable T, uint
                 if (k < me.nc) {
                     const uint32_t op = w[k] & 15u, n = w[k] >> 4;
                     if (dp_clip(op)) { if (pre) lead += n; else trail += n; }
-                    else { pre = false; trail = 0; reflen += dp_glen(op, n); }
+                    else { pre = false; trail = 0; reflen += cig_glen(op, n); }
                 }
             }
         }
@@ -232,52 +225,39 @@ __global__ __launch_bounds__(DP_THREADS) void k_dup(DevBatch b, DupTable T, uint
         if (ins) fresh = dp_insert(T, k0, k1, n, mode, over);
         {
             const uint64_t fm = __ballot(fresh != 0u);
-            if (fm && ln == 0) atomicAdd(&s_cnt[cnt][1], (uint32_t)__popcll((unsigned long long)fm));
+            if (fm && ln == 0) atomicAdd(&s_new[turn.cnt], (uint32_t)__popcll((unsigned long long)fm));
         }
-        // the long reads are listed
-        const uint64_t bl = __ballot(lng);
-        if (bl) {
-            uint32_t at = 0;
-            if (ln == 0) at = atomicAdd(&s_cnt[cnt][0], (uint32_t)__popcll((unsigned long long)bl));
-            at = __builtin_amdgcn_readfirstlane(at);
-            if (lng) {
-                s_r[par][tid] = me.r;
-                s_long[par][at + (uint32_t)__popcll((unsigned long long)(bl & ((1ull << ln) - 1ull)))] = tid;
-            }
-        }
-        block_sync();
-        const uint32_t n_long = s_cnt[cnt][0];
-        if (tid == 0) { // the step before's counters: added to last in front of this barrier, added to again behind the next
-            const uint32_t pv = cnt ? cnt - 1u : 2u, v = s_cnt[pv][1];
+        s_long.push(turn, lng, me.r); // the long reads are listed
+        const uint32_t n_long = s_long.close(turn);
+        if (tid == 0) { // the step before's new sets: added to last in front of this barrier, added to again behind the next
+            const uint32_t pv = turn.prev(), v = s_new[pv];
             if (v) gadd(T.n_sets, v);
-            s_cnt[pv][0] = 0; s_cnt[pv][1] = 0;
+            s_new[pv] = 0;
         }
         // the wave path: a wave per listed read
         for (uint32_t e = wave; e < n_long; e += DP_WAVES) {
-            const DpRead rd = dp_read(b, __builtin_amdgcn_readfirstlane(s_r[par][s_long[par][e]]), n_lanes, n_refs);
+            const DpRead rd = dp_read(b, __builtin_amdgcn_readfirstlane(s_long.read(turn, s_long.thread(turn, e))), n_lanes, n_refs);
             const uint32_t nc = __builtin_amdgcn_readfirstlane(rd.nc), coff = __builtin_amdgcn_readfirstlane(rd.coff);
             const bool rv = __builtin_amdgcn_readfirstlane(rd.info) & 1u;
             uint64_t ld = 0, tr = 0, rl = 0;
             bool pr = true;
-            uint32_t wd_n = ln < nc ? cg[(uint64_t)coff + ln] : 0u;
+            CigWalk<false> cw;
+            cw.start(cg, coff, nc);
             for (uint32_t p0 = 0; p0 < nc; p0 += WAVE) {
-                const uint32_t wd = wd_n;
-                const bool valid = p0 + ln < nc;
-                const uint32_t kn = p0 + WAVE + ln; // (nc <= 65 535: no wrap)
-                wd_n = kn < nc ? cg[(uint64_t)coff + kn] : 0u;
-                const uint32_t op = wd & 15u, len = wd >> 4;
+                uint32_t op, len;
+                const bool valid = cw.load(p0, op, len);
                 const bool clip = valid && dp_clip(op), other = valid && !clip;
                 const uint64_t ob = __ballot(other);
                 const uint32_t cn = clip ? len : 0u;
-                rl += dp_sum64(other ? dp_glen(op, len) : 0u);
+                rl += wave_sum_split(other ? cig_glen(op, len) : 0u);
                 if (!ob) {
-                    const uint64_t tot = dp_sum64(cn);
+                    const uint64_t tot = wave_sum_split(cn);
                     if (pr) ld += tot; else tr += tot;
                 } else {
                     const uint32_t first = (uint32_t)__ffsll((unsigned long long)ob) - 1u, last = 63u - (uint32_t)__clzll((long long)ob);
-                    if (pr) ld += dp_sum64(ln < first ? cn : 0u);
+                    if (pr) ld += wave_sum_split(ln < first ? cn : 0u);
                     pr = false;
-                    tr = dp_sum64(ln > last ? cn : 0u);
+                    tr = wave_sum_split(ln > last ? cn : 0u);
                 }
                 if (!rv && !pr) break; // (a forward read needs its leading clips only)
             }
@@ -286,10 +266,10 @@ __global__ __launch_bounds__(DP_THREADS) void k_dup(DevBatch b, DupTable T, uint
                 uint64_t q0, q1;
                 dp_keys(rd, ld, tr, rl, q0, q1);
                 fr = dp_insert(T, q0, q1, 1, mode, over);
-                if (fr) atomicAdd(&s_cnt[cnt][1], 1u);
+                if (fr) atomicAdd(&s_new[turn.cnt], 1u);
             }
         }
-        if (end - base <= DP_STEP) break; // (not left to the loop's test: base + DP_STEP may wrap)
+        if (last_step(base, end, DP_STEP)) break;
     }
     if (over) atomicOr(err, BQC_DEVERR_DUP);
     block_sync();
@@ -298,7 +278,7 @@ __global__ __launch_bounds__(DP_THREADS) void k_dup(DevBatch b, DupTable T, uint
         if (v) gadd(sums + t, v); // (a read group with a sum is below n_lanes)
     }
     if (tid == 0) { // what is left of the counters, and the look at the whole
-        const uint64_t v = (uint64_t)s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1];
+        const uint64_t v = (uint64_t)s_new[0] + s_new[1] + s_new[2];
         const dp_u64 before = __hip_atomic_fetch_add((gmem_u64*)(uintptr_t)T.n_sets, (dp_u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (before + v > T.capacity) atomicOr(err, BQC_DEVERR_DUP);
     }
@@ -359,18 +339,14 @@ extern "C" void bqc_launch_dup_clear(const DupTable& T, uint64_t* sums, uint32_t
     (void)hipMemsetAsync(sums, 0, (uint64_t)n_lanes * 5 * 8, s);
 }
 
-// workgroups: about one per CU, a small batch gets fewer; each takes `per` consecutive reads of the processing order.
 // Measuring switches: BQC_DUP_COMBINE=0 leaves equal signatures of a wave uncombined, =2 combines them in every wave;
 // BQC_DUP_HASH=1 keeps u5's low bits in the slot instead of mixing the whole signature.
 extern "C" void bqc_launch_dup(const DevBatch& b, const DupTable& T, uint64_t* sums, uint32_t* err, uint32_t n_lanes, uint32_t n_refs, uint32_t n_cu, hipStream_t s)
 {
     if (b.n_reads == 0) return;
-    static const uint32_t mode = [] {
-        const char *c = getenv("BQC_DUP_COMBINE"), *h = getenv("BQC_DUP_HASH");
-        return (c && c[0] == '0' && !c[1] ? 1u : 0u) | (c && c[0] == '2' && !c[1] ? 4u : 0u) | (h && h[0] == '1' && !h[1] ? 2u : 0u);
-    }();
-    const uint32_t g = std::max(1u, std::min(n_cu, (uint32_t)(((uint64_t)b.n_reads + 255) / 256)));
-    const uint32_t per = (uint32_t)(((uint64_t)b.n_reads + g - 1) / g);
+    static const uint32_t mode = (env_is("BQC_DUP_COMBINE", '0') ? 1u : 0u) | (env_is("BQC_DUP_COMBINE", '2') ? 4u : 0u) | (env_is("BQC_DUP_HASH", '1') ? 2u : 0u);
+    uint32_t per;
+    const uint32_t g = share_grid(b.n_reads, n_cu, &per);
     hipLaunchKernelGGL(k_dup, dim3(g), dim3(DP_THREADS), 0, s, b, T, sums, err, n_lanes, n_refs, per, mode);
 }
 

@@ -28,6 +28,7 @@
 // that changes and at the end; a counted read of another read group (only a step that spans a change holds one) goes to device memory.
 #include <algorithm>
 #include "kernels_common.h"
+#include "cigar_walk.h" // share_grid: the launch geometry of a kernel that shares the reads out
 
 #define GG_THREADS 256
 #define GG_ITEMS 9                   // dwords a thread counts for the scan (odd)
@@ -260,7 +261,7 @@ extern "C" void bqc_launch_gcb_genome(const GcbContig* tab, uint32_t n_contigs, 
 extern "C" void bqc_launch_gcb_reads(const DevBatch& b, const DevRefs& refs, uint64_t* tab, uint32_t W, const GcbDiv& D, uint32_t n_lanes, uint32_t n_cu, hipStream_t s)
 {
     if (b.n_reads == 0) return;
-    const uint32_t g = std::max(1u, std::min(n_cu, (uint32_t)(((uint64_t)b.n_reads + 255) / 256)));
-    const uint32_t per = (uint32_t)(((uint64_t)b.n_reads + g - 1) / g);
+    uint32_t per;
+    const uint32_t g = share_grid(b.n_reads, n_cu, &per);
     hipLaunchKernelGGL(k_gcb_reads, dim3(g), dim3(GR_THREADS), 0, s, b, refs, tab, W, D, n_lanes, per);
 }

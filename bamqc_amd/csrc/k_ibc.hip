@@ -3,16 +3,14 @@
 // length (64 bins, the last one open).  An optional module beside k_qcyc, k_mbc, k_adp and k_gcb_reads: its launch exists only when
 // bqc_enable_indel_by_cycle has been called.  The genome is not read.
 //
-// Mapping.  About one workgroup per CU, IB_WAVES waves; a workgroup takes a contiguous share of the batch's processing order, IB_STEP
-// reads at a time, thread t of a step fetching the columns of the step's read t (and those of the next step before this one is walked).
+// Mapping.  The walk frame of cigar_walk.h: about one workgroup per CU, IB_WAVES waves; a workgroup takes a contiguous share of the
+// batch's processing order, IB_STEP reads at a time, thread t of a step fetching the columns of the step's read t (and those of the
+// next step before this one is walked).
 // Short CIGARs.  A read of at most T operations (T = IB_T = 8 unless the launch says otherwise) is walked by its own thread: its first
 // IB_T words are loaded together into registers, the walk is 64-bit per thread.
 // Long CIGARs.  A read of more operations goes onto a list in LDS; behind the barrier the workgroup's waves take one listed read each at
-// a time.  A pass of a wave is 64 operations, one per lane: the stored index j of an operation is the carry of the passes before plus
-// the exclusive prefix of the pass's query-consuming lengths.  THE SCAN IS 64-BIT, not saturated: a length has 28 bits, so its low 16
-// and its high 12 bits are scanned apart by wave_scan_incl (sums below 2^22 and 2^18) and put together as hi << 16 + lo; the carry is a
-// 64-bit scalar (at most 65 535 x 2^28 < 2^44).  Every comparison of the rule is made on those exact values.  Once the carry has reached
-// L no later operation can be an event (both kinds need j < L), and the read is left.
+// a time, 64 operations a pass (CigWalk without the genome's side: the exact stored index j of every operation).  Once the carry has
+// reached L no later operation can be an event (both kinds need j < L), and the read is left.
 // Tile.  [2 mates][3 rows][IB_C cycles] + [2 mates][2][64] u32 in LDS (25 KiB); cycles at or behind IB_C go to the table in device memory
 // with gadd.  The tile belongs to one read group at a time: it is flushed (non-zero bins only) when the read group changes and at the
 // end.  u32 cannot wrap between flushes: a CIGAR operation adds at most 1 to one cycle bin and 1 to one length bin, a read 1 to one E
@@ -21,9 +19,7 @@
 // Hot bins.  Real data has ONE read length, and nearly every indel has length 1: 64 lanes adding to one LDS address serialise
 // (profiles/r4_lds_atomic.txt) — equal (mate, bin) pairs of a wave are counted by ballot and added once, for E, IL and DL.  IC and DC
 // take plain LDS atomics: an event's cycle is spread over the read.
-#include <algorithm>
-#include <cstdlib>
-#include "kernels_common.h"
+#include "cigar_walk.h"
 
 #define IB_THREADS 1024
 #define IB_WAVES (IB_THREADS / WAVE)
@@ -39,9 +35,8 @@ struct IbRead { uint32_t L, nc, coff, info, lane; }; // info: mate | reverse << 
 __device__ __forceinline__ IbRead ib_fetch(const DevBatch& b, uint64_t i, uint32_t end, uint32_t n_lanes)
 {
     IbRead o{0u, 0u, 0u, 0u, IB_NOLANE};
-    if (i >= end) return o;
-    const uint32_t r = b.order ? b.order[i] : (uint32_t)i;
-    if (r >= b.n_reads) return o;
+    const uint32_t r = batch_read(b, i, end);
+    if (r == WALK_NONE) return o;
     const uint32_t f = b.flag[r], L = b.l_seq[r], g = b.lane[r], nc = b.n_cigar[r];
     if ((f & 0x904u) || !(f & 0xC0u) || !L || !nc || g >= n_lanes) return o;
     o.L = L;
@@ -88,10 +83,6 @@ __device__ __forceinline__ bool ib_event(uint32_t op, uint32_t n, uint64_t j, ui
     }
     return ev && c < N;
 }
-__device__ __forceinline__ uint32_t ib_qlen(uint32_t op, uint32_t n) // bases of the read the operation consumes: M, I, S, =, X
-{
-    return (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) ? n : 0u;
-}
 
 // An event of every lane with `ev` (called by whole waves): its cycle bin by an atomic of its own, its length bin once per distinct
 // (mate, kind, bin) of the wave.  tm: the (lane, mate)'s words in device memory.
@@ -122,9 +113,8 @@ __global__ __launch_bounds__(IB_THREADS) void k_ibc(DevBatch b, uint64_t* __rest
     __shared__ uint32_t s_mm[4];          // [0] lowest, [1] highest read group of the step's examined reads, [2] the next one, [3] listed reads
     if (b.desc->fatal) return;
     const uint32_t tid = threadIdx.x, wave = tid / WAVE, ln = lane_id();
-    const uint64_t begin64 = (uint64_t)blockIdx.x * per;
-    if (begin64 >= b.n_reads) return;
-    const uint32_t begin = (uint32_t)begin64, end = (uint32_t)min((uint64_t)b.n_reads, begin64 + per);
+    uint32_t begin, end;
+    if (!wg_share(b.n_reads, per, begin, end)) return;
     const gmem_u32* cg = (const gmem_u32*)(uintptr_t)b.cigar;
     const uint64_t mw = BQC_IBC_MATE_WORDS(N);
     for (uint32_t t = tid; t < IB_TILE; t += IB_THREADS) tile[t] = 0;
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(IB_THREADS) void k_ibc(DevBatch b, uint64_t* __rest
         uint32_t w[IB_T];
 #pragma unroll
         for (uint32_t k = 0; k < IB_T; ++k) w[k] = thr && k < me.nc ? cg[(uint64_t)me.coff + k] : 0u; // (0: M of no bases, which does nothing)
-        if (end - base > IB_STEP) nx = ib_fetch(b, (uint64_t)base + IB_STEP + tid, end, n_lanes); // (in flight while this step is walked)
+        if (!last_step(base, end, IB_STEP)) nx = ib_fetch(b, (uint64_t)base + IB_STEP + tid, end, n_lanes); // (in flight while this step is walked)
         if (tid == 0) { s_mm[0] = IB_NOLANE; s_mm[1] = 0; s_mm[3] = 0; }
         block_sync();
         if (me.lane != IB_NOLANE) { atomicMin(&s_mm[0], me.lane); atomicMax(&s_mm[1], me.lane); }
@@ -177,7 +167,7 @@ __global__ __launch_bounds__(IB_THREADS) void k_ibc(DevBatch b, uint64_t* __rest
                     const uint32_t op = wd & 15u, n = wd >> 4;
                     uint32_t kind = 0, c = 0;
                     const bool ev = walk && ib_event(op, n, j, me.L, rev, N, kind, c);
-                    j += ib_qlen(op, n);
+                    j += cig_qlen(op, n);
                     ib_count(ev, mate, kind, c, n, tile, tm, N);
                 };
 #pragma unroll
@@ -203,20 +193,14 @@ __global__ __launch_bounds__(IB_THREADS) void k_ibc(DevBatch b, uint64_t* __rest
                 const uint32_t mt = info & 1u;
                 const bool rv = (info >> 1) & 1u;
                 uint64_t* tm = tl + (uint64_t)mt * mw;
-                uint64_t carry = 0;
-                uint32_t wd_n = ln < nc ? cg[(uint64_t)coff + ln] : 0u;
+                CigWalk<false> cw;
+                cw.start(cg, coff, nc, L);
                 for (uint32_t p = 0; p < nc; p += WAVE) {
-                    const uint32_t wd = wd_n;
-                    const uint32_t kn = p + WAVE + ln; // (nc <= 65 535: no wrap)
-                    wd_n = kn < nc ? cg[(uint64_t)coff + kn] : 0u;
-                    const uint32_t op = wd & 15u, n = wd >> 4, q = ib_qlen(op, n);
-                    const uint32_t lo = wave_scan_incl(q & 0xFFFFu), hi = wave_scan_incl(q >> 16);
-                    const uint64_t incl = ((uint64_t)hi << 16) + lo;
-                    uint32_t kind, c;
-                    const bool ev = ib_event(op, n, carry + incl - q, L, rv, N, kind, c);
+                    uint32_t op, n, kind, c; uint64_t jj; int64_t gg;
+                    cw.pass(p, op, n, jj, gg);
+                    const bool ev = ib_event(op, n, jj, L, rv, N, kind, c);
                     ib_count(ev, mt, kind, c, n, tile, tm, N);
-                    carry += ((uint64_t)__builtin_amdgcn_readlane(hi, 63) << 16) + __builtin_amdgcn_readlane(lo, 63);
-                    if (carry >= L) break; // (both kinds of event need j < L)
+                    if (!cw.advance()) break; // (both kinds of event need j < L)
                 }
             }
             if (cur == last) break;
@@ -228,24 +212,19 @@ __global__ __launch_bounds__(IB_THREADS) void k_ibc(DevBatch b, uint64_t* __rest
             cur = s_mm[2];
         }
         block_sync(); // (the step's list is read to here)
-        if (end - base <= IB_STEP) break; // (not left to the loop's test: base + IB_STEP may wrap)
+        if (last_step(base, end, IB_STEP)) break;
     }
     if (tile_lane != IB_NOLANE) ib_flush(tile, tab, tile_lane, N);
 }
 
 extern "C" uint64_t bqc_ibc_words(uint32_t n_lanes, uint32_t N) { return (uint64_t)n_lanes * 2 * BQC_IBC_MATE_WORDS(N); }
 
-// workgroups: about one per CU, a small batch gets fewer; each takes `per` consecutive reads of the processing order.
 // BQC_IBC_T=n (a measuring switch): reads of up to n operations take the thread path instead of IB_T.
 extern "C" void bqc_launch_ibc(const DevBatch& b, uint64_t* tab, uint32_t N, uint32_t n_lanes, uint32_t n_cu, hipStream_t s)
 {
     if (b.n_reads == 0) return;
-    static const uint32_t t_max = [] {
-        const char* e = getenv("BQC_IBC_T");
-        const long v = e && *e ? strtol(e, nullptr, 10) : 0;
-        return v >= IB_T && v <= 65535 ? (uint32_t)v : (uint32_t)IB_T;
-    }();
-    const uint32_t g = std::max(1u, std::min(n_cu, (uint32_t)(((uint64_t)b.n_reads + 255) / 256)));
-    const uint32_t per = (uint32_t)(((uint64_t)b.n_reads + g - 1) / g);
+    static const uint32_t t_max = env_uint("BQC_IBC_T", IB_T, 65535, IB_T);
+    uint32_t per;
+    const uint32_t g = share_grid(b.n_reads, n_cu, &per);
     hipLaunchKernelGGL(k_ibc, dim3(g), dim3(IB_THREADS), 0, s, b, tab, N, n_lanes, per, t_max);
 }

@@ -5,9 +5,9 @@
 //
 // k_rcv, per batch.  A join against intervals, but unlike k_sac's not one that rejects nearly every read: for a panel most reads hit,
 // so there is no survivor list for the short reads: the thread that fetched a read walks it.
-// Mapping.  About one workgroup per CU, RC_WAVES waves; a workgroup takes a contiguous share of the batch's processing order, RC_STEP
-// reads at a time, thread t of a step fetching the fixed columns of the step's read t (those of the next step before this one is
-// walked).
+// Mapping.  The walk frame of cigar_walk.h: about one workgroup per CU, RC_WAVES waves; a workgroup takes a contiguous share of the
+// batch's processing order, RC_STEP reads at a time, thread t of a step fetching the fixed columns of the step's read t (those of the
+// next step before this one is walked).
 // The first region of a base.  rc_find: "the first region of the contig with end > g", through the bucket index over the regions' ends
 // (device_types.h: RcvRegions): one index load and a binary search among the regions that end inside the bucket, at most 12 steps.
 // (mode 1, a measuring switch: a plain binary search over the contig's whole run instead.)
@@ -15,13 +15,11 @@
 // throughout; a CIGAR of one operation is the same code with one load.  The region index k only grows; a match-like operation whose
 // region has been left behind (a deletion, a skip, or plainly the read's progress) looks k up again through the index, and then loops
 // over the regions under it.  Abutting runs are not fused: a +1 and a -1 on one slot cancel in the sum.
-// Wave path.  A read of more than RC_T operations is listed in LDS and taken by a wave, 64 operations a pass: the stored index j and the
-// genome position g of every operation come from k_ibc's exact 64-bit scans (a length has 28 bits: its low 16 and high 12 bits are
-// scanned apart, the carries are 64-bit scalars), then every lane with a match-like operation looks up and takes that operation's
-// regions.  The read is left once the carry of j has reached l_seq.
-// E, T, A.  Three words a read group, so never one atomic a read: a wave sums them over its lanes by read group, the leader adds the
-// sums to the workgroup's LDS copy (read groups below RC_ETA_LANES; the others go to memory per wave), and the workgroup adds its copy
-// to memory once, at its end.
+// Wave path.  A read of more than RC_T operations is listed in LDS (StepList) and taken by a wave, 64 operations a pass (the
+// exact stored index j and genome position g of every operation, CigWalk's arithmetic written out here); every lane with a match-like operation looks up and takes that
+// operation's regions.
+// E, T, A.  Three words a read group: a wave sums them over its lanes by read group and hands them to eta_add (read groups below
+// RC_ETA_LANES in LDS, the others in memory).
 // The difference words go to device memory with gadd.
 //
 // k_rcv_final, at bqc_finalize only, over tiles of RC_TILE slots of a read group's B + R difference words, which it only reads:
@@ -35,9 +33,7 @@
 //                slots end, so a region inside one thread's slots costs one hand-over and a region that spans threads or tiles one per
 //                thread.  The histogram is privatised in LDS (u32, D + 1 <= 16384 bins; a tile adds at most RC_TILE to a bin) and added
 //                to memory bin by bin where not zero.  A closing slot whose prefix is not 0 gives its region's index to an atomic min.
-#include <algorithm>
-#include <cstdlib>
-#include "kernels_common.h"
+#include "cigar_walk.h"
 
 #define RC_THREADS 1024
 #define RC_WAVES (RC_THREADS / WAVE)
@@ -45,21 +41,21 @@
 #define RC_T 8                       // operations up to which a read is walked by a thread
 #define RC_BUCKET_SHIFT 12           // a bucket of the index: 4096 bases
 #define RC_ETA_LANES 64              // read groups whose E, T, A a workgroup sums in LDS
-#define RC_NONE 0xFFFFFFFFu
+#define RC_NONE WALK_NONE
 #define RC_POS_MAX 0x7FFFFFFEll      // the highest base of a region
 #define RC_TILE 4096                 // slots of a finalize tile
 #define RC_FTHREADS 256
 #define RC_PER (RC_TILE / RC_FTHREADS)
 #define RC_HBINS 16384
+static_assert(RC_ETA_LANES == ETA_LANES, "the E, T, A table of cigar_walk.h");
 
 // Read i of the processing order (r == RC_NONE: not examined)
 struct RcRead { uint32_t r, L, nc, coff, lane; int32_t rid, pos; };
 __device__ __forceinline__ RcRead rc_fetch(const DevBatch& b, uint64_t i, uint32_t end, uint32_t n_lanes, uint32_t n_refs, uint32_t MQ)
 {
     RcRead o{RC_NONE, 0u, 0u, 0u, 0u, 0, 0};
-    if (i >= end) return o;
-    const uint32_t r = b.order ? b.order[i] : (uint32_t)i;
-    if (r >= b.n_reads) return o;
+    const uint32_t r = batch_read(b, i, end);
+    if (r == WALK_NONE) return o;
     const uint32_t f = b.flag[r], L = b.l_seq[r], g = b.lane[r], nc = b.n_cigar[r], mq = b.mapq[r];
     const int32_t rid = b.rid[r];
     if ((f & 0xF04u) || mq < MQ || !L || !nc || g >= n_lanes || rid < 0 || (uint32_t)rid >= n_refs) return o;
@@ -95,10 +91,6 @@ __device__ __forceinline__ uint32_t rc_find(const RcvRegions& rg, uint32_t rid, 
     return lo;
 }
 
-__device__ __forceinline__ bool rc_match(uint32_t op) { return op == 0u || op == 7u || op == 8u; }
-__device__ __forceinline__ uint32_t rc_qlen(uint32_t op, uint32_t n) { return (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) ? n : 0u; }
-__device__ __forceinline__ uint32_t rc_glen(uint32_t op, uint32_t n) { return (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ? n : 0u; }
-
 // The covered bases [g, gend) of one operation against the regions from k on (k < send: the first region with end > g).  Leaves k at
 // the first region that may still hold a base at or behind gend.
 __device__ __forceinline__ bool rc_cover(const RcvRegions& rg, uint64_t* diff, uint32_t& k, uint32_t send, int64_t g, int64_t gend)
@@ -119,7 +111,7 @@ __device__ __forceinline__ bool rc_cover(const RcvRegions& rg, uint64_t* diff, u
 }
 
 // E, T and A of the wave's examined reads (ex), summed by read group: one LDS or memory add per sum and read group.  a <= l_seq.
-__device__ __forceinline__ void rc_eta(bool ex, uint32_t lane, bool hit, uint32_t a, unsigned long long (*s_eta)[3], uint64_t* state, uint64_t lane_words)
+__device__ __forceinline__ void rc_eta(bool ex, uint32_t lane, bool hit, uint32_t a, EtaTab s_eta, uint64_t* state, uint64_t lane_words)
 {
     uint64_t m = __ballot(ex);
     while (m) {
@@ -128,43 +120,29 @@ __device__ __forceinline__ void rc_eta(bool ex, uint32_t lane, bool hit, uint32_
         const bool same = ex && lane == gl;
         const uint64_t sm = __ballot(same);
         const uint64_t E = (uint64_t)__popcll((unsigned long long)sm), T = (uint64_t)__popcll((unsigned long long)__ballot(same && hit));
-        const uint64_t A = ((uint64_t)wave_sum(same ? a >> 16 : 0u) << 16) + wave_sum(same ? a & 0xFFFFu : 0u);
-        if (lane_id() == leader) {
-            if (gl < RC_ETA_LANES) {
-                atomicAdd(&s_eta[gl][0], (unsigned long long)E);
-                if (T) atomicAdd(&s_eta[gl][1], (unsigned long long)T);
-                atomicAdd(&s_eta[gl][2], (unsigned long long)A);
-            } else {
-                uint64_t* h = state + (uint64_t)gl * lane_words;
-                gadd(h, E);
-                if (T) gadd(h + 1, T);
-                gadd(h + 2, A);
-            }
-        }
+        const uint64_t A = wave_sum_split(same ? a : 0u);
+        if (lane_id() == leader) eta_add(s_eta, state, lane_words, gl, E, T, A);
         m &= ~sm;
     }
 }
 
 __global__ __launch_bounds__(RC_THREADS) void k_rcv(DevBatch b, RcvRegions rg, uint64_t* __restrict__ state, uint32_t MQ, uint32_t n_lanes, uint32_t per, uint32_t t_max, uint32_t mode)
 {
-    __shared__ uint32_t s_long[2][RC_STEP];                   // the long reads of a step: the threads that fetched them
-    __shared__ uint32_t s_r[2][RC_STEP];                      // their reads, by thread
-    __shared__ uint32_t s_n[3];                               // [step mod 3] listed reads
+    __shared__ StepList<RC_STEP> s_long;                      // the long reads of a step
     __shared__ unsigned long long s_eta[RC_ETA_LANES][3];     // the workgroup's E, T, A by read group
     if (b.desc->fatal) return;
     const uint32_t tid = threadIdx.x, wave = tid / WAVE, ln = lane_id();
-    const uint64_t begin64 = (uint64_t)blockIdx.x * per;
-    if (begin64 >= b.n_reads) return;
-    const uint32_t begin = (uint32_t)begin64, end = (uint32_t)min((uint64_t)b.n_reads, begin64 + per);
+    uint32_t begin, end;
+    if (!wg_share(b.n_reads, per, begin, end)) return;
     const gmem_u32* cg = (const gmem_u32*)(uintptr_t)b.cigar;
-    if (tid < 3) s_n[tid] = 0;
-    if (tid < RC_ETA_LANES * 3) s_eta[tid / 3][tid % 3] = 0;
+    s_long.zero();
+    eta_zero(s_eta);
     block_sync();
     RcRead nx = rc_fetch(b, (uint64_t)begin + tid, end, n_lanes, rg.n_refs, MQ);
-    uint32_t par = 0, cnt = 0; // the step's list and its counter
-    for (uint32_t base = begin; base < end; base += RC_STEP, par ^= 1u, cnt = cnt == 2u ? 0u : cnt + 1u) {
+    StepTurn turn;
+    for (uint32_t base = begin; base < end; base += RC_STEP, turn.next()) {
         const RcRead me = nx;
-        if (end - base > RC_STEP) nx = rc_fetch(b, (uint64_t)base + RC_STEP + tid, end, n_lanes, rg.n_refs, MQ); // (in flight while this step is walked)
+        if (!last_step(base, end, RC_STEP)) nx = rc_fetch(b, (uint64_t)base + RC_STEP + tid, end, n_lanes, rg.n_refs, MQ); // (in flight while this step is walked)
         const bool ex = me.r != RC_NONE, lng = ex && me.nc > t_max;
         // the thread path
         bool hit = false;
@@ -184,7 +162,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_rcv(DevBatch b, RcvRegions rg, u
             auto step = [&](uint32_t wd) {
                 const uint32_t op = wd & 15u, n = wd >> 4;
                 if (done) return;
-                if (rc_match(op)) {
+                if (cig_match(op)) {
                     const uint64_t left = (uint64_t)me.L - j; // (> 0: not done)
                     const uint32_t m = n < left ? n : (uint32_t)left;
                     a += m;
@@ -211,41 +189,30 @@ __global__ __launch_bounds__(RC_THREADS) void k_rcv(DevBatch b, RcvRegions rg, u
             }
         }
         rc_eta(ex && !lng, me.lane, hit, a, s_eta, state, rg.lane_words);
-        // the long reads are listed
-        const uint64_t bl = __ballot(lng);
-        if (bl) {
-            uint32_t at = 0;
-            if (ln == 0) at = atomicAdd(&s_n[cnt], (uint32_t)__popcll((unsigned long long)bl));
-            at = __builtin_amdgcn_readfirstlane(at);
-            if (lng) {
-                s_r[par][tid] = me.r;
-                s_long[par][at + (uint32_t)__popcll((unsigned long long)(bl & ((1ull << ln) - 1ull)))] = tid;
-            }
-        }
-        block_sync();
-        const uint32_t n_long = s_n[cnt];
-        if (tid == 0) s_n[cnt ? cnt - 1u : 2u] = 0; // (the step before's: read last in front of this barrier, added to again behind the next)
+        s_long.push(turn, lng, me.r); // the long reads are listed
+        const uint32_t n_long = s_long.close(turn);
         // the wave path: a wave per listed read
         for (uint32_t e = wave; e < n_long; e += RC_WAVES) {
-            const uint32_t t = s_long[par][e];
-            const uint32_t r = __builtin_amdgcn_readfirstlane(s_r[par][t]);
+            const uint32_t r = __builtin_amdgcn_readfirstlane(s_long.read(turn, s_long.thread(turn, e)));
             const uint32_t L = b.l_seq[r], nc = b.n_cigar[r], coff = b.cigar_off[r], rid = (uint32_t)b.rid[r], lane = b.lane[r];
             const int64_t pos = b.pos[r];
             uint64_t* diff = state + (uint64_t)lane * rg.lane_words + 4u;
-            uint64_t cj = 0, cgp = 0; // the carries: bases of the read and of the genome in front of this pass
             uint32_t la = 0;          // this lane's covered bases (their sum over the lanes is at most L)
             bool lhit = false;
+            // The pass is written out here, not taken from CigWalk (cigar_walk.h, which explains the scans): with the helper this kernel's
+            // long reads measured 1 to 3 % slower than before, with its own loop they do not.
+            uint64_t cj = 0, cgp = 0; // the carries: bases of the read and of the genome in front of this pass
             uint32_t wd_n = ln < nc ? cg[(uint64_t)coff + ln] : 0u;
             for (uint32_t p0 = 0; p0 < nc; p0 += WAVE) {
                 const uint32_t wd = wd_n;
                 const uint32_t kn = p0 + WAVE + ln; // (nc <= 65 535: no wrap)
                 wd_n = kn < nc ? cg[(uint64_t)coff + kn] : 0u;
-                const uint32_t op = wd & 15u, n = wd >> 4, q = rc_qlen(op, n), gl = rc_glen(op, n);
+                const uint32_t op = wd & 15u, n = wd >> 4, q = cig_qlen(op, n), gl = cig_glen(op, n);
                 const uint32_t qlo = wave_scan_incl(q & 0xFFFFu), qhi = wave_scan_incl(q >> 16);
                 const uint32_t glo = wave_scan_incl(gl & 0xFFFFu), ghi = wave_scan_incl(gl >> 16);
                 const uint64_t jj = cj + (((uint64_t)qhi << 16) + qlo) - q;
                 const int64_t gg = pos + (int64_t)(cgp + (((uint64_t)ghi << 16) + glo) - gl);
-                if (rc_match(op) && n && jj < L) {
+                if (cig_match(op) && n && jj < L) {
                     const uint64_t left = (uint64_t)L - jj;
                     const uint32_t m = n < left ? n : (uint32_t)left;
                     la += m;
@@ -256,29 +223,14 @@ __global__ __launch_bounds__(RC_THREADS) void k_rcv(DevBatch b, RcvRegions rg, u
                 cgp += ((uint64_t)__builtin_amdgcn_readlane(ghi, 63) << 16) + __builtin_amdgcn_readlane(glo, 63);
                 if (cj >= L) break; // (every later operation covers nothing)
             }
-            const uint64_t A = ((uint64_t)wave_sum(la >> 16) << 16) + wave_sum(la & 0xFFFFu);
+            const uint64_t A = wave_sum_split(la);
             const bool any = __ballot(lhit) != 0;
-            if (ln == 0) {
-                if (lane < RC_ETA_LANES) {
-                    atomicAdd(&s_eta[lane][0], 1ull);
-                    if (any) atomicAdd(&s_eta[lane][1], 1ull);
-                    atomicAdd(&s_eta[lane][2], (unsigned long long)A);
-                } else {
-                    uint64_t* h = state + (uint64_t)lane * rg.lane_words;
-                    gadd(h, 1);
-                    if (any) gadd(h + 1, 1);
-                    gadd(h + 2, A);
-                }
-            }
+            if (ln == 0) eta_add(s_eta, state, rg.lane_words, lane, 1, any ? 1 : 0, A);
         }
-        if (end - base <= RC_STEP) break; // (not left to the loop's test: base + RC_STEP may wrap)
+        if (last_step(base, end, RC_STEP)) break;
     }
     block_sync();
-    if (tid < RC_ETA_LANES * 3) {
-        const uint32_t l = tid / 3, w = tid % 3;
-        const unsigned long long v = s_eta[l][w];
-        if (v && l < n_lanes) gadd(state + (uint64_t)l * rg.lane_words + w, v);
-    }
+    eta_flush(s_eta, state, rg.lane_words, n_lanes);
 }
 
 // ---- finalize ----------------------------------------------------------------------------------------------------------------------
@@ -441,23 +393,15 @@ extern "C" uint32_t bqc_rcv_tiles(uint64_t B, uint32_t R) { return (uint32_t)((B
 // the words of bqc_launch_rcv_final's `out`
 extern "C" uint64_t bqc_rcv_out_words(uint32_t n_lanes, uint32_t R, uint32_t n_thr, uint32_t D) { return (uint64_t)n_lanes * ((uint64_t)R * (3u + n_thr) + D + 1u) + 1u; }
 
-// workgroups: about one per CU, a small batch gets fewer; each takes `per` consecutive reads of the processing order.
 // Measuring switches: BQC_RCV_T=n sends reads of up to n operations down the thread path instead of RC_T; BQC_RCV_INDEX=0 replaces
 // the bucket index by a binary search over the contig's whole run of regions.
 extern "C" void bqc_launch_rcv(const DevBatch& b, const RcvRegions& rg, uint64_t* state, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t s)
 {
     if (b.n_reads == 0) return;
-    static const uint32_t t_max = [] {
-        const char* e = getenv("BQC_RCV_T");
-        const long v = e && *e ? strtol(e, nullptr, 10) : 0;
-        return v >= RC_T && v <= 65535 ? (uint32_t)v : (uint32_t)RC_T;
-    }();
-    static const uint32_t mode = [] {
-        const char* e = getenv("BQC_RCV_INDEX");
-        return e && e[0] == '0' && !e[1] ? 1u : 0u;
-    }();
-    const uint32_t g = std::max(1u, std::min(n_cu, (uint32_t)(((uint64_t)b.n_reads + 255) / 256)));
-    const uint32_t per = (uint32_t)(((uint64_t)b.n_reads + g - 1) / g);
+    static const uint32_t t_max = env_uint("BQC_RCV_T", RC_T, 65535, RC_T);
+    static const uint32_t mode = env_is("BQC_RCV_INDEX", '0') ? 1u : 0u;
+    uint32_t per;
+    const uint32_t g = share_grid(b.n_reads, n_cu, &per);
     hipLaunchKernelGGL(k_rcv, dim3(g), dim3(RC_THREADS), 0, s, b, rg, state, MQ, n_lanes, per, t_max, mode);
 }
 

@@ -4,18 +4,18 @@
 // genome is not read, nor any base or quality.  The products (sums by contig, the histogram) are made on the host at finalize: there is
 // no second kernel.
 //
-// Mapping.  k_rcv's frame: about one workgroup per CU, WD_WAVES waves; a workgroup takes a contiguous share of the batch's processing
-// order, WD_STEP reads at a time, thread t of a step fetching the fixed columns of the step's read t (those of the next step before this
-// one is walked) and with them its contig's length and first window.
+// Mapping.  The walk frame of cigar_walk.h: about one workgroup per CU, WD_WAVES waves; a workgroup takes a contiguous share of the
+// batch's processing order, WD_STEP reads at a time, thread t of a step fetching the fixed columns of the step's read t (those of the
+// next step before this one is walked) and with them its contig's length and first window.
 // The walk is k_rcv's, operation by operation, 64-bit arithmetic throughout.  A match-like operation's run [g, g + m) is clipped to
 // [0, len) BEFORE its windows are looped over: what the clip takes away goes to X, a deletion or a skip costs nothing whatever its
 // length, and the loop takes at most nw[rid] rounds.
 // Thread path.  A read of at most WD_T operations: the operations are loaded together and walked in registers.  The loops are the
 // WAVE's, not the thread's: operation q of all 64 reads is taken together, then "while any lane has a window left" each lane presents one
 // add (word, bases).  That keeps the lanes in step, which the combining needs.
-// Wave path.  A read of more than WD_T operations is listed in LDS and taken by a wave, 64 operations a pass, with k_ibc's exact 64-bit
-// scans (a length has 28 bits: its low 16 and high 12 bits are scanned apart, the carries are 64-bit scalars); every lane with a
-// match-like operation then presents that operation's windows in the same loop.
+// Wave path.  A read of more than WD_T operations is listed in LDS (StepList) and taken by a wave, 64 operations a pass (CigWalk: the
+// exact stored index j and genome position g of every operation); every lane with a match-like operation then presents that
+// operation's windows in the same loop.
 // Combining (wd_add).  In a sorted file the 64 reads of a wave lie in one or two windows, and the operations of a long read lie side by
 // side: neighbouring lanes add to the same word.  A word is (read group, plane, window) — the index into the state, so two lanes of
 // different read groups or classes never share one.  The lanes' adds are summed over RUNS of equal words among the lanes that have an
@@ -23,19 +23,17 @@
 // atomic a run.  The default rule skips the six steps in a wave where no lane's word is that of the lane with an add below it
 // (shuffled input), which the one ballot already says.
 // BQC_WDP_COMBINE=0 never combines, =2 takes the six steps in every wave; all three give the same words (sums modulo 2^64 commute).
-// E, E_low, X.  Three words a read group, so never one atomic a read: a wave sums them over its lanes by read group, the leader adds the
-// sums to the workgroup's LDS copy (read groups below WD_ETA_LANES; the others go to memory per wave), and the workgroup adds its copy
-// to memory once, at its end.
-#include <algorithm>
-#include <cstdlib>
-#include "kernels_common.h"
+// E, E_low, X.  Three words a read group: a wave sums them over its lanes by read group and hands them to eta_add (read groups below
+// WD_ETA_LANES in LDS, the others in memory).
+#include "cigar_walk.h"
 
 #define WD_THREADS 1024
 #define WD_WAVES (WD_THREADS / WAVE)
 #define WD_STEP WD_THREADS           // reads whose columns a workgroup fetches at a time, one per thread
 #define WD_T 8                       // operations up to which a read is walked by a thread
 #define WD_ETA_LANES 64              // read groups whose E, E_low, X a workgroup sums in LDS
-#define WD_NONE 0xFFFFFFFFu
+#define WD_NONE WALK_NONE
+static_assert(WD_ETA_LANES == ETA_LANES, "the E, E_low, X table of cigar_walk.h");
 
 // floor(g / W) by a multiply and a shift.  With l = ceil(log2 W), shift = 31 + l and mul = ceil(2^shift / W): mul * W = 2^shift + e with
 // 0 <= e < W <= 2^l, so g * mul / 2^shift = g / W + g e / (W 2^shift), and the second term is below 1 / W for every g < 2^31: the
@@ -47,9 +45,8 @@ struct WdRead { uint32_t r, L, nc, coff, lane, len, woff; int32_t pos; bool good
 __device__ __forceinline__ WdRead wd_fetch(const DevBatch& b, const WdpTab& t, uint64_t i, uint32_t end, uint32_t n_lanes, uint32_t MQ)
 {
     WdRead o{WD_NONE, 0u, 0u, 0u, 0u, 0u, 0u, 0, false};
-    if (i >= end) return o;
-    const uint32_t r = b.order ? b.order[i] : (uint32_t)i;
-    if (r >= b.n_reads) return o;
+    const uint32_t r = batch_read(b, i, end);
+    if (r == WALK_NONE) return o;
     const uint32_t f = b.flag[r], L = b.l_seq[r], g = b.lane[r], nc = b.n_cigar[r], mq = b.mapq[r];
     const int32_t rid = b.rid[r];
     if ((f & 0xF04u) || !L || !nc || g >= n_lanes || rid < 0 || (uint32_t)rid >= t.n_refs) return o;
@@ -61,10 +58,6 @@ __device__ __forceinline__ WdRead wd_fetch(const DevBatch& b, const WdpTab& t, u
     o.good = mq >= MQ;
     return o;
 }
-
-__device__ __forceinline__ bool wd_match(uint32_t op) { return op == 0u || op == 7u || op == 8u; }
-__device__ __forceinline__ uint32_t wd_qlen(uint32_t op, uint32_t n) { return (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) ? n : 0u; }
-__device__ __forceinline__ uint32_t wd_glen(uint32_t op, uint32_t n) { return (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ? n : 0u; }
 
 // state[key] += val for every lane with act; the WHOLE WAVE calls.  mode 0: the adds of a run of lanes with one key become one add, in a
 // wave that has such a run; 1: never; 2: the sum is taken in every wave.  A run is over the lanes WITH an add: a lane without one
@@ -121,7 +114,7 @@ __device__ __forceinline__ void wd_windows(bool act, uint32_t lo, uint32_t hi, u
 }
 
 // E, E_low and X of the wave's examined reads (ex), summed by read group: one LDS or memory add per sum and read group.  x <= l_seq.
-__device__ __forceinline__ void wd_eta(bool ex, uint32_t lane, bool good, uint32_t x, unsigned long long (*s_eta)[3], uint64_t* state, uint32_t lane_words)
+__device__ __forceinline__ void wd_eta(bool ex, uint32_t lane, bool good, uint32_t x, EtaTab s_eta, uint64_t* state, uint32_t lane_words)
 {
     uint64_t m = __ballot(ex);
     while (m) {
@@ -131,43 +124,29 @@ __device__ __forceinline__ void wd_eta(bool ex, uint32_t lane, bool good, uint32
         const uint64_t sm = __ballot(same);
         const uint64_t E = (uint64_t)__popcll((unsigned long long)__ballot(same && good)), El = (uint64_t)__popcll((unsigned long long)sm) - E;
         uint64_t X = 0;
-        if (__ballot(same && x != 0u)) X = ((uint64_t)wave_sum(same ? x >> 16 : 0u) << 16) + wave_sum(same ? x & 0xFFFFu : 0u);
-        if (lane_id() == leader) {
-            if (gl < WD_ETA_LANES) {
-                if (E) atomicAdd(&s_eta[gl][0], (unsigned long long)E);
-                if (El) atomicAdd(&s_eta[gl][1], (unsigned long long)El);
-                if (X) atomicAdd(&s_eta[gl][2], (unsigned long long)X);
-            } else {
-                uint64_t* h = state + (uint64_t)gl * lane_words; // (gl < n_lanes: an examined read's)
-                if (E) gadd(h, E);
-                if (El) gadd(h + 1, El);
-                if (X) gadd(h + 2, X);
-            }
-        }
+        if (__ballot(same && x != 0u)) X = wave_sum_split(same ? x : 0u);
+        if (lane_id() == leader) eta_add(s_eta, state, lane_words, gl, E, El, X);
         m &= ~sm;
     }
 }
 
 __global__ __launch_bounds__(WD_THREADS) void k_wdp(DevBatch b, WdpTab t, uint64_t* __restrict__ state, uint32_t MQ, uint32_t n_lanes, uint32_t per, uint32_t mode)
 {
-    __shared__ uint32_t s_long[2][WD_STEP];                   // the long reads of a step: the threads that fetched them
-    __shared__ uint32_t s_r[2][WD_STEP];                      // their reads, by thread
-    __shared__ uint32_t s_n[3];                               // [step mod 3] listed reads
+    __shared__ StepList<WD_STEP> s_long;                      // the long reads of a step
     __shared__ unsigned long long s_eta[WD_ETA_LANES][3];     // the workgroup's E, E_low, X by read group
     if (b.desc->fatal) return;
     const uint32_t tid = threadIdx.x, wave = tid / WAVE, ln = lane_id();
-    const uint64_t begin64 = (uint64_t)blockIdx.x * per;
-    if (begin64 >= b.n_reads) return;
-    const uint32_t begin = (uint32_t)begin64, end = (uint32_t)min((uint64_t)b.n_reads, begin64 + per);
+    uint32_t begin, end;
+    if (!wg_share(b.n_reads, per, begin, end)) return;
     const gmem_u32* cg = (const gmem_u32*)(uintptr_t)b.cigar;
-    if (tid < 3) s_n[tid] = 0;
-    if (tid < WD_ETA_LANES * 3) s_eta[tid / 3][tid % 3] = 0;
+    s_long.zero();
+    eta_zero(s_eta);
     block_sync();
     WdRead nx = wd_fetch(b, t, (uint64_t)begin + tid, end, n_lanes, MQ);
-    uint32_t par = 0, cnt = 0; // the step's list and its counter
-    for (uint32_t base = begin; base < end; base += WD_STEP, par ^= 1u, cnt = cnt == 2u ? 0u : cnt + 1u) {
+    StepTurn turn;
+    for (uint32_t base = begin; base < end; base += WD_STEP, turn.next()) {
         const WdRead me = nx;
-        if (end - base > WD_STEP) nx = wd_fetch(b, t, (uint64_t)base + WD_STEP + tid, end, n_lanes, MQ); // (in flight while this step is walked)
+        if (!last_step(base, end, WD_STEP)) nx = wd_fetch(b, t, (uint64_t)base + WD_STEP + tid, end, n_lanes, MQ); // (in flight while this step is walked)
         const bool ex = me.r != WD_NONE, lng = ex && me.nc > WD_T, thr = ex && !lng;
         // the words of the read's contig: window 0 of the plane `reads` and of the read's plane of bases (lane < n_lanes and
         // woff[rid] + k < NW for a window k of the contig: inside the read group's words)
@@ -201,7 +180,7 @@ __global__ __launch_bounds__(WD_THREADS) void k_wdp(DevBatch b, WdpTab t, uint64
             uint32_t lo = 0, hi = 0;
             if (has) {
                 const uint32_t op = w[q] & 15u, n = w[q] >> 4;
-                if (wd_match(op)) {
+                if (cig_match(op)) {
                     const uint64_t left = (uint64_t)me.L - j; // (> 0: not done)
                     const uint32_t m = n < left ? n : (uint32_t)left;
                     const int64_t a0 = g > 0 ? g : 0, a1 = g + (int64_t)m < (int64_t)me.len ? g + (int64_t)m : (int64_t)me.len;
@@ -224,43 +203,24 @@ __global__ __launch_bounds__(WD_THREADS) void k_wdp(DevBatch b, WdpTab t, uint64
             wd_windows(act, lo, hi, key0, t, state, mode);
         }
         wd_eta(ex, me.lane, me.good, x, s_eta, state, t.lane_words); // (a long read's X follows from its wave)
-        // the long reads are listed
-        const uint64_t bl = __ballot(lng);
-        if (bl) {
-            uint32_t at = 0;
-            if (ln == 0) at = atomicAdd(&s_n[cnt], (uint32_t)__popcll((unsigned long long)bl));
-            at = __builtin_amdgcn_readfirstlane(at);
-            if (lng) {
-                s_r[par][tid] = me.r;
-                s_long[par][at + (uint32_t)__popcll((unsigned long long)(bl & ((1ull << ln) - 1ull)))] = tid;
-            }
-        }
-        block_sync();
-        const uint32_t n_long = s_n[cnt];
-        if (tid == 0) s_n[cnt ? cnt - 1u : 2u] = 0; // (the step before's: read last in front of this barrier, added to again behind the next)
+        s_long.push(turn, lng, me.r); // the long reads are listed
+        const uint32_t n_long = s_long.close(turn);
         // the wave path: a wave per listed read (an examined one: its columns passed wd_fetch's tests)
         for (uint32_t e = wave; e < n_long; e += WD_WAVES) {
-            const uint32_t tt = s_long[par][e];
-            const uint32_t r = __builtin_amdgcn_readfirstlane(s_r[par][tt]);
+            const uint32_t r = __builtin_amdgcn_readfirstlane(s_long.read(turn, s_long.thread(turn, e)));
             const uint32_t L = b.l_seq[r], nc = b.n_cigar[r], coff = b.cigar_off[r], rid = (uint32_t)b.rid[r], lane = b.lane[r];
             const int64_t pos = b.pos[r];
             const int64_t len = t.len[rid]; // (rid < n_refs, lane < n_lanes: wd_fetch let the read through)
             const uint32_t k0 = lane * t.lane_words + 4u + t.woff[rid] + (b.mapq[r] >= MQ ? t.NW : 2u * t.NW);
-            uint64_t cj = 0, cgp = 0; // the carries: bases of the read and of the genome in front of this pass
             uint32_t lx = 0;          // this lane's covered bases off the contig (their sum over the lanes is at most L)
-            uint32_t wd_n = ln < nc ? cg[(uint64_t)coff + ln] : 0u;
+            CigWalk<true> cw;
+            cw.start(cg, coff, nc, L, pos);
             for (uint32_t p0 = 0; p0 < nc; p0 += WAVE) {
-                const uint32_t wd = wd_n;
-                const uint32_t kn = p0 + WAVE + ln; // (nc <= 65 535: no wrap)
-                wd_n = kn < nc ? cg[(uint64_t)coff + kn] : 0u;
-                const uint32_t op = wd & 15u, n = wd >> 4, q = wd_qlen(op, n), gl = wd_glen(op, n);
-                const uint32_t qlo = wave_scan_incl(q & 0xFFFFu), qhi = wave_scan_incl(q >> 16);
-                const uint32_t glo = wave_scan_incl(gl & 0xFFFFu), ghi = wave_scan_incl(gl >> 16);
-                const uint64_t jj = cj + (((uint64_t)qhi << 16) + qlo) - q;
-                const int64_t gg = pos + (int64_t)(cgp + (((uint64_t)ghi << 16) + glo) - gl);
+                uint32_t op, n; uint64_t jj; int64_t gg;
+                cw.pass(p0, op, n, jj, gg);
                 bool act = false;
                 uint32_t lo = 0, hi = 0;
-                if (wd_match(op) && n && jj < L) {
+                if (cig_match(op) && n && jj < L) {
                     const uint64_t left = (uint64_t)L - jj;
                     const uint32_t m = n < left ? n : (uint32_t)left;
                     const int64_t a0 = gg > 0 ? gg : 0, a1 = gg + (int64_t)m < len ? gg + (int64_t)m : len;
@@ -271,39 +231,28 @@ __global__ __launch_bounds__(WD_THREADS) void k_wdp(DevBatch b, WdpTab t, uint64
                         lx += m - (uint32_t)(a1 - a0);
                     } else lx += m;
                 }
-                wd_windows(act, lo, hi, k0, t, state, mode);
-                cj += ((uint64_t)__builtin_amdgcn_readlane(qhi, 63) << 16) + __builtin_amdgcn_readlane(qlo, 63);
-                cgp += ((uint64_t)__builtin_amdgcn_readlane(ghi, 63) << 16) + __builtin_amdgcn_readlane(glo, 63);
-                if (cj >= L) break; // (every later operation covers nothing)
+                wd_windows(act, lo, hi, k0, t, state, mode); // (the whole wave, whatever its lanes hold)
+                if (!cw.advance()) break; // (every later operation covers nothing)
             }
             if (__ballot(lx != 0u)) {
-                const uint64_t X = ((uint64_t)wave_sum(lx >> 16) << 16) + wave_sum(lx & 0xFFFFu);
-                if (ln == 0) {
-                    if (lane < WD_ETA_LANES) atomicAdd(&s_eta[lane][2], (unsigned long long)X);
-                    else gadd(state + (uint64_t)lane * t.lane_words + 2, X);
-                }
+                const uint64_t X = wave_sum_split(lx);
+                if (ln == 0) eta_add(s_eta, state, t.lane_words, lane, 0, 0, X);
             }
         }
-        if (end - base <= WD_STEP) break; // (not left to the loop's test: base + WD_STEP may wrap)
+        if (last_step(base, end, WD_STEP)) break;
     }
     block_sync();
-    if (tid < WD_ETA_LANES * 3) {
-        const uint32_t l = tid / 3, w3 = tid % 3;
-        const unsigned long long v = s_eta[l][w3];
-        if (v && l < n_lanes) gadd(state + (uint64_t)l * t.lane_words + w3, v);
-    }
+    eta_flush(s_eta, state, t.lane_words, n_lanes);
 }
 
 extern "C" uint64_t bqc_wdp_words(uint32_t n_lanes, uint64_t NW) { return (uint64_t)n_lanes * (4u + 3u * NW); }
 
-// workgroups: about one per CU, a small batch gets fewer; each takes `per` consecutive reads of the processing order.
 // Measuring switch, read at every launch: BQC_WDP_COMBINE=0 leaves every lane's add alone, =2 takes the segmented sum in every wave.
 extern "C" void bqc_launch_wdp(const DevBatch& b, const WdpTab& t, uint64_t* state, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t s)
 {
     if (b.n_reads == 0) return;
-    const char* e = getenv("BQC_WDP_COMBINE");
-    const uint32_t mode = e && e[0] == '0' && !e[1] ? 1u : e && e[0] == '2' && !e[1] ? 2u : 0u;
-    const uint32_t g = std::max(1u, std::min(n_cu, (uint32_t)(((uint64_t)b.n_reads + 255) / 256)));
-    const uint32_t per = (uint32_t)(((uint64_t)b.n_reads + g - 1) / g);
+    const uint32_t mode = env_is("BQC_WDP_COMBINE", '0') ? 1u : env_is("BQC_WDP_COMBINE", '2') ? 2u : 0u;
+    uint32_t per;
+    const uint32_t g = share_grid(b.n_reads, n_cu, &per);
     hipLaunchKernelGGL(k_wdp, dim3(g), dim3(WD_THREADS), 0, s, b, t, state, MQ, n_lanes, per, mode);
 }

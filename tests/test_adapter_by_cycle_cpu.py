@@ -191,7 +191,8 @@ def test_launch_constants_are_the_kernels():
     def define(name):
         return re.search(r"#define %s\s+(\S+)" % name, src).group(1)
     assert int(define("AD_THREADS")) == adp_steps.AD_STEP and define("AD_STEP") == "AD_THREADS" and int(define("AD_C")) == adp_steps.AD_C
-    assert "+ 255) / 256" in src  # WG_READS
+    walk = open(os.path.join(ROOT, "bamqc_amd", "csrc", "cigar_walk.h")).read()  # (the launch geometry: stated once)
+    assert "share_grid(b.n_reads" in src and "+ 255) / 256" in walk  # WG_READS
     la = adp_steps.adp_launch(1000, 256)
     assert (la["grid"], la["per"], la["steps"]) == (4, 250, [1, 1, 1, 1])
     lay = adp_steps.step_layout(8)

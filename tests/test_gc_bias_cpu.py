@@ -201,7 +201,8 @@ def test_launch_constants_are_the_kernels():
         return re.search(r"#define %s\s+(\S+)" % name, src).group(1)
     assert int(define("GG_THREADS")) == gcb_steps.GG_THREADS and int(define("GG_ITEMS")) == gcb_steps.GG_ITEMS and int(define("GG_SHARE")) == gcb_steps.GG_SHARE
     assert int(define("GR_THREADS")) == gcb_steps.GR_STEP and define("GR_STEP") == "GR_THREADS"
-    assert "+ 255) / 256" in src  # WG_READS
+    walk = open(os.path.join(ROOT, "bamqc_amd", "csrc", "cigar_walk.h")).read()  # (the launch geometry: stated once)
+    assert "share_grid(b.n_reads" in src and "+ 255) / 256" in walk  # WG_READS
     types = open(os.path.join(ROOT, "bamqc_amd", "csrc", "device_types.h")).read()
     assert re.search(r"#define BQC_GCB_WMIN\s+20\b", types) and re.search(r"#define BQC_GCB_WMAX\s+1000\b", types) and re.search(r"#define BQC_GCB_BINS\s+101\b", types)
     la = gcb_steps.reads_launch(1000, 256)

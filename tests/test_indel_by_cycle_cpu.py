@@ -66,14 +66,15 @@ def test_abi_mirror():
 def test_constants_are_the_kernels():
     src = open(os.path.join(ROOT, "bamqc_amd", "csrc", "k_ibc.hip")).read()
     dev = open(os.path.join(ROOT, "bamqc_amd", "csrc", "device_types.h")).read()
+    walk = open(os.path.join(ROOT, "bamqc_amd", "csrc", "cigar_walk.h")).read()  # (the wave's pass and the launch geometry: stated once)
 
     def define(name, text=src):
         return re.search(r"#define %s\s+(\S+)" % name, text).group(1)
     assert int(define("IB_THREADS")) == ibc_steps.IB_STEP and define("IB_STEP") == "IB_THREADS"
     assert int(define("IB_T")) == ibc_steps.IB_T and int(define("IB_C")) == ibc_steps.IB_C
     assert int(define("BQC_IBC_K", dev)) == ibc_steps.K == ibc_ref.K and int(define("BQC_IBC_ROWS", dev)) == 3
-    assert "p += WAVE" in src and ibc_steps.PASS == 64
-    assert "((uint64_t)b.n_reads + 255) / 256" in src and ibc_steps.WG_READS == 256
+    assert "p += WAVE" in src and "p0 + WAVE + ln" in walk and ibc_steps.PASS == 64
+    assert "share_grid(b.n_reads" in src and "((uint64_t)n_reads + 255) / 256" in walk and ibc_steps.WG_READS == 256
     la = ibc_steps.ibc_launch(1000, 256)
     assert la["grid"] == 4 and la["per"] == 250 and la["steps"] == [1, 1, 1, 1]
     la = ibc_steps.ibc_launch(256 * 1024 + 1, 256)

@@ -15,6 +15,7 @@ from tests.rcv_steps import BUCKET, D, EQ, FIRST, I, LAST, M, N_, P, RC_T, RC_TI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL = open(os.path.join(ROOT, "bamqc_amd", "csrc", "k_rcv.hip")).read()
+WALK = open(os.path.join(ROOT, "bamqc_amd", "csrc", "cigar_walk.h")).read()  # (the wave's pass: stated once)
 
 
 def ask(*args):
@@ -76,8 +77,9 @@ def test_constants_are_the_kernels():
     assert int(define("RC_THREADS")) == rcv_steps.RC_STEP and define("RC_STEP") == "RC_THREADS"
     assert int(define("RC_T")) == RC_T == 8 and 1 << int(define("RC_BUCKET_SHIFT")) == BUCKET == 4096 and int(define("RC_TILE")) == RC_TILE
     assert int(define("RC_POS_MAX").rstrip("l"), 16) == rcv_ref.END_MAX - 1
-    assert RC_TILE % int(define("RC_FTHREADS")) == 0 and int(define("RC_HBINS")) == 16384 and "p0 += WAVE" in KERNEL and rcv_steps.PASS == 64
-    assert "gadd(" in KERNEL and "asm" not in KERNEL
+    assert RC_TILE % int(define("RC_FTHREADS")) == 0 and int(define("RC_HBINS")) == 16384
+    assert "p0 += WAVE" in KERNEL and "p0 + WAVE + ln" in WALK and rcv_steps.PASS == 64
+    assert "gadd(" in KERNEL and "asm" not in KERNEL and "gadd(" in WALK and "asm" not in WALK
     api = open(os.path.join(ROOT, "bamqc_amd", "csrc", "bqc_api.cpp")).read()
     assert "end[first[r + 1] - 1] >> 12" in api and "k << 12" in api  # (the host builds the index with the kernel's bucket)
 

@@ -15,6 +15,7 @@ from tests.sac_steps import D, EQ, FIRST, H, I, LAST, M, N_, P, P_, REV, S, X, c
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL = open(os.path.join(ROOT, "bamqc_amd", "csrc", "k_sac.hip")).read()  # (what tests/sac_steps.py restates the constants of)
+WALK = open(os.path.join(ROOT, "bamqc_amd", "csrc", "cigar_walk.h")).read()  # (the wave's pass and the launch geometry: stated once)
 A, C, G, T = 0, 1, 2, 3
 
 
@@ -75,8 +76,9 @@ def test_constants_are_the_kernels():
     assert int(define("SA_THREADS")) == sac_steps.SA_STEP and define("SA_STEP") == "SA_THREADS"
     assert int(define("SA_T")) == sac_steps.SA_T and 1 << int(define("SA_BUCKET_SHIFT")) == sac_steps.BUCKET
     assert int(define("SA_POS_MAX").rstrip("l"), 16) == sac_steps.POS_MAX == sac_ref.POS_MAX
-    assert "b.n_reads + 255) / 256" in src and sac_steps.WG_READS == 256 and "p0 += WAVE" in src and sac_steps.PASS == 64
-    assert "gadd(" in src and "asm" not in src
+    assert "share_grid(b.n_reads" in src and "n_reads + 255) / 256" in WALK and sac_steps.WG_READS == 256
+    assert "p0 += WAVE" in src and "p0 + WAVE + ln" in WALK and sac_steps.PASS == 64
+    assert "gadd(" in src and "asm" not in src and "gadd(" in WALK and "asm" not in WALK
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
