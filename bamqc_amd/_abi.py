@@ -155,6 +155,16 @@ class DupView(C.Structure):  # bqc_dup_view: by class (0 single, 1 pair) the set
                 ("hist", u64p * 2), ("estimated_library_size", C.c_uint64), ("lanes", u64p)]
 
 
+class OvrSeq(C.Structure):  # bqc_ovr_seq: a listed set's letters, its reads and its possible source
+    _fields_ = [("seq", C.c_char_p), ("count", C.c_uint64), ("source", C.c_char_p)]
+
+
+class OvrView(C.Structure):  # bqc_ovr_view: K, ppm, capacity, lanes [n_lanes][4], by mate the sets, the largest set, 256 sets by size, the threshold and the list
+    _fields_ = [("prefix_len", C.c_uint32), ("ppm", C.c_uint32), ("capacity", C.c_uint64), ("n_lanes", C.c_uint32), ("pad", C.c_uint32), ("lanes", u64p),
+                ("distinct", C.c_uint64 * 2), ("largest", C.c_uint64 * 2), ("hist", u64p * 2), ("threshold", C.c_uint64 * 2), ("n_listed", C.c_uint32 * 2),
+                ("listed", C.POINTER(OvrSeq) * 2)]
+
+
 class WdpView(C.Structure):  # bqc_wdp_view: W, MQ, NW, n_refs, woff [n_refs + 1], ref_len [n_refs], E, E_low, X, three planes [NW], contigs [n_refs][3], hist [1001]
     _fields_ = [("window", C.c_uint32), ("min_mapq", C.c_uint32), ("n_windows", C.c_uint32), ("n_refs", C.c_uint32), ("woff", u32p), ("ref_len", u32p),
                 ("reads_examined", C.c_uint64), ("reads_low_mapq", C.c_uint64), ("bases_outside", C.c_uint64), ("reads", u64p), ("bases", u64p),

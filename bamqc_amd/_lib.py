@@ -80,6 +80,9 @@ _SIGNATURES = {
     "bqc_enable_duplicate_sets": (C.c_int, [C.c_void_p, C.c_uint64]),
     "bqc_duplicate_sets": (C.c_int, [C.c_void_p, C.POINTER(_abi.DupView)]),
     "bqc_write_duplicate_sets": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.c_char_p]),
+    "bqc_enable_overrepresented": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]),
+    "bqc_overrepresented": (C.c_int, [C.c_void_p, C.POINTER(_abi.OvrView)]),
+    "bqc_write_overrepresented": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.c_char_p]),
     "bqc_enable_window_depth": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.c_uint32]),
     "bqc_window_depth": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(_abi.WdpView)]),
     "bqc_write_window_depth": (C.c_int, [C.c_void_p, C.POINTER(_abi.HeaderInfo), C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p]),

@@ -40,7 +40,8 @@ class DeviceBatch:
 class Aggregator:
     def __init__(self, adapter_by_cycle=None, adapters=None, gc_bias=None, indel_by_cycle=None, substitutions=None, subst_min_qual=20, subst_min_mapq=30,
                  site_alleles=None, site_min_qual=20, site_min_mapq=20, regions=None, region_min_mapq=20, region_thresholds=(1, 10, 20, 30, 50, 100),
-                 region_depth_cap=1000, duplicate_sets=None, window_depth=None, window_min_mapq=20, **options):
+                 region_depth_cap=1000, duplicate_sets=None, window_depth=None, window_min_mapq=20, overrepresented=None, overrepresented_ppm=1000,
+                 **options):
         self.lib = _lib.load()
         self.opt, self._keep = _abi.make_options(**options)
         self.h = C.c_void_p()
@@ -99,6 +100,16 @@ class Aggregator:
             except BamQCError:
                 self.close()
                 raise
+
+        if overrepresented is not None:  # the same way: sets of equal read sequences, overrepresented = (K, capacity)
+            try:
+                self.enable_overrepresented(overrepresented[0], overrepresented_ppm, overrepresented[1])
+            except BamQCError:
+                self.close()
+                raise
+
+    def enable_overrepresented(self, prefix_len=50, ppm=1000, capacity=1 << 26):
+        self._chk(self.lib.bqc_enable_overrepresented(self.h, prefix_len, ppm, capacity))
 
     def enable_window_depth(self, window=1000, ref_len=None, min_mapq=20):
         """ref_len: the lengths of the context's n_refs contigs (None: a null list, which the library refuses)."""
@@ -391,6 +402,29 @@ class Aggregator:
             self.finalize_raw()
         hdr, keep = self._header(sample_id, lane_names, lane_index)
         self._chk(self.lib.bqc_write_duplicate_sets(self.h, C.byref(hdr), path.encode()))
+
+    def overrepresented(self):
+        """The sets of equal read sequences over all read groups (option overrepresented=(K, capacity); valid after finalize): a dict of K,
+        ppm, capacity, lanes (n_lanes, 4) — examined first, examined second, skipped first, skipped second — and by mate distinct (2,),
+        largest (2,), hist (2, 256) (hist[m][i - 1]: the sets of i reads, the last bin open), threshold (2,) and listed: two lists of
+        (sequence, count, possible source), sorted by count descending, then sequence."""
+        if self._counts is None:
+            self.finalize_raw()
+        v = _abi.OvrView()
+        self._chk(self.lib.bqc_overrepresented(self.h, C.byref(v)))
+        return {"K": int(v.prefix_len), "ppm": int(v.ppm), "capacity": int(v.capacity),
+                "lanes": np.ctypeslib.as_array(v.lanes, shape=(v.n_lanes, 4)).copy(),
+                "distinct": np.array(list(v.distinct), np.uint64), "largest": np.array(list(v.largest), np.uint64),
+                "hist": np.stack([np.ctypeslib.as_array(v.hist[m], shape=(256,)).copy() for m in range(2)]),
+                "threshold": np.array(list(v.threshold), np.uint64),
+                "listed": [[(v.listed[m][e].seq.decode(), int(v.listed[m][e].count), v.listed[m][e].source.decode()) for e in range(v.n_listed[m])] for m in range(2)]}
+
+    def write_overrepresented(self, path, sample_id="", lane_names=("",), lane_index=None):
+        """The `.ovr` text."""
+        if self._counts is None:
+            self.finalize_raw()
+        hdr, keep = self._header(sample_id, lane_names, lane_index)
+        self._chk(self.lib.bqc_write_overrepresented(self.h, C.byref(hdr), path.encode()))
 
     def window_depth(self, lane=0):
         """The depth of a read group in fixed genome windows (option window_depth=(W, ref_len); valid after finalize): a dict of window,

@@ -3,6 +3,26 @@
 #pragma once
 #include <cstring>
 #include <string>
+#include "../../include/bamqc.h"
+
+// The built-in adapter set (include/bamqc.h), in the set's order: bqc_create_ex's when none is given, and what the overrepresented
+// sequences' possible source is looked up in.
+inline const bqc_adapter* bqc_builtin_adapters(uint32_t* n)
+{
+    static const bqc_adapter builtin[] = {{"Illumina_Universal", "AGATCGGAAGAG"}, {"Illumina_SmallRNA_3p", "TGGAATTCTCGG"}, {"Illumina_SmallRNA_5p", "GATCGTCGGACT"},
+                                          {"Nextera_Transposase", "CTGTCTCTTATA"}, {"PolyA", "AAAAAAAAAAAA"}, {"PolyG", "GGGGGGGGGGGG"}};
+    *n = (uint32_t)(sizeof builtin / sizeof builtin[0]);
+    return builtin;
+}
+// the name of the first built-in adapter that occurs letter for letter in `seq`, else "-"
+inline const char* bqc_possible_source(const char* seq)
+{
+    uint32_t n;
+    const bqc_adapter* set = bqc_builtin_adapters(&n);
+    for (uint32_t a = 0; a < n; ++a)
+        if (strstr(seq, set[a].seq)) return set[a].name;
+    return "-";
+}
 
 // "" when the adapter is good, else what is wrong with it, naming the offending thing
 inline std::string bqc_adapter_fault(const char* name, const char* seq)

@@ -42,6 +42,9 @@ uint64_t bqc_dup_slots(uint64_t capacity);
 uint64_t bqc_dup_out_words(void);
 void bqc_launch_dup_clear(const DupTable& T, uint64_t* sums, uint32_t n_lanes, uint32_t n_cu, hipStream_t s);
 void bqc_launch_dup_final(const DupTable& T, uint64_t* out, uint32_t n_cu, hipStream_t s);
+uint64_t bqc_ovr_out_words(uint64_t list_cap);
+void bqc_launch_ovr_clear(const DupTable& T, uint64_t* sums, uint32_t n_lanes, uint32_t n_cu, hipStream_t s);
+void bqc_launch_ovr_final(const DupTable& T, const uint64_t* thr, uint64_t* out, uint64_t list_cap, uint32_t* err, uint32_t n_cu, hipStream_t s);
 uint32_t bqc_gcb_share(void);
 void bqc_launch_gcb_genome(const GcbContig* tab, uint32_t n_contigs, uint64_t n_shares, uint32_t W, const GcbDiv& D, uint64_t* G, uint32_t n_cu, hipStream_t s);
 hipError_t bqc_long_init();
@@ -91,10 +94,10 @@ static int reset_stream_records(bqc_ctx* c)
 // n_adapters = 0: the built-in set.  Returns 0, or BQC_ERR_ARG with the message set.
 static int adapter_set(const bqc_modules* mod, std::vector<std::string>& names, std::vector<std::string>& seqs, AdpPatterns& P)
 {
-    static const bqc_adapter builtin[] = {{"Illumina_Universal", "AGATCGGAAGAG"}, {"Illumina_SmallRNA_3p", "TGGAATTCTCGG"}, {"Illumina_SmallRNA_5p", "GATCGTCGGACT"},
-                                          {"Nextera_Transposase", "CTGTCTCTTATA"}, {"PolyA", "AAAAAAAAAAAA"}, {"PolyG", "GGGGGGGGGGGG"}};
+    uint32_t n_builtin;
+    const bqc_adapter* builtin = bqc_builtin_adapters(&n_builtin);
     const bqc_adapter* set = mod->n_adapters ? mod->adapters : builtin;
-    const uint32_t n = mod->n_adapters ? mod->n_adapters : (uint32_t)(sizeof builtin / sizeof builtin[0]);
+    const uint32_t n = mod->n_adapters ? mod->n_adapters : n_builtin;
     if (n > BQC_ADP_MAX) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: %u adapters given, at most %d are taken", n, BQC_ADP_MAX);
     if (!set) return fail(nullptr, BQC_ERR_ARG, "bqc_create_ex: n_adapters is %u and adapters is null", n);
     memset(&P, 0, sizeof P);
@@ -397,6 +400,7 @@ extern "C" void bqc_destroy(bqc_ctx* c)
     if (c->d_rcv_tab) (void)hipFree(c->d_rcv_tab);
     if (c->d_rcv_out) (void)hipFree(c->d_rcv_out);
     if (c->d_dup) (void)hipFree(c->d_dup);
+    if (c->d_ovr) (void)hipFree(c->d_ovr);
     if (c->d_gcb_g) (void)hipFree(c->d_gcb_g);
     if (c->d_gcb_tab) (void)hipFree(c->d_gcb_tab);
     (void)hipFree(c->d_state); (void)hipFree(c->d_err0); (void)hipFree(c->d_cursor); (void)hipFree(c->d_fasta_index); (void)hipFree(c->d_t8rows); (void)hipFree(c->d_t8used); (void)hipFree(c->d_kl_cyc); (void)hipFree(c->d_kl_cyc_used); (void)hipFree(c->d_carry); (void)hipFree(c->d_parity);
@@ -515,6 +519,10 @@ extern "C" int bqc_reset(bqc_ctx* c)
         bqc_launch_dup_clear(c->dup_tab, c->d_dup_sums, c->opt.n_lanes, c->n_cu, c->stream);
         HIPCHK(c, hipGetLastError());
     }
+    if (c->d_ovr) { // (the same for the table of the overrepresented sequences)
+        bqc_launch_ovr_clear(c->ovr_tab, c->d_ovr_sums, c->opt.n_lanes, c->n_cu, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
     for (bool& f : c->finalised) f = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cov.assign(c->opt.n_lanes, LaneCov());
@@ -627,8 +635,8 @@ static uint32_t last_nonzero_len(const uint64_t* p, uint32_t n)
     return n;
 }
 
-// A kernel of bqc_finalize (k_gcb_genome, k_rcv_final, k_dup_final).  With timing on, bqc_last_timing shows it afterwards, as it shows a
-// batch's kernels, which are over; `shown`: of several in one bqc_finalize the GC bias's comes first, then the regions', then the sets'.
+// A kernel of bqc_finalize (k_gcb_genome, k_rcv_final, k_dup_final, k_ovr_final).  With timing on, bqc_last_timing shows it afterwards, as it shows a
+// batch's kernels, which are over; `shown`: of several in one bqc_finalize the GC bias's comes first, then the regions', then the sets', then the sequences'.
 template <class Launch> static void timed_launch(bqc_ctx* c, bool shown, const char* name, Launch&& launch)
 {
     const bool timed = shown && c->timing && c->ev.size() >= 2;
@@ -1001,6 +1009,75 @@ extern "C" int bqc_enable_duplicate_sets(bqc_ctx* c, uint64_t capacity)
     return 0;
 }
 
+// The table of k_ovr.hip: one allocation, [C slots][the counter of sets, 7 spare words][n_lanes][4 sums][k_ovr_final's products: the
+// head and a list of 2 floor(10^6 / ppm) sets].  The clear is left on the compute stream, in front of the first batch.
+extern "C" int bqc_enable_overrepresented(bqc_ctx* c, uint32_t K, uint32_t ppm, uint64_t capacity)
+{
+    if (!c) return BQC_ERR_ARG;
+    if (K < BQC_OVR_KMIN || K > BQC_OVR_KMAX) return fail(c, BQC_ERR_ARG, "bqc_enable_overrepresented: prefix length %u is outside %d ... %d bases", K, BQC_OVR_KMIN, BQC_OVR_KMAX);
+    if (ppm < 10 || ppm > 1000000) return fail(c, BQC_ERR_ARG, "bqc_enable_overrepresented: threshold %u is outside 10 ... 1000000 reads per million", ppm);
+    if (capacity < 16 || capacity > 1ull << 31)
+        return fail(c, BQC_ERR_ARG, "bqc_enable_overrepresented: capacity %llu is outside 16 ... 2147483648 (2^31) sequences", (unsigned long long)capacity);
+    if (c->d_ovr) return fail(c, BQC_ERR_STATE, "bqc_enable_overrepresented: the module is on already (prefix length %u, capacity %llu)", c->ovr_k, (unsigned long long)c->ovr_tab.capacity);
+    if (int rc = too_late(c, __func__)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t C = bqc_dup_slots(capacity), list_cap = 2ull * (1000000u / ppm);
+    const uint64_t bytes = C * sizeof(DupSlot) + (8 + (uint64_t)c->opt.n_lanes * 4 + bqc_ovr_out_words(list_cap)) * 8;
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_overrepresented: the table of %llu slots for a capacity of %llu sequences (%llu bytes) could not be allocated", (unsigned long long)C, (unsigned long long)capacity, (unsigned long long)bytes);
+    }
+    DupTable& T = c->ovr_tab;
+    T.slots = (DupSlot*)d;
+    T.n_sets = (uint64_t*)(T.slots + C);
+    T.mask = C - 1;
+    T.capacity = capacity;
+    c->d_ovr_sums = T.n_sets + 8;
+    c->d_ovr_out = c->d_ovr_sums + (uint64_t)c->opt.n_lanes * 4;
+    bqc_launch_ovr_clear(T, c->d_ovr_sums, c->opt.n_lanes, c->n_cu, c->stream);
+    if (hipGetLastError() != hipSuccess) {
+        (void)hipFree(d);
+        T = DupTable{};
+        c->d_ovr_sums = c->d_ovr_out = nullptr;
+        return fail(c, BQC_ERR_DEVICE, "bqc_enable_overrepresented: the table could not be cleared");
+    }
+    c->d_ovr = d;
+    c->ovr_k = K;
+    c->ovr_ppm = ppm;
+    c->ovr_list_cap = list_cap;
+    return 0;
+}
+
+// The view's list from k_ovr_final's (c->h_ovr_out): letters, possible source, and the order — mate, count descending, sequence ascending.
+static void ovr_make_list(bqc_ctx* c, uint64_t n_sets)
+{
+    struct Item { std::string seq; uint64_t count; uint32_t mate; };
+    std::vector<Item> items(n_sets);
+    for (uint64_t e = 0; e < n_sets; ++e) {
+        const uint64_t* w = c->h_ovr_out.data() + BQC_OVR_HEAD + 3 * e;
+        const uint32_t n = (uint32_t)(w[0] >> 56) & 63u;
+        Item& it = items[e];
+        it.mate = (uint32_t)(w[0] >> 62) & 1u;
+        it.count = w[2];
+        it.seq.resize(n);
+        for (uint32_t i = 0; i < n; ++i) it.seq[i] = "ACGT"[(i < 28 ? w[0] >> (2 * i) : w[1] >> (2 * (i - 28))) & 3u];
+    }
+    std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) {
+        if (a.mate != b.mate) return a.mate < b.mate;
+        if (a.count != b.count) return a.count > b.count;
+        return a.seq < b.seq;
+    });
+    c->ovr_text.resize(n_sets);
+    c->ovr_listed.resize(n_sets);
+    c->ovr_n_listed[0] = c->ovr_n_listed[1] = 0;
+    for (uint64_t e = 0; e < n_sets; ++e) {
+        c->ovr_text[e].swap(items[e].seq);
+        c->ovr_listed[e] = bqc_ovr_seq{c->ovr_text[e].c_str(), items[e].count, bqc_possible_source(c->ovr_text[e].c_str())};
+        ++c->ovr_n_listed[items[e].mate];
+    }
+}
+
 // Picard's estimateLibrarySize: the library size x with c = x (1 - exp(-n / x)) for n read pairs of which c are unique, by bisection
 static uint64_t dup_library_size(uint64_t n_reads, uint64_t n_unique)
 {
@@ -1172,6 +1249,34 @@ extern "C" int bqc_finalize(bqc_ctx* c, const bqc_counts** out)
         for (uint32_t l = 0; l < c->opt.n_lanes; ++l) pairs += c->h_dup_sums[(size_t)l * 5 + 1];
         c->dup_estimate = dup_library_size(pairs, c->dup_sets[1]);
         c->finalised[MOD_DUP] = true;
+    }
+    if (c->d_ovr) { // k_ovr_final: the sets by mate and size and the list from the table, which it leaves as it is; the thresholds come from the sums
+        const uint32_t n_lanes = c->opt.n_lanes;
+        c->finalised[MOD_OVR] = false;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->h_ovr_sums.resize((size_t)n_lanes * 4);
+        HIPCHK(c, hipMemcpy(c->h_ovr_sums.data(), c->d_ovr_sums, c->h_ovr_sums.size() * 8, hipMemcpyDeviceToHost));
+        for (uint32_t m = 0; m < 2; ++m) {
+            uint64_t entered = 0;
+            for (uint32_t l = 0; l < n_lanes; ++l) entered += c->h_ovr_sums[(size_t)l * 4 + m] - c->h_ovr_sums[(size_t)l * 4 + 2 + m];
+            c->ovr_threshold[m] = std::max<uint64_t>(2, (entered * c->ovr_ppm + 999999) / 1000000); // (entered < 2^40 reads: the product stays below 2^60)
+        }
+        timed_launch(c, !c->seg[SEG_GCB].d && !c->seg[SEG_RCV].d && !c->d_dup, "k_ovr_final", [&] { bqc_launch_ovr_final(c->ovr_tab, c->ovr_threshold, c->d_ovr_out, c->ovr_list_cap, &c->d_err0->flags, c->n_cu, c->stream); });
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->h_ovr_out.resize(BQC_OVR_HEAD);
+        HIPCHK(c, hipMemcpy(c->h_ovr_out.data(), c->d_ovr_out, BQC_OVR_HEAD * 8, hipMemcpyDeviceToHost));
+        const uint64_t n_sets = c->h_ovr_out[BQC_OVR_HEAD - 2];
+        if (n_sets > c->ovr_list_cap)
+            return fail(c, BQC_ERR_DEVICE, "internal error: overrepresented sequences: %llu sets reach the thresholds, the list holds %llu", (unsigned long long)n_sets, (unsigned long long)c->ovr_list_cap);
+        c->h_ovr_out.resize(bqc_ovr_out_words(n_sets));
+        if (n_sets) HIPCHK(c, hipMemcpy(c->h_ovr_out.data() + BQC_OVR_HEAD, c->d_ovr_out + BQC_OVR_HEAD, n_sets * 24, hipMemcpyDeviceToHost));
+        for (uint32_t m = 0; m < 2; ++m) {
+            c->ovr_distinct[m] = 0;
+            for (uint32_t i = 0; i < BQC_DUP_BINS; ++i) c->ovr_distinct[m] += c->h_ovr_out[(size_t)m * BQC_DUP_BINS + i];
+        }
+        ovr_make_list(c, n_sets);
+        c->finalised[MOD_OVR] = true;
     }
     if (c->seg[SEG_WDP].d) { // the sums by contig and the histogram over the main contigs' windows: one pass over a copy of the words, no kernel
         const uint32_t n_lanes = c->opt.n_lanes, n_refs = c->opt.n_refs, W = c->wdp_tab.W;
@@ -1379,6 +1484,29 @@ extern "C" int bqc_duplicate_sets(bqc_ctx* c, bqc_dup_view* out)
     }
     out->estimated_library_size = c->dup_estimate;
     out->lanes = c->h_dup_sums.data();
+    return 0;
+}
+
+extern "C" int bqc_overrepresented(bqc_ctx* c, bqc_ovr_view* out)
+{
+    if (!c || !out) return BQC_ERR_ARG;
+    if (!c->d_ovr) return fail(c, BQC_ERR_STATE, "bqc_overrepresented: bqc_enable_overrepresented has not been called for the context");
+    if (!c->finalised[MOD_OVR]) return fail(c, BQC_ERR_STATE, "bqc_overrepresented: nothing has been finalised");
+    out->prefix_len = c->ovr_k;
+    out->ppm = c->ovr_ppm;
+    out->capacity = c->ovr_tab.capacity;
+    out->n_lanes = c->opt.n_lanes;
+    out->pad = 0;
+    out->lanes = c->h_ovr_sums.data();
+    for (uint32_t m = 0; m < 2; ++m) {
+        out->distinct[m] = c->ovr_distinct[m];
+        out->largest[m] = c->h_ovr_out[2 * BQC_DUP_BINS + m];
+        out->hist[m] = c->h_ovr_out.data() + (size_t)m * BQC_DUP_BINS;
+        out->threshold[m] = c->ovr_threshold[m];
+        out->n_listed[m] = c->ovr_n_listed[m];
+    }
+    out->listed[0] = c->ovr_listed.data();
+    out->listed[1] = c->ovr_listed.data() + c->ovr_n_listed[0];
     return 0;
 }
 

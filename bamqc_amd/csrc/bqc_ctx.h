@@ -154,6 +154,7 @@ enum Seg {
     SEG_QCYC, // base quality by cycle: [n_lanes][2][N][224]
     N_SEG,
     MOD_DUP = N_SEG, // the duplicate sets: a module with views (bqc_ctx::finalised), no part of the vector
+    MOD_OVR,         // the overrepresented sequences: the same
     N_MOD
 };
 struct StateSeg {
@@ -287,6 +288,19 @@ struct bqc_ctx {
     uint64_t* d_dup_out = nullptr;     // k_dup_final's products: [2][256] sets by size, the two largest sets
     std::vector<uint64_t> h_dup_out, h_dup_sums; // bqc_finalize's copies
     uint64_t dup_sets[2] = {0, 0}, dup_estimate = 0;
+    // overrepresented sequences (k_ovr.hip; bqc_enable_overrepresented(K, ppm, capacity) after creation — nothing below exists without it,
+    // and none of it is part of the state vector)
+    DupTable ovr_tab{};                // the table's slots (d_ovr), the counter of sets behind them, C - 1 and the capacity
+    void* d_ovr = nullptr;             // one allocation: [C slots][n_sets, 7 spare words][n_lanes][4 sums][k_ovr_final's products]
+    uint64_t* d_ovr_sums = nullptr;    // [n_lanes][4: examined first, examined second, skipped first, skipped second]
+    uint64_t* d_ovr_out = nullptr;     // k_ovr_final's products: BQC_OVR_HEAD words, then the list of ovr_list_cap sets
+    uint32_t ovr_k = 0, ovr_ppm = 0;   // the prefix length K and the list's threshold in reads per million
+    uint64_t ovr_list_cap = 0;         // 2 floor(10^6 / ppm): the sets both mates can list
+    std::vector<uint64_t> h_ovr_out, h_ovr_sums; // bqc_finalize's copies
+    uint64_t ovr_distinct[2] = {0, 0}, ovr_threshold[2] = {0, 0};
+    std::vector<bqc_ovr_seq> ovr_listed; // the list as the view shows it: mate 0's sets, then mate 1's, each sorted
+    std::vector<std::string> ovr_text;   // ... and its sequences' letters
+    uint32_t ovr_n_listed[2] = {0, 0};
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -42,6 +42,7 @@ void bqc_launch_sac(const DevBatch&, const SacSites&, uint64_t* table, uint32_t 
 void bqc_launch_rcv(const DevBatch&, const RcvRegions&, uint64_t* state, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_wdp(const DevBatch&, const WdpTab&, uint64_t* state, uint32_t MQ, uint32_t n_lanes, uint32_t n_cu, hipStream_t);
 void bqc_launch_dup(const DevBatch&, const DupTable&, uint64_t* sums, uint32_t* err, uint32_t n_lanes, uint32_t n_refs, uint32_t n_cu, hipStream_t);
+void bqc_launch_ovr(const DevBatch&, const DupTable&, uint64_t* sums, uint32_t* err, uint32_t n_lanes, uint32_t K, uint32_t n_cu, hipStream_t);
 }
 
 using clk = std::chrono::steady_clock;
@@ -625,6 +626,7 @@ static int enqueue_batch(bqc_ctx* c, BatchMem& m, bool& forked)
     if (c->seg[SEG_WDP].d) { bqc_launch_wdp(d, c->wdp_tab, c->seg[SEG_WDP].d, c->wdp_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_wdp"); }
     if (c->seg[SEG_RCV].d) { bqc_launch_rcv(d, c->rcv_regions, c->seg[SEG_RCV].d, c->rcv_mq, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_rcv"); }
     if (c->d_dup) { bqc_launch_dup(d, c->dup_tab, c->d_dup_sums, err, c->opt.n_lanes, c->opt.n_refs, c->n_cu, c->stream); tick(c, "k_dup"); }
+    if (c->d_ovr) { bqc_launch_ovr(d, c->ovr_tab, c->d_ovr_sums, err, c->opt.n_lanes, c->ovr_k, c->n_cu, c->stream); tick(c, "k_ovr"); }
     if (c->seg[SEG_ADP].d) { bqc_launch_adp(d, c->adp_pat, c->seg[SEG_ADP].d, c->adp_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_adp"); }
     if (c->seg[SEG_GCB].d) { bqc_launch_gcb_reads(d, refs, c->seg[SEG_GCB].d, c->gcb_w, c->gcb_div, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_gcb_reads"); }
     if (c->seg[SEG_IBC].d) { bqc_launch_ibc(d, c->seg[SEG_IBC].d, c->ibc_n, c->opt.n_lanes, c->n_cu, c->stream); tick(c, "k_ibc"); }
@@ -666,6 +668,8 @@ int bqc_report_errors(bqc_ctx* c, const ErrRec& e)
     if (e.flags & BQC_DEVERR_MATE) return bqc_fail(c, BQC_ERR_NO_MATE_FLAG, "ERROR: No first or second flag in read");
     if (e.flags & BQC_DEVERR_DUP)
         return bqc_fail(c, BQC_ERR_RANGE, "duplicate sets: the reads hold more than %llu different alignment signatures, the table's capacity (--duplicate-sets-capacity)", (unsigned long long)c->dup_tab.capacity);
+    if (e.flags & BQC_DEVERR_OVR)
+        return bqc_fail(c, BQC_ERR_RANGE, "overrepresented sequences: the reads hold more than %llu different sequence keys, the table's capacity (--overrepresented-capacity)", (unsigned long long)c->ovr_tab.capacity);
     if (e.flags & BQC_DEVERR_RANGE) return bqc_fail(c, BQC_ERR_RANGE, "mismatch/deletion/insertion count exceeds hist_cap (or NM < D+I)");
     return bqc_fail(c, BQC_ERR_RANGE, "base quality above 222 cannot be represented by the reference (q+33 wraps)");
 }

@@ -417,6 +417,45 @@ extern "C" int bqc_write_duplicate_sets(bqc_ctx* ctx, const bqc_header_info* hdr
     return write_file(o, path);
 }
 
+// The overrepresented sequences as text (include/bamqc.h): the parameters, per lane of `hdr` the four sums, then per mate the sets over
+// all read groups and the list.
+extern "C" int bqc_write_overrepresented(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path)
+{
+    if (!ctx || !hdr || !path) return BQC_ERR_ARG;
+    bqc_ovr_view v;
+    const int rc = bqc_overrepresented(ctx, &v);
+    if (rc) return rc;
+    Out o;
+    o.s.reserve(1 << 14);
+    o.str("sample_id "); o.str(hdr->sample_id ? hdr->sample_id : ""); o.s.push_back('\n');
+    o.line_u64("overrepresented_len", v.prefix_len);
+    o.line_u64("overrepresented_ppm", v.ppm);
+    o.line_u64("overrepresented_capacity", v.capacity);
+    for (uint32_t n = 0; n < hdr->n_names; ++n) {
+        if (hdr->lane_index[n] >= v.n_lanes) return BQC_ERR_ARG;
+        const uint64_t* s = v.lanes + (uint64_t)hdr->lane_index[n] * 4;
+        o.str("lane "); o.str(hdr->lane_names[n]); o.s.push_back('\n');
+        o.line_u64("sequence_reads_examined_first", s[0]);
+        o.line_u64("sequence_reads_examined_second", s[1]);
+        o.line_u64("sequence_reads_skipped_first", s[2]);
+        o.line_u64("sequence_reads_skipped_second", s[3]);
+    }
+    o.str("all_lanes\n");
+    for (uint32_t m = 0; m < 2; ++m) {
+        const std::string mate = m ? "_second" : "_first";
+        o.line_u64(("sequences_distinct" + mate).c_str(), v.distinct[m]);
+        o.line_u64(("sequence_set_largest" + mate).c_str(), v.largest[m]);
+        o.array(("sequence_set_size_histogram" + mate).c_str(), v.hist[m], 256);
+        o.line_u64(("overrepresented_threshold" + mate).c_str(), v.threshold[m]);
+        o.line_u64(("overrepresented_sequences" + mate).c_str(), v.n_listed[m]);
+        for (uint32_t e = 0; e < v.n_listed[m]; ++e) {
+            const bqc_ovr_seq& q = v.listed[m][e];
+            o.str(q.seq); o.s.push_back(' '); o.u64(q.count); o.s.push_back(' '); o.str(q.source); o.s.push_back('\n');
+        }
+    }
+    return write_file(o, path);
+}
+
 // The depth in fixed genome windows as text (include/bamqc.h): per lane the scalars and the histogram (its length first), one line a
 // contig in the header's order — name, length, windows and the three sums — then one line for every window with a word that is not 0,
 // in order: the contig's name, the window's start and end, its reads, bases and bases of low mapping quality.

@@ -25,6 +25,7 @@
 #define BQC_DEVERR_MATE  4u      // neither first nor last flag
 #define BQC_DEVERR_INTERNAL 8u   // a kernel found its own layout assumptions violated (never expected)
 #define BQC_DEVERR_DUP 16u       // k_dup: more signatures than the table's capacity
+#define BQC_DEVERR_OVR 32u       // k_ovr: more sequence keys than the table's capacity
 
 struct Chunk {        // lane-uniform run of reads (indices into perm, or read ids when perm == nullptr)
     uint32_t first, count, lane;
@@ -246,6 +247,14 @@ struct DupTable {
     uint64_t mask;      // C - 1, C a power of two >= 2 capacity
     uint64_t capacity;  // the signatures asked for
 };
+
+// Overrepresented sequences (k_ovr.hip; the rule: include/bamqc.h).  The table is a DupTable of its own whose key words are
+// k0 = sequenced bases 0..27 (2 bits a base, A 0 C 1 G 2 T 3, base 0 lowest) | n << 56 | mate << 62, k1 = bases 28..55: neither can be
+// all ones.  k_ovr_final's products: [2 mates][BQC_DUP_BINS] sets by size, the two largest sets, the list's counter, a spare word —
+// BQC_OVR_HEAD words — then the list, 3 words a set (k0, k1, count).
+#define BQC_OVR_KMIN 20
+#define BQC_OVR_KMAX 56
+#define BQC_OVR_HEAD (2 * BQC_DUP_BINS + 4)
 
 struct DevRefs {
     const uint8_t* const* ref; // [n_refs] Dna5 codes, nullptr if not loaded

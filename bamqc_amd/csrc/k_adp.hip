@@ -7,7 +7,7 @@
 // reads at a time, thread t of a step fetching the columns of the step's read t (and those of the next step before this one is searched).
 // A lane OWNS 16 stored bases of a read and looks 15 ahead: the 31 bases are the 16 bytes behind the lane's first byte, taken as five
 // aligned dwords and byte shifts (the bytes of a read start anywhere); only aligned dwords that hold a byte of the read are touched.
-// A dword of eight nibbles becomes 16 bits of 2-bit codes and 8 bits of "is one of A, C, G, T"; what lies behind the read's last base —
+// A dword of eight nibbles becomes (ad_pack8, kernels_common.h) 16 bits of 2-bit codes and 8 bits of "is one of A, C, G, T"; what lies behind the read's last base —
 // the pad nibble of an odd length, the next read's bytes, a dword that was not loaded — is cleared from the validity bits and so matches
 // nothing.  Per adapter and offset 0..15 the test is one 64-bit shift, a mask, a compare and the validity test; the patterns are kernel
 // arguments.  A reverse read is searched in STORED order for the reverse complement: its first hit in sequencing order is its LAST
@@ -32,24 +32,6 @@
 #define AD_WORDS (AD_TILE + 4 * AD_STEP + BQC_ADP_MAX * AD_STEP + 8)
 #define AD_NOLANE 0xFFFFFFFFu
 #define AD_NOHIT 0xFFFFFFFFu
-
-// eight BAM nibbles (a dword of the payload: byte 0 lowest, a byte's first base in its high nibble) -> 16 bits of 2-bit codes, base 0
-// lowest, and 8 bits that say which of them are A, C, G or T (codes 1, 2, 4, 8)
-__device__ __forceinline__ void ad_pack8(uint32_t x, uint32_t& codes, uint32_t& valid)
-{
-    const uint32_t M = 0x11111111u;
-    x = ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu); // base i in nibble i
-    const uint32_t p0 = x & M, p1 = (x >> 1) & M, p2 = (x >> 2) & M, p3 = (x >> 3) & M;
-    const uint32_t s = p0 + p1 + p2 + p3;                    // bits set per nibble
-    uint32_t oh = s & ~(s >> 1) & ~(s >> 2) & M;             // exactly one
-    uint32_t c = (p1 | p3) | ((p2 | p3) << 1);               // 1 -> 0, 2 -> 1, 4 -> 2, 8 -> 3 in the low bits of every nibble
-    c = (c | (c >> 2)) & 0x0F0F0F0Fu;
-    c = (c | (c >> 4)) & 0x00FF00FFu;
-    codes = (c | (c >> 8)) & 0xFFFFu;
-    oh = (oh | (oh >> 3)) & 0x03030303u;
-    oh = (oh | (oh >> 6)) & 0x000F000Fu;
-    valid = (oh | (oh >> 12)) & 0xFFu;
-}
 
 // Chunk k of a read (stored bases 16 k .. 16 k + 30, the read has L > 16 k of them, its bytes start at seq + soff): every adapter's
 // occurrences that START at one of the chunk's 16 owned bases, the one that comes first in sequencing order to the read's slot.

@@ -4,7 +4,7 @@
 // exist only when bqc_enable_duplicate_sets has been called.  The genome is not read, nor any base or quality.  The module's state is
 // NOT part of the flat state vector: the table cannot be summed word by word.
 //
-// The table.  C slots (a power of two, at least twice the capacity in signatures) of DupSlot {k0, k1, count}, open addressing with
+// The table (dup_table.h: its code is shared with k_ovr.hip).  C slots (a power of two, at least twice the capacity in signatures) of DupSlot {k0, k1, count}, open addressing with
 // linear probing; an empty key word is all ones (k0 has 49 bits; k1's low half is a rid >= 0).  Every access to a key word or a count
 // while reads are inserted is an 8-byte agent-scope atomic: nothing is fenced, and no L1 can serve a stale key.
 // The insert never waits for another thread.  At a slot: (1) k0 is loaded, and if empty claimed by a compare-and-swap; (2) if the
@@ -35,67 +35,15 @@
 // k_dup_final, at bqc_finalize only: one pass over the C slots, which it only reads: the sets by class and size into LDS histograms
 // (one add a bin and workgroup to memory), the largest set by a maximum per wave.
 #include "cigar_walk.h"
+#include "dup_table.h" // the table: slot, claim, insert, clear (also k_ovr.hip's)
 
 #define DP_THREADS 1024
 #define DP_WAVES (DP_THREADS / WAVE)
 #define DP_STEP DP_THREADS
 #define DP_T 8                       // operations up to which a read's CIGAR is summed by its own thread
-#define DP_CHECK 64                  // slots of a probe sequence between two looks at the counter of sets
 #define DP_LANES 256                 // read groups (the lane column is a byte)
 #define DP_NONE WALK_NONE
 #define DP_FTHREADS 256
-
-typedef unsigned long long dp_u64;
-__device__ __forceinline__ dp_u64 dp_load(const uint64_t* p) { return __hip_atomic_load((const gmem_u64*)(uintptr_t)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// compare-and-swap of an empty word with `mine`: what the word holds afterwards; won: this thread's swap took place
-__device__ __forceinline__ dp_u64 dp_claim(uint64_t* p, dp_u64 mine, bool& won)
-{
-    dp_u64 seen = BQC_DUP_EMPTY;
-    won = __hip_atomic_compare_exchange_strong((gmem_u64*)(uintptr_t)p, &seen, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return won ? mine : seen;
-}
-
-__device__ __forceinline__ uint64_t dp_mix(uint64_t x)
-{
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-    x ^= x >> 33;
-    return x;
-}
-__device__ __forceinline__ uint64_t dp_slot(uint64_t k0, uint64_t k1, uint64_t mask, uint32_t mode)
-{
-    if (!(mode & 2u)) return dp_mix(k0 ^ dp_mix(k1)) & mask;
-    return ((dp_mix((k0 >> 6) ^ dp_mix(k1)) << 6) | (k0 & 63u)) & mask; // (rid, u5 >> 6, the rest): k1 whole and k0 without u5's low 6 bits
-}
-
-// n reads of one signature.  Returns 1 when the set is new, 0 when it was there or the sequence gave up (`over`).
-__device__ __forceinline__ uint32_t dp_insert(const DupTable& T, uint64_t k0, uint64_t k1, uint64_t n, uint32_t mode, bool& over)
-{
-    uint64_t s = dp_slot(k0, k1, T.mask, mode);
-    for (uint64_t probes = 0; probes <= T.mask; ++probes, s = (s + 1u) & T.mask) {
-        if ((probes & (DP_CHECK - 1u)) == DP_CHECK - 1u && dp_load(T.n_sets) > T.capacity) break;
-        DupSlot* sl = T.slots + s;
-        bool won = false;
-        dp_u64 a = dp_load(&sl->k0);
-        if (a == BQC_DUP_EMPTY) a = dp_claim(&sl->k0, k0, won);
-        if (a != k0) continue;
-        won = false;
-        dp_u64 b = dp_load(&sl->k1);
-        if (b == BQC_DUP_EMPTY) b = dp_claim(&sl->k1, k1, won);
-        if (b != k1) continue;
-        gadd(&sl->count, n);
-        return won ? 1u : 0u;
-    }
-    over = true;
-    return 0;
-}
-
-__global__ void k_dup_clear(DupSlot* slots, uint64_t C)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t* w = (uint64_t*)slots;
-    for (uint64_t x = i; x < 3u * C; x += step) w[x] = x % 3u == 2u ? 0ull : BQC_DUP_EMPTY;
-}
 
 // Read i of the processing order.  cls: 0 single, 1 pair, 2 second end, DP_NONE not examined
 struct DpRead { uint32_t cls, r, nc, coff, lane, info; int32_t rid, pos, tlen; }; // info: strand | mate strand << 1 | flagged << 2
@@ -320,22 +268,14 @@ __global__ __launch_bounds__(DP_FTHREADS) void k_dup_final(const DupSlot* __rest
     }
 }
 
-// the slots of a table for `capacity` signatures: the smallest power of two >= 2 capacity (capacity <= 2^31)
-extern "C" uint64_t bqc_dup_slots(uint64_t capacity)
-{
-    uint64_t C = 32;
-    while (C < 2 * capacity) C <<= 1;
-    return C;
-}
+// the slots of a table for `capacity` signatures (dup_table.h)
+extern "C" uint64_t bqc_dup_slots(uint64_t capacity) { return dp_slots(capacity); }
 extern "C" uint64_t bqc_dup_out_words(void) { return 2 * BQC_DUP_BINS + 2; }
 
 // The table, the counter of sets behind it and the sums: empty.
 extern "C" void bqc_launch_dup_clear(const DupTable& T, uint64_t* sums, uint32_t n_lanes, uint32_t n_cu, hipStream_t s)
 {
-    const uint64_t C = T.mask + 1u;
-    const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_cu * 8, (3 * C + 1023) / 1024));
-    hipLaunchKernelGGL(k_dup_clear, dim3(g), dim3(1024), 0, s, T.slots, C);
-    (void)hipMemsetAsync(T.n_sets, 0, 8, s);
+    dp_clear(T, n_cu, s);
     (void)hipMemsetAsync(sums, 0, (uint64_t)n_lanes * 5 * 8, s);
 }
 

@@ -87,3 +87,20 @@ __device__ __forceinline__ uint32_t reverse8x2(uint32_t h) // reverse the order 
     return ((x & 0xAAAAu) >> 1) | ((x & 0x5555u) << 1);   // swap the two bits of every base back
 }
 
+// eight BAM nibbles (a dword of the payload: byte 0 lowest, a byte's first base in its high nibble) -> 16 bits of 2-bit codes, base 0
+// lowest, and 8 bits that say which of them are A, C, G or T (codes 1, 2, 4, 8)
+__device__ __forceinline__ void ad_pack8(uint32_t x, uint32_t& codes, uint32_t& valid)
+{
+    const uint32_t M = 0x11111111u;
+    x = ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu); // base i in nibble i
+    const uint32_t p0 = x & M, p1 = (x >> 1) & M, p2 = (x >> 2) & M, p3 = (x >> 3) & M;
+    const uint32_t s = p0 + p1 + p2 + p3;                    // bits set per nibble
+    uint32_t oh = s & ~(s >> 1) & ~(s >> 2) & M;             // exactly one
+    uint32_t c = (p1 | p3) | ((p2 | p3) << 1);               // 1 -> 0, 2 -> 1, 4 -> 2, 8 -> 3 in the low bits of every nibble
+    c = (c | (c >> 2)) & 0x0F0F0F0Fu;
+    c = (c | (c >> 4)) & 0x00FF00FFu;
+    codes = (c | (c >> 8)) & 0xFFFFu;
+    oh = (oh | (oh >> 3)) & 0x03030303u;
+    oh = (oh | (oh >> 6)) & 0x000F000Fu;
+    valid = (oh | (oh >> 12)) & 0xFFu;
+}

@@ -804,6 +804,11 @@ struct ProgramOptions {
     // --duplicate-sets / --duplicate-sets-capacity N: duplicate sets by alignment signature into <output>.dup
     bool duplicate_sets = false;
     uint64_t duplicate_sets_capacity = 1ull << 26; // signatures the table takes (3 GiB of slots)
+    // --overrepresented / --overrepresented-len K / --overrepresented-ppm P / --overrepresented-capacity N: sets of equal read
+    // sequences and the list of the overrepresented ones into <output>.ovr
+    bool overrepresented = false;
+    uint32_t overrepresented_len = 50, overrepresented_ppm = 1000;
+    uint64_t overrepresented_capacity = 1ull << 26; // sequence keys the table takes (3 GiB of slots)
     // --window-depth / --window-depth-size W / --window-depth-min-mapq MQ: depth in fixed genome windows into <output>.wdp
     bool window_depth = false;
     uint32_t window_depth_size = 1000, window_depth_min_mapq = 20;
@@ -873,6 +878,16 @@ void usage(FILE* f)
             "          duplication rate and observed against flagged duplicates are folds of it).  Not with --gpus.\n"
             "    --duplicate-sets-capacity INT\n          The different signatures the table takes (16 to 2147483648, default 67108864: 3 GiB on the card).\n"
             "          Needs --duplicate-sets.\n"
+            "    --overrepresented\n          Overrepresented sequences: reads whose first 50 bases as sequenced (a reverse read's last stored bases,\n"
+            "          reverse-complemented) are equal, of the same mate, are one set; unmapped reads count, reads with a base\n"
+            "          other than A, C, G, T among them are skipped.  Per read group the examined and the skipped reads, per mate\n"
+            "          over all read groups the sets, the largest set, the sets by size and every sequence that makes up 1000 reads\n"
+            "          per million or more (at least 2 reads) with its count and the built-in adapter it contains, into OUT.ovr\n"
+            "          (duplication by sequence and contaminant spotting are folds of it).  Not with --gpus.\n"
+            "    --overrepresented-len INT\n          The same for the first INT bases (20 to 56).  Implies --overrepresented.\n"
+            "    --overrepresented-ppm INT\n          The same listing sequences of INT reads per million or more (10 to 1000000).  Implies --overrepresented.\n"
+            "    --overrepresented-capacity INT\n          The different sequences the table takes (16 to 2147483648, default 67108864: 3 GiB on the card).\n"
+            "          Implies --overrepresented.\n"
             "    --window-depth\n          Depth in fixed genome windows of 1000 bases over every contig of the header: per read group and window\n"
             "          the reads that begin in it and the covered bases of reads of mapping quality 20 and more, the covered bases\n"
             "          of the reads below it, the same summed by contig, and a histogram of the main contigs' window depths, into\n"
@@ -957,6 +972,11 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
     auto dup_somewhere = [&]() { // (the same for the duplicate sets: a set may have members in two workers' shards)
         for (int k = 1; k < argc; ++k)
             if (strcmp(argv[k], "--duplicate-sets") == 0 || strncmp(argv[k], "--duplicate-sets-capacity", 25) == 0) return true;
+        return false;
+    };
+    auto ovr_somewhere = [&]() { // (and for the overrepresented sequences, for the same reason)
+        for (int k = 1; k < argc; ++k)
+            if (strncmp(argv[k], "--overrepresented", 17) == 0) return true;
         return false;
     };
     std::vector<std::string> pos;
@@ -1119,6 +1139,22 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             want_rcv_value = key;
         }
         else if (key == "--duplicate-sets") { o.duplicate_sets = true; }
+        else if (key == "--overrepresented") { o.overrepresented = true; }
+        else if (key == "--overrepresented-len" || key == "--overrepresented-ppm" || key == "--overrepresented-capacity") {
+            if (!need(i, key, v, inl)) return 1;
+            const bool len = key == "--overrepresented-len", ppm = key == "--overrepresented-ppm";
+            const unsigned long long lo = len ? 20 : ppm ? 10 : 16, hi = len ? 56 : ppm ? 1000000 : 1ull << 31;
+            char* end = nullptr;
+            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' || v.size() > 10 ? 0ull : strtoull(v.c_str(), &end, 10);
+            if (!end || *end || x < lo || x > hi) {
+                err = "bamqualcheck: the given value '" + v + "' is not a " + (len ? "prefix length (--overrepresented-len wants 20 to 56)" : ppm ? "number of reads per million (--overrepresented-ppm wants 10 to 1000000)" : "number of sequences (--overrepresented-capacity wants 16 to 2147483648)");
+                return 1;
+            }
+            if (len) o.overrepresented_len = (uint32_t)x;
+            else if (ppm) o.overrepresented_ppm = (uint32_t)x;
+            else o.overrepresented_capacity = x;
+            o.overrepresented = true;
+        }
         else if (key == "--window-depth") { o.window_depth = true; }
         else if (key == "--window-depth-size" || key == "--window-depth-min-mapq") {
             if (!need(i, key, v, inl)) return 1;
@@ -1151,6 +1187,7 @@ int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err,
             o.gc_bias = (uint32_t)x;
         }
         else if (key == "--gpus" && dup_somewhere()) { err = "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)"; return 1; }
+        else if (key == "--gpus" && ovr_somewhere()) { err = "bamqualcheck: --overrepresented with --gpus is not supported: a set may have members in two workers' shards (run one process)"; return 1; }
         else if (key == "--gpus" && gcb_somewhere()) { err = "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)"; return 1; }
         else if (key == "--manifest") { if (!need(i, key, v, inl)) return 1; o.manifest = v; have_m = true; }
         else if (a[0] == '-') { err = "bamqualcheck: illegal option -- " + a.substr(a.rfind("--", 0) == 0 ? 2 : 1); return 1; }
@@ -1281,6 +1318,8 @@ struct CtxKey {
     uint32_t regions_min_mapq = 0, regions_depth_cap = 0;
     std::vector<uint64_t> regions_thresholds;
     uint64_t duplicate_sets = 0; // --duplicate-sets: the capacity (0: off)
+    uint64_t overrepresented = 0; // --overrepresented: the capacity (0: off), the prefix length and the threshold
+    uint32_t overrepresented_len = 0, overrepresented_ppm = 0;
     uint32_t window_depth = 0, window_depth_min_mapq = 0; // --window-depth: the window size (0: off)
     std::vector<int32_t> window_depth_lens;               // and the contigs' lengths of the job's header
     int isize = 0, seed = 0, device = 0;
@@ -1291,7 +1330,7 @@ struct CtxKey {
     std::vector<uint8_t> main_chrom;
     bool operator==(const CtxKey& o) const
     {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && region_rid == o.region_rid && region_start == o.region_start && region_end == o.region_end && regions_min_mapq == o.regions_min_mapq && regions_depth_cap == o.regions_depth_cap && regions_thresholds == o.regions_thresholds && duplicate_sets == o.duplicate_sets && window_depth == o.window_depth && window_depth_min_mapq == o.window_depth_min_mapq && window_depth_lens == o.window_depth_lens && isize == o.isize && seed == o.seed && device == o.device &&
+        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && region_rid == o.region_rid && region_start == o.region_start && region_end == o.region_end && regions_min_mapq == o.regions_min_mapq && regions_depth_cap == o.regions_depth_cap && regions_thresholds == o.regions_thresholds && duplicate_sets == o.duplicate_sets && overrepresented == o.overrepresented && overrepresented_len == o.overrepresented_len && overrepresented_ppm == o.overrepresented_ppm && window_depth == o.window_depth && window_depth_min_mapq == o.window_depth_min_mapq && window_depth_lens == o.window_depth_lens && isize == o.isize && seed == o.seed && device == o.device &&
                sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
     }
 };
@@ -1336,6 +1375,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (pr == 1) { fprintf(stderr, "%s\n", perr.c_str()); return 1; }
     // (a worker of --gpus N holds only the contigs its batches touch: none has the genome table; the front end says so before it forks)
     if (shard && opt.duplicate_sets) { fprintf(stderr, "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)\n"); return 1; }
+    if (shard && opt.overrepresented) { fprintf(stderr, "bamqualcheck: --overrepresented with --gpus is not supported: a set may have members in two workers' shards (run one process)\n"); return 1; }
     if (shard && opt.gc_bias) { fprintf(stderr, "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)\n"); return 1; }
     using clk = std::chrono::steady_clock;
     const bool timing = getenv("BQC_TIMING") && getenv("BQC_TIMING")[0] == '1'; // BQC_TIMING=1: where the wall time of a run goes (stderr)
@@ -1602,6 +1642,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         if (!site_rid.empty()) { ctx_key.site_rid = site_rid; ctx_key.site_pos = site_pos; ctx_key.site_min_qual = opt.site_min_qual; ctx_key.site_min_mapq = opt.site_min_mapq; }
         if (!region_rid.empty()) { ctx_key.region_rid = region_rid; ctx_key.region_start = region_start; ctx_key.region_end = region_end; ctx_key.regions_min_mapq = opt.regions_min_mapq; ctx_key.regions_depth_cap = opt.regions_depth_cap; ctx_key.regions_thresholds = opt.regions_thresholds; }
         if (opt.duplicate_sets) ctx_key.duplicate_sets = opt.duplicate_sets_capacity;
+        if (opt.overrepresented) { ctx_key.overrepresented = opt.overrepresented_capacity; ctx_key.overrepresented_len = opt.overrepresented_len; ctx_key.overrepresented_ppm = opt.overrepresented_ppm; }
         if (opt.window_depth) { ctx_key.window_depth = opt.window_depth_size; ctx_key.window_depth_min_mapq = opt.window_depth_min_mapq; ctx_key.window_depth_lens = wdp_lens; }
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
         ctx_key.main_chrom = main_chrom;
@@ -1643,6 +1684,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
                 rc = bqc_enable_region_coverage(ctx, (uint32_t)region_rid.size(), region_rid.data(), region_start.data(), region_end.data(), opt.regions_min_mapq,
                                                 (uint32_t)opt.regions_thresholds.size(), opt.regions_thresholds.data(), opt.regions_depth_cap);
             if (!rc && opt.duplicate_sets) rc = bqc_enable_duplicate_sets(ctx, opt.duplicate_sets_capacity);
+            if (!rc && opt.overrepresented) rc = bqc_enable_overrepresented(ctx, opt.overrepresented_len, opt.overrepresented_ppm, opt.overrepresented_capacity);
             if (!rc && opt.window_depth) rc = bqc_enable_window_depth(ctx, opt.window_depth_size, wdp_lens.data(), opt.window_depth_min_mapq);
             if (rc) create_err = bqc_last_error(ctx);
         }
@@ -1969,6 +2011,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         {!region_rid.empty(), ".rcv", [&](const char* p) { return bqc_write_region_coverage(ctx, &hi, sac_names.data(), n_refs, p); }},
         {opt.duplicate_sets != 0, ".dup", [&](const char* p) { return bqc_write_duplicate_sets(ctx, &hi, p); }},
         {opt.window_depth != 0, ".wdp", [&](const char* p) { return bqc_write_window_depth(ctx, &hi, sac_names.data(), n_refs, p); }},
+        {opt.overrepresented, ".ovr", [&](const char* p) { return bqc_write_overrepresented(ctx, &hi, p); }},
     };
     std::string path = opt.outputFile; // the file last written: where rc, the one that failed
     for (const ModuleFile& f : module_files) {

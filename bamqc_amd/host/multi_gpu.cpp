@@ -497,6 +497,11 @@ extern "C" int bqc_main_multi(int argc, const char** argv, int n_gpus)
                 fprintf(stderr, "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)\n");
                 return 1;
             }
+        for (int k = 1; k < argc; ++k) // (the same for the sets of equal sequences)
+            if (strncmp(argv[k], "--overrepresented", 17) == 0) {
+                fprintf(stderr, "bamqualcheck: --overrepresented with --gpus is not supported: a set may have members in two workers' shards (run one process)\n");
+                return 1;
+            }
         if (!path[0]) { fprintf(stderr, "bamqualcheck: --gpus with --manifest is not supported: run one process per card (--device), each with a list of its own\n"); return 1; }
         bam = path;
         // (said once, here, before any worker exists: every worker's run_program would say it too)

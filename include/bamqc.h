@@ -810,6 +810,71 @@ typedef struct bqc_wdp_view {
 int bqc_window_depth(bqc_ctx* ctx, uint32_t lane, bqc_wdp_view* out);   /* after bqc_finalize */
 int bqc_write_window_depth(bqc_ctx* ctx, const bqc_header_info* hdr, const char* const* ref_names, uint32_t n_refs, const char* path);
 
+/* ---- overrepresented sequences and duplication by sequence (bqc_enable_overrepresented; not in the reference) -----------------------
+ * Which read sequences occur far too often, and how duplicated the reads are AS SEQUENCES (FastQC's overrepresented sequences and
+ * duplication levels, with exact counts): adapter dimers, rRNA and PhiX carry-over, primer artefacts, poly-G tails, amplicon
+ * dominance.  It is the duplication measure that also works where the duplicate sets cannot: unaligned and unmapped reads.
+ * Examined reads.  flag & 0x900 == 0;  flag & 0xC0 != 0;  l_seq > 0;  lane < n_lanes.  The mate is 0 with 0x40, else 1 (k_qcyc's
+ * rule).  Unmapped reads, QC-fail reads, duplicates and BQC_FLAG_NO_QUAL reads are examined.  No quality, CIGAR, contig or genome is
+ * read.
+ * Key.  K is the prefix length, 20 ... 56 (the program's default 50), and n = min(l_seq, K).  The key is the first n bases AS
+ * SEQUENCED, together with n and the mate: of a forward read the stored bases 0 ... n-1; of a reverse read (0x10) the stored bases
+ * L-1 down to L-n, each complemented — a reverse read that stores revcomp(S) and a forward read that stores S have one key.  Two reads
+ * are in one SET iff their keys are equal; the read group is NOT part of the key, as in the duplicate sets.  Reads that agree in the
+ * first K bases and differ behind them are in one set; ACGT and ACGTA, with l_seq 4 and 5, are two sets.  If any of the n bases is not
+ * A, C, G or T (stored codes 1, 2, 4, 8; the other twelve, N and = among them), the read is SKIPPED: counted per read group and mate,
+ * and no part of any set.  (FastQC counts a poly-N read as a sequence; here a run of them shows up as `skipped`.)
+ * Products.  Per read group, pure sums: examined[2] and skipped[2] by mate.  Per mate m, over all read groups: entered_m = the sum of
+ * examined - skipped;  distinct_m = the number of sets;  largest_m = the reads of the largest set;  hist_m[i], i = 1 ... 256 = the sets
+ * of i reads (bin 256: 256 and more).  distinct / entered is the share of reads that remains if deduplicated.
+ * The list.  ppm is 10 ... 10^6 (the program's default 1000: FastQC's 0.1 %); the threshold is T_m = max(2, ceil(entered_m * ppm /
+ * 10^6)) in 64-bit integer arithmetic (the product stays below 2^60).  Every set of mate m with count >= T_m is listed with its
+ * sequence as letters, its count and a POSSIBLE SOURCE: the name of the first adapter of the adapter-by-cycle module's BUILT-IN set,
+ * in the set's order, that occurs letter for letter in the listed sequence, else "-".  The list is sorted by mate, then count
+ * descending, then sequence ascending as text.  The listed counts of a mate sum to at most entered_m, so at most floor(10^6 / ppm)
+ * sets of a mate can be listed: the list's buffer has that size.
+ * State.  A hash table in device memory of its own, the duplicate sets' kind: 24 bytes a slot, C = the smallest power of two >= 2
+ * capacity (and >= 32) slots, capacity 16 ... 2^31 keys (the program's default 2^26: 3 GiB), and the per-lane sums.  NONE of it is part
+ * of the flat state vector: bqc_state_words and every offset are the same with the module on, export and import carry none of it,
+ * shards cannot be merged (a set may have members in two shards: --gpus N is refused by the program).  bqc_reset empties the table and
+ * the sums and keeps the allocation.
+ * Overflow.  When the reads hold more than `capacity` different keys (both mates together) the stream fails with BQC_ERR_RANGE where
+ * other errors found on the card surface (a later submit, sync, flush or finalize); the message names the capacity and
+ * --overrepresented-capacity.
+ * bqc_enable_overrepresented switches the module on, after creation, in any order with the other enable calls (the ABI version stays
+ * 2).  BQC_ERR_ARG, the message names the value: K outside 20 ... 56, ppm outside 10 ... 10^6, capacity outside 16 ... 2^31, in this
+ * order.  BQC_ERR_STATE: a second call; a call after the context has taken a batch, has exported or imported state, or has been
+ * finalised.  Without the call: no allocation, no launch.  With it: every other output is the same bytes as without it.
+ * bqc_overrepresented: valid after bqc_finalize (which leaves the table as it is: it may be called again); the view is owned by the
+ * context until the next finalize / destroy.  BQC_ERR_STATE: the module is off, or nothing has been finalised.
+ * bqc_write_overrepresented: the text, lanes in the order of `hdr`, key-then-values lines:
+ *   sample_id <id> / overrepresented_len <K> / overrepresented_ppm <ppm> / overrepresented_capacity <capacity> /
+ *   lane <name> / sequence_reads_examined_first <n> / sequence_reads_examined_second <n> / sequence_reads_skipped_first <n> /
+ *   sequence_reads_skipped_second <n>                                                                     (these five per read group)
+ *   all_lanes / sequences_distinct_first <U> / sequence_set_largest_first <n> / sequence_set_size_histogram_first v1 ... v256 /
+ *   overrepresented_threshold_first <T> / overrepresented_sequences_first <lines that follow> /
+ *   <sequence> <count> <possible source or ->                                                             (one line per listed set)
+ *   then the same five keys and the list with _second */
+int bqc_enable_overrepresented(bqc_ctx* ctx, uint32_t prefix_len, uint32_t ppm, uint64_t capacity);
+typedef struct bqc_ovr_seq {
+    const char* seq;     /* the n letters of the set's key, as sequenced */
+    uint64_t count;
+    const char* source;  /* a built-in adapter's name, or "-" */
+} bqc_ovr_seq;
+typedef struct bqc_ovr_view {
+    uint32_t prefix_len, ppm;
+    uint64_t capacity;
+    uint32_t n_lanes, pad;
+    const uint64_t* lanes;              /* [n_lanes][4]: examined first, examined second, skipped first, skipped second */
+    uint64_t distinct[2], largest[2];   /* [mate] */
+    const uint64_t* hist[2];            /* [256]: sets of 1 ... 255 reads, of 256 and more */
+    uint64_t threshold[2];
+    uint32_t n_listed[2];
+    const bqc_ovr_seq* listed[2];       /* [n_listed[m]], sorted */
+} bqc_ovr_view;
+int bqc_overrepresented(bqc_ctx* ctx, bqc_ovr_view* out);   /* after bqc_finalize */
+int bqc_write_overrepresented(bqc_ctx* ctx, const bqc_header_info* hdr, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
