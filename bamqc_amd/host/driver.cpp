@@ -1,5 +1,5 @@
 // driver.cpp — the `bamqualcheck` program as a library function: drop-in for the reference's main()
-// (src/bamqualcheck.cpp:239-457) and command line (src/CommandLineParser.hpp:43-149), with the
+// (src/bamqualcheck.cpp:239-457; its command line: host/program_options.h), with the
 // record loop's body replaced by the GPU aggregation of include/bamqc.h.  Also: FASTA loader
 // (replaces Genome / SequenceStream, src/TripletCounting.hpp:60-104) and the C wrappers of
 // include/bamqc_host.h around the BAM reader.
@@ -19,10 +19,10 @@
 #include <functional>
 #include <memory>
 #include <mutex>
-#include <set>
 #include <string>
 #include <chrono>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -34,7 +34,7 @@
 #include "inflate_fast.h"
 #include "host_tools.h"
 #include "input_route.h"
-#include "../csrc/adapter_rule.h"
+#include "program_options.h"
 #include "../csrc/gpu_bam.h"
 #include "../csrc/gpu_sam.h"
 #include <hip/hip_runtime_api.h>
@@ -767,467 +767,9 @@ extern "C" int bqc_synth_stream(const bqc_synth_params* p, const char* const* re
     return w.close() ? 0 : BQC_ERR_IO;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// command line (CommandLineParser.hpp:43-149)
-// ---------------------------------------------------------------------------------------------------
+using namespace bqc_cli; // the command line — ProgramOptions, parse_args, usage, the manifest's list: host/program_options.h
+
 namespace {
-struct ProgramOptions {
-    std::string bamFile, referenceFile = "genome.fa", outputFile;
-    std::string chroms = "chr1,chr2,chr3,chr4,chr5,chr6,chr7,chr8,chr9,chr10,chr11,chr12,chr13,chr14,chr15,chr16,chr17,chr18,chr19,chr20,chr21,chr22";
-    std::vector<int32_t> klist;
-    std::vector<uint32_t> q_cutoff;
-    double e = 0.01;
-    int seed = 1;
-    int isize = 1000;
-    // extensions (not in the reference)
-    uint32_t max_read_len = 65536, hist_cap = 65536;
-    int device = 0;
-    uint32_t batch_reads = [] { const char* e = getenv("BQC_BATCH_READS"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 1u << 20; }(); // (the variable: experiments; --batch-reads)
-    bool no_sketch = false;
-    uint32_t qual_by_cycle = 0; // --qual-by-cycle / --qual-by-cycle-len N: per-cycle base quality histograms into <output>.qbc (0: off, else N)
-    uint32_t mismatch_by_cycle = 0; // --mismatch-by-cycle / --mismatch-by-cycle-len N: compared bases and mismatches by cycle and quality into <output>.mbc
-    // --adapter-by-cycle / --adapter-by-cycle-len N / --adapter NAME=SEQ: adapter content by cycle into <output>.adp (0: off, else N;
-    // adapters empty: the built-in set)
-    uint32_t adapter_by_cycle = 0;
-    std::vector<std::pair<std::string, std::string>> adapters;
-    uint32_t gc_bias = 0; // --gc-bias / --gc-bias-window W: GC bias into <output>.gcb (0: off, else the window length W)
-    uint32_t indel_by_cycle = 0; // --indel-by-cycle / --indel-by-cycle-len N: indels by cycle and by length into <output>.ibc (0: off, else N)
-    // --substitutions / --substitutions-len N / --substitutions-min-qual Q / --substitutions-min-mapq MQ: substitutions by context and by cycle into <output>.sbc
-    uint32_t substitutions = 0, subst_min_qual = 20, subst_min_mapq = 30; // (substitutions 0: off, else N)
-    // --site-alleles FILE / --site-alleles-min-qual Q / --site-alleles-min-mapq MQ: allele counts at the sites of FILE into <output>.sac
-    std::string site_alleles; // (empty: off)
-    uint32_t site_min_qual = 20, site_min_mapq = 20;
-    // --regions FILE / --regions-min-mapq MQ / --regions-thresholds LIST / --regions-depth-cap D: depth over the regions of FILE into <output>.rcv
-    std::string regions; // (empty: off)
-    uint32_t regions_min_mapq = 20, regions_depth_cap = 1000;
-    std::vector<uint64_t> regions_thresholds{1, 10, 20, 30, 50, 100};
-    // --duplicate-sets / --duplicate-sets-capacity N: duplicate sets by alignment signature into <output>.dup
-    bool duplicate_sets = false;
-    uint64_t duplicate_sets_capacity = 1ull << 26; // signatures the table takes (3 GiB of slots)
-    // --overrepresented / --overrepresented-len K / --overrepresented-ppm P / --overrepresented-capacity N: sets of equal read
-    // sequences and the list of the overrepresented ones into <output>.ovr
-    bool overrepresented = false;
-    uint32_t overrepresented_len = 50, overrepresented_ppm = 1000;
-    uint64_t overrepresented_capacity = 1ull << 26; // sequence keys the table takes (3 GiB of slots)
-    // --window-depth / --window-depth-size W / --window-depth-min-mapq MQ: depth in fixed genome windows into <output>.wdp
-    bool window_depth = false;
-    uint32_t window_depth_size = 1000, window_depth_min_mapq = 20;
-    // --manifest LIST: many files through one resident worker (INPUT<TAB>OUTPUT per line); bamFile and outputFile stay empty
-    std::string manifest;
-    std::vector<std::pair<std::string, std::string>> jobs;
-};
-
-const char* kVersion = "dev"; // src/version.h:12
-
-void usage(FILE* f)
-{
-    fprintf(f,
-            "bamqualcheck - String Modifier\n==============================\n\nSYNOPSIS\n    bamqualcheck [OPTIONS] BAMFILE\n\n"
-            "DESCRIPTION\n    Program for bam quality checks. The program can read from bamfile or stdin(sam format)\n\n"
-            "    -h, --help\n          Displays this help message.\n    --version\n          Display version information\n\n"
-            "  General options:\n    -r, --reference FILENAME\n          Reference genome filename. Default: genome.fa.\n"
-            "    -i, --insert-size INT\n          Upper bound for the insert size in insert size histogram. Default: 1000.\n"
-            "    -c, --chromosomes STRING\n          Comma separated list of the main chromosome names.\n"
-            "    -o, --output-file OUT\n          Output filename.\n\n"
-            "  Kmerstream options:\n    -k, --kmer-size STRING\n          Comma-separated list of k-mer sizes. Default: 32.\n"
-            "    -q, --quality-cutoff STRING\n          Comma-separated list of PHRED quality thresholds. Default: 17.\n"
-            "    -e, --error-rate DOUBLE\n          Error rate guaranteed. Default: 0.01.\n"
-            "    -s, --seed INT\n          Seed value for the randomness. Default: 1.\n\n"
-            "  MI355X options (not in the reference):\n    --device INT, --max-read-len INT, --hist-cap INT, --batch-reads INT, --no-sketch\n"
-            "    --qual-by-cycle\n          Per-cycle base quality histograms (read group x mate x cycle x Phred value) into OUT.qbc,\n"
-            "          for the first 1024 cycles of every read.\n"
-            "    --qual-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).\n"
-            "    --mismatch-by-cycle\n          Bases compared with the reference genome, and those that differ from it (read group x mate x\n"
-            "          cycle x Phred value), into OUT.mbc, for the first 1024 cycles of every read.\n"
-            "    --mismatch-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).\n"
-            "    --adapter-by-cycle\n          Adapter content by cycle: per read group, mate and adapter the reads whose first occurrence of the\n"
-            "          adapter starts at each cycle, and the reads by length, into OUT.adp, for the first 1024 cycles.\n"
-            "    --adapter-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).\n"
-            "    --adapter NAME=SEQ\n          An adapter to look for (repeatable, at most 8; the first one replaces the built-in set): NAME is 1 to 31\n"
-            "          characters of [A-Za-z0-9_.-], SEQ 8 to 16 letters of ACGT.  Implies --adapter-by-cycle.\n"
-            "    --gc-bias\n          GC bias: the genome's windows of 100 bases by GC bin, and per read group the reads that start in a\n"
-            "          window of each bin, their bases and the sum of their base qualities, into OUT.gcb.  Not with --gpus.\n"
-            "    --gc-bias-window INT\n          The same for windows of INT bases (at least 20, at most 1000).  Implies --gc-bias.\n"
-            "    --indel-by-cycle\n          Insertions and deletions by cycle (read group x mate x the first 1024 cycles) and by length (1 to 64\n"
-            "          and more), with the reads by length they are rates of, into OUT.ibc.\n"
-            "    --indel-by-cycle-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).  Implies --indel-by-cycle.\n"
-            "    --substitutions\n          Substitutions as sequenced: the pairs (genome base, read base) by trinucleotide context, per read group,\n"
-            "          mate and strand, and by cycle (the first 1024), over bases of quality 20 and more in reads of mapping\n"
-            "          quality 30 and more, into OUT.sbc (oxidation, deamination and strand artefacts are folds of it).\n"
-            "    --substitutions-len INT\n          The same for the first INT cycles (at least 1, at most --max-read-len).  Implies --substitutions.\n"
-            "    --substitutions-min-qual INT\n          The same over bases of quality INT and more (0 to 222).  Implies --substitutions.\n"
-            "    --substitutions-min-mapq INT\n          The same over reads of mapping quality INT and more (0 to 255).  Implies --substitutions.\n"
-            "    --site-alleles FILE\n          Allele counts at given sites: per read group and site of FILE (lines CONTIG<TAB>POS, POS counted from 1,\n"
-            "          as the body lines of a VCF are), the reads that show A, C, G and T there, by strand, over bases of quality\n"
-            "          20 and more in reads of mapping quality 20 and more, into OUT.sac (fingerprint, lane swap and\n"
-            "          contamination checks are folds of it).\n"
-            "    --site-alleles-min-qual INT\n          The same over bases of quality INT and more (0 to 222).  Needs --site-alleles.\n"
-            "    --site-alleles-min-mapq INT\n          The same over reads of mapping quality INT and more (0 to 255).  Needs --site-alleles.\n"
-            "    --regions FILE\n          Depth over given regions: FILE is a BED file (lines CONTIG<TAB>START<TAB>END, START counted from 0, END\n"
-            "          exclusive; regions that overlap or abut are merged).  Per read group the reads and aligned bases on the\n"
-            "          regions, a histogram of the depth over their bases and per region the depth's sum, minimum and maximum\n"
-            "          and the bases at depth 1, 10, 20, 30, 50 and 100 or more, over reads of mapping quality 20 and more,\n"
-            "          into OUT.rcv (on-target rate, mean target depth, fold-80 and the list of gaps are folds of it).\n"
-            "    --regions-min-mapq INT\n          The same over reads of mapping quality INT and more (0 to 255).  Needs --regions.\n"
-            "    --regions-thresholds LIST\n          The same with the depths of LIST: up to 8 numbers of 1 to 4294967295, increasing, separated by\n"
-            "          commas.  Needs --regions.\n"
-            "    --regions-depth-cap INT\n          The histogram's last bin: depth INT and more (1 to 16383, default 1000).  Needs --regions.\n"
-            "    --duplicate-sets\n          Duplicate sets: reads of equal alignment signature (class, strands, contig, unclipped 5' position and\n"
-            "          template length) are one set.  Per read group the examined and the flagged (0x400) reads, over all read\n"
-            "          groups the sets, the largest set, the sets by size and the estimated library size, into OUT.dup (the\n"
-            "          duplication rate and observed against flagged duplicates are folds of it).  Not with --gpus.\n"
-            "    --duplicate-sets-capacity INT\n          The different signatures the table takes (16 to 2147483648, default 67108864: 3 GiB on the card).\n"
-            "          Needs --duplicate-sets.\n"
-            "    --overrepresented\n          Overrepresented sequences: reads whose first 50 bases as sequenced (a reverse read's last stored bases,\n"
-            "          reverse-complemented) are equal, of the same mate, are one set; unmapped reads count, reads with a base\n"
-            "          other than A, C, G, T among them are skipped.  Per read group the examined and the skipped reads, per mate\n"
-            "          over all read groups the sets, the largest set, the sets by size and every sequence that makes up 1000 reads\n"
-            "          per million or more (at least 2 reads) with its count and the built-in adapter it contains, into OUT.ovr\n"
-            "          (duplication by sequence and contaminant spotting are folds of it).  Not with --gpus.\n"
-            "    --overrepresented-len INT\n          The same for the first INT bases (20 to 56).  Implies --overrepresented.\n"
-            "    --overrepresented-ppm INT\n          The same listing sequences of INT reads per million or more (10 to 1000000).  Implies --overrepresented.\n"
-            "    --overrepresented-capacity INT\n          The different sequences the table takes (16 to 2147483648, default 67108864: 3 GiB on the card).\n"
-            "          Implies --overrepresented.\n"
-            "    --window-depth\n          Depth in fixed genome windows of 1000 bases over every contig of the header: per read group and window\n"
-            "          the reads that begin in it and the covered bases of reads of mapping quality 20 and more, the covered bases\n"
-            "          of the reads below it, the same summed by contig, and a histogram of the main contigs' window depths, into\n"
-            "          OUT.wdp (sex and aneuploidy checks, the share of reads off the main contigs and coverage evenness are\n"
-            "          folds of it).\n"
-            "    --window-depth-size INT\n          The same in windows of INT bases (100 to 16777216).  Implies --window-depth.\n"
-            "    --window-depth-min-mapq INT\n          The same with mapping quality INT as the border between the two classes (0 to 255).  Implies\n"
-            "          --window-depth.\n"
-            "    --manifest LIST\n          Many files, one resident worker: LIST holds INPUT<TAB>OUTPUT per line (instead of BAMFILE and -o).\n"
-            "          With a list (only then), \"{dir}\" in the reference's filename stands for the directory of each\n"
-            "          job's input; in a single run the filename is taken as it is.\n\n"
-            "VERSION\n    bamqualcheck version: %s\n    Last update August 2019\n",
-            kVersion);
-}
-
-// the positional rule (valid values: "- bam sam" by file extension, CommandLineParser.hpp:59-60), for a path that is not "-"
-bool input_extension_ok(const std::string& path, std::string& err)
-{
-    // (input_kind: ".sam.gz" is two extensions, and a pipe has no name to speak of — /dev/stdin, /dev/fd/N, a process substitution)
-    const InputKind k = input_kind(path.c_str());
-    if (k == IN_OTHER || k == IN_STDIN) { err = "bamqualcheck: the given path '" + path + "' does not have one of the valid file extensions [*.-, *.bam, *.sam, *.sam.gz]"; return false; }
-    return true;
-}
-
-// --manifest LIST: one job per line, INPUT<TAB>OUTPUT; empty lines and lines that start with '#' are skipped, a '\r' in front of the
-// '\n' is dropped.  Everything that is wrong with the list is found here, before any job runs or any output file is touched.
-bool read_manifest(const std::string& path, std::vector<std::pair<std::string, std::string>>& jobs, std::string& err)
-{
-    std::string text;
-    {
-        FILE* f = fopen(path.c_str(), "rb");
-        if (!f) { err = "bamqualcheck: the manifest '" + path + "' cannot be read"; return false; }
-        char buf[1 << 16];
-        size_t n;
-        while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
-        const bool bad = ferror(f) != 0;
-        fclose(f);
-        if (bad) { err = "bamqualcheck: the manifest '" + path + "' cannot be read"; return false; }
-    }
-    std::set<std::string> outputs;
-    size_t line_no = 0;
-    for (size_t p = 0; p < text.size();) {
-        size_t e = text.find('\n', p);
-        if (e == std::string::npos) e = text.size();
-        std::string line = text.substr(p, e - p);
-        p = e + 1;
-        ++line_no;
-        if (!line.empty() && line.back() == '\r') line.pop_back();
-        if (line.empty() || line[0] == '#') continue;
-        const std::string where = "bamqualcheck: manifest '" + path + "' line " + std::to_string(line_no) + ": ";
-        const size_t tab = line.find('\t');
-        if (tab == std::string::npos || line.find('\t', tab + 1) != std::string::npos || tab == 0 || tab + 1 == line.size()) { err = where + "expected INPUT<TAB>OUTPUT"; return false; }
-        const std::string in = line.substr(0, tab), out = line.substr(tab + 1);
-        if (in == "-") { err = where + "a stream on stdin is not a job"; return false; }
-        std::string xerr;
-        if (!input_extension_ok(in, xerr)) { err = where + xerr.substr(strlen("bamqualcheck: ")); return false; }
-        if (!outputs.insert(out).second) { err = where + "the output '" + out + "' is named twice"; return false; }
-        jobs.emplace_back(in, out);
-    }
-    if (jobs.empty()) { err = "bamqualcheck: the manifest '" + path + "' names no job"; return false; }
-    return true;
-}
-
-// returns 0 = ok, 1 = parse error, 2 = help/version printed (exit 0)
-// session_form: the options of a session (bqc_session_open) — the program's without an input, -o and --manifest
-int parse_args(int argc, const char** argv, ProgramOptions& o, std::string& err, bool session_form = false)
-{
-    std::string kstr = "32", qstr = "17";
-    bool have_r = false, have_o = false, have_m = false;
-    bool want_adp = false; // --adapter-by-cycle or an --adapter: the module at 1024 cycles unless --adapter-by-cycle-len says otherwise
-    bool want_gcb = false; // --gc-bias: the module with windows of 100 bases unless --gc-bias-window says otherwise
-    std::string want_sac_value; // a threshold option of --site-alleles was given: it needs the sites
-    std::string want_rcv_value; // a parameter option of --regions was given: it needs the regions
-    std::string want_dup_value; // --duplicate-sets-capacity was given: it needs --duplicate-sets
-    // (--gpus N is the front end's and never reaches this parser from it; given here, it is an illegal option — said in the option's
-    // own terms where the GC bias is asked for as well, which no worker of --gpus could compute)
-    auto gcb_somewhere = [&]() {
-        for (int k = 1; k < argc; ++k)
-            if (strcmp(argv[k], "--gc-bias") == 0 || strncmp(argv[k], "--gc-bias-window", 16) == 0) return true;
-        return false;
-    };
-    auto dup_somewhere = [&]() { // (the same for the duplicate sets: a set may have members in two workers' shards)
-        for (int k = 1; k < argc; ++k)
-            if (strcmp(argv[k], "--duplicate-sets") == 0 || strncmp(argv[k], "--duplicate-sets-capacity", 25) == 0) return true;
-        return false;
-    };
-    auto ovr_somewhere = [&]() { // (and for the overrepresented sequences, for the same reason)
-        for (int k = 1; k < argc; ++k)
-            if (strncmp(argv[k], "--overrepresented", 17) == 0) return true;
-        return false;
-    };
-    std::vector<std::string> pos;
-    auto need = [&](int& i, const std::string& name, std::string& val, const char* inl) -> bool {
-        if (inl) { val = inl; return true; }
-        if (i + 1 >= argc) { err = "bamqualcheck: option requires an argument -- " + name; return false; }
-        val = argv[++i];
-        return true;
-    };
-    for (int i = 1; i < argc; ++i) {
-        std::string a = argv[i];
-        if (a == "-") { pos.push_back(a); continue; }
-        if (a == "-h" || a == "--help") { usage(stdout); return 2; }
-        if (a == "--version") { printf("bamqualcheck version: %s\nLast update August 2019\n", kVersion); return 2; }
-        const char* inl = nullptr;
-        std::string key = a;
-        if (a.rfind("--", 0) == 0) {
-            size_t eq = a.find('=');
-            if (eq != std::string::npos) { key = a.substr(0, eq); inl = argv[i] + eq + 1; }
-        } else if (a.size() > 2 && a[0] == '-') { // -ovalue
-            key = a.substr(0, 2);
-            inl = argv[i] + 2;
-        }
-        std::string v;
-        if (key == "-r" || key == "--reference") { if (!need(i, key, v, inl)) return 1; o.referenceFile = v; have_r = true; }
-        else if (key == "-o" || key == "--output-file") { if (!need(i, key, v, inl)) return 1; o.outputFile = v; have_o = true; }
-        else if (key == "-c" || key == "--chromosomes") { if (!need(i, key, v, inl)) return 1; o.chroms = v; }
-        else if (key == "-i" || key == "--insert-size") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            long x = strtol(v.c_str(), &end, 10);
-            if (!end || *end || v.empty()) { err = "bamqualcheck: the given value '" + v + "' cannot be casted to integer"; return 1; }
-            o.isize = (int)x;
-        }
-        else if (key == "-k" || key == "--kmer-size") { if (!need(i, key, v, inl)) return 1; kstr = v; }
-        else if (key == "-q" || key == "--quality-cutoff") { if (!need(i, key, v, inl)) return 1; qstr = v; }
-        else if (key == "-e" || key == "--error-rate") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            o.e = strtod(v.c_str(), &end);
-            if (!end || *end || v.empty()) { err = "bamqualcheck: the given value '" + v + "' cannot be casted to double"; return 1; }
-            if (o.e < 0) { err = "bamqualcheck: the given value '" + v + "' is smaller than the minimum value of 0"; return 1; }
-        }
-        else if (key == "-s" || key == "--seed") { if (!need(i, key, v, inl)) return 1; o.seed = atoi(v.c_str()); }
-        else if (key == "--device") { if (!need(i, key, v, inl)) return 1; o.device = atoi(v.c_str()); }
-        else if (key == "--max-read-len") { if (!need(i, key, v, inl)) return 1; o.max_read_len = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
-        else if (key == "--hist-cap") { if (!need(i, key, v, inl)) return 1; o.hist_cap = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
-        else if (key == "--batch-reads") { if (!need(i, key, v, inl)) return 1; o.batch_reads = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
-        else if (key == "--no-sketch") { o.no_sketch = true; }
-        else if (key == "--qual-by-cycle") { if (!o.qual_by_cycle) o.qual_by_cycle = 1024; }
-        else if (key == "--qual-by-cycle-len") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--qual-by-cycle-len wants 1 or more)"; return 1; }
-            o.qual_by_cycle = (uint32_t)x;
-        }
-        else if (key == "--mismatch-by-cycle") { if (!o.mismatch_by_cycle) o.mismatch_by_cycle = 1024; }
-        else if (key == "--mismatch-by-cycle-len") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--mismatch-by-cycle-len wants 1 or more)"; return 1; }
-            o.mismatch_by_cycle = (uint32_t)x;
-        }
-        else if (key == "--adapter-by-cycle") { want_adp = true; }
-        else if (key == "--adapter-by-cycle-len") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--adapter-by-cycle-len wants 1 or more)"; return 1; }
-            o.adapter_by_cycle = (uint32_t)x;
-        }
-        else if (key == "--adapter") {
-            if (!need(i, key, v, inl)) return 1;
-            const size_t eq = v.find('=');
-            if (eq == std::string::npos) { err = "bamqualcheck: the given value '" + v + "' is not an adapter (--adapter wants NAME=SEQ)"; return 1; }
-            const std::string nm = v.substr(0, eq), sq = v.substr(eq + 1);
-            const std::string fault = bqc_adapter_fault(nm.c_str(), sq.c_str());
-            if (!fault.empty()) { err = "bamqualcheck: --adapter " + v + ": " + fault; return 1; }
-            for (const auto& ad : o.adapters)
-                if (ad.first == nm) { err = "bamqualcheck: --adapter " + v + ": the adapter name '" + nm + "' is given twice"; return 1; }
-            if (o.adapters.size() == 8) { err = "bamqualcheck: --adapter " + v + ": at most 8 adapters are taken"; return 1; }
-            o.adapters.emplace_back(nm, sq);
-            want_adp = true;
-        }
-        else if (key == "--gc-bias") { want_gcb = true; }
-        else if (key == "--indel-by-cycle") { if (!o.indel_by_cycle) o.indel_by_cycle = 1024; }
-        else if (key == "--indel-by-cycle-len") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x == 0 || x > 0x3FFFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--indel-by-cycle-len wants 1 or more)"; return 1; }
-            o.indel_by_cycle = (uint32_t)x;
-        }
-        else if (key == "--substitutions") { if (!o.substitutions) o.substitutions = 1024; }
-        else if (key == "--substitutions-len") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x == 0 || x > 0x7FFFFFFull) { err = "bamqualcheck: the given value '" + v + "' is not a number of cycles (--substitutions-len wants 1 or more)"; return 1; }
-            o.substitutions = (uint32_t)x;
-        }
-        else if (key == "--substitutions-min-qual" || key == "--substitutions-min-mapq") {
-            if (!need(i, key, v, inl)) return 1;
-            const bool qual = key == "--substitutions-min-qual";
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? ~0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x > (qual ? 222ull : 255ull)) {
-                err = "bamqualcheck: the given value '" + v + "' is not a " + (qual ? "base quality (--substitutions-min-qual wants 0 to 222)" : "mapping quality (--substitutions-min-mapq wants 0 to 255)");
-                return 1;
-            }
-            (qual ? o.subst_min_qual : o.subst_min_mapq) = (uint32_t)x;
-            if (!o.substitutions) o.substitutions = 1024;
-        }
-        else if (key == "--site-alleles") { if (!need(i, key, v, inl)) return 1; o.site_alleles = v; }
-        else if (key == "--site-alleles-min-qual" || key == "--site-alleles-min-mapq") {
-            if (!need(i, key, v, inl)) return 1;
-            const bool qual = key == "--site-alleles-min-qual";
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? ~0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x > (qual ? 222ull : 255ull)) {
-                err = "bamqualcheck: the given value '" + v + "' is not a " + (qual ? "base quality (--site-alleles-min-qual wants 0 to 222)" : "mapping quality (--site-alleles-min-mapq wants 0 to 255)");
-                return 1;
-            }
-            (qual ? o.site_min_qual : o.site_min_mapq) = (uint32_t)x;
-            want_sac_value = key;
-        }
-        else if (key == "--regions") { if (!need(i, key, v, inl)) return 1; o.regions = v; }
-        else if (key == "--regions-min-mapq" || key == "--regions-depth-cap") {
-            if (!need(i, key, v, inl)) return 1;
-            const bool mq = key == "--regions-min-mapq";
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? ~0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x > (mq ? 255ull : 16383ull) || (!mq && x < 1)) {
-                err = "bamqualcheck: the given value '" + v + "' is not a " + (mq ? "mapping quality (--regions-min-mapq wants 0 to 255)" : "histogram cap (--regions-depth-cap wants 1 to 16383)");
-                return 1;
-            }
-            (mq ? o.regions_min_mapq : o.regions_depth_cap) = (uint32_t)x;
-            want_rcv_value = key;
-        }
-        else if (key == "--regions-thresholds") {
-            if (!need(i, key, v, inl)) return 1;
-            std::vector<uint64_t> t;
-            bool ok = !v.empty();
-            for (size_t at = 0; ok && at <= v.size();) {
-                const size_t comma = std::min(v.find(',', at), v.size());
-                const std::string f = v.substr(at, comma - at);
-                char* end = nullptr;
-                const unsigned long long x = f.empty() || f[0] < '0' || f[0] > '9' || f.size() > 10 ? 0ull : strtoull(f.c_str(), &end, 10);
-                ok = end && !*end && x >= 1 && x <= 0xFFFFFFFFull && (t.empty() || x > t.back()) && t.size() < 8;
-                t.push_back(x);
-                at = comma + 1;
-            }
-            if (!ok) {
-                err = "bamqualcheck: the given value '" + v + "' is not a list of depths (--regions-thresholds wants up to 8 increasing numbers of 1 to 4294967295, separated by commas)";
-                return 1;
-            }
-            o.regions_thresholds = t;
-            want_rcv_value = key;
-        }
-        else if (key == "--duplicate-sets") { o.duplicate_sets = true; }
-        else if (key == "--overrepresented") { o.overrepresented = true; }
-        else if (key == "--overrepresented-len" || key == "--overrepresented-ppm" || key == "--overrepresented-capacity") {
-            if (!need(i, key, v, inl)) return 1;
-            const bool len = key == "--overrepresented-len", ppm = key == "--overrepresented-ppm";
-            const unsigned long long lo = len ? 20 : ppm ? 10 : 16, hi = len ? 56 : ppm ? 1000000 : 1ull << 31;
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' || v.size() > 10 ? 0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x < lo || x > hi) {
-                err = "bamqualcheck: the given value '" + v + "' is not a " + (len ? "prefix length (--overrepresented-len wants 20 to 56)" : ppm ? "number of reads per million (--overrepresented-ppm wants 10 to 1000000)" : "number of sequences (--overrepresented-capacity wants 16 to 2147483648)");
-                return 1;
-            }
-            if (len) o.overrepresented_len = (uint32_t)x;
-            else if (ppm) o.overrepresented_ppm = (uint32_t)x;
-            else o.overrepresented_capacity = x;
-            o.overrepresented = true;
-        }
-        else if (key == "--window-depth") { o.window_depth = true; }
-        else if (key == "--window-depth-size" || key == "--window-depth-min-mapq") {
-            if (!need(i, key, v, inl)) return 1;
-            const bool mq = key == "--window-depth-min-mapq";
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' || v.size() > 10 ? ~0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x > (mq ? 255ull : 1ull << 24) || (!mq && x < 100)) {
-                err = "bamqualcheck: the given value '" + v + "' is not a " + (mq ? "mapping quality (--window-depth-min-mapq wants 0 to 255)" : "window size (--window-depth-size wants 100 to 16777216)");
-                return 1;
-            }
-            (mq ? o.window_depth_min_mapq : o.window_depth_size) = (uint32_t)x;
-            o.window_depth = true;
-        }
-        else if (key == "--duplicate-sets-capacity") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' || v.size() > 10 ? 0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x < 16 || x > 1ull << 31) {
-                err = "bamqualcheck: the given value '" + v + "' is not a number of signatures (--duplicate-sets-capacity wants 16 to 2147483648)";
-                return 1;
-            }
-            o.duplicate_sets_capacity = x;
-            want_dup_value = key;
-        }
-        else if (key == "--gc-bias-window") {
-            if (!need(i, key, v, inl)) return 1;
-            char* end = nullptr;
-            const unsigned long long x = v.empty() || v[0] < '0' || v[0] > '9' ? 0ull : strtoull(v.c_str(), &end, 10);
-            if (!end || *end || x < 20 || x > 1000) { err = "bamqualcheck: the given value '" + v + "' is not a window length (--gc-bias-window wants 20 to 1000)"; return 1; }
-            o.gc_bias = (uint32_t)x;
-        }
-        else if (key == "--gpus" && dup_somewhere()) { err = "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)"; return 1; }
-        else if (key == "--gpus" && ovr_somewhere()) { err = "bamqualcheck: --overrepresented with --gpus is not supported: a set may have members in two workers' shards (run one process)"; return 1; }
-        else if (key == "--gpus" && gcb_somewhere()) { err = "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)"; return 1; }
-        else if (key == "--manifest") { if (!need(i, key, v, inl)) return 1; o.manifest = v; have_m = true; }
-        else if (a[0] == '-') { err = "bamqualcheck: illegal option -- " + a.substr(a.rfind("--", 0) == 0 ? 2 : 1); return 1; }
-        else pos.push_back(a);
-    }
-    if (want_adp && !o.adapter_by_cycle) o.adapter_by_cycle = 1024;
-    if (want_gcb && !o.gc_bias) o.gc_bias = 100;
-    if (!want_sac_value.empty() && o.site_alleles.empty()) { err = "bamqualcheck: option " + want_sac_value + " needs --site-alleles FILE (the sites it applies to)"; return 1; }
-    if (!want_rcv_value.empty() && o.regions.empty()) { err = "bamqualcheck: option " + want_rcv_value + " needs --regions FILE (the regions it applies to)"; return 1; }
-    if (!want_dup_value.empty() && !o.duplicate_sets) { err = "bamqualcheck: option " + want_dup_value + " needs --duplicate-sets (the table it sizes)"; return 1; }
-    if (!have_r) { err = "bamqualcheck: option requires an argument -- r (required option -r/--reference missing)"; return 1; }
-    if (session_form) {
-        if (have_o || have_m || !pos.empty()) { err = "bamqualcheck: a session takes the program's options without an input, -o and --manifest"; return 1; }
-    } else if (have_m) {
-        if (have_o) { err = "bamqualcheck: --manifest names every job's output: -o cannot be given with it"; return 1; }
-        if (!pos.empty()) { err = "bamqualcheck: --manifest names every job's input: no BAMFILE can be given with it"; return 1; }
-        if (!read_manifest(o.manifest, o.jobs, err)) return 1;
-    } else {
-        if (!have_o) { err = "bamqualcheck: option requires an argument -- o (required option -o/--output-file missing)"; return 1; }
-        if (pos.size() != 1) { err = pos.empty() ? "bamqualcheck: Not enough arguments were provided." : "bamqualcheck: Too many arguments were provided!"; return 1; }
-        o.bamFile = pos[0];
-        if (o.bamFile != "-" && !input_extension_ok(o.bamFile, err)) return 1;
-    }
-    // comma separated lists, parsed like the reference's stringstream loops (:121-143)
-    auto split_nums = [](const std::string& s, auto& out) {
-        size_t p = 0;
-        while (p < s.size()) {
-            char* end = nullptr;
-            long v = strtol(s.c_str() + p, &end, 10);
-            if (end == s.c_str() + p) break;
-            out.push_back((typename std::remove_reference<decltype(out)>::type::value_type)v);
-            p = (size_t)(end - s.c_str());
-            if (p < s.size() && s[p] == ',') ++p;
-        }
-    };
-    split_nums(kstr, o.klist);
-    split_nums(qstr, o.q_cutoff);
-    return 0;
-}
-
 // Page-locked decode buffers: the columns of every HostBatch the decoder fills are registered with the HIP runtime once
 // (hipHostRegister, ~40 ms per GB of touched pages), so that bqc_submit_async copies them to the device without a staging
 // copy; a block that a growing vector frees is released first (bqc_raw_vector_free_hook).
@@ -1308,31 +850,22 @@ RefKey make_ref_key(const std::string& fasta, const BamHeader& H)
     k.sq_names = H.ref_names; k.sq_lens = H.ref_lens;
     return k;
 }
-// The options that size a context (bqc_options): equal ones mean bqc_reset instead of bqc_create.
+// What a context was made with (bqc_options and the modules): equal ones mean bqc_reset instead of bqc_create.
 struct CtxKey {
-    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0, qual_by_cycle = 0, mismatch_by_cycle = 0, adapter_by_cycle = 0, gc_bias = 0, indel_by_cycle = 0, substitutions = 0, subst_min_qual = 0, subst_min_mapq = 0;
+    ModuleSettings mod;                                        // the modules' settings in use (settings_in_use: a module that is off adds nothing)
     std::vector<std::pair<std::string, std::string>> adapters; // (empty: the built-in set)
-    std::vector<int32_t> site_rid, site_pos; // --site-alleles: the list as mapped to the job's header (empty: off)
-    uint32_t site_min_qual = 0, site_min_mapq = 0;
-    std::vector<int32_t> region_rid, region_start, region_end; // --regions: the list as mapped to the job's header (empty: off)
-    uint32_t regions_min_mapq = 0, regions_depth_cap = 0;
-    std::vector<uint64_t> regions_thresholds;
-    uint64_t duplicate_sets = 0; // --duplicate-sets: the capacity (0: off)
-    uint64_t overrepresented = 0; // --overrepresented: the capacity (0: off), the prefix length and the threshold
-    uint32_t overrepresented_len = 0, overrepresented_ppm = 0;
-    uint32_t window_depth = 0, window_depth_min_mapq = 0; // --window-depth: the window size (0: off)
-    std::vector<int32_t> window_depth_lens;               // and the contigs' lengths of the job's header
-    int isize = 0, seed = 0, device = 0;
-    bool sketch = false;
+    // what the options name, as mapped to the job's header (empty: off)
+    std::vector<int32_t> site_rid, site_pos, region_rid, region_start, region_end, window_depth_lens;
+    std::vector<uint8_t> main_chrom;
+    uint32_t n_lanes = 0, n_refs = 0, max_read_len = 0, hist_cap = 0;
+    int isize = 0, device = 0;
+    bool sketch = false; // and with it:
     double e = 0;
+    int seed = 0;
     std::vector<int32_t> klist;
     std::vector<uint32_t> qlist;
-    std::vector<uint8_t> main_chrom;
-    bool operator==(const CtxKey& o) const
-    {
-        return n_lanes == o.n_lanes && n_refs == o.n_refs && max_read_len == o.max_read_len && hist_cap == o.hist_cap && qual_by_cycle == o.qual_by_cycle && mismatch_by_cycle == o.mismatch_by_cycle && adapter_by_cycle == o.adapter_by_cycle && adapters == o.adapters && gc_bias == o.gc_bias && indel_by_cycle == o.indel_by_cycle && substitutions == o.substitutions && subst_min_qual == o.subst_min_qual && subst_min_mapq == o.subst_min_mapq && site_rid == o.site_rid && site_pos == o.site_pos && site_min_qual == o.site_min_qual && site_min_mapq == o.site_min_mapq && region_rid == o.region_rid && region_start == o.region_start && region_end == o.region_end && regions_min_mapq == o.regions_min_mapq && regions_depth_cap == o.regions_depth_cap && regions_thresholds == o.regions_thresholds && duplicate_sets == o.duplicate_sets && overrepresented == o.overrepresented && overrepresented_len == o.overrepresented_len && overrepresented_ppm == o.overrepresented_ppm && window_depth == o.window_depth && window_depth_min_mapq == o.window_depth_min_mapq && window_depth_lens == o.window_depth_lens && isize == o.isize && seed == o.seed && device == o.device &&
-               sketch == o.sketch && e == o.e && klist == o.klist && qlist == o.qlist && main_chrom == o.main_chrom;
-    }
+    auto members() const { return std::tie(mod, adapters, site_rid, site_pos, region_rid, region_start, region_end, window_depth_lens, main_chrom, n_lanes, n_refs, max_read_len, hist_cap, isize, device, sketch, e, seed, klist, qlist); }
+    bool operator==(const CtxKey& o) const { return members() == o.members(); }
 };
 }
 
@@ -1374,9 +907,9 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     if (pr == 2) return 0;
     if (pr == 1) { fprintf(stderr, "%s\n", perr.c_str()); return 1; }
     // (a worker of --gpus N holds only the contigs its batches touch: none has the genome table; the front end says so before it forks)
-    if (shard && opt.duplicate_sets) { fprintf(stderr, "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)\n"); return 1; }
-    if (shard && opt.overrepresented) { fprintf(stderr, "bamqualcheck: --overrepresented with --gpus is not supported: a set may have members in two workers' shards (run one process)\n"); return 1; }
-    if (shard && opt.gc_bias) { fprintf(stderr, "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)\n"); return 1; }
+    const ModuleSettings& mod = opt.mod;
+    const std::string conflict = shard ? gpus_conflict(mod) : std::string();
+    if (!conflict.empty()) { fprintf(stderr, "%s\n", conflict.c_str()); return 1; }
     using clk = std::chrono::steady_clock;
     const bool timing = getenv("BQC_TIMING") && getenv("BQC_TIMING")[0] == '1'; // BQC_TIMING=1: where the wall time of a run goes (stderr)
     auto since_launch = [&](const char* what) { // (BQC_T0: the launcher's CLOCK_MONOTONIC seconds when it started the program)
@@ -1437,16 +970,16 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         return shard_abort();
     }
     std::vector<int32_t> wdp_lens; // --window-depth: the contigs' lengths as this header gives them (every worker of --gpus N takes them from its own copy)
-    if (opt.window_depth) {
+    if (mod.window_depth) {
         uint64_t NW = 0;
         for (const uint32_t len : rd.header().ref_lens) {
             wdp_lens.push_back((int32_t)std::min<uint32_t>(len, 0x7FFFFFFFu));
-            NW += ((uint64_t)len + opt.window_depth_size - 1) / opt.window_depth_size;
+            NW += ((uint64_t)len + mod.window_depth_size - 1) / mod.window_depth_size;
         }
         const uint64_t lanes = std::max(1u, rd.header().lane_count);
         if (lanes * (4 + 3 * NW) > 1ull << 28) { // said here in the option's terms, before the output file is opened
             fprintf(stderr, "ERROR: %s: %llu windows of %u bases x 3 planes x %llu read groups are more than 268435456 (2^28) words; --window-depth-size wants a larger window for this header\n",
-                    opt.bamFile.c_str(), (unsigned long long)NW, opt.window_depth_size, (unsigned long long)lanes);
+                    opt.bamFile.c_str(), (unsigned long long)NW, (uint32_t)mod.window_depth_size, (unsigned long long)lanes);
             return shard_abort();
         }
     }
@@ -1608,8 +1141,8 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     bo.max_read_len = opt.max_read_len; bo.hist_cap = opt.hist_cap;
     bo.main_chrom = main_chrom.data(); bo.fasta_index = nullptr; bo.device = opt.device; // (FASTA order: bqc_set_fasta_index below)
     bo.shard_tail = shard && shard->index > 0 ? 1u : 0u;
-    bo.qual_by_cycle = opt.qual_by_cycle;
-    bo.mismatch_by_cycle = opt.mismatch_by_cycle;
+    bo.qual_by_cycle = (uint32_t)mod.qual_by_cycle;
+    bo.mismatch_by_cycle = (uint32_t)mod.mismatch_by_cycle;
     if (!opt.no_sketch) {
         bo.sketch.n_k = (uint32_t)opt.klist.size(); bo.sketch.klist = opt.klist.data();
         bo.sketch.n_q = (uint32_t)opt.q_cutoff.size(); bo.sketch.qlist = opt.q_cutoff.data();
@@ -1621,7 +1154,7 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     bqc_modules bm;
     memset(&bm, 0, sizeof bm);
     bm.struct_size = sizeof bm;
-    bm.adapter_by_cycle = opt.adapter_by_cycle;
+    bm.adapter_by_cycle = (uint32_t)mod.adapter_by_cycle;
     bm.n_adapters = (uint32_t)adp_set.size(); bm.adapters = adp_set.empty() ? nullptr : adp_set.data();
     bqc_ctx* ctx = nullptr;
     int rc = 0;
@@ -1635,17 +1168,13 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     bool refs_kept = false, ctx_kept = false;
     if (S) {
         ref_key = make_ref_key(opt.referenceFile, H);
-        ctx_key.n_lanes = bo.n_lanes; ctx_key.n_refs = bo.n_refs; ctx_key.max_read_len = bo.max_read_len; ctx_key.hist_cap = bo.hist_cap; ctx_key.isize = bo.isize;
-        ctx_key.device = bo.device; ctx_key.sketch = !opt.no_sketch; ctx_key.qual_by_cycle = bo.qual_by_cycle; ctx_key.mismatch_by_cycle = bo.mismatch_by_cycle;
-        ctx_key.adapter_by_cycle = opt.adapter_by_cycle; ctx_key.adapters = opt.adapters; ctx_key.gc_bias = opt.gc_bias; ctx_key.indel_by_cycle = opt.indel_by_cycle;
-        ctx_key.substitutions = opt.substitutions; ctx_key.subst_min_qual = opt.subst_min_qual; ctx_key.subst_min_mapq = opt.subst_min_mapq;
-        if (!site_rid.empty()) { ctx_key.site_rid = site_rid; ctx_key.site_pos = site_pos; ctx_key.site_min_qual = opt.site_min_qual; ctx_key.site_min_mapq = opt.site_min_mapq; }
-        if (!region_rid.empty()) { ctx_key.region_rid = region_rid; ctx_key.region_start = region_start; ctx_key.region_end = region_end; ctx_key.regions_min_mapq = opt.regions_min_mapq; ctx_key.regions_depth_cap = opt.regions_depth_cap; ctx_key.regions_thresholds = opt.regions_thresholds; }
-        if (opt.duplicate_sets) ctx_key.duplicate_sets = opt.duplicate_sets_capacity;
-        if (opt.overrepresented) { ctx_key.overrepresented = opt.overrepresented_capacity; ctx_key.overrepresented_len = opt.overrepresented_len; ctx_key.overrepresented_ppm = opt.overrepresented_ppm; }
-        if (opt.window_depth) { ctx_key.window_depth = opt.window_depth_size; ctx_key.window_depth_min_mapq = opt.window_depth_min_mapq; ctx_key.window_depth_lens = wdp_lens; }
+        ctx_key.mod = settings_in_use(mod, !site_rid.empty(), !region_rid.empty());
+        ctx_key.adapters = opt.adapters;
+        ctx_key.site_rid = site_rid; ctx_key.site_pos = site_pos; ctx_key.region_rid = region_rid; ctx_key.region_start = region_start; ctx_key.region_end = region_end; // (empty where the module is off)
+        ctx_key.window_depth_lens = wdp_lens; ctx_key.main_chrom = main_chrom;
+        ctx_key.n_lanes = bo.n_lanes; ctx_key.n_refs = bo.n_refs; ctx_key.max_read_len = bo.max_read_len; ctx_key.hist_cap = bo.hist_cap; ctx_key.isize = bo.isize; ctx_key.device = bo.device;
+        ctx_key.sketch = !opt.no_sketch;
         if (!opt.no_sketch) { ctx_key.klist = opt.klist; ctx_key.qlist = opt.q_cutoff; ctx_key.e = opt.e; ctx_key.seed = opt.seed; }
-        ctx_key.main_chrom = main_chrom;
         refs_kept = S->ctx && ref_key == S->ref_key;
         ctx_kept = refs_kept && ctx_key == S->ctx_key;
     }
@@ -1673,19 +1202,20 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
         // go to the card while the reader still waits for its stream.
         const auto c1 = clk::now();
         const auto c2 = clk::now();
-        rc = opt.adapter_by_cycle ? bqc_create_ex(&bo, &bm, &ctx) : bqc_create(&bo, &ctx);
+        rc = mod.adapter_by_cycle ? bqc_create_ex(&bo, &bm, &ctx) : bqc_create(&bo, &ctx);
         if (rc) create_err = bqc_last_error(nullptr);
         else { // the modules that are switched on right behind the creation, to the first that fails
-            if (opt.gc_bias) rc = bqc_enable_gc_bias(ctx, opt.gc_bias);
-            if (!rc && opt.indel_by_cycle) rc = bqc_enable_indel_by_cycle(ctx, opt.indel_by_cycle);
-            if (!rc && opt.substitutions) rc = bqc_enable_substitutions(ctx, opt.substitutions, opt.subst_min_qual, opt.subst_min_mapq);
-            if (!rc && !site_rid.empty()) rc = bqc_enable_site_alleles(ctx, (uint32_t)site_rid.size(), site_rid.data(), site_pos.data(), opt.site_min_qual, opt.site_min_mapq);
+            const auto u32 = [](uint64_t x) { return (uint32_t)x; }; // (the parser's bounds keep every such word below 2^32)
+            if (mod.gc_bias) rc = bqc_enable_gc_bias(ctx, u32(mod.gc_bias));
+            if (!rc && mod.indel_by_cycle) rc = bqc_enable_indel_by_cycle(ctx, u32(mod.indel_by_cycle));
+            if (!rc && mod.substitutions) rc = bqc_enable_substitutions(ctx, u32(mod.substitutions), u32(mod.subst_min_qual), u32(mod.subst_min_mapq));
+            if (!rc && !site_rid.empty()) rc = bqc_enable_site_alleles(ctx, (uint32_t)site_rid.size(), site_rid.data(), site_pos.data(), u32(mod.site_min_qual), u32(mod.site_min_mapq));
             if (!rc && !region_rid.empty())
-                rc = bqc_enable_region_coverage(ctx, (uint32_t)region_rid.size(), region_rid.data(), region_start.data(), region_end.data(), opt.regions_min_mapq,
-                                                (uint32_t)opt.regions_thresholds.size(), opt.regions_thresholds.data(), opt.regions_depth_cap);
-            if (!rc && opt.duplicate_sets) rc = bqc_enable_duplicate_sets(ctx, opt.duplicate_sets_capacity);
-            if (!rc && opt.overrepresented) rc = bqc_enable_overrepresented(ctx, opt.overrepresented_len, opt.overrepresented_ppm, opt.overrepresented_capacity);
-            if (!rc && opt.window_depth) rc = bqc_enable_window_depth(ctx, opt.window_depth_size, wdp_lens.data(), opt.window_depth_min_mapq);
+                rc = bqc_enable_region_coverage(ctx, (uint32_t)region_rid.size(), region_rid.data(), region_start.data(), region_end.data(), u32(mod.regions_min_mapq),
+                                                u32(mod.n_regions_thresholds), mod.regions_thresholds, u32(mod.regions_depth_cap));
+            if (!rc && mod.duplicate_sets) rc = bqc_enable_duplicate_sets(ctx, mod.duplicate_sets_capacity);
+            if (!rc && mod.overrepresented) rc = bqc_enable_overrepresented(ctx, u32(mod.overrepresented_len), u32(mod.overrepresented_ppm), mod.overrepresented_capacity);
+            if (!rc && mod.window_depth) rc = bqc_enable_window_depth(ctx, u32(mod.window_depth_size), wdp_lens.data(), u32(mod.window_depth_min_mapq));
             if (rc) create_err = bqc_last_error(ctx);
         }
         if (!rc && old) { // the same genome under another context: its contigs change owner, nothing is uploaded
@@ -2001,17 +1531,17 @@ static int run_program(int argc, const char** argv, const ShardArgs* shard, bool
     for (const auto& nm : H.ref_names) sac_names.push_back(nm.c_str());
     struct ModuleFile { bool on; const char* suffix; std::function<int(const char*)> write; };
     const ModuleFile module_files[] = {
-        {opt.qual_by_cycle != 0, ".qbc", [&](const char* p) { return bqc_write_qual_by_cycle(ctx, &hi, p); }},
-        {opt.mismatch_by_cycle != 0, ".mbc", [&](const char* p) { return bqc_write_mismatch_by_cycle(ctx, &hi, p); }},
-        {opt.adapter_by_cycle != 0, ".adp", [&](const char* p) { return bqc_write_adapter_by_cycle(ctx, &hi, p); }},
-        {opt.gc_bias != 0, ".gcb", [&](const char* p) { return bqc_write_gc_bias(ctx, &hi, p); }},
-        {opt.indel_by_cycle != 0, ".ibc", [&](const char* p) { return bqc_write_indel_by_cycle(ctx, &hi, p); }},
-        {opt.substitutions != 0, ".sbc", [&](const char* p) { return bqc_write_substitutions(ctx, &hi, p); }},
+        {mod.qual_by_cycle != 0, ".qbc", [&](const char* p) { return bqc_write_qual_by_cycle(ctx, &hi, p); }},
+        {mod.mismatch_by_cycle != 0, ".mbc", [&](const char* p) { return bqc_write_mismatch_by_cycle(ctx, &hi, p); }},
+        {mod.adapter_by_cycle != 0, ".adp", [&](const char* p) { return bqc_write_adapter_by_cycle(ctx, &hi, p); }},
+        {mod.gc_bias != 0, ".gcb", [&](const char* p) { return bqc_write_gc_bias(ctx, &hi, p); }},
+        {mod.indel_by_cycle != 0, ".ibc", [&](const char* p) { return bqc_write_indel_by_cycle(ctx, &hi, p); }},
+        {mod.substitutions != 0, ".sbc", [&](const char* p) { return bqc_write_substitutions(ctx, &hi, p); }},
         {!site_rid.empty(), ".sac", [&](const char* p) { return bqc_write_site_alleles(ctx, &hi, sac_names.data(), n_refs, p); }},
         {!region_rid.empty(), ".rcv", [&](const char* p) { return bqc_write_region_coverage(ctx, &hi, sac_names.data(), n_refs, p); }},
-        {opt.duplicate_sets != 0, ".dup", [&](const char* p) { return bqc_write_duplicate_sets(ctx, &hi, p); }},
-        {opt.window_depth != 0, ".wdp", [&](const char* p) { return bqc_write_window_depth(ctx, &hi, sac_names.data(), n_refs, p); }},
-        {opt.overrepresented, ".ovr", [&](const char* p) { return bqc_write_overrepresented(ctx, &hi, p); }},
+        {mod.duplicate_sets != 0, ".dup", [&](const char* p) { return bqc_write_duplicate_sets(ctx, &hi, p); }},
+        {mod.window_depth != 0, ".wdp", [&](const char* p) { return bqc_write_window_depth(ctx, &hi, sac_names.data(), n_refs, p); }},
+        {mod.overrepresented != 0, ".ovr", [&](const char* p) { return bqc_write_overrepresented(ctx, &hi, p); }},
     };
     std::string path = opt.outputFile; // the file last written: where rc, the one that failed
     for (const ModuleFile& f : module_files) {

@@ -38,6 +38,7 @@
 
 #include "../../include/bamqc_host.h"
 #include "host_tools.h"
+#include "program_options.h"
 
 namespace {
 // ---- framed messages over a socket pair --------------------------------------------------------------------------------
@@ -487,21 +488,8 @@ extern "C" int bqc_main_multi(int argc, const char** argv, int n_gpus)
         const int pr = bqc_program_args(argc, argv, path, sizeof path);
         if (pr == 2) return 0;
         if (pr != 0) return 1;
-        for (int k = 1; k < argc; ++k) // (a worker holds only the contigs its batches touch: none has the genome table)
-            if (strcmp(argv[k], "--gc-bias") == 0 || strncmp(argv[k], "--gc-bias-window", 16) == 0) {
-                fprintf(stderr, "bamqualcheck: --gc-bias with --gpus is not supported: no worker holds the whole genome (run one process)\n");
-                return 1;
-            }
-        for (int k = 1; k < argc; ++k) // (a set may have members in two workers' shards, and the tables cannot be merged)
-            if (strcmp(argv[k], "--duplicate-sets") == 0 || strncmp(argv[k], "--duplicate-sets-capacity", 25) == 0) {
-                fprintf(stderr, "bamqualcheck: --duplicate-sets with --gpus is not supported: a set may have members in two workers' shards (run one process)\n");
-                return 1;
-            }
-        for (int k = 1; k < argc; ++k) // (the same for the sets of equal sequences)
-            if (strncmp(argv[k], "--overrepresented", 17) == 0) {
-                fprintf(stderr, "bamqualcheck: --overrepresented with --gpus is not supported: a set may have members in two workers' shards (run one process)\n");
-                return 1;
-            }
+        const std::string conflict = bqc_cli::gpus_conflict(argc, argv); // (a module whose table no set of workers can make)
+        if (!conflict.empty()) { fprintf(stderr, "%s\n", conflict.c_str()); return 1; }
         if (!path[0]) { fprintf(stderr, "bamqualcheck: --gpus with --manifest is not supported: run one process per card (--device), each with a list of its own\n"); return 1; }
         bam = path;
         // (said once, here, before any worker exists: every worker's run_program would say it too)
